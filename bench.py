@@ -231,11 +231,25 @@ def cpu_baseline(mg, table, corpus, term_lists, gpu_rows, seconds):
             "parity_checked": checked, "parity_mismatches": mismatches}
 
 
+def dump_outputs(path, totals, n_docs, docs, scores):
+    """--dump-outputs: the rows the timed executor returned for its last timed step, one float64 .npy per array (doc ids
+    and counts are exact in float64). Page slots past a query's n_docs hold no result and are written as 0."""
+    filled = np.arange(docs.shape[1])[None, :] < n_docs.astype(np.int64)[:, None]
+    arrays = {"totals": totals, "n_docs": n_docs, "docs": np.where(filled, docs, 0), "scores": np.where(filled, scores, 0.0)}
+    assert sum(a.size * 8 for a in arrays.values()) <= 64 << 20, "--dump-outputs is capped at 64 MB"
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.asarray(a, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the last step's results (totals, n_docs, docs, scores) as "
+                         "DIR/<name>.npy, float64; the inputs are seeded, so runs with the same arguments compare")
     args = ap.parse_args()
 
     import torch
@@ -425,6 +439,8 @@ def main():
         thr1 = thread_cpu_ms()
         host_cpu_by_thread = {k: round((v - thr0.get(k, 0.0)) / max(1, args.steps), 4) for k, v in thr1.items()
                               if v - thr0.get(k, 0.0) > 0.0005 * args.steps}
+        if args.dump_outputs and rank == 0:  # step j waits into outs[j % depth]: the last step's rows are still there
+            dump_outputs(args.dump_outputs, *outs[(args.steps - 1) % depth][:4])
     else:
         ex_batches = batches
 
