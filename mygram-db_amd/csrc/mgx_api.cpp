@@ -705,7 +705,13 @@ static int IndexCreateImpl(const mgx_index_desc* d, mgx_index** out) {
   if (d->device < 0 || d->device >= ndev) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_index_create: bad device");
   MGX_HIP(hipSetDevice(d->device));
   MGX_HIP(hipStreamCreateWithFlags(&idx->stream, hipStreamNonBlocking));
-  MGX_HIP(hipStreamCreateWithFlags(&idx->side_stream, hipStreamNonBlocking));
+  // The side stream (the few queries the main launch does not take: cand_kernel, the list-operand and general kernels)
+  // is created at the device's highest priority. At the default priority it shared a hardware queue with the batch
+  // streams, so its launch — a few dozen workgroups for ~0.27 ms on the benchmark batch — ran BEFORE the main launch
+  // instead of beside it; a high-priority stream gets a queue of its own.
+  int prio_least = 0, prio_greatest = 0;
+  MGX_HIP(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
+  MGX_HIP(hipStreamCreateWithPriority(&idx->side_stream, hipStreamNonBlocking, prio_greatest));
   const uint32_t n_tiles = static_cast<uint32_t>((n_docs + mgx::kTileDocs - 1) >> mgx::kTileShift);
   idx->n_grams = G;
   idx->h_offsets.assign(d->offsets, d->offsets + G + 1);

@@ -5,6 +5,9 @@
 # gpurun_out/prof_<tag>/summary.json (tools/pmc_agg.py) + stats.csv. Counters are collected in their own passes with
 # --kernel-trace only (no --sys-trace / --hip-trace beside --pmc: refused on this pool), FETCH_SIZE and WRITE_SIZE in
 # separate passes (TCC slots). The program after `--` is python3 itself (no env/bash hop under the profiler).
+# Every pass runs under its own time limit (PROFILE_PASS_SECONDS, default 600) and the script stops at the first pass
+# that does not exit 0 — a fault, an abort (134), a segmentation fault (139) or a time limit (124, 137) included: nothing
+# more is started on a device that may have just faulted.
 set -u
 TAG=${1:?tag}; KERNEL=${2:-bitmap_score_kernel}; shift; shift || true
 for kv in "$@"; do export "$kv"; done
@@ -14,9 +17,17 @@ OUT=$PWD/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 BENCH="python3 $PWD/bench.py --steps ${PROFILE_STEPS:-6} --warmup 2"
+LIMIT=${PROFILE_PASS_SECONDS:-600}
 run() { # name, rocprofv3 options...
   local name=$1; shift
-  (cd /tmp && rocprofv3 "$@" --kernel-trace --output-format csv -d "$OUT/$name" -- $BENCH > "$OUT/$name.log" 2>&1) || echo "pass $name failed"
+  local st=0
+  (cd /tmp && timeout -k 10 "$LIMIT" rocprofv3 "$@" --kernel-trace --output-format csv -d "$OUT/$name" -- $BENCH \
+     > "$OUT/$name.log" 2>&1) || st=$?
+  if [ "$st" -ne 0 ]; then
+    echo "pass $name failed with status $st (124/137: time limit, 134: abort, 139: segfault); stopping" >&2
+    tail -n 20 "$OUT/$name.log" >&2
+    exit "$st"
+  fi
   echo "pass $name done"
 }
 # (one batch in flight for the duration pass: with the default four, launches of different batches overlap on the device
