@@ -13,13 +13,13 @@ SHIM := mygram-db_amd/libmygram_shim.so
 
 all: $(LIB) $(SHIM) oracle
 
-$(CSRC)/mgx_kernels.o: $(CSRC)/mgx_kernels.hip $(CSRC)/mgx_internal.hpp $(CSRC)/mgx_launch.hpp
+$(CSRC)/mgx_kernels.o: $(CSRC)/mgx_kernels.hip $(CSRC)/mgx_internal.hpp $(CSRC)/mgx_launch.hpp $(CSRC)/mgx_fuzzy.hpp $(CSRC)/mgx_text.hpp
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 $(CSRC)/mgx_api.o: $(CSRC)/mgx_api.cpp $(CSRC)/mgx_internal.hpp $(CSRC)/mgx_launch.hpp $(CSRC)/mgx_host.hpp include/mygram_gpu.h
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
 $(CSRC)/mgx_columns.o: $(CSRC)/mgx_columns.cpp $(CSRC)/mgx_host.hpp $(CSRC)/mgx_text.hpp include/mygram_gpu.h
 	g++ $(CXXFLAGS) -pthread -c $< -o $@
-$(CSRC)/mgx_tools.o: $(CSRC)/mgx_tools.cpp include/mygram_tools.h
+$(CSRC)/mgx_tools.o: $(CSRC)/mgx_tools.cpp include/mygram_tools.h $(CSRC)/mgx_fuzzy.hpp $(CSRC)/mgx_text.hpp
 	g++ $(CXXFLAGS) -pthread -c $< -o $@
 
 $(LIB): $(OBJS)

@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define MGX_ABI_VERSION 3U
+#define MGX_ABI_VERSION 4U
 
 /* Values of mygram::utils::ErrorCode used on this path (src/utils/error.h:37-48,100). */
 #define MGX_OK 0
@@ -330,6 +330,15 @@ typedef struct mgx_query {
    * nothing, as in the reference. */
   const uint32_t* score_terms;
   uint32_t n_score_terms;
+  /* FUZZY verify_text post-filter (PostFilterByFuzzyText, search_pipeline.cpp:1746-1755), next to exact_text: 0 = off;
+   * 1 or 2 = the query's FUZZY distance d. After NOT terms and filters (and before the exact_text filter), keep only the
+   * docs whose text holds EVERY positive term exactly (text.find) or within d edits (ContainsFuzzyMatch,
+   * src/utils/edit_distance.cpp:199-296: per whitespace-delimited word, U+3000 / U+00A0 count as spaces; code-point
+   * windows inside non-ASCII words). The caller sets it when ExecuteWithFuzzy would (:1722-1731:
+   * ShouldApplyVerifyText(memory.verify_text, terms)). Every positive term must carry its normalized `text`; needs
+   * mgx_index_attach_text. after_filters still counts the docs before this filter, `total` those after it. The query
+   * runs on the general kernel, in a launch of its own. */
+  uint32_t fuzzy_verify_distance;
 } mgx_query;
 
 typedef struct mgx_batch mgx_batch;

@@ -32,6 +32,12 @@ int mgxt_measure_read_bandwidth(int device, uint64_t bytes, int iters, double* g
  * the library fail with an out-of-memory error. count <= 0 switches the hook off. Process-wide. */
 void mgxt_fail_device_allocs(int after, int count);
 
+/* Test hook: the host build of the matcher the FUZZY verify_text post-filter runs on the device (kOpVerifyFuzzy, one
+ * source: mygram-db_amd/csrc/mgx_fuzzy.hpp) — ContainsFuzzyMatch(text, term, max_distance) of the reference
+ * (src/utils/edit_distance.cpp:199-296). 1 / 0, or -1 for max_distance > 2. */
+int mgxt_contains_fuzzy_match(const uint8_t* text, size_t text_len, const uint8_t* term, size_t term_len,
+                              uint32_t max_distance);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # MGX_LIBRARY: tools only (e.g. the -DMGX_ABLATION build of `make ablation`); the product is libmygram_gpu.so
 LIB_PATH = os.environ.get("MGX_LIBRARY") or os.path.join(_HERE, "libmygram_gpu.so")
 
-ABI_VERSION = 3
+ABI_VERSION = 4
 GRAM_ABSENT = 0xFFFFFFFF
 SORT_DOCID, SORT_SCORE = 0, 1
 
@@ -32,6 +32,7 @@ EXPORTS = [
     "mgx_batch_exchange", "mgx_batch_exchange_df", "mgx_batch_execute_sharded", "mgx_batch_execute_gather", "mgx_batch_algorithmic_bytes", "mgx_batch_kernel_time_ms", "mgx_batch_destroy",
     "mgx_and", "mgx_or", "mgx_not", "mgx_threshold", "mgx_retain", "mgx_score_documents", "mgx_sort_by_score",
     "mgxt_corpus_generate", "mgxt_corpus_view", "mgxt_corpus_destroy", "mgxt_measure_read_bandwidth", "mgxt_fail_device_allocs",
+    "mgxt_contains_fuzzy_match",
 ]
 
 
@@ -78,7 +79,7 @@ class Query(C.Structure):
                 ("k1", C.c_double), ("b", C.c_double), ("total_docs", C.c_uint64), ("avg_doc_length", C.c_double),
                 ("expr", C.c_void_p), ("n_expr", C.c_uint32), ("universe_first", C.c_uint32),
                 ("universe_count", C.c_uint64), ("exact_text", C.c_uint32), ("score_terms", C.c_void_p),
-                ("n_score_terms", C.c_uint32)]
+                ("n_score_terms", C.c_uint32), ("fuzzy_verify_distance", C.c_uint32)]
 
 
 class DumpView(C.Structure):
@@ -198,6 +199,7 @@ def load():
     L.mgxt_measure_read_bandwidth.argtypes = [i32, u64, i32, C.POINTER(C.c_double)]
     L.mgxt_fail_device_allocs.argtypes = [i32, i32]
     L.mgxt_fail_device_allocs.restype = None
+    L.mgxt_contains_fuzzy_match.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, u32]
     _lib = L
     return L
 

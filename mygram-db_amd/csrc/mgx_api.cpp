@@ -1275,6 +1275,7 @@ struct QuerySpec {
   std::vector<double> deep_idfs;
   uint32_t pat_off = 0, pat_len = 0;  // kModeTextDf specs: the term in the batch's pattern pool
   uint32_t vt_begin = 0;              // first of the query's verify patterns in the batch-wide array
+  uint32_t fz_distance = 0;           // kOpVerifyFuzzy: d; the query then runs the FZ instantiation of the general kernel
   // back to the freshly constructed state, keeping the vectors' storage (a re-prepared batch object compiles its new
   // queries into the specs of the old ones)
   void Clear() {
@@ -1296,7 +1297,7 @@ struct QuerySpec {
     wave_ok = flat = fast_score_ok = true;
     est_density = 0.0;
     total_docs = 0;
-    pat_off = pat_len = vt_begin = 0;
+    pat_off = pat_len = vt_begin = fz_distance = 0;
   }
 };
 
@@ -1580,6 +1581,23 @@ static int CompileQuery(const mgx_index* idx, const mgx_query& in, QuerySpec* ou
     c.Emit(in.filters[i].negate ? kOpAndNot : kOpAnd, id);
   }
   c.Emit(kOpCount, 3);
+  if (in.fuzzy_verify_distance != 0) {
+    // PostFilterByFuzzyText (search_pipeline.cpp:1746-1755), before the exact-text rule of :1733-1741
+    if (in.fuzzy_verify_distance > 2)
+      return Fail(MGX_ERR_INVALID_ARGUMENT, "fuzzy_verify_distance must be 0, 1 or 2");
+    if (!idx->dev.text) return Fail(MGX_ERR_INVALID_ARGUMENT, "fuzzy_verify_distance without mgx_index_attach_text");
+    const uint32_t first_fz = static_cast<uint32_t>(out->verify_patterns.size());
+    for (uint32_t i = 0; i < in.n_terms; ++i) {
+      const mgx_term& t = in.terms[i];
+      if (!t.text || t.text_len == 0 || t.text_len > 4096)
+        return Fail(MGX_ERR_INVALID_ARGUMENT,
+                    "fuzzy_verify_distance: every positive term needs its normalized text (1..4096 bytes)");
+      out->verify_patterns.emplace_back(reinterpret_cast<const char*>(t.text), t.text_len);
+    }
+    // (not a flat op: the query runs on the general kernel's FZ instantiation) argument: first pattern | count << 12
+    c.Emit(kOpVerifyFuzzy, first_fz | (in.n_terms << 12));
+    out->fz_distance = in.fuzzy_verify_distance;
+  }
   if (in.exact_text) {
     if (!idx->dev.text) return Fail(MGX_ERR_INVALID_ARGUMENT, "exact_text without mgx_index_attach_text");
     const uint32_t first_exact = static_cast<uint32_t>(out->verify_patterns.size());
@@ -1727,6 +1745,8 @@ struct mgx_batch {
     DevBuf d_queries, d_leaves, d_prog, d_score, d_explicit, d_counters, d_ident, d_items, d_list_begin;
     uint32_t n_items = 0;
     uint32_t n_items_plain = 0;  // block-kernel items [0, n_items_plain): queries of bitmap-form operands only (LaunchTileEval)
+    uint32_t n_items_fz = 0;     // the last n_items_fz block-kernel items: queries with kOpVerifyFuzzy (a launch of their own)
+    uint32_t n_page_fz = 0;      // the same at the end of dev_page_block
     std::vector<unsigned long long> h_counters;
   };
   Group score, bitmap;
@@ -1845,6 +1865,7 @@ static int UploadGroup(mgx_batch* b, mgx_batch::Group& g, uint32_t mode, const s
     q.pat_len = s.pat_len;
     q.vt_begin = s.vt_begin;
     q.vt_count = static_cast<uint32_t>(s.verify_patterns.size());
+    q.fz_distance = s.fz_distance;
     q.k1 = s.k1;
     q.b = s.b;
     q.one_minus_b = 1.0 - s.b;
@@ -2125,6 +2146,9 @@ static int UploadGroup(mgx_batch* b, mgx_batch::Group& g, uint32_t mode, const s
   }
   if (g.plan.bytes > 160 * 1024)
     return Fail(MGX_ERR_NOT_IMPLEMENTED, "query shape exceeds the 160 KiB LDS of a CU");
+  for (uint32_t i = 0; i < n; ++i)
+    if (specs[g.qids[i]].fz_distance != 0 && g.plan.bytes + kFzLdsBytes > 160 * 1024)
+      return Fail(MGX_ERR_NOT_IMPLEMENTED, "query shape with the fuzzy text filter exceeds the 160 KiB LDS of a CU");
   sec.Mark(1);
   MGX_HIP(Upload(g.d_queries, dq.data(), dq.size()));
   MGX_HIP(Upload(g.d_leaves, leaves.data(), leaves.size()));
@@ -2329,14 +2353,22 @@ static int UploadGroup(mgx_batch* b, mgx_batch::Group& g, uint32_t mode, const s
   }
   {
     // block-kernel items: queries whose operands are all bitmap-form first (plain instantiation), then the queries with a
-    // sorted list, an explicit id list or a slot range among their operands (the instantiation that skips / jumps over tiles)
+    // sorted list, an explicit id list or a slot range among their operands (the instantiation that skips / jumps over tiles),
+    // and last the queries with kOpVerifyFuzzy (the FZ instantiation, launched apart)
     std::vector<uint8_t> listlike(n, 0);
-    for (uint32_t i = 0; i < n; ++i)
+    for (uint32_t i = 0; i < n; ++i) {
       for (const DevLeaf& lf : specs[g.qids[i]].leaves)
         if (lf.kind == kLeafList || lf.kind == kLeafExplicit || lf.kind == kLeafRange) listlike[i] = 1;
+      if (specs[g.qids[i]].fz_distance != 0) listlike[i] = 2;
+    }
     std::stable_partition(items_block.begin(), items_block.end(), [&](const DevItem& it) { return listlike[it.query] == 0; });
-    g.n_items_plain = 0;
-    for (const DevItem& it : items_block) g.n_items_plain += listlike[it.query] == 0 ? 1u : 0u;
+    if (std::find(listlike.begin(), listlike.end(), 2) != listlike.end())
+      std::stable_partition(items_block.begin(), items_block.end(), [&](const DevItem& it) { return listlike[it.query] != 2; });
+    g.n_items_plain = g.n_items_fz = 0;
+    for (const DevItem& it : items_block) {
+      g.n_items_plain += listlike[it.query] == 0 ? 1u : 0u;
+      g.n_items_fz += listlike[it.query] == 2 ? 1u : 0u;
+    }
   }
   g.n_items = static_cast<uint32_t>(items_block.size());
   g.n_items_wave = static_cast<uint32_t>(items_wave.size());
@@ -2441,7 +2473,14 @@ static int UploadGroup(mgx_batch* b, mgx_batch::Group& g, uint32_t mode, const s
   if (page_mode) {
     std::vector<DevItem> pw, pb;
     for (uint32_t i = 0; i < n; ++i)
-      if (on_wave[i] != 4) (on_wave[i] ? pw : pb).push_back(DevItem{i, 0, 0, 0});  // (cand_kernel writes its own pages)
+      if (on_wave[i] != 4 && specs[g.qids[i]].fz_distance == 0)
+        (on_wave[i] ? pw : pb).push_back(DevItem{i, 0, 0, 0});  // (cand_kernel writes its own pages)
+    g.n_page_fz = 0;
+    for (uint32_t i = 0; i < n; ++i)  // (kOpVerifyFuzzy: general kernel, FZ launch)
+      if (specs[g.qids[i]].fz_distance != 0) {
+        pb.push_back(DevItem{i, 0, 0, 0});
+        ++g.n_page_fz;
+      }
     MGX_HIP(Upload(g.d_pq_wave, pw.data(), pw.size()));
     MGX_HIP(Upload(g.d_pq_block, pb.data(), pb.size()));
     g.dev_page_wave = d;
@@ -2836,7 +2875,7 @@ static int ExecuteImpl(mgx_batch* b, hipStream_t s, const SeedGather* sg = nullp
     }
     MGX_LAUNCH(LaunchCand(kModeScore, idx->dev, g.dev_cand, g.cand_leaves, g.cand_instr, g.cand_cap, side));
     MGX_LAUNCH(LaunchWaveScore(idx->dev, g.dev_wave_lists, g.wplan_lists, side));
-    MGX_LAUNCH(LaunchTileEval(kModeScore, idx->dev, g.dev, g.plan, side, g.n_items_plain));
+    MGX_LAUNCH(LaunchTileEval(kModeScore, idx->dev, g.dev, g.plan, side, g.n_items_plain, g.n_items_fz));
     // (both conditions are the same on every rank: the collective is entered by all or by none)
     static const uint64_t kMinShardDocs = std::getenv("MGX_SEED_EXCHANGE_MIN_DOCS") ? static_cast<uint64_t>(atoll(std::getenv("MGX_SEED_EXCHANGE_MIN_DOCS"))) : 1000000ull;
     if (sg && sg->fn && g.seed_k != 0 && g.seed_table_docs / static_cast<uint64_t>(sg->world) >= kMinShardDocs) {
@@ -2890,7 +2929,7 @@ static int ExecuteImpl(mgx_batch* b, hipStream_t s, const SeedGather* sg = nullp
     if (b->timing && !timed) {
       MGX_HIP(hipEventRecord(ev0, s));
     }
-    MGX_LAUNCH(LaunchTileEval(kModeBitmap, idx->dev, g.dev, g.plan, s, g.n_items_plain));
+    MGX_LAUNCH(LaunchTileEval(kModeBitmap, idx->dev, g.dev, g.plan, s, g.n_items_plain, g.n_items_fz));
     if (b->timing && !timed) {
       MGX_HIP(hipEventRecord(ev1, s));
       timed = true;
@@ -2919,7 +2958,7 @@ static int ExecuteImpl(mgx_batch* b, hipStream_t s, const SeedGather* sg = nullp
       MGX_HIP(hipEventRecord(b->res->join_ev, idx->side_stream));
     }
     MGX_LAUNCH(LaunchWaveCount(idx->dev, g.dev_wave, g.wplan, false, s));
-    MGX_LAUNCH(LaunchTileEval(kModeDocCount, idx->dev, g.dev, g.plan, s, g.n_items_plain));
+    MGX_LAUNCH(LaunchTileEval(kModeDocCount, idx->dev, g.dev, g.plan, s, g.n_items_plain, g.n_items_fz));
     if (b->timing && !timed) {
       MGX_HIP(hipEventRecord(ev1, s));
       timed = true;
@@ -2928,7 +2967,7 @@ static int ExecuteImpl(mgx_batch* b, hipStream_t s, const SeedGather* sg = nullp
                                const_cast<uint64_t*>(g.dev.totals), s, g.d_cand_skip.as<uint8_t>()));
     if (!cand_side) MGX_LAUNCH(LaunchCand(kModeDocPage, idx->dev, g.dev_cand, g.cand_leaves, g.cand_instr, 0, s));
     MGX_LAUNCH(LaunchWavePage(idx->dev, g.dev_page_wave, g.wplan, s));
-    MGX_LAUNCH(LaunchTileEval(kModeDocPage, idx->dev, g.dev_page_block, g.plan, s));
+    MGX_LAUNCH(LaunchTileEval(kModeDocPage, idx->dev, g.dev_page_block, g.plan, s, 0xFFFFFFFFu, g.n_page_fz));
     if (cand_side) MGX_HIP(hipStreamWaitEvent(s, b->res->join_ev, 0));
   }
   if (b->timing) {

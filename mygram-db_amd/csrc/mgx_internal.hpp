@@ -67,6 +67,9 @@ enum Op : uint32_t {
   kOpThreshEnd,     // acc = (counters >= arg)
   kOpVerifyText,    // acc &= docs whose text contains every pattern of the query (PostFilterByText,
                     // search_pipeline.cpp:1239-1246); general workgroup kernel only
+  kOpVerifyFuzzy,   // acc &= docs whose text contains every pattern exactly or within DevQuery::fz_distance edits
+                    // (PostFilterByFuzzyText, search_pipeline.cpp:1746-1755); argument like kOpVerifyText's. Only the
+                    // FZ instantiation of the general kernel runs it, in a launch of its own
 };
 inline constexpr uint32_t MakeInstr(Op op, uint32_t arg) { return (static_cast<uint32_t>(op) << 24) | (arg & 0xFFFFFFu); }
 
@@ -107,8 +110,14 @@ struct DevQuery {
   uint32_t out_slot;  // row of this query in the per-mode output arrays
   uint32_t pat_off, pat_len;  // kModeTextDf: the term searched in the candidates' text
   uint32_t vt_begin, vt_count;  // kOpVerifyText: the query's patterns in DevBatch::verify_terms
+  uint32_t fz_distance, fz_pad;  // kOpVerifyFuzzy: d (1 or 2); 0 = the query has no such op
   double k1, b, one_minus_b, k1_plus_1, avgdl_clamped;  // BM25 constants, pre-evaluated on the host
 };
+
+// LDS the FZ instantiation of the general kernel takes beyond LdsPlan::bytes (kOpVerifyFuzzy): the tile's drop mask
+// (one u64 per thread), the four waves' candidate counts, and kFzBuf candidate slots shared by the workgroup per round.
+constexpr uint32_t kFzBuf = 2048;
+constexpr uint32_t kFzLdsBytes = kWordsPerTile * 8 + 16 + kFzBuf * 2;
 
 struct DevIndex {
   const uint64_t* offsets;

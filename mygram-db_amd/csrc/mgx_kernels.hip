@@ -19,6 +19,7 @@
 #include <algorithm>
 #include <cstdlib>
 
+#include "mgx_fuzzy.hpp"
 #include "mgx_internal.hpp"
 #include "mgx_launch.hpp"
 
@@ -702,10 +703,70 @@ __device__ __forceinline__ bool tile_may_match(const uint32_t* prog, uint32_t n_
   return acc;
 }
 
+// kOpVerifyFuzzy (PostFilterByFuzzyText, search_pipeline.cpp:1746-1755): a candidate stays when every pattern of the
+// instruction occurs in its text exactly (text.find) or within d edits (ContainsFuzzyMatch, mgx_fuzzy.hpp). A FUZZY
+// candidate set can cover much of a tile and the matcher's cost per doc varies with its text, so the tile's candidates
+// are first compacted across the WORKGROUP (prefix sum of the per-thread counts into an LDS slot list, kFzBuf per
+// round) and shared out evenly, instead of each thread walking its own 64-bit word. The failing docs are collected in an
+// LDS drop mask and cleared from `acc` at the end. Workgroup scope is safe: tile_eval_body runs the program's instruction
+// loop with workgroup-uniform control flow (one query per workgroup, the program in LDS, every skip of a tile taken by
+// all threads), so all 256 threads arrive here together and reach every barrier below. Inlined: as a call it
+// made the FZ instantiation spill 74-94 VGPRs around it (12-21 inlined).
+__device__ __forceinline__ uint64_t verify_fuzzy(const DevIndex& ix, const DevBatch& bt, uint32_t vt_begin, uint32_t d,
+                                              uint32_t arg, uint32_t tile, uint64_t acc, unsigned char* lds) {
+  uint64_t* const drop = reinterpret_cast<uint64_t*>(lds);
+  uint32_t* const wave_tot = reinterpret_cast<uint32_t*>(lds + kWordsPerTile * 8);
+  uint16_t* const slots = reinterpret_cast<uint16_t*>(lds + kWordsPerTile * 8 + 16);
+  const uint32_t tid = threadIdx.x;
+  drop[tid] = 0;
+  const uint32_t mine = __popcll(acc);
+  const uint32_t inc = wave_incl_scan(mine);
+  if (lane_id() == 63) wave_tot[wave_id()] = inc;
+  __syncthreads();
+  uint32_t first = inc - mine, total = 0;
+  for (int w = 0; w < kBlock / 64; ++w) {
+    const uint32_t t = wave_tot[w];
+    if (w < wave_id()) first += t;
+    total += t;
+  }
+  const uint32_t vfirst = arg & 0xFFFu, vcount = arg >> 12;
+  for (uint32_t rb = 0; rb < total; rb += kFzBuf) {  // (total is workgroup-uniform)
+    if (first < rb + kFzBuf && first + mine > rb) {
+      uint64_t bits = acc;
+      uint32_t r = first;
+      while (bits) {
+        const uint32_t bpos = __builtin_ctzll(bits);
+        bits &= bits - 1;
+        if (r >= rb && r < rb + kFzBuf) slots[r - rb] = static_cast<uint16_t>(tid * 64 + bpos);
+        ++r;
+      }
+    }
+    __syncthreads();
+    const uint32_t n = min(kFzBuf, total - rb);
+    for (uint32_t j = tid; j < n; j += kBlock) {
+      const uint32_t ts = slots[j];
+      const uint32_t slot = tile * kTileDocs + ts;
+      const uint64_t t0 = ix.text_off[slot], t1 = ix.text_off[slot + 1];
+      bool all = true;
+      for (uint32_t v = 0; all && v < vcount; ++v) {
+        const DevTextTerm vt = bt.verify_terms[vt_begin + vfirst + v];
+        const uint8_t* const pat = bt.patterns + vt.pat_off;
+        if (text_count_occurrences(ix.text, t0, t1, text_pattern(pat, vt.pat_len), true) != 0) continue;
+        all = d == 1 ? fuzzy::ContainsFuzzyMatch<1>(ix.text + t0, t1 - t0, pat, vt.pat_len)
+                     : fuzzy::ContainsFuzzyMatch<2>(ix.text + t0, t1 - t0, pat, vt.pat_len);
+      }
+      if (!all) atomicOr(reinterpret_cast<unsigned long long*>(&drop[ts >> 6]), 1ull << (ts & 63u));
+    }
+    __syncthreads();  // (the slot list is refilled by the next round; the drop mask is complete after the last one)
+  }
+  return acc & ~drop[tid];
+}
+
 // JUMP: the query has an operand that can be absent from a tile (a sorted list, an explicit id list, a slot range): tiles
 // are tested / jumped over as described above. Queries of bitmap-form operands only run the plain instantiation — the
 // same tile loop without that machinery (its registers cost the text-level scoring path 6 % when they shared one kernel).
-template <int MODE, bool JUMP>
+// FZ: the query may carry kOpVerifyFuzzy (launched apart from every other query; its LDS holds kFzLdsBytes more).
+template <int MODE, bool JUMP, bool FZ>
 __device__ __forceinline__ void tile_eval_body(const DevIndex& ix, const DevBatch& bt, const LdsPlan& plan) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const LdsOffsets lo_ = carve(plan, MODE == kModeScore || MODE == kModeTextDf);
@@ -986,6 +1047,12 @@ __device__ __forceinline__ void tile_eval_body(const DevIndex& ix, const DevBatc
       for (uint32_t pc = 0; pc < q.n_instr; ++pc) {
         const uint32_t ins = prog[pc];
         const uint32_t op = ins >> 24, arg = ins & 0xFFFFFFu;
+        if constexpr (FZ) {
+          if (op == kOpVerifyFuzzy) {
+            acc = verify_fuzzy(ix, bt, q.vt_begin, q.fz_distance, arg, tile, acc, smem + lo_.total);
+            continue;
+          }
+        }
         switch (op) {
           case kOpLoad: acc = W(arg); break;
           case kOpAnd: acc &= W(arg); break;
@@ -1266,11 +1333,16 @@ __device__ __forceinline__ void tile_eval_body(const DevIndex& ix, const DevBatc
 
 // One launch for both kinds of item (two launches meant two tails): the host puts the plain items first, the workgroup
 // picks its instantiation by its index. The two bodies share no registers in flight; the kernel's budget is the larger one's.
-template <int MODE>
+// FZ: the launch of the queries that carry kOpVerifyFuzzy (every workgroup runs the jumping body, which takes any query).
+template <int MODE, bool FZ>
 __global__ __launch_bounds__(kBlock, (MODE == kModeScore ? 3 : 4)) void tile_eval_kernel(DevIndex ix, DevBatch bt, LdsPlan plan,
                                                                                          uint32_t n_plain) {
-  if (blockIdx.x < n_plain) tile_eval_body<MODE, false>(ix, bt, plan);
-  else tile_eval_body<MODE, true>(ix, bt, plan);
+  if constexpr (FZ) {
+    tile_eval_body<MODE, true, true>(ix, bt, plan);
+  } else {
+    if (blockIdx.x < n_plain) tile_eval_body<MODE, false, false>(ix, bt, plan);
+    else tile_eval_body<MODE, true, false>(ix, bt, plan);
+  }
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -3826,24 +3898,48 @@ int LaunchBuildBitmaps(const uint32_t* docids, const uint64_t* row_lo, const uin
 
 // Items [0, n_plain) belong to queries of bitmap-form operands only (plain instantiation), the rest to queries with an
 // operand that can be absent from a tile (jumping instantiation); n_plain >= n_items: everything plain.
-int LaunchTileEval(int mode, const DevIndex& ix, const DevBatch& bt, const LdsPlan& plan, hipStream_t s, uint32_t n_plain) {
+// The last n_fz items belong to queries with kOpVerifyFuzzy: they run the FZ instantiation in a launch of their own, so
+// that no other query pays for it.
+int LaunchTileEval(int mode, const DevIndex& ix, const DevBatch& bt, const LdsPlan& plan, hipStream_t s, uint32_t n_plain,
+                   uint32_t n_fz) {
   const uint64_t grid = bt.n_items;
   if (grid == 0) return 0;
-  if (grid > 0x7FFFFFFFull) return static_cast<int>(hipErrorInvalidValue);
-  auto* kernel = mode == kModeScore      ? &tile_eval_kernel<kModeScore>
-                 : mode == kModeBitmap   ? &tile_eval_kernel<kModeBitmap>
-                 : mode == kModeDocCount ? &tile_eval_kernel<kModeDocCount>
-                 : mode == kModeDocPage  ? &tile_eval_kernel<kModeDocPage>
-                                         : &tile_eval_kernel<kModeTextDf>;
-  if (plan.bytes > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(plan.bytes));
-    if (e != hipSuccess) return static_cast<int>(e);
-  }
+  if (grid > 0x7FFFFFFFull || n_fz > grid || (n_fz != 0 && mode == kModeTextDf)) return static_cast<int>(hipErrorInvalidValue);
   // (the page pass has one item per query: eight workgroups share each query's tiles)
   const uint32_t parts = mode == kModeDocPage ? 8u : 1u;
-  hipLaunchKernelGGL(kernel, dim3(static_cast<uint32_t>(grid), parts), dim3(kBlock), plan.bytes, s, ix, bt, plan, n_plain);
-  MGX_KCHECK();
+  const uint32_t n_main = static_cast<uint32_t>(grid) - n_fz;
+  if (n_main != 0) {
+    auto* kernel = mode == kModeScore      ? &tile_eval_kernel<kModeScore, false>
+                   : mode == kModeBitmap   ? &tile_eval_kernel<kModeBitmap, false>
+                   : mode == kModeDocCount ? &tile_eval_kernel<kModeDocCount, false>
+                   : mode == kModeDocPage  ? &tile_eval_kernel<kModeDocPage, false>
+                                           : &tile_eval_kernel<kModeTextDf, false>;
+    if (plan.bytes > 64 * 1024) {
+      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(plan.bytes));
+      if (e != hipSuccess) return static_cast<int>(e);
+    }
+    hipLaunchKernelGGL(kernel, dim3(n_main, parts), dim3(kBlock), plan.bytes, s, ix, bt, plan, n_plain);
+    MGX_KCHECK();
+  }
+  if (n_fz != 0) {
+    auto* kernel = mode == kModeScore      ? &tile_eval_kernel<kModeScore, true>
+                   : mode == kModeBitmap   ? &tile_eval_kernel<kModeBitmap, true>
+                   : mode == kModeDocCount ? &tile_eval_kernel<kModeDocCount, true>
+                                           : &tile_eval_kernel<kModeDocPage, true>;
+    const uint32_t lds = plan.bytes + kFzLdsBytes;
+    if (lds > 160 * 1024) return static_cast<int>(hipErrorInvalidValue);
+    if (lds > 64 * 1024) {
+      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
+      if (e != hipSuccess) return static_cast<int>(e);
+    }
+    DevBatch fz = bt;
+    fz.items += n_main;
+    fz.n_items = n_fz;
+    hipLaunchKernelGGL(kernel, dim3(n_fz, parts), dim3(kBlock), lds, s, ix, fz, plan, 0u);
+    MGX_KCHECK();
+  }
   return 0;
 }
 

@@ -17,7 +17,7 @@ int LaunchBuildBitmaps(const uint32_t* docids, const uint64_t* row_lo, const uin
                        uint32_t first_doc_id, uint32_t first_row, uint64_t tile_stride, uint64_t row_stride,
                        uint64_t* bitmaps, hipStream_t s);
 int LaunchTileEval(int mode, const DevIndex& ix, const DevBatch& bt, const LdsPlan& plan, hipStream_t s,
-                   uint32_t n_plain = 0xFFFFFFFFu);
+                   uint32_t n_plain = 0xFFFFFFFFu, uint32_t n_fz = 0);
 int LaunchWaveScore(const DevIndex& ix, const DevBatch& bt, const WavePlan& plan, hipStream_t s);
 int LaunchBitmapScore(uint32_t n_score, const DevIndex& ix, const DevBatch& bt, const FastPlan& plan, hipStream_t s);
 int LaunchWavePage(const DevIndex& ix, const DevBatch& bt, const WavePlan& plan, hipStream_t s);

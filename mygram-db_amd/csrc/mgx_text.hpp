@@ -11,10 +11,17 @@
 #include <utility>
 #include <vector>
 
+// ParseUtf8 is also compiled for the device (the fuzzy matcher of the tile kernel, mgx_fuzzy.hpp)
+#if defined(__HIPCC__)
+#define MGX_TEXT_HD __host__ __device__ inline
+#else
+#define MGX_TEXT_HD inline
+#endif
+
 namespace mgx::text {
 
 // src/utils/string_utils.cpp:94-164 (TryParseUtf8Char): bytes consumed, or -1 for an invalid sequence
-inline int ParseUtf8(const uint8_t* d, size_t avail, uint32_t* cp) {
+MGX_TEXT_HD int ParseUtf8(const uint8_t* d, size_t avail, uint32_t* cp) {
   const uint8_t b0 = d[0];
   if (b0 < 0x80) {
     *cp = b0;

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/mygram_tools.h"
+#include "mgx_fuzzy.hpp"
 
 namespace {
 
@@ -157,3 +158,9 @@ int mgxt_corpus_view(const mgxt_corpus* c, const uint8_t** text_bytes, const uin
 void mgxt_corpus_destroy(mgxt_corpus* c) { delete c; }
 
 }  // extern "C"
+
+extern "C" int mgxt_contains_fuzzy_match(const uint8_t* text, size_t text_len, const uint8_t* term, size_t term_len,
+                                         uint32_t max_distance) {
+  if ((text == nullptr && text_len != 0) || (term == nullptr && term_len != 0)) return -1;
+  return mgx::fuzzy::ContainsFuzzyMatchD(text, text_len, term, term_len, max_distance);
+}

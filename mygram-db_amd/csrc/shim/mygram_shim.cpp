@@ -2207,8 +2207,6 @@ void PlanQuery(const index::Index& index, const BatchQuery& q, uint64_t total_do
   if (q.fuzzy_max_distance > 0) {
     // ---- ExecuteWithFuzzy (search_pipeline.cpp:1659-1744): no size sort; theta per term; unknown grams are skipped by
     // Index::SearchByThreshold (index.cpp:512-523) unless theta asks for every gram (then it is SearchAnd) ------------
-    if (q.verify_text)
-      return Fail(p, ErrorCode::kNotImplemented, "FUZZY with verify_text is a host path (edit distance over texts)");
     p->ids.reserve(q.terms.size() + q.not_terms.size());
     p->has_score_list = q.sort_by_score;
     for (const auto& raw : q.terms) {
@@ -2241,18 +2239,24 @@ void PlanQuery(const index::Index& index, const BatchQuery& q, uint64_t total_do
       mgx_term mt{ids.data(), static_cast<uint32_t>(ids.size()), thr, 0.0, nullptr, 0};
       // SORT _score: the EXACT term is scored (GenerateTermInfos' infos, search_pipeline.cpp:1895-1899 ->
       // search_handler.cpp:428-456). A term with an unknown n-gram occurs in no text (tf = df = 0): left out.
+      bool with_text = q.verify_text;  // PostFilterByFuzzyText (:1722-1731, :1746-1755) checks every normalized term
       if (q.sort_by_score && !empty && ids.size() == grams.size()) {
         p->score_list.push_back(static_cast<uint32_t>(p->terms.size()));
         if (grams.size() == 1 && grams[0] == normalized) {
           uint32_t gid = 0;
           uint64_t ps = 0;
           im->Resolve(grams[0], &gid, &ps);
+          // (with the text attached for the filter the term is scored from its text: tf = CountTermOccurrences, which
+          // is what its gram's tf column holds, and df = its posting count, the same idf)
           mt.idf = index::BM25Scorer::ComputeIDF(total_docs, ps);
         } else {
-          p->texts.push_back(normalized);
-          mt.text = reinterpret_cast<const uint8_t*>(p->texts.back().data());
-          mt.text_len = static_cast<uint32_t>(p->texts.back().size());
+          with_text = true;
         }
+      }
+      if (with_text) {
+        p->texts.push_back(normalized);
+        mt.text = reinterpret_cast<const uint8_t*>(p->texts.back().data());
+        mt.text_len = static_cast<uint32_t>(p->texts.back().size());
       }
       p->terms.push_back(mt);
     }
@@ -2260,6 +2264,7 @@ void PlanQuery(const index::Index& index, const BatchQuery& q, uint64_t total_do
     if (!add_filters()) return;
     finish(q.sort_by_score ? MGX_SORT_SCORE : MGX_SORT_DOCID);
     p->q.offset = q.sort_by_score ? q.offset : 0;
+    p->q.fuzzy_verify_distance = q.verify_text ? q.fuzzy_max_distance : 0u;
     return;
   }
   std::vector<TermInfo>& tis = p->tis;

@@ -392,7 +392,9 @@ struct BatchQuery {
   uint32_t fuzzy_max_distance = 0;     // FUZZY d (query_parser_clauses.cpp:454: 1 or 2); 0 = not a fuzzy query.
                                        // ExecuteWithFuzzy (search_pipeline.cpp:1659-1744): per term "at least theta of
                                        // its n-grams", AND across terms in the order given; SORT _score scores the
-                                       // exact terms. Not combined with verify_text here (edit-distance verification)
+                                       // exact terms. With verify_text the result is then cut to the docs whose
+                                       // text holds every term exactly or within d edits (PostFilterByFuzzyText
+                                       // :1746-1755, on the device: mgx_query.fuzzy_verify_distance)
   bool sort_by_score = false;          // SORT _score
   bool verify_text = false;            // the caller's ShouldApplyVerifyText(memory.verify_text, terms) decision
                                        // (search_pipeline.cpp:42-66); mixed-script fragments force it (:858-866)

@@ -803,6 +803,8 @@ class Index:
                     continue
                 cterms = (_capi.Term * len(tis))()
                 scored = []
+                if q.verify_text:
+                    self.ensure_text()  # PostFilterByFuzzyText (search_pipeline.cpp:1746-1755) reads the stored texts
                 for j, t in enumerate(tis):
                     ids_list = [_capi.GRAM_ABSENT] if (t.fuzzy_empty or not t.fuzzy_ids) else t.fuzzy_ids
                     ids = np.asarray(ids_list, dtype=np.uint32)
@@ -821,6 +823,12 @@ class Index:
                             text_ptr, text_len = tb.ctypes.data, len(tb)
                         else:
                             idf = compute_idf(self.total_docs, t.df)
+                    if q.verify_text and text_ptr is None:
+                        # the filter checks every normalized term (a scored single-gram term then takes tf from the
+                        # text, which equals its gram's tf column, and df from the df pass, which equals t.df)
+                        tb = np.frombuffer(t.normalized.encode("utf-8"), dtype=np.uint8).copy()
+                        keep.append(tb)
+                        text_ptr, text_len = tb.ctypes.data, len(tb)
                     cterms[j] = _capi.Term(ids.ctypes.data, len(ids), thr, idf, text_ptr, text_len)
                 nts = []
                 for nt in q.not_terms:
@@ -843,6 +851,8 @@ class Index:
                                  C.cast(cf, C.c_void_p), len(q.filters),
                                  _capi.SORT_SCORE if q.sort_score else _capi.SORT_DOCID, q.limit, q.offset,
                                  int(q.descending), q.k1, q.b, self.total_docs, self.avg_doc_length)
+                if q.verify_text:
+                    cq.fuzzy_verify_distance = q.fuzzy
                 if q.sort_score:
                     sc = np.asarray(scored, dtype=np.uint32)
                     keep.append(sc)
