@@ -1631,14 +1631,30 @@ static int CompileQuery(const mgx_index* idx, const mgx_query& in, QuerySpec* ou
       // materialised like a docid-ordered result, then scored and sorted whole at fetch time.
       for (uint32_t k = 0; k < n_scored; ++k) {
         const mgx_term& t = in.terms[scored_index(k)];
-        if (t.text != nullptr || t.n_grams != 1)
-          return Fail(MGX_ERR_NOT_IMPLEMENTED,
-                      "SORT _score beyond offset+limit 1024 with a text-level term: score with "
-                      "mgx_score_documents_text and page with mgx_sort_by_score");
+        if (t.text != nullptr) {
+          // a text-level term, as the fused path scores it: tf from the doc text, idf from the batch's df pass
+          // (PrepareInto numbers the term and puts kDeepText | its number in deep_grams[k])
+          if (!idx->dev.text)
+            return Fail(MGX_ERR_INVALID_ARGUMENT, "text-level scored term without mgx_index_attach_text");
+          if (t.text_len == 0 || t.text_len > 4096)
+            return Fail(MGX_ERR_OUT_OF_RANGE, "text-level scored term: length must be 1..4096 bytes");
+          QuerySpec::TextTerm tt;
+          tt.pattern.assign(reinterpret_cast<const char*>(t.text), t.text_len);
+          tt.grams.assign(t.gram_ids, t.gram_ids + t.n_grams);
+          tt.score_index = k;
+          out->text_terms.push_back(std::move(tt));
+          out->deep_grams.push_back(kDeepText);
+          out->deep_idfs.push_back(0.0);
+          continue;
+        }
+        if (t.n_grams != 1)
+          return Fail(MGX_ERR_INVALID_ARGUMENT,
+                      "a scored term of several n-grams needs its text (mgx_term.text) for tf and df");
         out->deep_grams.push_back(t.gram_ids[0] == MGX_GRAM_ABSENT ? kNoRow : t.gram_ids[0]);
         out->deep_idfs.push_back(t.idf);
       }
       out->deep_score = true;
+      out->total_docs = in.total_docs;
       out->mode = kModeBitmap;
       if (out->leaves.size() > kMaxLeaves)
         return Fail(MGX_ERR_NOT_IMPLEMENTED, "more than 192 distinct operands in one query");
@@ -1787,6 +1803,13 @@ struct mgx_batch {
   bool merged_shards = false;
   // bitmap group outputs
   DevBuf d_rbits, d_tile_cnt, d_tile_start, d_totals, d_take, d_out_off, d_reverse, d_out;
+  // mutable tables (mgx_batch_merge_local): the bitmap group's sizes are known only at fetch time, so the merge of that
+  // group runs inside mgx_batch_fetch(primary). merge_other: on the primary, the batch whose bitmap-group queries the
+  // fetch merges in; merged_away: on that other batch, its bitmap-group pages went into the primary's result.
+  mgx_batch* merge_other = nullptr;
+  bool merged_away = false;
+  hipStream_t merge_stream = nullptr;
+  DevBuf d_merge;  // scratch of the merged fetch: runs, keys, page, run descriptors (grown, never shrunk)
   // docid-page group (kModeDocPage): per-tile counts / rank offsets, and one packed result block
   // [counters n*8 u64 | totals n u64 | page docs n*stride u32] mirrored in pinned host memory
   Group page;
@@ -2611,7 +2634,8 @@ static int PrepareInto(mgx_batch* b, mgx_index* idx, std::vector<QuerySpec>&& sp
         const auto key = std::make_pair(tt.pattern, s.total_docs);
         const auto hit = seen.find(key);
         if (hit != seen.end()) {
-          s.score[tt.score_index].text_term = hit->second;
+          if (s.deep_score) s.deep_grams[tt.score_index] = kDeepText | hit->second;
+          else s.score[tt.score_index].text_term = hit->second;
           continue;
         }
         const uint32_t id = static_cast<uint32_t>(tts.size());
@@ -2619,7 +2643,8 @@ static int PrepareInto(mgx_batch* b, mgx_index* idx, std::vector<QuerySpec>&& sp
         DevTextTerm d{static_cast<uint32_t>(pool.size()), static_cast<uint32_t>(tt.pattern.size())};
         pool += tt.pattern;
         tts.push_back(d);
-        s.score[tt.score_index].text_term = id;
+        if (s.deep_score) s.deep_grams[tt.score_index] = kDeepText | id;
+        else s.score[tt.score_index].text_term = id;
         b->text_total_docs.push_back(s.total_docs);
         QuerySpec ds;
         ds.mode = kModeTextDf;
@@ -2798,6 +2823,8 @@ static int ExecuteImpl(mgx_batch* b, hipStream_t s, const SeedGather* sg = nullp
     if (rc) return rc;
   }
   b->merged_shards = false;
+  b->merge_other = nullptr;
+  b->merged_away = false;
   {  // contribution tables built while this (or any earlier) batch was compiled travel on the index's table stream
     std::lock_guard<std::mutex> lock(idx->table_mu);
     MGX_HIP(FlushTableJobs(idx));
@@ -2987,6 +3014,199 @@ static int ExecuteImpl(mgx_batch* b, hipStream_t s, const SeedGather* sg = nullp
   return MGX_OK;
 }
 
+// Deep SORT _score: the idf of every scored term in scored-term order (text-level terms: from the batch's df pass).
+static std::vector<double> DeepIdfs(const mgx_batch* b, const QuerySpec& sp) {
+  std::vector<double> idfs = sp.deep_idfs;
+  for (size_t k = 0; k < idfs.size(); ++k)
+    if (sp.deep_grams[k] != kNoRow && (sp.deep_grams[k] & kDeepText) != 0)
+      idfs[k] = b->h_text_idf[sp.deep_grams[k] & ~kDeepText];
+  return idfs;
+}
+
+// The bitmap group of a mutable table's primary batch, merged with the other batch's (mgx_batch_merge_local): for every
+// query the table-wide total and exactly the page an index built from the table's current documents returns.
+//   - one synchronisation brings both indexes' totals; each side then materialises what the page can need
+//     (min(total, limit) in page order for docid pages, every match for limit 0 and for deep SORT _score);
+//   - deep SORT _score: each side scores its matches with its own index's columns on local slots, then the delta's
+//     slots become table ids, and each side's (key, docid') run is sorted by the bitonic network;
+//   - rank_merge_kernel cuts every query's page from the two sorted, disjoint runs, in one launch.
+// Everything lives in the batch's d_merge scratch.
+struct MergedPages {
+  std::vector<uint64_t> total, page_off, page_n;
+  std::vector<uint32_t> docs;
+  std::vector<double> scores;
+};
+
+static uint64_t Align8(uint64_t x) { return (x + 7) & ~7ull; }
+
+static int FetchBitmapMerged(mgx_batch* a, MergedPages* m) {
+  mgx_batch* b = a->merge_other;
+  mgx_batch* const side[2] = {a, b};
+  hipStream_t s = a->merge_stream;
+  mgx_batch::Group& g = a->bitmap;
+  const size_t n = g.qids.size();
+  for (mgx_batch* x : side)
+    if (x->last_stream != s) MGX_HIP(hipStreamSynchronize(x->last_stream));
+  // ---- the one synchronisation of the group: counters of the primary, totals of both ----
+  std::vector<uint64_t> tot[2] = {std::vector<uint64_t>(n), std::vector<uint64_t>(n)};
+  MGX_HIP(hipMemcpyAsync(g.h_counters.data(), g.d_counters.p, n * 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+  for (int k = 0; k < 2; ++k) MGX_HIP(hipMemcpyAsync(tot[k].data(), side[k]->d_totals.p, n * 8, hipMemcpyDeviceToHost, s));
+  MGX_HIP(hipStreamSynchronize(s));
+  // ---- sizes and the scratch layout ----
+  m->total.resize(n);
+  m->page_off.resize(n);
+  m->page_n.resize(n);
+  std::vector<uint64_t> take[2], off[2], soff[2], koff[2], n2[2], toff[2];
+  for (int k = 0; k < 2; ++k) {
+    take[k].assign(n, 0);
+    off[k].assign(n, 0);
+    soff[k].assign(n, 0);
+    koff[k].assign(n, 0);
+    n2[k].assign(n, 0);
+    toff[k].assign(n, 0);
+  }
+  std::vector<DevMergeRun> runs(n);
+  std::vector<uint64_t> run_start(n + 1);
+  std::vector<uint32_t> terms;
+  std::vector<double> idfs;
+  uint64_t at[2] = {0, 0}, n_scores = 0, n_keys = 0, pages = 0, elems = 0;
+  for (size_t i = 0; i < n; ++i) {
+    const QuerySpec& sp = a->specs[g.qids[i]];
+    const uint64_t t = tot[0][i] + tot[1][i];
+    uint64_t lo = 0, hi = 0;
+    if (sp.deep_score) {
+      lo = std::min<uint64_t>(sp.offset, t);
+      hi = sp.limit == 0 ? t : std::min<uint64_t>(lo + sp.limit, t);
+    } else {
+      hi = sp.limit == 0 ? t : std::min<uint64_t>(t, sp.limit);  // (docid order: no offset, see Compile)
+    }
+    m->total[i] = t;
+    m->page_off[i] = pages;
+    m->page_n[i] = hi - lo;
+    pages += hi - lo;
+    DevMergeRun& r = runs[i];
+    r.kind = sp.deep_score ? kMergeScore : sp.reverse ? kMergeDocDesc : kMergeDocAsc;
+    r.descending = sp.reverse ? 1u : 0u;
+    r.lo = static_cast<uint32_t>(lo);
+    r.hi = static_cast<uint32_t>(hi);
+    r.out_off = m->page_off[i];
+    for (int k = 0; k < 2; ++k) {
+      // a docid page needs each side's first hi ids in page order; a score page needs every match
+      take[k][i] = hi == lo ? 0 : sp.deep_score ? tot[k][i] : std::min<uint64_t>(tot[k][i], hi);
+      off[k][i] = at[k];
+      at[k] += take[k][i];
+      if (sp.deep_score && take[k][i] != 0) {
+        const QuerySpec& ks = side[k]->specs[g.qids[i]];
+        soff[k][i] = n_scores;
+        n_scores += take[k][i];
+        n2[k][i] = 2048;  // (LaunchSortPairs: a power of two, at least one LDS run)
+        while (n2[k][i] < take[k][i]) n2[k][i] <<= 1;
+        koff[k][i] = n_keys;
+        n_keys += n2[k][i];
+        toff[k][i] = terms.size();
+        const std::vector<double> ki = DeepIdfs(side[k], ks);
+        terms.insert(terms.end(), ks.deep_grams.begin(), ks.deep_grams.end());
+        idfs.insert(idfs.end(), ki.begin(), ki.end());
+      }
+    }
+    r.a_n = static_cast<uint32_t>(take[0][i]);
+    r.b_n = static_cast<uint32_t>(take[1][i]);
+    run_start[i] = elems;
+    elems += take[0][i] + take[1][i];
+  }
+  run_start[n] = elems;
+  if (elems > 0xFFFFFFFFull || pages > 0xFFFFFFFFull || n_keys > 0xFFFFFFFFull)
+    return Fail(MGX_ERR_OUT_OF_RANGE, "batch result exceeds 2^32 doc ids");
+  for (size_t i = 0; i < n; ++i) {
+    DevMergeRun& r = runs[i];
+    r.a_off = r.kind == kMergeScore ? koff[0][i] : off[0][i];
+    r.b_off = r.kind == kMergeScore ? koff[1][i] : at[0] + off[1][i];
+  }
+  // [runs | run_start | terms | idfs] uploaded as one block, then device-only arrays
+  const uint64_t o_start = Align8(n * sizeof(DevMergeRun));
+  const uint64_t o_terms = o_start + (n + 1) * 8;
+  const uint64_t o_idfs = Align8(o_terms + terms.size() * 4);
+  const uint64_t up_bytes = o_idfs + idfs.size() * 8;
+  const uint64_t o_docs = Align8(up_bytes);
+  const uint64_t o_scores = Align8(o_docs + (at[0] + at[1]) * 4);
+  const uint64_t o_keys = o_scores + n_scores * 8;
+  const uint64_t o_dprime = o_keys + n_keys * 8;
+  const uint64_t o_pdocs = Align8(o_dprime + n_keys * 4);
+  const uint64_t o_pscores = Align8(o_pdocs + pages * 4);
+  const uint64_t bytes = o_pscores + pages * 8;
+  if (a->d_merge.bytes < bytes) MGX_HIP(a->d_merge.Alloc(bytes));
+  char* base = static_cast<char*>(a->d_merge.p);
+  std::vector<char> up(up_bytes);
+  std::memcpy(up.data(), runs.data(), n * sizeof(DevMergeRun));
+  std::memcpy(up.data() + o_start, run_start.data(), (n + 1) * 8);
+  if (!terms.empty()) std::memcpy(up.data() + o_terms, terms.data(), terms.size() * 4);
+  if (!idfs.empty()) std::memcpy(up.data() + o_idfs, idfs.data(), idfs.size() * 8);
+  MGX_HIP(hipMemcpyAsync(base, up.data(), up_bytes, hipMemcpyHostToDevice, s));
+  uint32_t* docs = reinterpret_cast<uint32_t*>(base + o_docs);
+  double* scores = reinterpret_cast<double*>(base + o_scores);
+  uint64_t* keys = reinterpret_cast<uint64_t*>(base + o_keys);
+  uint32_t* dprime = reinterpret_cast<uint32_t*>(base + o_dprime);
+  uint32_t* pdocs = reinterpret_cast<uint32_t*>(base + o_pdocs);
+  double* pscores = reinterpret_cast<double*>(base + o_pscores);
+  // ---- each side materialises its part (expand_kernel, page order: ascending, or descending for reverse docid pages)
+  std::vector<uint64_t> out_off[2];
+  for (int k = 0; k < 2; ++k) {
+    mgx_batch* x = side[k];
+    out_off[k] = off[k];
+    if (k == 1)
+      for (uint64_t& o : out_off[k]) o += at[0];
+    MGX_HIP(hipMemcpyAsync(x->d_take.p, take[k].data(), n * 8, hipMemcpyHostToDevice, s));
+    MGX_HIP(hipMemcpyAsync(x->d_out_off.p, out_off[k].data(), n * 8, hipMemcpyHostToDevice, s));
+    if (at[k])
+      MGX_LAUNCH(LaunchExpand(x->bitmap.dev.rbits, x->d_tile_start.as<uint64_t>(), x->d_totals.as<uint64_t>(),
+                              x->d_take.as<uint64_t>(), x->d_out_off.as<uint64_t>(), x->d_reverse.as<uint32_t>(),
+                              static_cast<uint32_t>(n), x->idx->dev.n_tiles, x->idx->dev.first_doc_id, docs, s));
+  }
+  // ---- deep SORT _score: scores on each side's own columns, by local slot ----
+  const uint32_t* d_terms = reinterpret_cast<const uint32_t*>(base + o_terms);
+  const double* d_idfs = reinterpret_cast<const double*>(base + o_idfs);
+  for (size_t i = 0; i < n; ++i)
+    for (int k = 0; k < 2; ++k) {
+      if (n2[k][i] == 0) continue;
+      mgx_batch* x = side[k];
+      const QuerySpec& ks = x->specs[g.qids[i]];
+      MGX_LAUNCH(LaunchScoreCandidatesMixed(x->idx->dev, docs + out_off[k][i], take[k][i], d_terms + toff[k][i],
+                                            d_idfs + toff[k][i], static_cast<uint32_t>(ks.deep_grams.size()),
+                                            x->d_patterns.as<uint8_t>(), x->d_text_terms.as<DevTextTerm>(), ks.k1,
+                                            ks.b, ks.avgdl, scores + soff[k][i], s));
+    }
+  // ---- local slots -> table ids (a delta index numbers its documents in ascending table-id order) ----
+  for (int k = 0; k < 2; ++k) {
+    const mgx_index* ix = side[k]->idx;
+    if (ix->d_doc_map.p && at[k])
+      MGX_LAUNCH(LaunchRemapDocs(docs + (k == 0 ? 0 : at[0]), at[k], ix->d_doc_map.as<uint32_t>(), ix->dev.first_doc_id,
+                                 ix->dev.n_docs, s));
+  }
+  // ---- deep SORT _score: (key, docid') runs, each sorted best first (padding (0, 0) sorts to the tail) ----
+  if (n_keys) {
+    MGX_HIP(hipMemsetAsync(keys, 0, n_keys * 8, s));
+    MGX_HIP(hipMemsetAsync(dprime, 0, n_keys * 4, s));
+  }
+  for (size_t i = 0; i < n; ++i)
+    for (int k = 0; k < 2; ++k) {
+      if (n2[k][i] == 0) continue;
+      MGX_LAUNCH(LaunchMakeSortKeys(docs + out_off[k][i], scores + soff[k][i], take[k][i], runs[i].descending,
+                                    keys + koff[k][i], dprime + koff[k][i], s));
+      MGX_LAUNCH(LaunchSortPairs(keys + koff[k][i], dprime + koff[k][i], n2[k][i], s));
+    }
+  // ---- every query's page from its two runs ----
+  MGX_LAUNCH(LaunchRankMerge(reinterpret_cast<const DevMergeRun*>(base), reinterpret_cast<const uint64_t*>(base + o_start),
+                             static_cast<uint32_t>(n), elems, docs, keys, dprime, pdocs, pscores, s));
+  m->docs.resize(pages);
+  m->scores.resize(pages);
+  if (pages) {
+    MGX_HIP(hipMemcpyAsync(m->docs.data(), pdocs, pages * 4, hipMemcpyDeviceToHost, s));
+    MGX_HIP(hipMemcpyAsync(m->scores.data(), pscores, pages * 8, hipMemcpyDeviceToHost, s));
+  }
+  MGX_HIP(hipStreamSynchronize(s));
+  return MGX_OK;
+}
+
 static int FetchImpl(mgx_batch* b, mgx_result_view* out) {
   mgx_index* idx = b->idx;
   MGX_HIP(hipSetDevice(idx->device));
@@ -3036,7 +3256,12 @@ static int FetchImpl(mgx_batch* b, mgx_result_view* out) {
   std::vector<uint32_t> bm_docs;
   std::vector<std::vector<uint32_t>> deep_docs;
   std::vector<std::vector<double>> deep_scores;
-  if (!b->bitmap.qids.empty()) {
+  MergedPages merged;
+  const bool bm_merged = b->merge_other != nullptr && !b->bitmap.qids.empty();
+  if (bm_merged) {
+    int rc = FetchBitmapMerged(b, &merged);
+    if (rc) return rc;
+  } else if (!b->bitmap.qids.empty()) {
     mgx_batch::Group& g = b->bitmap;
     const size_t n = g.qids.size();
     MGX_HIP(hipStreamSynchronize(s));  // (this group's sizes make a host round trip)
@@ -3048,7 +3273,9 @@ static int FetchImpl(mgx_batch* b, mgx_result_view* out) {
     uint64_t at = 0;
     for (size_t i = 0; i < n; ++i) {
       const QuerySpec& sp = b->specs[g.qids[i]];
-      take[i] = (sp.limit == 0 || sp.deep_score) ? totals[i] : std::min<uint64_t>(totals[i], sp.limit);
+      take[i] = b->merged_away                   ? 0  // (the primary's fetch returned these pages, merged)
+                : (sp.limit == 0 || sp.deep_score) ? totals[i]
+                                                   : std::min<uint64_t>(totals[i], sp.limit);
       out_off[i] = at;
       at += take[i];
     }
@@ -3081,15 +3308,26 @@ static int FetchImpl(mgx_batch* b, mgx_result_view* out) {
       const uint32_t* cand = b->d_out.as<uint32_t>() + out_off[i];
       DevBuf d_g, d_i, d_sc, d_k, d_d, d_pd, d_ps;
       MGX_HIP(Upload(d_g, sp.deep_grams.data(), sp.deep_grams.size()));
-      MGX_HIP(Upload(d_i, sp.deep_idfs.data(), sp.deep_idfs.size()));
+      if (sp.text_terms.empty()) {
+        MGX_HIP(Upload(d_i, sp.deep_idfs.data(), sp.deep_idfs.size()));
+      } else {
+        const std::vector<double> idfs = DeepIdfs(b, sp);
+        MGX_HIP(Upload(d_i, idfs.data(), idfs.size()));
+      }
       MGX_HIP(d_sc.Alloc(m * 8));
       MGX_HIP(d_k.Alloc(n2 * 8));
       MGX_HIP(d_d.Alloc(n2 * 4));
       MGX_HIP(d_pd.Alloc(static_cast<size_t>(hi - lo) * 4));
       MGX_HIP(d_ps.Alloc(static_cast<size_t>(hi - lo) * 8));
-      MGX_LAUNCH(LaunchScoreCandidates(idx->dev, cand, m, d_g.as<uint32_t>(), d_i.as<double>(),
-                                       static_cast<uint32_t>(sp.deep_grams.size()), sp.k1, sp.b, sp.avgdl,
-                                       d_sc.as<double>(), s));
+      if (sp.text_terms.empty())
+        MGX_LAUNCH(LaunchScoreCandidates(idx->dev, cand, m, d_g.as<uint32_t>(), d_i.as<double>(),
+                                         static_cast<uint32_t>(sp.deep_grams.size()), sp.k1, sp.b, sp.avgdl,
+                                         d_sc.as<double>(), s));
+      else  // text-level scored terms: tf counted in the doc text, summed in scored-term order like the fused path
+        MGX_LAUNCH(LaunchScoreCandidatesMixed(idx->dev, cand, m, d_g.as<uint32_t>(), d_i.as<double>(),
+                                              static_cast<uint32_t>(sp.deep_grams.size()), b->d_patterns.as<uint8_t>(),
+                                              b->d_text_terms.as<DevTextTerm>(), sp.k1, sp.b, sp.avgdl,
+                                              d_sc.as<double>(), s));
       MGX_HIP(hipMemsetAsync(d_k.as<uint64_t>() + m, 0, (n2 - m) * 8, s));
       MGX_HIP(hipMemsetAsync(d_d.as<uint32_t>() + m, 0, (n2 - m) * 4, s));
       MGX_LAUNCH(LaunchMakeSortKeys(cand, d_sc.as<double>(), m, sp.reverse ? 1 : 0, d_k.as<uint64_t>(),
@@ -3133,8 +3371,10 @@ static int FetchImpl(mgx_batch* b, mgx_result_view* out) {
     r.total = c[4];
     if (sc && b->merged_shards) r.total = override_tot[gi];
     if (pg && b->merged_shards) r.total = dp_totals[gi];
+    if (!sc && !pg && bm_merged) r.total = merged.total[gi];
     r.n_docs = sc                         ? page_n[gi]
                : pg                       ? static_cast<uint32_t>(std::min<uint64_t>(r.total, b->specs[qi].limit))
+               : bm_merged                ? static_cast<uint32_t>(merged.page_n[gi])
                : b->specs[qi].deep_score ? static_cast<uint32_t>(deep_docs[gi].size())
                                           : static_cast<uint32_t>(take[gi]);
     r.docs_begin = static_cast<uint32_t>(n_out);
@@ -3155,6 +3395,11 @@ static int FetchImpl(mgx_batch* b, mgx_result_view* out) {
                   r.n_docs * sizeof(double));
     } else if (mode == kModeDocPage) {
       std::memcpy(dst, dp_docs + static_cast<size_t>(gi) * b->doc_page_stride, r.n_docs * sizeof(uint32_t));
+    } else if (bm_merged) {
+      std::memcpy(dst, merged.docs.data() + merged.page_off[gi], r.n_docs * sizeof(uint32_t));
+      if (b->specs[qi].deep_score)
+        std::memcpy(b->h_scores.data() + r.docs_begin, merged.scores.data() + merged.page_off[gi],
+                    r.n_docs * sizeof(double));
     } else if (b->specs[qi].deep_score) {
       std::memcpy(dst, deep_docs[gi].data(), r.n_docs * sizeof(uint32_t));
       std::memcpy(b->h_scores.data() + r.docs_begin, deep_scores[gi].data(), r.n_docs * sizeof(double));
@@ -3424,16 +3669,27 @@ int mgx_batch_merge_local(mgx_batch* primary, mgx_batch* const* others, uint32_t
   if (!primary || (n_others && !others)) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_batch_merge_local: null argument");
   if (primary->n_queries == 0) return MGX_OK;
   if (!primary->res) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_batch_merge_local: not a prepared batch object");
-  if (!primary->bitmap.qids.empty())
+  if (!primary->bitmap.qids.empty() && n_others > 1)
     return mgx::Fail(MGX_ERR_NOT_IMPLEMENTED,
-                     "mgx_batch_merge_local: a query without a page bound (limit 0 or > 16384, not SORT _score) cannot be merged");
+                     "mgx_batch_merge_local: a query without a page bound (limit 0 or > 16384, deep SORT _score) merges "
+                     "two batches, not more");
   try {
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     for (uint32_t j = 0; j < n_others; ++j)
-      if (!others[j] || others[j]->n_queries != primary->n_queries || others[j]->idx->device != primary->idx->device ||
-          others[j]->score.qids.size() != primary->score.qids.size() || others[j]->page.qids.size() != primary->page.qids.size())
+      if (!others[j] || others[j] == primary || others[j]->n_queries != primary->n_queries ||
+          others[j]->idx->device != primary->idx->device ||
+          others[j]->score.qids.size() != primary->score.qids.size() ||
+          others[j]->page.qids.size() != primary->page.qids.size() ||
+          others[j]->bitmap.qids != primary->bitmap.qids || !others[j]->executed)
         return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_batch_merge_local: the batches do not hold the same queries");
     MGX_HIP(hipSetDevice(primary->idx->device));
+    if (!primary->bitmap.qids.empty() && n_others == 1) {
+      // the bitmap group's page sizes need the totals on the host: its merge runs inside mgx_batch_fetch(primary)
+      primary->merge_other = others[0];
+      primary->merge_stream = s;
+      others[0]->merged_away = true;
+    }
+    if (primary->score.qids.empty() && primary->page.qids.empty()) return MGX_OK;
     // a mixed batch has two groups (SORT _score queries, docid-ordered pages): each is exported, remapped and merged on its own
     uint64_t need = 0;
     for (int pass = 0; pass < 2; ++pass) {

@@ -87,6 +87,20 @@ struct DevTextTerm {
   uint32_t pat_off, pat_len;  // the normalized term in DevBatch::patterns
 };
 
+// Deep SORT _score (the full-sort fallback): one scored term, in scored-term order, is a gram row (tf from its posting),
+// kNoRow (a gram this index lacks: tf 0), or kDeepText | t (text-level term t of the batch: tf counted in the doc text).
+constexpr uint32_t kDeepText = 0x80000000u;
+
+// One query of the rank merge (rank_merge_kernel): two sorted, disjoint runs A and B, and the merged ranks [lo, hi) to
+// write at out_off. Docid runs index the docid buffer, score runs the (key, docid') buffers.
+enum MergeKind : uint32_t { kMergeDocAsc = 0, kMergeDocDesc = 1, kMergeScore = 2 };
+struct DevMergeRun {
+  uint64_t a_off, b_off, out_off;
+  uint32_t a_n, b_n, lo, hi;
+  uint32_t kind;       // MergeKind
+  uint32_t descending;  // score runs: the key's direction (key_score)
+};
+
 enum QueryMode : uint32_t {
   kModeScore = 0,   // fused BM25 + per-workgroup top-k
   kModeBitmap = 1,  // result bitmaps + per-tile counts to HBM (expanded to docids afterwards)

@@ -4537,4 +4537,167 @@ int LaunchSortByScore(const uint32_t* docs, const double* scores, uint64_t n, in
   return 0;
 }
 
+
+// ---------------------------------------------------------------------------------------------------------------
+// merged bitmap-group pages of a mutable table (main index + delta index, mgx_batch_merge_local)
+// ---------------------------------------------------------------------------------------------------------------
+
+// Deep SORT _score: BM25Scorer::ScoreDocuments (bm25_scorer.cpp:71-91) over explicit candidates with the scored terms of
+// the fused path — a gram term takes tf from its posting, a text-level term (kDeepText | t) counts it in the doc text —
+// summed in scored-term order, so the result equals the fused kernel's to the last bit. One thread per candidate.
+__global__ void score_candidates_mixed_kernel(DevIndex ix, const uint32_t* __restrict__ cand, uint64_t n_cand,
+                                              const uint32_t* __restrict__ terms, const double* __restrict__ idfs,
+                                              uint32_t n_terms, const uint8_t* __restrict__ patterns,
+                                              const DevTextTerm* __restrict__ text_terms, double k1, double b,
+                                              double one_minus_b, double k1_plus_1, double avgdl_clamped,
+                                              double* __restrict__ scores) {
+  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= n_cand) return;
+  const uint32_t d = cand[i];
+  double score = 0.0;
+  if (d >= ix.first_doc_id && static_cast<uint64_t>(d) - ix.first_doc_id < ix.n_docs) {
+    const uint32_t slot = d - ix.first_doc_id;
+    const uint32_t dli = ix.doc_len[slot];
+    if (dli > 0) {  // empty / missing text => 0.0
+      const double dl = static_cast<double>(dli);
+      const double length_norm = one_minus_b + b * dl / avgdl_clamped;
+      for (uint32_t t = 0; t < n_terms; ++t) {
+        const uint32_t g = terms[t];
+        if (g == kNoRow) continue;  // term unknown to the index: tf = 0 everywhere
+        double tf = 0.0;
+        if (g & kDeepText) {
+          const DevTextTerm tt = text_terms[g & ~kDeepText];
+          tf = static_cast<double>(text_count_occurrences(ix.text, ix.text_off[slot], ix.text_off[slot + 1],
+                                                          text_pattern(patterns + tt.pat_off, tt.pat_len), false));
+        } else {
+          uint64_t lo = ix.offsets[g], hi = ix.offsets[g + 1];
+          const uint32_t row = ix.skip_row[g];
+          if (row != kNoRow) {
+            const uint32_t* r = ix.tile_off + static_cast<uint64_t>(row) * (ix.n_tiles + 1);
+            hi = lo + r[(slot >> kTileShift) + 1];
+            lo = lo + r[slot >> kTileShift];
+          }
+          const uint64_t p = lower_bound_u32(ix.docids, lo, hi, d);
+          if (p < hi && ix.docids[p] == d) tf = static_cast<double>(posting_tf(ix, p));
+        }
+        if (tf > 0.0) {
+          const double numerator = tf * k1_plus_1;
+          const double denominator = tf + k1 * length_norm;
+          score += idfs[t] * numerator / denominator;
+        }
+      }
+    }
+  }
+  scores[i] = score;
+}
+
+// Local doc slots -> table ids through the index's doc map, in place (docs[i] = first_doc_id + slot as expand_kernel
+// writes them). The map is ascending, so every run keeps its order.
+__global__ __launch_bounds__(256) void remap_docs_kernel(uint32_t* __restrict__ docs, uint64_t n,
+                                                         const uint32_t* __restrict__ map, uint32_t first_doc_id,
+                                                         uint32_t n_docs) {
+  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t local = docs[i] - first_doc_id;
+  if (local < n_docs) docs[i] = map[local];
+}
+
+// The order of a merge: before(x, y) = x comes first in the merged page.
+struct MergeDocAsc {
+  __device__ static bool before(uint64_t, uint32_t x, uint64_t, uint32_t y) { return x < y; }
+};
+struct MergeDocDesc {
+  __device__ static bool before(uint64_t, uint32_t x, uint64_t, uint32_t y) { return x > y; }
+};
+struct MergeScoreKey {  // (key, docid') pairs sorted best first by the bitonic network
+  __device__ static bool before(uint64_t kx, uint32_t x, uint64_t ky, uint32_t y) { return better(kx, x, ky, y); }
+};
+
+// Rank of element j of run `own`: j + the elements of run `other` that come before it (a binary search). The runs are
+// disjoint (different doc ids), so the ranks of both runs together are 0..a_n+b_n-1, each taken once.
+template <class Order>
+__device__ __forceinline__ void rank_merge_elem(const DevMergeRun& r, uint32_t j, bool from_a,
+                                                const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals,
+                                                uint32_t* __restrict__ out_docs, double* __restrict__ out_scores) {
+  const uint64_t own = from_a ? r.a_off : r.b_off, other = from_a ? r.b_off : r.a_off;
+  const uint32_t other_n = from_a ? r.b_n : r.a_n;
+  const uint64_t kx = keys ? keys[own + j] : 0;
+  const uint32_t x = vals[own + j];
+  uint32_t lo = 0, hi = other_n;
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    const uint64_t km = keys ? keys[other + mid] : 0;
+    if (Order::before(km, vals[other + mid], kx, x)) lo = mid + 1;
+    else hi = mid;
+  }
+  const uint32_t rank = j + lo;
+  if (rank < r.lo || rank >= r.hi) return;
+  const uint64_t o = r.out_off + (rank - r.lo);
+  if (keys) {
+    out_docs[o] = r.descending ? x : ~x;
+    out_scores[o] = key_score(kx, r.descending != 0);
+  } else {
+    out_docs[o] = x;
+    out_scores[o] = 0.0;
+  }
+}
+
+// The merged page of every query of a batch in one launch. Elements are indexed flat over the batch (run_start: the
+// exclusive prefix sum of a_n + b_n per query, n_runs + 1 entries), so one huge query and many small ones balance.
+__global__ __launch_bounds__(256) void rank_merge_kernel(const DevMergeRun* __restrict__ runs,
+                                                         const uint64_t* __restrict__ run_start, uint32_t n_runs,
+                                                         const uint32_t* __restrict__ docs,
+                                                         const uint64_t* __restrict__ keys,
+                                                         const uint32_t* __restrict__ dprime,
+                                                         uint32_t* __restrict__ out_docs,
+                                                         double* __restrict__ out_scores) {
+  const uint64_t e = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (e >= run_start[n_runs]) return;
+  uint32_t lo = 0, hi = n_runs;  // the run q with run_start[q] <= e < run_start[q + 1]
+  while (hi - lo > 1) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (run_start[mid] <= e) lo = mid;
+    else hi = mid;
+  }
+  const DevMergeRun r = runs[lo];
+  const uint32_t j = static_cast<uint32_t>(e - run_start[lo]);
+  const bool from_a = j < r.a_n;
+  const uint32_t k = from_a ? j : j - r.a_n;
+  if (r.kind == kMergeScore) rank_merge_elem<MergeScoreKey>(r, k, from_a, keys, dprime, out_docs, out_scores);
+  else if (r.kind == kMergeDocDesc) rank_merge_elem<MergeDocDesc>(r, k, from_a, nullptr, docs, out_docs, out_scores);
+  else rank_merge_elem<MergeDocAsc>(r, k, from_a, nullptr, docs, out_docs, out_scores);
+}
+
+int LaunchScoreCandidatesMixed(const DevIndex& ix, const uint32_t* cand, uint64_t n_cand, const uint32_t* terms,
+                               const double* idfs, uint32_t n_terms, const uint8_t* patterns,
+                               const DevTextTerm* text_terms, double k1, double b, double avgdl, double* scores,
+                               hipStream_t s) {
+  if (n_cand == 0) return 0;
+  const double avg = avgdl > 1.0 ? avgdl : 1.0;
+  hipLaunchKernelGGL(score_candidates_mixed_kernel, dim3(static_cast<uint32_t>((n_cand + 255) / 256)), dim3(256), 0, s,
+                     ix, cand, n_cand, terms, idfs, n_terms, patterns, text_terms, k1, b, 1.0 - b, k1 + 1.0, avg,
+                     scores);
+  MGX_KCHECK();
+  return 0;
+}
+
+int LaunchRemapDocs(uint32_t* docs, uint64_t n, const uint32_t* map, uint32_t first_doc_id, uint32_t n_docs,
+                    hipStream_t s) {
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(remap_docs_kernel, dim3(static_cast<uint32_t>((n + 255) / 256)), dim3(256), 0, s, docs, n, map,
+                     first_doc_id, n_docs);
+  MGX_KCHECK();
+  return 0;
+}
+
+int LaunchRankMerge(const DevMergeRun* runs, const uint64_t* run_start, uint32_t n_runs, uint64_t n_elems,
+                    const uint32_t* docs, const uint64_t* keys, const uint32_t* dprime, uint32_t* out_docs,
+                    double* out_scores, hipStream_t s) {
+  if (n_runs == 0 || n_elems == 0) return 0;
+  hipLaunchKernelGGL(rank_merge_kernel, dim3(static_cast<uint32_t>((n_elems + 255) / 256)), dim3(256), 0, s, runs,
+                     run_start, n_runs, docs, keys, dprime, out_docs, out_scores);
+  MGX_KCHECK();
+  return 0;
+}
+
 }  // namespace mgx

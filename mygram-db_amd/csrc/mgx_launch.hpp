@@ -82,6 +82,16 @@ int LaunchSortPage(const uint64_t* keys, const uint32_t* dprime, uint32_t lo, ui
                    uint32_t* out_docs, double* out_scores, hipStream_t s);
 int LaunchMakeSortKeys(const uint32_t* docs, const double* scores, uint64_t n, int descending, uint64_t* keys,
                        uint32_t* dprime, hipStream_t s);
+// merged bitmap-group pages of a mutable table (mgx_batch_merge_local)
+int LaunchScoreCandidatesMixed(const DevIndex& ix, const uint32_t* cand, uint64_t n_cand, const uint32_t* terms,
+                               const double* idfs, uint32_t n_terms, const uint8_t* patterns,
+                               const DevTextTerm* text_terms, double k1, double b, double avgdl, double* scores,
+                               hipStream_t s);
+int LaunchRemapDocs(uint32_t* docs, uint64_t n, const uint32_t* map, uint32_t first_doc_id, uint32_t n_docs,
+                    hipStream_t s);
+int LaunchRankMerge(const DevMergeRun* runs, const uint64_t* run_start, uint32_t n_runs, uint64_t n_elems,
+                    const uint32_t* docs, const uint64_t* keys, const uint32_t* dprime, uint32_t* out_docs,
+                    double* out_scores, hipStream_t s);
 int LaunchSortByScore(const uint32_t* docs, const double* scores, uint64_t n, int descending, uint32_t lo,
                       uint32_t hi, uint64_t* keys_tmp, uint32_t* dprime_tmp, uint32_t* out, hipStream_t s);
 

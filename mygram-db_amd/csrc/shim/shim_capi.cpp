@@ -4,6 +4,7 @@
 #include <chrono>
 #include <cstring>
 #include <memory>
+#include <mutex>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -23,7 +24,10 @@ struct mgxs_executor {
   std::unique_ptr<BatchExecutor> ex;
   std::vector<BatchQuery> queries;  // re-used between submits
   std::vector<mygramdb::search_pipeline::BatchResult> results;  // re-used between waits
-  std::unordered_map<uint64_t, uint32_t> limits;  // ticket -> row pitch of mgxs_wait's docs / scores
+  // ticket -> row pitch of mgxs_wait's docs / scores. mgxs_submit and mgxs_wait may run on different threads at the same
+  // time (one submitting thread, one waiting thread, as bench.py drives the executor), so the map has a lock of its own.
+  std::mutex limits_mu;
+  std::unordered_map<uint64_t, uint32_t> limits;
 };
 
 struct mgxs_batcher {
@@ -196,7 +200,10 @@ int mgxs_submit(mgxs_executor* ex, uint32_t n_queries, const uint32_t* n_terms, 
     auto r = ex->ex->Submit(std::move(ex->queries));  // (hands an earlier batch's objects back: built into again above)
     if (!r) return Fail(static_cast<int>(r.error().code()), r.error().message());
     *ticket = *r;
-    ex->limits[*r] = limit;
+    {
+      std::lock_guard<std::mutex> lock(ex->limits_mu);
+      ex->limits[*r] = limit;
+    }
     return MGX_OK;
   } catch (const std::exception& e) {
     return Fail(MGX_ERR_INTERNAL, e.what());
@@ -208,9 +215,15 @@ int mgxs_wait(mgxs_executor* ex, uint64_t ticket, uint64_t* totals, uint32_t* n_
   if (!ex || !totals || !n_docs || !docs) return Fail(MGX_ERR_INVALID_ARGUMENT, "mgxs_wait: null argument");
   try {
     BatchExecutor::Timing tm;
-    const auto lim = ex->limits.find(ticket);
-    const uint32_t limit = lim != ex->limits.end() ? lim->second : 0;
-    if (lim != ex->limits.end()) ex->limits.erase(lim);
+    uint32_t limit = 0;
+    {
+      std::lock_guard<std::mutex> lock(ex->limits_mu);
+      const auto lim = ex->limits.find(ticket);
+      if (lim != ex->limits.end()) {
+        limit = lim->second;
+        ex->limits.erase(lim);
+      }
+    }
     const auto err = ex->ex->WaitInto(ticket, &ex->results, &tm);
     if (err.code() != mygram::utils::ErrorCode::kSuccess) return Fail(static_cast<int>(err.code()), err.message());
     const auto& res = ex->results;

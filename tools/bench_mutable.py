@@ -3,9 +3,12 @@
 1024-query batches of 3-term AND + BM25 top-10 through search_pipeline::BatchExecutor — measured on the static table and
 again after documents were updated, removed and added (live row on the main index + delta index, merged on the device).
 Also timed: the mutation calls themselves and the first batch after them (ApplyMutations: live row, delta build,
-statistics). One JSON line per delta size. Not used by the driver.
+statistics). One JSON line per delta size. Not used by the driver. --limit / --offset / --sort time other page shapes:
+deep SORT _score pages (offset+limit > 1024) and docid pages past 16384 rows or with limit 0 are merged at fetch time
+(rank_merge_kernel); a smaller --batch keeps their host buffers small.
 
     python tools/bench_mutable.py [--docs 10000000] [--steps 100] [--deltas 1000,10000,100000]
+    python tools/bench_mutable.py --batch 64 --deltas 10000 --sort score --offset 10000 --limit 100
 """
 import argparse
 import json
@@ -22,6 +25,7 @@ import bench  # noqa: E402
 
 
 HOST_MS = np.zeros(4)  # plan, compile, enqueue, wait of the last run(), mean per batch
+PAGE = {"limit": 10, "offset": 0, "sort_by_score": True}  # the page every submitted batch asks for (--limit/--offset/--sort)
 
 
 def run(ex, qbs, steps, depth, outs):
@@ -32,7 +36,7 @@ def run(ex, qbs, steps, depth, outs):
     for j in range(steps):
         if len(pending) == depth:
             acc += ex.wait(pending.pop(0), outs[j % depth])[4][:4]
-        pending.append(ex.submit(qbs[j % len(qbs)], limit=10))
+        pending.append(ex.submit(qbs[j % len(qbs)], **PAGE))
     for k, t in enumerate(pending):
         acc += ex.wait(t, outs[k % depth])[4][:4]
     HOST_MS[:] = acc / steps
@@ -47,7 +51,12 @@ def main():
     ap.add_argument("--deltas", default="1000,10000,100000")
     ap.add_argument("--depth", type=int, default=2)
     ap.add_argument("--write-rate", type=float, default=0.0, help="steady writer: changes per second (0: skip)")
+    ap.add_argument("--limit", type=int, default=10, help="page size (0: every match)")
+    ap.add_argument("--offset", type=int, default=0, help="page offset (SORT _score)")
+    ap.add_argument("--sort", choices=("score", "docid"), default="score")
     args = ap.parse_args()
+    PAGE.update(limit=args.limit, offset=args.offset, sort_by_score=args.sort == "score")
+    page = {"limit": args.limit, "offset": args.offset, "sort": args.sort}
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("needs an MI355X")
@@ -68,13 +77,14 @@ def main():
     depth = args.depth
     ex = S.Executor(shim_table, depth=depth, planner_threads=6)
     qbs = [S.QueryBatch(tb) for tb in term_batches]
-    ex.warm(qbs[-1], limit=10, rounds=3)
-    outs = [(np.zeros(args.batch, np.uint64), np.zeros(args.batch, np.uint32), np.zeros((args.batch, 10), np.uint32),
-             np.zeros((args.batch, 10), np.float64), np.zeros(5, np.float64)) for _ in range(depth)]
+    ex.warm(qbs[-1], rounds=3, **PAGE)
+    width = max(args.limit, 1)
+    outs = [(np.zeros(args.batch, np.uint64), np.zeros(args.batch, np.uint32), np.zeros((args.batch, width), np.uint32),
+             np.zeros((args.batch, width), np.float64), np.zeros(5, np.float64)) for _ in range(depth)]
     run(ex, qbs, 20, depth, outs)
     dt = run(ex, qbs, args.steps, depth, outs)
     static_qps = args.batch * args.steps / dt
-    print(json.dumps({"table": "static", "docs": args.docs, "queries_per_s": static_qps, "ms_per_step": 1e3 * dt / args.steps,
+    print(json.dumps({"table": "static", "docs": args.docs, "page": page, "queries_per_s": static_qps, "ms_per_step": 1e3 * dt / args.steps,
                       "host_ms_plan_compile_enqueue_wait": HOST_MS.round(3).tolist()}), flush=True)
     rng = np.random.default_rng(7)
     texts = {}
@@ -104,12 +114,12 @@ def main():
         calls_s = time.perf_counter() - t0
         done = target
         t0 = time.perf_counter()
-        ex.wait(ex.submit(qbs[0], limit=10), outs[0])  # the first batch applies the changes
+        ex.wait(ex.submit(qbs[0], **PAGE), outs[0])  # the first batch applies the changes
         apply_s = time.perf_counter() - t0
         run(ex, qbs, 10, depth, outs)
         dt = run(ex, qbs, args.steps, depth, outs)
         st = shim_table.mutation_stats()
-        print(json.dumps({"table": "mutable", "changed_documents": target, "delta_documents": st["delta_documents"],
+        print(json.dumps({"table": "mutable", "page": page, "changed_documents": target, "delta_documents": st["delta_documents"],
                           "removed_from_main": st["removed_from_main"], "mutation_calls_s": calls_s,
                           "calls_per_s": n_new / calls_s, "first_batch_after_changes_s": apply_s,
                           "queries_per_s": args.batch * args.steps / dt, "ms_per_step": 1e3 * dt / args.steps,
