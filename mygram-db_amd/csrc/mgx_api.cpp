@@ -1724,45 +1724,46 @@ struct mgx_batch {
   mgx::BatchResources* res = nullptr;              // = res_owned.get(), or the index's single-operator resources
   uint32_t n_queries = 0;
   std::vector<mgx::QuerySpec> specs;
+  // One launch of a group: the group's descriptor with the items of one route (mgx::Route), in launch order
+  struct RouteLaunch {
+    mgx::DevBatch dev{};
+    DevBuf d_items;
+  };
   // per mode: the queries of that mode, in batch order
   struct Group {
     std::vector<uint32_t> qids;  // batch index of each member
-    mgx::DevBatch dev{};
+    mgx::DevBatch dev{};         // queries, tables and outputs, without items: every RouteLaunch adds its own
     mgx::LdsPlan plan{};
     mgx::WavePlan wplan{};
-    // score mode: queries the wave kernel can run (flat program, dense scored operands) and the rest are launched
-    // separately, over disjoint item lists, into the same candidate arrays
-    mgx::DevBatch dev_wave{};
-    DevBuf d_items_wave, d_tables;
-    uint32_t n_items_wave = 0;
+    // The routes' launches run over disjoint item lists into the same outputs.
+    RouteLaunch block;           // general kernel
+    uint32_t n_items_plain = 0;  // block items [0, n_items_plain): queries of bitmap-form operands only (LaunchTileEval)
+    uint32_t n_items_fz = 0;     // the last n_items_fz block items: queries with kOpVerifyFuzzy (a launch of their own)
+    // wave kernel: flat programs (score mode: dense or sparse scored operands, contribution tables in d_tables)
+    RouteLaunch wave;
+    DevBuf d_tables;
     // score mode: wave-kernel queries with a sorted-list operand (bigger LDS plan, launched beside the others)
     mgx::WavePlan wplan_lists{};
-    mgx::DevBatch dev_wave_lists{};
-    DevBuf d_items_wave_lists;
-    // score mode, fast path (bitmap_score_kernel<T>): resolved query descriptors and one item list per number of scored terms
+    RouteLaunch wave_lists;
+    // score mode, fast path (bitmap_score_kernel<T>): resolved query descriptors and one launch per number of scored terms
     mgx::FastPlan fplan{};
-    mgx::DevBatch dev_fast[mgx::kFastMaxScore]{};
-    uint32_t n_seed_fast[mgx::kFastMaxScore] = {0, 0, 0, 0, 0};  // seed items at the front of d_items_fast[t]
-    uint32_t seed_k = 0;       // keys per query in the seed-bound exchange (0: none; rank-independent, see UploadGroup)
+    RouteLaunch fast[mgx::kFastMaxScore];
+    uint32_t n_seed_fast[mgx::kFastMaxScore] = {0, 0, 0, 0, 0};  // seed items at the front of fast[t]
+    uint32_t seed_k = 0;       // keys per query in the seed-bound exchange (0: none; rank-independent, see ScheduleItems)
     uint64_t seed_table_docs = 0;  // table-wide doc count of those queries (BM25 N): the exchange pays on large shards only
     DevBuf d_has_seed;         // [n] u8: the query's first candidate list is a seed item's
-    DevBuf d_fast_queries, d_items_fast[mgx::kFastMaxScore];
+    DevBuf d_fast_queries;
     // selective flat queries (a sparse posting list drives: cand_kernel), score and docid-page groups
-    mgx::DevBatch dev_cand{};
-    DevBuf d_items_cand, d_cand_skip;  // d_cand_skip [n] u8: the query is candidate-driven (docid-page group)
+    RouteLaunch cand;
+    DevBuf d_cand_skip;  // [n] u8: the query is candidate-driven (docid-page group)
     uint32_t cand_leaves = 0, cand_instr = 0, cand_cap = 0;
     // SORT _score over long sorted posting arrays (merge_score_kernel: the driver's tile segments against staged bitmaps)
-    mgx::DevBatch dev_merge{};
-    DevBuf d_items_merge;
+    RouteLaunch merge;
     uint32_t merge_leaves = 0, merge_instr = 0, merge_ops = 0, merge_cap = 0;
     // docid-page group: the page pass runs one workgroup per query; flat programs on the wave kernel
-    mgx::DevBatch dev_page_wave{}, dev_page_block{};
-    DevBuf d_pq_wave, d_pq_block;
-    DevBuf d_queries, d_leaves, d_prog, d_score, d_explicit, d_counters, d_ident, d_items, d_list_begin;
-    uint32_t n_items = 0;
-    uint32_t n_items_plain = 0;  // block-kernel items [0, n_items_plain): queries of bitmap-form operands only (LaunchTileEval)
-    uint32_t n_items_fz = 0;     // the last n_items_fz block-kernel items: queries with kOpVerifyFuzzy (a launch of their own)
-    uint32_t n_page_fz = 0;      // the same at the end of dev_page_block
+    RouteLaunch page_wave, page_block;
+    uint32_t n_page_fz = 0;  // the same as n_items_fz at the end of page_block
+    DevBuf d_queries, d_leaves, d_prog, d_score, d_explicit, d_counters, d_ident, d_list_begin;
     std::vector<unsigned long long> h_counters;
   };
   Group score, bitmap;
@@ -1832,9 +1833,10 @@ struct mgx_batch {
 namespace mgx {
 
 // MGX_TRACE_HOST: where a batch's host time goes (microseconds per section, printed by mgx_batch_reset every 64 batches)
-static std::atomic<uint64_t> g_section_us[8];
-static const char* const kSectionNames[8] = {"queries+leaves", "fast-path resolution", "table uploads", "wave tables",
-                                              "items", "launch order", "item uploads", "rest of PrepareInto"};
+constexpr int kSections = 7;
+static std::atomic<uint64_t> g_section_us[kSections];
+static const char* const kSectionNames[kSections] = {"queries+leaves", "routes", "table uploads", "result blocks",
+                                                      "items", "launch order", "descriptors+items"};
 struct SectionTimer {
   static bool On() {
     static const bool on = std::getenv("MGX_TRACE_HOST") != nullptr;
@@ -1850,26 +1852,65 @@ struct SectionTimer {
   }
 };
 
-static int UploadGroup(mgx_batch* b, mgx_batch::Group& g, uint32_t mode, const std::vector<QuerySpec>& specs) {
-  const bool score_mode = mode == kModeScore, df_mode = mode == kModeTextDf, page_mode = mode == kModeDocPage;
-  const uint32_t n = static_cast<uint32_t>(g.qids.size());
-  if (n == 0) return MGX_OK;
-  SectionTimer sec;
-  std::vector<DevQuery> dq(n);
+using Group = mgx_batch::Group;
+using RouteLaunch = mgx_batch::RouteLaunch;
+
+// The kernel path of one query of a group (each route has its own item list and launch)
+enum class Route : uint8_t {
+  kBlock,      // tile_eval_kernel, the general workgroup kernel
+  kWave,       // wave_score_kernel (score), wave_count_kernel + wave_page_kernel (docid page, df)
+  kWaveLists,  // wave_score_lists_kernel: score-mode wave queries with a sorted-list operand
+  kFast,       // bitmap_score_kernel<T>, T = the number of scored terms
+  kCand,       // cand_kernel: a sparse posting list drives, the rest is probed per candidate
+  kMerge,      // merge_score_kernel: a long driver's tile segments against staged bitmaps
+};
+
+static bool EnvZero(const char* name) { return std::getenv(name) && atoi(std::getenv(name)) == 0; }
+// Which kernel paths a group may take, read on every UploadGroup call (tests flip them inside one process).
+// MGX_FORCE_BLOCK_KERNEL puts every query on the general kernel.
+struct PathSwitches {
+  const bool wave = std::getenv("MGX_FORCE_BLOCK_KERNEL") == nullptr;
+  const bool fast = wave && !EnvZero("MGX_FAST_PATH"), cand = wave && !EnvZero("MGX_CAND");
+  const bool merge = wave && !EnvZero("MGX_MERGE");
+};
+
+// A group's host-side plan, filled by UploadGroup's steps in order.
+struct GroupPlan {
+  GroupPlan(uint32_t n_, uint32_t mode)
+      : n(n_), score_mode(mode == kModeScore), df_mode(mode == kModeTextDf), page_mode(mode == kModeDocPage) {}
+  const uint32_t n;
+  const bool score_mode, df_mode, page_mode;
+  std::vector<DevQuery> dq;  // (a) the DevQuery rows and the pools they index
   std::vector<DevLeaf> leaves;
   std::vector<uint32_t> prog;
   std::vector<DevScoreTerm> score;
   std::vector<uint32_t> expl;
+  uint32_t max_limit = 1, max_needed = 1;  // the largest page, and offset + limit, of the group's queries
+  std::vector<Route> route;  // (b) each query's route, and what it resolved ([n] or empty)
+  std::vector<DevFastQuery> fastq;
+  std::vector<uint64_t> wave_tables;  // [n][kWaveScoreSlots] the scored terms' contribution tables (score-mode wave)
+  std::vector<uint32_t> cand_driver;
+  std::vector<DevItem> items;  // (d) grouped by query, (e) in launch order; query i's lists [list_begin[i], list_begin[i + 1])
+  std::vector<uint32_t> list_begin, item_begin;
+  std::vector<DevItem> block, wave, wave_lists, fast[kFastMaxScore], cand, merge;  // (e) each route's, in launch order
+  std::vector<uint8_t> has_seed;
+};
+
+// (a) DevQuery rows, the leaf / program / score / explicit-id pools they index, and the general kernel's LDS plan.
+static int LayOutQueries(mgx_batch* b, Group& g, const std::vector<QuerySpec>& specs, GroupPlan& p) {
+  std::vector<DevLeaf>& leaves = p.leaves;
+  std::vector<uint32_t>& expl = p.expl;
+  p.dq.resize(p.n);
   uint32_t max_leaves = 0, max_lds_leaves = 0, max_score = 0, max_stack = 0, max_instr = 0, max_cap = 64;
-  for (uint32_t i = 0; i < n; ++i) {
+  for (uint32_t i = 0; i < p.n; ++i) {
     const QuerySpec& s = specs[g.qids[i]];
-    DevQuery& q = dq[i];
+    DevQuery& q = p.dq[i];
     std::memset(&q, 0, sizeof(q));
     q.leaf_begin = static_cast<uint32_t>(leaves.size());
     q.n_leaves = static_cast<uint32_t>(s.leaves.size());
-    q.prog_begin = static_cast<uint32_t>(prog.size());
+    q.prog_begin = static_cast<uint32_t>(p.prog.size());
     q.n_instr = static_cast<uint32_t>(s.prog.size());
-    q.score_begin = static_cast<uint32_t>(score.size());
+    q.score_begin = static_cast<uint32_t>(p.score.size());
     q.n_score = static_cast<uint32_t>(s.score.size());
     q.mode = s.mode;
     q.limit = s.limit;
@@ -1910,8 +1951,8 @@ static int UploadGroup(mgx_batch* b, mgx_batch::Group& g, uint32_t mode, const s
       return Fail(MGX_ERR_NOT_IMPLEMENTED,
                   "query " + std::to_string(g.qids[i]) + ": more than 64 sorted-list / scored operands in one query");
     max_lds_leaves = std::max(max_lds_leaves, n_lds);
-    prog.insert(prog.end(), s.prog.begin(), s.prog.end());
-    score.insert(score.end(), s.score.begin(), s.score.end());
+    p.prog.insert(p.prog.end(), s.prog.begin(), s.prog.end());
+    p.score.insert(p.score.end(), s.score.begin(), s.score.end());
     expl.insert(expl.end(), s.explicit_ids.begin(), s.explicit_ids.end());
     while (expl.size() % 4) expl.push_back(0xFFFFFFFFu);
     max_leaves = std::max(max_leaves, q.n_leaves);
@@ -1919,125 +1960,208 @@ static int UploadGroup(mgx_batch* b, mgx_batch::Group& g, uint32_t mode, const s
     max_stack = std::max(max_stack, q.stack_depth);
     max_instr = std::max(max_instr, q.n_instr);
     max_cap = std::max(max_cap, q.cap);
-    if (!df_mode) b->list_bytes += 4 * s.list_postings;
+    p.max_limit = std::max(p.max_limit, q.limit);
+    p.max_needed = std::max(p.max_needed, q.needed);
+    if (!p.df_mode) b->list_bytes += 4 * s.list_postings;
   }
-  g.plan = PlanLds(max_leaves, max_lds_leaves, max_score, max_stack, max_instr, max_cap, score_mode || df_mode);
-  sec.Mark(0);
-  std::vector<uint8_t> on_wave(n, 0);  // 0 general kernel, 1 wave kernel, 2 wave kernel with list operands, 3 fast path
-  std::vector<DevFastQuery> fastq;
-  std::vector<uint64_t> wave_tables;
-  if (score_mode) {
-    // ---- fast path (bitmap_score_kernel): flat programs over bitmap-form operands, 1..5 scored terms that are dense
+  g.plan = PlanLds(max_leaves, max_lds_leaves, max_score, max_stack, max_instr, max_cap, p.score_mode || p.df_mode);
+  return MGX_OK;
+}
+
+// Fast path: the query's resolved bitmap_score_kernel descriptor; false when the query does not fit the path.
+static bool ResolveFast(mgx_index* idx, const QuerySpec& s, const DevQuery& q, DevFastQuery* out) {
+  DevFastQuery& f = *out;
+  for (uint32_t ins : s.prog) {
+    const uint32_t op = ins >> 24, arg = ins & 0xFFFFFFu;
+    if (op == kOpCount) {
+      if (f.n_ops == 0) return false;
+      f.ops[f.n_ops - 1].code |= arg << 8;
+      continue;
+    }
+    const DevLeaf& lf = s.leaves[arg];
+    if (f.n_ops == static_cast<uint32_t>(kFastMaxOps) || (op == kOpLoad) != (f.n_ops == 0)) return false;
+    FastOp o{};
+    uint64_t stride = 0;
+    if (lf.kind == kLeafGramBitmap) {
+      o.base = reinterpret_cast<uint64_t>(idx->dev.gram_bitmaps + static_cast<uint64_t>(lf.b) * idx->dev.gb_row_stride);
+      stride = idx->dev.gb_tile_stride * 8;
+    } else if (lf.kind == kLeafFilterBitmap) {  // rows are appended at run time and may move: relative to the base
+      o.base = static_cast<uint64_t>(lf.b) * idx->dev.fb_row_stride * 8;
+      stride = idx->dev.fb_tile_stride * 8;
+      o.code |= 16u;
+    } else {
+      return false;
+    }
+    if (stride > 0xFFFFFFFFull) return false;
+    o.tile_stride = static_cast<uint32_t>(stride);
+    o.code |= (op == kOpLoad || op == kOpOr) ? kFastOr : op == kOpAnd ? kFastAnd : kFastAndNot;
+    f.ops[f.n_ops++] = o;
+  }
+  if (f.n_ops == 0) return false;
+  for (size_t t = 0; t < s.score.size(); ++t) {
+    const DevLeaf& lf = s.leaves[s.score[t].leaf];
+    if (lf.kind != kLeafGramBitmap) return false;
+    FastScore& fs = f.score[t];
+    fs.nib = reinterpret_cast<uint64_t>(idx->dev.tfnib + static_cast<uint64_t>(lf.b) * idx->dev.nib_row_stride);
+    fs.idf = s.score[t].idf;
+    fs.gram = lf.a;
+    fs.skip_row = lf.row;
+  }
+  if (s.reverse != 0) {  // SORT _score DESC: top-k pruning by block-max bounds
+    double step = 0.0;
+    f.blockmax = GetBlockMax(idx, s.k1, s.b, s.avgdl, &step, &f.blockmax_fine);
+    if (f.blockmax) {
+      f.bm_tile_stride = idx->n_bitmap_rows * 256u;
+      f.bmf_tile_stride = idx->n_fine_rows * 1024u;
+      // integer form of the bound: unit = step * (largest idf / 255); W_i = ceil(idf_i / (largest idf / 255))
+      double idf_max = 0.0;
+      for (size_t t = 0; t < s.score.size(); ++t) idf_max = std::max(idf_max, s.score[t].idf);
+      const double wunit = idf_max > 0.0 ? idf_max * (1.0 + 0x1p-40) / 255.0 : 1.0;
+      f.bm_inv_unit = 1.0 / (wunit * step);
+      f.bm_wpack = f.bm_w4 = f.bm_cint = 0;
+      for (size_t t = 0; t < s.score.size(); ++t) {
+        const uint32_t w = static_cast<uint32_t>(std::min(255.0, std::ceil(s.score[t].idf / wunit)));
+        if (t < 4) f.bm_wpack |= w << (8 * t); else f.bm_w4 = w;
+      }
+      for (size_t t = 0; t < s.score.size(); ++t) {
+        const DevLeaf& lf = s.leaves[s.score[t].leaf];
+        FastScore& fs = f.score[t];
+        const uint32_t frow = f.blockmax_fine ? idx->h_fine_map[lf.b] : kNoRow;
+        fs.bm_mode = frow != kNoRow ? 2u : 1u;
+        fs.bm_off = frow != kNoRow ? frow * 1024u : lf.b * 256u;
+      }
+    }
+  }
+  f.n_score = static_cast<uint32_t>(s.score.size());
+  f.needed = q.needed;
+  f.cap = q.cap;
+  f.descending = q.descending;
+  f.k1 = q.k1;
+  f.b = q.b;
+  f.one_minus_b = q.one_minus_b;
+  f.k1_plus_1 = q.k1_plus_1;
+  f.avgdl_clamped = q.avgdl_clamped;
+  return true;
+}
+
+// (b) score and docid-page groups, selective queries: candidate-driven (cand_kernel). The smallest positive operand
+// drives when it is a sorted posting array (a gram too sparse for a bitmap row) that the program loads before its first
+// COUNT — terms arrive smallest-first (search_pipeline.cpp:2012-2014), so that is a gram of the first term and every
+// funnel counter is a count of candidates. Everything else of the query is probed per candidate.
+static void RouteCandMerge(mgx_batch* b, Group& g, const std::vector<QuerySpec>& specs, const PathSwitches& sw,
+                           GroupPlan& p) {
+  static const uint64_t kMaxPerTile = std::getenv("MGX_CAND_MAX_PER_TILE") ? static_cast<uint64_t>(atoll(std::getenv("MGX_CAND_MAX_PER_TILE"))) : 64ull;
+  const mgx_index* idx = b->idx;
+  for (uint32_t i = 0; sw.cand && i < p.n; ++i) {
+    const QuerySpec& s = specs[g.qids[i]];
+    if (p.route[i] == Route::kFast || !s.flat || s.prog.empty()) continue;
+    if (p.score_mode && (!s.fast_score_ok || s.score.empty())) continue;
+    bool ok = true, counted = false;
+    uint32_t driver = kNoLeaf;
+    uint64_t best = ~0ull, longest_list = 0;
+    for (size_t pc = 0; ok && pc < s.prog.size(); ++pc) {
+      const uint32_t op = s.prog[pc] >> 24, arg = s.prog[pc] & 0xFFFFFFu;
+      if (op == kOpCount) {
+        counted = true;
+        continue;
+      }
+      if ((op == kOpLoad) != (pc == 0) || (op != kOpLoad && op != kOpAnd && op != kOpAndNot)) { ok = false; break; }
+      const DevLeaf& lf = s.leaves[arg];
+      if (lf.kind != kLeafList && lf.kind != kLeafGramBitmap && lf.kind != kLeafFilterBitmap) { ok = false; break; }
+      if (lf.kind == kLeafList) longest_list = std::max<uint64_t>(longest_list, idx->h_offsets[lf.a + 1] - idx->h_offsets[lf.a]);
+      // any positive gram loaded before the first COUNT makes every counter a count of candidates; the smallest of them
+      // drives (with terms in the reference's order that is the smallest gram of the whole query)
+      if (op == kOpAndNot || lf.kind == kLeafFilterBitmap || counted) continue;
+      const uint64_t sz = idx->h_offsets[lf.a + 1] - idx->h_offsets[lf.a];
+      if (sz < best) {
+        best = sz;
+        driver = arg;
+      }
+    }
+    if (!ok || driver == kNoLeaf || s.leaves[driver].kind != kLeafList) continue;
+    for (uint32_t ins : s.prog)  // NOT of the driver's own gram: the tile program handles it (the result is empty)
+      if ((ins >> 24) == kOpAndNot && (ins & 0xFFFFFFu) == driver) ok = false;
+    if (p.score_mode)
+      for (const DevScoreTerm& st : s.score)
+        ok = ok && st.leaf != kNoLeaf && (s.leaves[st.leaf].kind == kLeafList || s.leaves[st.leaf].kind == kLeafGramBitmap);
+    if (!ok) continue;
+    DevQuery& q = p.dq[i];
+    // probing a LONG sorted list costs a binary search of its tile segment per candidate (14 dependent loads on a segment
+    // of 16384): such operands are staged per tile instead (the merge kernel), whatever the driver's size
+    const bool long_probe = longest_list > 8 * kMaxPerTile * idx->dev.n_tiles;
+    if (best > kMaxPerTile * idx->dev.n_tiles || long_probe) {
+      // a LONG driver: too many candidates to probe one by one — the tile-synchronous merge (SORT _score only; docid
+      // pages of such queries stay on the counting kernels, which have no per-match work)
+      uint32_t staged = 0;
+      for (size_t li = 0; li < s.leaves.size(); ++li) staged += li != driver ? 1u : 0u;
+      if (!p.score_mode || !sw.merge || staged > kMergeMaxOps || q.cap > 256) continue;
+      q.pat_off = driver;  // (unused by score-mode queries otherwise: where the kernel finds its driver)
+      p.route[i] = Route::kMerge;
+      g.merge_leaves = std::max(g.merge_leaves, q.n_leaves);
+      g.merge_instr = std::max(g.merge_instr, q.n_instr);
+      g.merge_ops = std::max(g.merge_ops, staged);
+      g.merge_cap = std::max(g.merge_cap, q.cap);
+      continue;
+    }
+    if (p.cand_driver.empty()) p.cand_driver.assign(p.n, kNoLeaf);
+    p.cand_driver[i] = driver;
+    p.route[i] = Route::kCand;
+    g.cand_leaves = std::max(g.cand_leaves, q.n_leaves);
+    g.cand_instr = std::max(g.cand_instr, q.n_instr);
+    g.cand_cap = std::max(g.cand_cap, q.cap);
+  }
+  if (CandLdsBytes(g.cand_leaves, g.cand_instr, p.score_mode ? g.cand_cap : 0) > 150 * 1024) {
+    for (Route& r : p.route)
+      if (r == Route::kCand) r = Route::kBlock;  // (a page of a thousand entries with many operands: the general kernel takes these)
+    p.cand_driver.clear();
+  }
+  if (MergeLdsBytes(g.merge_leaves, g.merge_instr, g.merge_ops, g.merge_cap) > 150 * 1024)
+    for (Route& r : p.route)
+      if (r == Route::kMerge) r = Route::kBlock;
+}
+
+// (b) Every query's route: each path with its plan and its LDS-capacity fallback; then the shapes no kernel can hold.
+static int ChooseRoutes(mgx_batch* b, Group& g, const std::vector<QuerySpec>& specs, const PathSwitches& sw,
+                        GroupPlan& p) {
+  mgx_index* idx = b->idx;
+  p.route.assign(p.n, Route::kBlock);
+  if (p.score_mode) {
+    // fast path (bitmap_score_kernel): flat programs over bitmap-form operands, 1..5 scored terms that are dense
     // grams, a page of at most 128 entries, one (k1, b, avgdl) for the whole set (they are table constants)
-    const bool allow_fast = std::getenv("MGX_FORCE_BLOCK_KERNEL") == nullptr &&
-                            !(std::getenv("MGX_FAST_PATH") && atoi(std::getenv("MGX_FAST_PATH")) == 0);
-    mgx_index* idx = b->idx;
     uint32_t fcap = 64;
     bool have_params = false;
     double pk1 = 0, pb = 0, pavg = 0;
-    for (uint32_t i = 0; allow_fast && i < n; ++i) {
+    for (uint32_t i = 0; sw.fast && i < p.n; ++i) {
       const QuerySpec& s = specs[g.qids[i]];
       if (!s.flat || !s.fast_score_ok || s.score.empty() || s.score.size() > static_cast<size_t>(kFastMaxScore)) continue;
-      if (dq[i].cap > 128) continue;
+      if (p.dq[i].cap > 128) continue;
       if (have_params && (Bits(s.k1) != Bits(pk1) || Bits(s.b) != Bits(pb) || Bits(s.avgdl) != Bits(pavg))) continue;
       DevFastQuery f{};
-      bool ok = true;
-      for (uint32_t ins : s.prog) {
-        const uint32_t op = ins >> 24, arg = ins & 0xFFFFFFu;
-        if (op == kOpCount) {
-          if (f.n_ops == 0) { ok = false; break; }
-          f.ops[f.n_ops - 1].code |= arg << 8;
-          continue;
-        }
-        const DevLeaf& lf = s.leaves[arg];
-        if (f.n_ops == static_cast<uint32_t>(kFastMaxOps) || (op == kOpLoad) != (f.n_ops == 0)) { ok = false; break; }
-        FastOp o{};
-        uint64_t stride = 0;
-        if (lf.kind == kLeafGramBitmap) {
-          o.base = reinterpret_cast<uint64_t>(idx->dev.gram_bitmaps + static_cast<uint64_t>(lf.b) * idx->dev.gb_row_stride);
-          stride = idx->dev.gb_tile_stride * 8;
-        } else if (lf.kind == kLeafFilterBitmap) {  // rows are appended at run time and may move: relative to the base
-          o.base = static_cast<uint64_t>(lf.b) * idx->dev.fb_row_stride * 8;
-          stride = idx->dev.fb_tile_stride * 8;
-          o.code |= 16u;
-        } else {
-          ok = false;
-          break;
-        }
-        if (stride > 0xFFFFFFFFull) { ok = false; break; }
-        o.tile_stride = static_cast<uint32_t>(stride);
-        o.code |= (op == kOpLoad || op == kOpOr) ? kFastOr : op == kOpAnd ? kFastAnd : kFastAndNot;
-        f.ops[f.n_ops++] = o;
-      }
-      if (!ok || f.n_ops == 0) continue;
-      for (size_t t = 0; ok && t < s.score.size(); ++t) {
-        const DevLeaf& lf = s.leaves[s.score[t].leaf];
-        if (lf.kind != kLeafGramBitmap) { ok = false; break; }
-        FastScore& fs = f.score[t];
-        fs.nib = reinterpret_cast<uint64_t>(idx->dev.tfnib + static_cast<uint64_t>(lf.b) * idx->dev.nib_row_stride);
-        fs.idf = s.score[t].idf;
-        fs.gram = lf.a;
-        fs.skip_row = lf.row;
-      }
-      if (!ok) continue;
-      if (s.reverse != 0) {  // SORT _score DESC: top-k pruning by block-max bounds
-        double step = 0.0;
-        f.blockmax = GetBlockMax(idx, s.k1, s.b, s.avgdl, &step, &f.blockmax_fine);
-        if (f.blockmax) {
-          f.bm_tile_stride = idx->n_bitmap_rows * 256u;
-          f.bmf_tile_stride = idx->n_fine_rows * 1024u;
-          // integer form of the bound: unit = step * (largest idf / 255); W_i = ceil(idf_i / (largest idf / 255))
-          double idf_max = 0.0;
-          for (size_t t = 0; t < s.score.size(); ++t) idf_max = std::max(idf_max, s.score[t].idf);
-          const double wunit = idf_max > 0.0 ? idf_max * (1.0 + 0x1p-40) / 255.0 : 1.0;
-          f.bm_inv_unit = 1.0 / (wunit * step);
-          f.bm_wpack = f.bm_w4 = f.bm_cint = 0;
-          for (size_t t = 0; t < s.score.size(); ++t) {
-            const uint32_t w = static_cast<uint32_t>(std::min(255.0, std::ceil(s.score[t].idf / wunit)));
-            if (t < 4) f.bm_wpack |= w << (8 * t); else f.bm_w4 = w;
-          }
-          for (size_t t = 0; t < s.score.size(); ++t) {
-            const DevLeaf& lf = s.leaves[s.score[t].leaf];
-            FastScore& fs = f.score[t];
-            const uint32_t frow = f.blockmax_fine ? idx->h_fine_map[lf.b] : kNoRow;
-            fs.bm_mode = frow != kNoRow ? 2u : 1u;
-            fs.bm_off = frow != kNoRow ? frow * 1024u : lf.b * 256u;
-          }
-        }
-      }
+      if (!ResolveFast(idx, s, p.dq[i], &f)) continue;
       if (!have_params) {
         pk1 = s.k1;
         pb = s.b;
         pavg = s.avgdl;
         have_params = true;
       }
-      f.n_score = static_cast<uint32_t>(s.score.size());
-      f.needed = dq[i].needed;
-      f.cap = dq[i].cap;
-      f.descending = dq[i].descending;
-      f.k1 = dq[i].k1;
-      f.b = dq[i].b;
-      f.one_minus_b = dq[i].one_minus_b;
-      f.k1_plus_1 = dq[i].k1_plus_1;
-      f.avgdl_clamped = dq[i].avgdl_clamped;
-      if (fastq.empty()) fastq.resize(n);
-      fastq[i] = f;
-      on_wave[i] = 3;
+      if (p.fastq.empty()) p.fastq.resize(p.n);
+      p.fastq[i] = f;
+      p.route[i] = Route::kFast;
       fcap = std::max(fcap, f.cap);
     }
     if (have_params) {
       const double* ktab = GetLengthNormTable(idx, pk1, pb, pavg);
       g.fplan = PlanFast(fcap, ktab);
       if (ktab == nullptr || g.fplan.bytes > 64 * 1024)
-        for (auto& w : on_wave) w = 0;
+        for (Route& r : p.route) r = Route::kBlock;
     }
-    const bool allow = std::getenv("MGX_FORCE_BLOCK_KERNEL") == nullptr;
+
+    // wave kernel: the remaining queries it can run, with their scored terms' contribution tables
     uint32_t wl = 0, wsc = 0, wi = 0, wc = 64;
-    bool has_list = false;
-    for (uint32_t i = 0; i < n; ++i) {
-      if (on_wave[i] == 3) continue;
+    for (uint32_t i = 0; i < p.n; ++i) {
+      if (p.route[i] == Route::kFast) continue;
       const QuerySpec& s = specs[g.qids[i]];
-      bool ok = allow && s.wave_ok;
+      bool ok = sw.wave && s.wave_ok;
       // scored terms: dense grams (tf nibbles by doc slot) or sparse ones (exact posting lookup per match)
       for (const DevScoreTerm& st : s.score)
         ok = ok && (s.leaves[st.leaf].kind == kLeafGramBitmap || s.leaves[st.leaf].kind == kLeafList);
@@ -2054,135 +2178,60 @@ static int UploadGroup(mgx_batch* b, mgx_batch::Group& g, uint32_t mode, const s
         ok = tabs[t] != 0;
       }
       if (!ok) continue;
-      if (wave_tables.empty()) wave_tables.assign(static_cast<size_t>(n) * kWaveScoreSlots, 0);
-      for (int t = 0; t < kWaveScoreSlots; ++t) wave_tables[static_cast<size_t>(i) * kWaveScoreSlots + t] = tabs[t];
+      if (p.wave_tables.empty()) p.wave_tables.assign(static_cast<size_t>(p.n) * kWaveScoreSlots, 0);
+      for (int t = 0; t < kWaveScoreSlots; ++t) p.wave_tables[static_cast<size_t>(i) * kWaveScoreSlots + t] = tabs[t];
       bool lists = false;
       for (const DevLeaf& lf : s.leaves) lists = lists || lf.kind == kLeafList || lf.kind == kLeafExplicit;
-      on_wave[i] = lists ? 2 : 1;
-      has_list = has_list || lists;
-      wl = std::max<uint32_t>(wl, dq[i].n_leaves);
-      wsc = std::max<uint32_t>(wsc, dq[i].n_score);
-      wi = std::max<uint32_t>(wi, dq[i].n_instr);
-      wc = std::max<uint32_t>(wc, dq[i].cap);
+      p.route[i] = lists ? Route::kWaveLists : Route::kWave;
+      wl = std::max<uint32_t>(wl, p.dq[i].n_leaves);
+      wsc = std::max<uint32_t>(wsc, p.dq[i].n_score);
+      wi = std::max<uint32_t>(wi, p.dq[i].n_instr);
+      wc = std::max<uint32_t>(wc, p.dq[i].cap);
     }
-    g.wplan = PlanWave(wl, wsc, wi, wc, b->idx->dev.max_doc_len, false);
-    g.wplan_lists = PlanWave(wl, wsc, wi, wc, b->idx->dev.max_doc_len, true);
-    (void)has_list;
+    g.wplan = PlanWave(wl, wsc, wi, wc, idx->dev.max_doc_len, false);
+    g.wplan_lists = PlanWave(wl, wsc, wi, wc, idx->dev.max_doc_len, true);
     if (g.wplan_lists.bytes > 160 * 1024)
-      for (auto& w : on_wave)
-        if (w != 3) w = 0;
+      for (Route& r : p.route)
+        if (r != Route::kFast) r = Route::kBlock;
   }
-  if (page_mode || df_mode) {
+  if (p.page_mode || p.df_mode) {
     // flat programs count on the wave kernel (registers only, two tiles in flight per wave); the df pass of a
     // text-level term (always a flat AND of its grams) enumerates and scans its candidates there too
-    const bool allow = std::getenv("MGX_FORCE_BLOCK_KERNEL") == nullptr;
     uint32_t wl = 1, wi = 1;
     bool has_list = false;
-    for (uint32_t i = 0; i < n; ++i) {
+    for (uint32_t i = 0; i < p.n; ++i) {
       const QuerySpec& s = specs[g.qids[i]];
-      if (!(allow && s.wave_ok)) continue;
-      on_wave[i] = 1;
+      if (!(sw.wave && s.wave_ok)) continue;
+      p.route[i] = Route::kWave;
       for (const DevLeaf& lf : s.leaves) has_list = has_list || lf.kind == kLeafList || lf.kind == kLeafExplicit;
-      wl = std::max<uint32_t>(wl, dq[i].n_leaves);
-      wi = std::max<uint32_t>(wi, dq[i].n_instr);
+      wl = std::max<uint32_t>(wl, p.dq[i].n_leaves);
+      wi = std::max<uint32_t>(wi, p.dq[i].n_instr);
     }
     g.wplan = WavePlan{wl, 0, wi, 0, 0, has_list ? 1u : 0u, 0};
   }
-  // ---- selective queries: candidate-driven (cand_kernel). The smallest positive operand drives when it is a sorted
-  // posting array (a gram too sparse for a bitmap row) that the program loads before its first COUNT — terms arrive
-  // smallest-first (search_pipeline.cpp:2012-2014), so that is a gram of the first term and every funnel counter is a
-  // count of candidates. Everything else of the query is probed per candidate.
-  std::vector<uint32_t> cand_driver;
   g.cand_leaves = g.cand_instr = g.cand_cap = 0;
   g.merge_leaves = g.merge_instr = g.merge_ops = g.merge_cap = 0;
-  if (score_mode || page_mode) {
-    const bool allow_cand = std::getenv("MGX_FORCE_BLOCK_KERNEL") == nullptr &&
-                                   !(std::getenv("MGX_CAND") && atoi(std::getenv("MGX_CAND")) == 0);
-    static const uint64_t kMaxPerTile = std::getenv("MGX_CAND_MAX_PER_TILE") ? static_cast<uint64_t>(atoll(std::getenv("MGX_CAND_MAX_PER_TILE"))) : 64ull;
-    const mgx_index* idx = b->idx;
-    for (uint32_t i = 0; allow_cand && i < n; ++i) {
-      const QuerySpec& s = specs[g.qids[i]];
-      if (on_wave[i] == 3 || !s.flat || s.prog.empty()) continue;
-      if (score_mode && (!s.fast_score_ok || s.score.empty())) continue;
-      bool ok = true, counted = false;
-      uint32_t driver = kNoLeaf;
-      uint64_t best = ~0ull, longest_list = 0;
-      for (size_t pc = 0; ok && pc < s.prog.size(); ++pc) {
-        const uint32_t op = s.prog[pc] >> 24, arg = s.prog[pc] & 0xFFFFFFu;
-        if (op == kOpCount) {
-          counted = true;
-          continue;
-        }
-        if ((op == kOpLoad) != (pc == 0) || (op != kOpLoad && op != kOpAnd && op != kOpAndNot)) { ok = false; break; }
-        const DevLeaf& lf = s.leaves[arg];
-        if (lf.kind != kLeafList && lf.kind != kLeafGramBitmap && lf.kind != kLeafFilterBitmap) { ok = false; break; }
-        if (lf.kind == kLeafList) longest_list = std::max<uint64_t>(longest_list, idx->h_offsets[lf.a + 1] - idx->h_offsets[lf.a]);
-        // any positive gram loaded before the first COUNT makes every counter a count of candidates; the smallest of them
-        // drives (with terms in the reference's order that is the smallest gram of the whole query)
-        if (op == kOpAndNot || lf.kind == kLeafFilterBitmap || counted) continue;
-        const uint64_t sz = idx->h_offsets[lf.a + 1] - idx->h_offsets[lf.a];
-        if (sz < best) {
-          best = sz;
-          driver = arg;
-        }
-      }
-      if (!ok || driver == kNoLeaf || s.leaves[driver].kind != kLeafList) continue;
-      for (uint32_t ins : s.prog)  // NOT of the driver's own gram: the tile program handles it (the result is empty)
-        if ((ins >> 24) == kOpAndNot && (ins & 0xFFFFFFu) == driver) ok = false;
-      if (score_mode)
-        for (const DevScoreTerm& st : s.score)
-          ok = ok && st.leaf != kNoLeaf && (s.leaves[st.leaf].kind == kLeafList || s.leaves[st.leaf].kind == kLeafGramBitmap);
-      if (!ok) continue;
-      // probing a LONG sorted list costs a binary search of its tile segment per candidate (14 dependent loads on a segment
-      // of 16384): such operands are staged per tile instead (the merge kernel), whatever the driver's size
-      const bool long_probe = longest_list > 8 * kMaxPerTile * b->idx->dev.n_tiles;
-      if (best > kMaxPerTile * b->idx->dev.n_tiles || long_probe) {
-        // a LONG driver: too many candidates to probe one by one — the tile-synchronous merge (SORT _score only; docid
-        // pages of such queries stay on the counting kernels, which have no per-match work)
-        const bool allow_merge = !(std::getenv("MGX_MERGE") && atoi(std::getenv("MGX_MERGE")) == 0);
-        uint32_t staged = 0;
-        for (size_t li = 0; li < s.leaves.size(); ++li) staged += li != driver ? 1u : 0u;
-        if (!score_mode || !allow_merge || staged > kMergeMaxOps || dq[i].cap > 256) continue;
-        dq[i].pat_off = driver;  // (unused by score-mode queries otherwise: where the kernel finds its driver)
-        on_wave[i] = 5;
-        g.merge_leaves = std::max(g.merge_leaves, dq[i].n_leaves);
-        g.merge_instr = std::max(g.merge_instr, dq[i].n_instr);
-        g.merge_ops = std::max(g.merge_ops, staged);
-        g.merge_cap = std::max(g.merge_cap, dq[i].cap);
-        continue;
-      }
-      if (cand_driver.empty()) cand_driver.assign(n, kNoLeaf);
-      cand_driver[i] = driver;
-      on_wave[i] = 4;
-      g.cand_leaves = std::max(g.cand_leaves, dq[i].n_leaves);
-      g.cand_instr = std::max(g.cand_instr, dq[i].n_instr);
-      g.cand_cap = std::max(g.cand_cap, dq[i].cap);
-    }
-    if (CandLdsBytes(g.cand_leaves, g.cand_instr, score_mode ? g.cand_cap : 0) > 150 * 1024) {
-      for (auto& w : on_wave)
-        if (w == 4) w = 0;  // (a page of a thousand entries with many operands: the general kernel takes these)
-      cand_driver.clear();
-    }
-    if (MergeLdsBytes(g.merge_leaves, g.merge_instr, g.merge_ops, g.merge_cap) > 150 * 1024)
-      for (auto& w : on_wave)
-        if (w == 5) w = 0;
-  }
+  if (p.score_mode || p.page_mode) RouteCandMerge(b, g, specs, sw, p);
   if (g.plan.bytes > 160 * 1024)
     return Fail(MGX_ERR_NOT_IMPLEMENTED, "query shape exceeds the 160 KiB LDS of a CU");
-  for (uint32_t i = 0; i < n; ++i)
+  for (uint32_t i = 0; i < p.n; ++i)
     if (specs[g.qids[i]].fz_distance != 0 && g.plan.bytes + kFzLdsBytes > 160 * 1024)
       return Fail(MGX_ERR_NOT_IMPLEMENTED, "query shape with the fuzzy text filter exceeds the 160 KiB LDS of a CU");
-  sec.Mark(1);
-  MGX_HIP(Upload(g.d_queries, dq.data(), dq.size()));
-  MGX_HIP(Upload(g.d_leaves, leaves.data(), leaves.size()));
-  MGX_HIP(Upload(g.d_prog, prog.data(), prog.size()));
-  MGX_HIP(Upload(g.d_score, score.data(), score.size()));
-  MGX_HIP(Upload(g.d_explicit, expl.data(), expl.size(), 4));
+  return MGX_OK;
+}
+
+// (c) The query tables (section 2), then the result blocks of the group's mode and the identity query map.
+static int UploadTables(mgx_batch* b, Group& g, const GroupPlan& p, SectionTimer& sec) {
+  const uint32_t n = p.n;
+  MGX_HIP(Upload(g.d_queries, p.dq.data(), p.dq.size()));
+  MGX_HIP(Upload(g.d_leaves, p.leaves.data(), p.leaves.size()));
+  MGX_HIP(Upload(g.d_prog, p.prog.data(), p.prog.size()));
+  MGX_HIP(Upload(g.d_score, p.score.data(), p.score.size()));
+  MGX_HIP(Upload(g.d_explicit, p.expl.data(), p.expl.size(), 4));
   sec.Mark(2);
   // [n][8] counters followed by [n] pruning bounds: one memset clears both before every execute
-  if (score_mode) {
-    uint32_t max_limit = 1;
-    for (const DevQuery& q : dq) max_limit = std::max(max_limit, q.limit);
+  if (p.score_mode) {
+    const size_t max_limit = p.max_limit;
     b->so_override = static_cast<size_t>(n) * 9 * 8;
     b->so_scores = b->so_override + static_cast<size_t>(n) * 8;
     b->so_docs = b->so_scores + static_cast<size_t>(n) * max_limit * 8;
@@ -2190,10 +2239,9 @@ static int UploadGroup(mgx_batch* b, mgx_batch::Group& g, uint32_t mode, const s
     b->so_bytes = b->so_n + static_cast<size_t>(n) * 4;
     MGX_HIP(b->d_score_out.Alloc(b->so_bytes));
     MGX_HIP(b->res->Pinned(0, b->so_bytes, &b->h_score_out));
-  } else if (page_mode) {
-    uint32_t max_limit = 1;
-    for (const DevQuery& q : dq) max_limit = std::max(max_limit, q.limit);
-    b->doc_page_stride = max_limit;
+  } else if (p.page_mode) {
+    const size_t max_limit = p.max_limit;
+    b->doc_page_stride = p.max_limit;
     b->po_totals = static_cast<size_t>(n) * 8 * 8;
     b->po_docs = b->po_totals + static_cast<size_t>(n) * 8;
     b->po_bytes = b->po_docs + static_cast<size_t>(n) * max_limit * 4;
@@ -2209,207 +2257,199 @@ static int UploadGroup(mgx_batch* b, mgx_batch::Group& g, uint32_t mode, const s
   std::vector<uint32_t> ident(n);
   for (uint32_t i = 0; i < n; ++i) ident[i] = i;
   MGX_HIP(Upload(g.d_ident, ident.data(), n));
-  sec.Mark(3);
-  // ---- work items: cut every query into runs of tiles of about equal estimated cost ------------------------------
-  // cost of one tile ~ 1 (operand fetch, program) + matches/128 (enumeration + scoring); a workgroup gets ~48 units.
-  std::vector<DevItem> items;
-  std::vector<uint32_t> list_begin(n + 1, 0);
+  return MGX_OK;
+}
+
+// (d) Work items: every query cut into runs of tiles of about equal estimated cost, grouped by query.
+// Cost of one tile ~ 1 (operand fetch, program) + matches/128 (enumeration + scoring); a workgroup gets ~48 units.
+static void CutItems(const mgx_batch* b, const Group& g, const std::vector<QuerySpec>& specs, GroupPlan& p) {
+  static const double kMatchesPerUnit = std::getenv("MGX_ITEM_MATCHES") ? atof(std::getenv("MGX_ITEM_MATCHES")) : 256.0;
+  static const double kItemCost = std::getenv("MGX_ITEM_COST") ? atof(std::getenv("MGX_ITEM_COST")) : 192.0;
+  static const uint32_t kMaxTiles = std::getenv("MGX_MAX_ITEM_TILES") ? static_cast<uint32_t>(atoi(std::getenv("MGX_MAX_ITEM_TILES"))) : static_cast<uint32_t>(kMaxTilesPerItem);
+  static const uint64_t want_items = std::getenv("MGX_WANT_ITEMS") ? static_cast<uint64_t>(atoll(std::getenv("MGX_WANT_ITEMS"))) : 4ull * 768ull;  // ~4 rounds of the 768 workgroups a launch keeps resident
+  static const uint32_t kSeedTiles = std::getenv("MGX_SEED_TILES") ? static_cast<uint32_t>(atoi(std::getenv("MGX_SEED_TILES"))) : 16u;
+  const uint32_t n = p.n, n_tiles = b->idx->dev.n_tiles;
+  p.list_begin.assign(n + 1, 0);
+  p.item_begin.assign(n + 1, 0);  // a query's own items (none for the members of a group)
   uint32_t n_lists = 0;
-  std::vector<uint32_t> item_begin(n + 1, 0);  // a query's own items (none for the members of a group)
-  {
-    const uint32_t n_tiles = b->idx->dev.n_tiles;
-    for (uint32_t i = 0; i < n; ++i) {
-      const QuerySpec& s = specs[g.qids[i]];
-      item_begin[i] = static_cast<uint32_t>(items.size());
-      static const double kMatchesPerUnit = std::getenv("MGX_ITEM_MATCHES") ? atof(std::getenv("MGX_ITEM_MATCHES")) : 256.0;
-      static const double kItemCost = std::getenv("MGX_ITEM_COST") ? atof(std::getenv("MGX_ITEM_COST")) : 192.0;
-      // (a text scan per candidate costs about what scoring a match does)
-      static const uint32_t kMaxTiles = std::getenv("MGX_MAX_ITEM_TILES") ? static_cast<uint32_t>(atoi(std::getenv("MGX_MAX_ITEM_TILES"))) : static_cast<uint32_t>(kMaxTilesPerItem);
-      // The fast path prunes most matches once a query has a k-th best score, and a longer item keeps that bound in the
-      // workgroup: 4x the tiles per item (measured on the benchmark batch: 1.55 -> 1.49 ms; 8x loses to the tail).
-      const bool fast = on_wave[i] == 3;
-      const double per_tile = 1.0 + (score_mode || df_mode ? s.est_density * kTileDocs / (fast ? kMatchesPerUnit / 2 : kMatchesPerUnit) : 0.0);
-      // (a small shard wants shorter items than a whole table: 2x..4x the base cost as the tile count goes 77 -> 611,
-      // measured at 1.25M docs — 0.47 -> 0.39 ms — and at 10M)
-      const double fast_scale = std::min(4.0, std::max(2.0, static_cast<double>(n_tiles) / 150.0));
-      uint32_t tiles = static_cast<uint32_t>((fast ? fast_scale * kItemCost : kItemCost) / per_tile);
-      tiles = std::max<uint32_t>(8, std::min<uint32_t>(tiles, fast ? 2 * kMaxTiles : kMaxTiles)) & ~7u;  // whole rounds of the waves of a workgroup
-      // a small shard (few tiles per query) still wants a few workgroups per CU slot, or the launch is one ragged round
-      if (score_mode) {
-        static const uint64_t want_items = std::getenv("MGX_WANT_ITEMS") ? static_cast<uint64_t>(atoll(std::getenv("MGX_WANT_ITEMS"))) : 4ull * 768ull;  // ~4 rounds of the 768 workgroups a launch keeps resident
-        const uint64_t cap = std::max<uint64_t>(8, (static_cast<uint64_t>(n_tiles) * n / want_items + 7) & ~7ull);
-        tiles = static_cast<uint32_t>(std::min<uint64_t>(tiles, cap));
-      }
-      // the workgroup kernel walks its tiles one after the other (~4 us each): short items keep the few queries it
-      // serves from becoming the tail of the step
-      if (score_mode && !on_wave[i]) tiles = 8;
-      list_begin[i] = n_lists;
-      if (on_wave[i] == 4) {  // candidate-driven: one workgroup holds the whole query (tile_begin = the driver's leaf)
-        items.push_back(DevItem{i, cand_driver[i], 0, n_lists++});
-        continue;
-      }
-      uint32_t t0 = 0;
-      // Fast path: a short "seed" item first (two tiles per wave), launched ahead of everything else (below): it scores
-      // its tiles unpruned and publishes the query's first k-th best score, so the long items start pruning at once.
-      static const uint32_t kSeedTiles = std::getenv("MGX_SEED_TILES") ? static_cast<uint32_t>(atoi(std::getenv("MGX_SEED_TILES"))) : 16u;
-      const uint32_t seed_tiles = std::min<uint32_t>(kSeedTiles, (n_tiles / 8) & ~7u);  // (8 on a 77-tile shard)
-      if (fast && seed_tiles && n_tiles > 4 * seed_tiles) {
-        items.push_back(DevItem{i, 0, seed_tiles, n_lists++});
-        t0 = seed_tiles;
-      }
-      for (uint32_t t = t0; t < n_tiles; t += tiles) {
-        DevItem it{i, t, std::min(tiles, n_tiles - t), n_lists++};  // candidate lists stay grouped by query
-        items.push_back(it);
-      }
+  for (uint32_t i = 0; i < n; ++i) {
+    const QuerySpec& s = specs[g.qids[i]];
+    const Route route = p.route[i];
+    p.item_begin[i] = static_cast<uint32_t>(p.items.size());
+    // The fast path prunes most matches once a query has a k-th best score, and a longer item keeps that bound in the
+    // workgroup: 4x the tiles per item (measured on the benchmark batch: 1.55 -> 1.49 ms; 8x loses to the tail).
+    const bool fast = route == Route::kFast;
+    const double per_tile = 1.0 + (p.score_mode || p.df_mode ? s.est_density * kTileDocs / (fast ? kMatchesPerUnit / 2 : kMatchesPerUnit) : 0.0);
+    // (a text scan per candidate costs about what scoring a match does)
+    // (a small shard wants shorter items than a whole table: 2x..4x the base cost as the tile count goes 77 -> 611,
+    // measured at 1.25M docs — 0.47 -> 0.39 ms — and at 10M)
+    const double fast_scale = std::min(4.0, std::max(2.0, static_cast<double>(n_tiles) / 150.0));
+    uint32_t tiles = static_cast<uint32_t>((fast ? fast_scale * kItemCost : kItemCost) / per_tile);
+    tiles = std::max<uint32_t>(8, std::min<uint32_t>(tiles, fast ? 2 * kMaxTiles : kMaxTiles)) & ~7u;  // whole rounds of the waves of a workgroup
+    // a small shard (few tiles per query) still wants a few workgroups per CU slot, or the launch is one ragged round
+    if (p.score_mode) {
+      const uint64_t cap = std::max<uint64_t>(8, (static_cast<uint64_t>(n_tiles) * n / want_items + 7) & ~7ull);
+      tiles = static_cast<uint32_t>(std::min<uint64_t>(tiles, cap));
     }
-    list_begin[n] = n_lists;
-    item_begin[n] = static_cast<uint32_t>(items.size());
-    sec.Mark(4);
-    // Launch order: by doc band (kSortTiles tiles), so concurrent workgroups share operand tiles in L2/MALL; inside a
-    // band by the query's largest gram (its bitmap and tf column are the lines the band re-reads most), dealt so that
-    // workgroup j — which runs on XCD j % 8 under round-robin dispatch, every XCD with its own L2 — gets a contiguous
-    // eighth of that order. One bucket pass (counts, offsets, scatter): a fresh batch is scheduled per step, and two
-    // stable sorts of ~12,000 items were a third of the host's compile time.
-    static const uint32_t kSortTiles = std::getenv("MGX_SORT_TILES") ? static_cast<uint32_t>(atoi(std::getenv("MGX_SORT_TILES"))) : 16u;
-    static const bool kXcdAffinity = std::getenv("MGX_XCD_AFFINITY") ? atoi(std::getenv("MGX_XCD_AFFINITY")) != 0 : true;
-    std::vector<uint32_t> order(n);  // queries in the order they appear inside a band
-    for (uint32_t i = 0; i < n; ++i) order[i] = i;
-    if (kXcdAffinity && score_mode) {
-      std::vector<uint32_t> heavy(n, 0);
-      for (uint32_t i = 0; i < n; ++i) {
-        uint64_t best = 0;
-        for (const DevLeaf& lf : specs[g.qids[i]].leaves) {
-          if (lf.kind != kLeafGramBitmap && lf.kind != kLeafList) continue;
-          const uint64_t sz = b->idx->h_offsets[lf.a + 1] - b->idx->h_offsets[lf.a];
-          if (sz > best) {
-            best = sz;
-            heavy[i] = lf.a;
-          }
-        }
-      }
-      std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return heavy[x] < heavy[y]; });
+    // the workgroup kernel walks its tiles one after the other (~4 us each): short items keep the few queries it
+    // serves from becoming the tail of the step
+    if (p.score_mode && route == Route::kBlock) tiles = 8;
+    p.list_begin[i] = n_lists;
+    if (route == Route::kCand) {  // one workgroup holds the whole query (tile_begin = the driver's leaf)
+      p.items.push_back(DevItem{i, p.cand_driver[i], 0, n_lists++});
+      continue;
     }
-    const uint32_t n_bands = n_tiles / kSortTiles + 1;
-    // A heavy query's items (thousands of matches per tile: tens of microseconds per tile visit, where most take one or
-    // two) are pulled forward in the launch order — its last bands would otherwise start when the launch is nearly over
-    // and finish alone, the tail of the step. They stay in doc order, so the query's bound still grows from band to band.
-    static const double kHeavyDensity = std::getenv("MGX_HEAVY_DENSITY") ? atof(std::getenv("MGX_HEAVY_DENSITY")) : 0.05;
-    // (measured: 0.346 -> 0.327 ms on a 77-tile shard at 0.6; on the 611-tile table the tail is a smaller share of the
-    // step and a later start of the query's last bands — a better bound — is worth as much: neutral, left in order)
-    static const double kSqueezeEnv = std::getenv("MGX_HEAVY_SQUEEZE") ? atof(std::getenv("MGX_HEAVY_SQUEEZE")) : -1.0;
-    const double kHeavySqueeze = kSqueezeEnv >= 0.0 ? kSqueezeEnv : 0.6 + 0.4 * std::min(1.0, n_tiles / 600.0);
-    auto band_of = [&](const DevItem& it) {
-      if (on_wave[it.query] == 4) return 0u;  // (a candidate-driven item covers the whole query; tile_begin holds its driver)
-      const uint32_t band = it.tile_begin / kSortTiles;
-      if (score_mode && on_wave[it.query] == 3 && specs[g.qids[it.query]].est_density >= kHeavyDensity)
-        return static_cast<uint32_t>(band * kHeavySqueeze);
-      return band;
-    };
-    std::vector<uint32_t> band_at(n_bands + 1, 0);
-    for (const DevItem& it : items) band_at[band_of(it) + 1]++;
-    for (uint32_t k = 0; k < n_bands; ++k) band_at[k + 1] += band_at[k];
-    std::vector<DevItem> sorted(items.size());
-    {
-      std::vector<uint32_t> cur(band_at.begin(), band_at.end() - 1);
-      for (uint32_t oi = 0; oi < n; ++oi) {
-        const uint32_t i = order[oi];
-        for (uint32_t k = item_begin[i]; k < item_begin[i + 1]; ++k) sorted[cur[band_of(items[k])]++] = items[k];
-      }
+    uint32_t t0 = 0;
+    // Fast path: a short "seed" item first (two tiles per wave), launched ahead of everything else (ScheduleItems): it
+    // scores its tiles unpruned and publishes the query's first k-th best score, so the long items start pruning at once.
+    const uint32_t seed_tiles = std::min<uint32_t>(kSeedTiles, (n_tiles / 8) & ~7u);  // (8 on a 77-tile shard)
+    if (fast && seed_tiles && n_tiles > 4 * seed_tiles) {
+      p.items.push_back(DevItem{i, 0, seed_tiles, n_lists++});
+      t0 = seed_tiles;
     }
-    if (kXcdAffinity && score_mode) {
-      for (uint32_t k = 0; k < n_bands; ++k) {
-        const size_t lo = band_at[k], m = band_at[k + 1] - lo, per = (m + 7) / 8;
-        size_t w = lo;
-        for (size_t r = 0; r < per; ++r)
-          for (size_t x = 0; x < 8; ++x)
-            if (x * per + r < m) items[w++] = sorted[lo + x * per + r];
-      }
-    } else {
-      items.swap(sorted);
+    for (uint32_t t = t0; t < n_tiles; t += tiles) {
+      DevItem it{i, t, std::min(tiles, n_tiles - t), n_lists++};  // candidate lists stay grouped by query
+      p.items.push_back(it);
     }
   }
-  const uint32_t n_lists_all = n_lists;
-  std::vector<DevItem> items_wave, items_block, items_wave_lists, items_fast[kFastMaxScore], items_cand, items_merge;
-  std::vector<uint8_t> has_seed(n, 0);
-  uint32_t seed_k = 0;
+  p.list_begin[n] = n_lists;
+  p.item_begin[n] = static_cast<uint32_t>(p.items.size());
+}
+
+// (e) Launch order, then the items of each route in that order with the fast path's seed items at the front of theirs,
+// then the shape of the seed-key exchange. Launch order: by doc band (kSortTiles tiles), so concurrent workgroups share
+// operand tiles in L2/MALL; inside a band by the query's largest gram (its bitmap and tf column are the lines the band
+// re-reads most), dealt so that workgroup j — which runs on XCD j % 8 under round-robin dispatch, every XCD with its own
+// L2 — gets a contiguous eighth of that order. One bucket pass (counts, offsets, scatter): a fresh batch is scheduled
+// per step, and two stable sorts of ~12,000 items were a third of the host's compile time.
+static int ScheduleItems(const mgx_batch* b, Group& g, const std::vector<QuerySpec>& specs, GroupPlan& p) {
+  static const uint32_t kSortTiles = std::getenv("MGX_SORT_TILES") ? static_cast<uint32_t>(atoi(std::getenv("MGX_SORT_TILES"))) : 16u;
+  static const bool kXcdAffinity = std::getenv("MGX_XCD_AFFINITY") ? atoi(std::getenv("MGX_XCD_AFFINITY")) != 0 : true;
+  static const double kHeavyDensity = std::getenv("MGX_HEAVY_DENSITY") ? atof(std::getenv("MGX_HEAVY_DENSITY")) : 0.05;
+  static const double kSqueezeEnv = std::getenv("MGX_HEAVY_SQUEEZE") ? atof(std::getenv("MGX_HEAVY_SQUEEZE")) : -1.0;
+  const uint32_t n = p.n, n_tiles = b->idx->dev.n_tiles;
+  const bool deal = kXcdAffinity && p.score_mode;
+  std::vector<uint32_t> order(n);  // queries in the order they appear inside a band
+  for (uint32_t i = 0; i < n; ++i) order[i] = i;
+  if (deal) {
+    std::vector<uint32_t> heavy(n, 0);
+    for (uint32_t i = 0; i < n; ++i) {
+      uint64_t best = 0;
+      for (const DevLeaf& lf : specs[g.qids[i]].leaves) {
+        if (lf.kind != kLeafGramBitmap && lf.kind != kLeafList) continue;
+        const uint64_t sz = b->idx->h_offsets[lf.a + 1] - b->idx->h_offsets[lf.a];
+        if (sz > best) {
+          best = sz;
+          heavy[i] = lf.a;
+        }
+      }
+    }
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return heavy[x] < heavy[y]; });
+  }
+  const uint32_t n_bands = n_tiles / kSortTiles + 1;
+  // A heavy query's items (thousands of matches per tile: tens of microseconds per tile visit, where most take one or
+  // two) are pulled forward in the launch order — its last bands would otherwise start when the launch is nearly over
+  // and finish alone, the tail of the step. They stay in doc order, so the query's bound still grows from band to band.
+  // (measured: 0.346 -> 0.327 ms on a 77-tile shard at 0.6; on the 611-tile table the tail is a smaller share of the
+  // step and a later start of the query's last bands — a better bound — is worth as much: neutral, left in order)
+  const double kHeavySqueeze = kSqueezeEnv >= 0.0 ? kSqueezeEnv : 0.6 + 0.4 * std::min(1.0, n_tiles / 600.0);
+  auto band_of = [&](const DevItem& it) {
+    const Route route = p.route[it.query];
+    if (route == Route::kCand) return 0u;  // (the item covers the whole query; tile_begin holds its driver)
+    const uint32_t band = it.tile_begin / kSortTiles;
+    if (p.score_mode && route == Route::kFast && specs[g.qids[it.query]].est_density >= kHeavyDensity)
+      return static_cast<uint32_t>(band * kHeavySqueeze);
+    return band;
+  };
+  std::vector<uint32_t> band_at(n_bands + 1, 0);
+  for (const DevItem& it : p.items) band_at[band_of(it) + 1]++;
+  for (uint32_t k = 0; k < n_bands; ++k) band_at[k + 1] += band_at[k];
+  std::vector<DevItem> sorted(p.items.size());
+  {
+    std::vector<uint32_t> cur(band_at.begin(), band_at.end() - 1);
+    for (uint32_t oi = 0; oi < n; ++oi) {
+      const uint32_t i = order[oi];
+      for (uint32_t k = p.item_begin[i]; k < p.item_begin[i + 1]; ++k) sorted[cur[band_of(p.items[k])]++] = p.items[k];
+    }
+  }
+  if (deal) {
+    for (uint32_t k = 0; k < n_bands; ++k) {
+      const size_t lo = band_at[k], m = band_at[k + 1] - lo, per = (m + 7) / 8;
+      size_t w = lo;
+      for (size_t r = 0; r < per; ++r)
+        for (size_t x = 0; x < 8; ++x)
+          if (x * per + r < m) p.items[w++] = sorted[lo + x * per + r];
+    }
+  } else {
+    p.items.swap(sorted);
+  }
+  p.has_seed.assign(n, 0);
   for (int pass = 0; pass < 2; ++pass) {  // pass 0: the fast path's seed items (a query's first list), then the rest
-    for (const DevItem& it : items) {
-      const uint8_t w = on_wave[it.query];
-      const bool seed = w == 3 && it.list == list_begin[it.query] && it.tile_begin == 0 &&
-                        list_begin[it.query + 1] - list_begin[it.query] > 1 && it.n_tiles <= 16;
+    for (const DevItem& it : p.items) {
+      const Route route = p.route[it.query];
+      const bool seed = route == Route::kFast && it.list == p.list_begin[it.query] && it.tile_begin == 0 &&
+                        p.list_begin[it.query + 1] - p.list_begin[it.query] > 1 && it.n_tiles <= 16;
       if (seed != (pass == 0)) continue;
-      if (w == 3) items_fast[fastq[it.query].n_score - 1].push_back(it);
-      else if (w == 4) items_cand.push_back(it);
-      else if (w == 5) items_merge.push_back(it);
-      else (w == 2 && score_mode ? items_wave_lists : w ? items_wave : items_block).push_back(it);
-      if (seed && fastq[it.query].blockmax != 0) has_seed[it.query] = 1;  // (a query that prunes: its seed's keys are worth sharing)
+      switch (route) {
+        case Route::kBlock: p.block.push_back(it); break;
+        case Route::kWave: p.wave.push_back(it); break;
+        case Route::kWaveLists: p.wave_lists.push_back(it); break;
+        case Route::kFast: p.fast[p.fastq[it.query].n_score - 1].push_back(it); break;
+        case Route::kCand: p.cand.push_back(it); break;
+        case Route::kMerge: p.merge.push_back(it); break;
+      }
+      if (seed && p.fastq[it.query].blockmax != 0) p.has_seed[it.query] = 1;  // (a query that prunes: its seed's keys are worth sharing)
     }
     if (pass == 0)
-      for (int t = 0; t < kFastMaxScore; ++t) g.n_seed_fast[t] = static_cast<uint32_t>(items_fast[t].size());
+      for (int t = 0; t < kFastMaxScore; ++t) g.n_seed_fast[t] = static_cast<uint32_t>(p.fast[t].size());
   }
   // The shape of the seed-key exchange of a sharded table must be the same on every rank, whatever this shard's own
   // index looks like (a gram may be a bitmap here and a list there, a shard a tile shorter): it is made from the QUERIES
   // alone — keys per query = the largest page of the group's SORT _score DESC queries that fit the fast path's lists —
   // and a query without a seed on this rank contributes zeros.
+  g.seed_k = 0;
   g.seed_table_docs = 0;
-  if (score_mode) {
-    for (uint32_t i = 0; i < n; ++i) {
-      const QuerySpec& sp = specs[g.qids[i]];
-      if (sp.reverse != 0 && dq[i].needed != 0 && dq[i].needed <= 128u) {
-        seed_k = std::max(seed_k, dq[i].needed);
-        g.seed_table_docs = std::max<uint64_t>(g.seed_table_docs, sp.total_docs);
-      }
+  for (uint32_t i = 0; p.score_mode && i < n; ++i) {
+    const QuerySpec& sp = specs[g.qids[i]];
+    if (sp.reverse != 0 && p.dq[i].needed != 0 && p.dq[i].needed <= 128u) {
+      g.seed_k = std::max(g.seed_k, p.dq[i].needed);
+      g.seed_table_docs = std::max<uint64_t>(g.seed_table_docs, sp.total_docs);
     }
   }
-  g.seed_k = seed_k;
-  if (seed_k) MGX_HIP(Upload(g.d_has_seed, has_seed.data(), has_seed.size()));
-  sec.Mark(5);
-  if (!fastq.empty()) MGX_HIP(Upload(g.d_fast_queries, fastq.data(), fastq.size()));
-  for (int t = 0; t < kFastMaxScore; ++t) MGX_HIP(Upload(g.d_items_fast[t], items_fast[t].data(), items_fast[t].size()));
-  MGX_HIP(Upload(g.d_items_wave_lists, items_wave_lists.data(), items_wave_lists.size()));
-  MGX_HIP(Upload(g.d_items_cand, items_cand.data(), items_cand.size()));
-  MGX_HIP(Upload(g.d_items_merge, items_merge.data(), items_merge.size()));
-  if (page_mode && !items_cand.empty()) {
-    std::vector<uint8_t> skip(n, 0);
-    for (uint32_t i = 0; i < n; ++i) skip[i] = on_wave[i] == 4 ? 1 : 0;
-    MGX_HIP(Upload(g.d_cand_skip, skip.data(), skip.size()));
+  if (g.seed_k) MGX_HIP(Upload(g.d_has_seed, p.has_seed.data(), p.has_seed.size()));
+  return MGX_OK;
+}
+
+// One route's launch: the group's descriptor over these items.
+static hipError_t MakeRoute(RouteLaunch& r, const DevBatch& base, const std::vector<DevItem>& items) {
+  r.dev = base;
+  r.dev.n_items = static_cast<uint32_t>(items.size());
+  const hipError_t e = Upload(r.d_items, items.data(), items.size());
+  r.dev.items = r.d_items.as<DevItem>();
+  return e;
+}
+
+// (f, g) Block-kernel items: queries whose operands are all bitmap-form first (plain instantiation), then the queries
+// with a sorted list, an explicit id list or a slot range among their operands (the instantiation that skips / jumps
+// over tiles), and last the queries with kOpVerifyFuzzy (the FZ instantiation, launched apart). Then the group's
+// descriptor with the outputs sized by its candidate lists, and one launch per route over it.
+static int UploadItems(mgx_batch* b, Group& g, const std::vector<QuerySpec>& specs, GroupPlan& p) {
+  const uint32_t n = p.n;
+  std::vector<uint8_t> listlike(n, 0);
+  for (uint32_t i = 0; i < n; ++i) {
+    for (const DevLeaf& lf : specs[g.qids[i]].leaves)
+      if (lf.kind == kLeafList || lf.kind == kLeafExplicit || lf.kind == kLeafRange) listlike[i] = 1;
+    if (specs[g.qids[i]].fz_distance != 0) listlike[i] = 2;
   }
-  {
-    // block-kernel items: queries whose operands are all bitmap-form first (plain instantiation), then the queries with a
-    // sorted list, an explicit id list or a slot range among their operands (the instantiation that skips / jumps over tiles),
-    // and last the queries with kOpVerifyFuzzy (the FZ instantiation, launched apart)
-    std::vector<uint8_t> listlike(n, 0);
-    for (uint32_t i = 0; i < n; ++i) {
-      for (const DevLeaf& lf : specs[g.qids[i]].leaves)
-        if (lf.kind == kLeafList || lf.kind == kLeafExplicit || lf.kind == kLeafRange) listlike[i] = 1;
-      if (specs[g.qids[i]].fz_distance != 0) listlike[i] = 2;
-    }
-    std::stable_partition(items_block.begin(), items_block.end(), [&](const DevItem& it) { return listlike[it.query] == 0; });
-    if (std::find(listlike.begin(), listlike.end(), 2) != listlike.end())
-      std::stable_partition(items_block.begin(), items_block.end(), [&](const DevItem& it) { return listlike[it.query] != 2; });
-    g.n_items_plain = g.n_items_fz = 0;
-    for (const DevItem& it : items_block) {
-      g.n_items_plain += listlike[it.query] == 0 ? 1u : 0u;
-      g.n_items_fz += listlike[it.query] == 2 ? 1u : 0u;
-    }
+  std::stable_partition(p.block.begin(), p.block.end(), [&](const DevItem& it) { return listlike[it.query] == 0; });
+  if (std::find(listlike.begin(), listlike.end(), 2) != listlike.end())
+    std::stable_partition(p.block.begin(), p.block.end(), [&](const DevItem& it) { return listlike[it.query] != 2; });
+  g.n_items_plain = g.n_items_fz = 0;
+  for (const DevItem& it : p.block) {
+    g.n_items_plain += listlike[it.query] == 0 ? 1u : 0u;
+    g.n_items_fz += listlike[it.query] == 2 ? 1u : 0u;
   }
-  g.n_items = static_cast<uint32_t>(items_block.size());
-  g.n_items_wave = static_cast<uint32_t>(items_wave.size());
-  MGX_HIP(Upload(g.d_items, items_block.data(), items_block.size()));
-  MGX_HIP(Upload(g.d_items_wave, items_wave.data(), items_wave.size()));
-  MGX_HIP(Upload(g.d_list_begin, list_begin.data(), list_begin.size()));
-  sec.Mark(6);
-  if (std::getenv("MGX_VERBOSE"))
-    fprintf(stderr,
-            "[mgx] %s group: %u queries; fast path %zu items (lds %u B, ring %u), wave kernel %u items (lds %u B), "
-            "block kernel %u items (lds %u B), candidate-driven %zu queries, list merge %zu items\n",
-            score_mode ? "score" : page_mode ? "docid-page" : df_mode ? "df" : "bitmap", n,
-            items_fast[0].size() + items_fast[1].size() + items_fast[2].size() + items_fast[3].size() + items_fast[4].size(),
-            g.fplan.bytes, g.fplan.ring, g.n_items_wave + static_cast<uint32_t>(items_wave_lists.size()), g.wplan.bytes, g.n_items,
-            g.plan.bytes, items_cand.size(), items_merge.size());
   DevBatch& d = g.dev;
-  d.items = g.d_items.as<DevItem>();
-  d.n_items = g.n_items;
   d.queries = g.d_queries.as<DevQuery>();
   d.leaves = g.d_leaves.as<DevLeaf>();
   d.prog = g.d_prog.as<uint32_t>();
@@ -2420,33 +2460,27 @@ static int UploadGroup(mgx_batch* b, mgx_batch::Group& g, uint32_t mode, const s
   d.text_idf = b->d_text_idf.as<double>();
   d.verify_terms = b->d_verify_terms.as<DevTextTerm>();
   d.n_queries = n;
-  d.counters = score_mode  ? b->sc_counters()
-               : page_mode ? b->d_page_out.as<unsigned long long>()
-                           : g.d_counters.as<unsigned long long>();
-  if (page_mode) {
+  d.counters = p.score_mode  ? b->sc_counters()
+               : p.page_mode ? b->d_page_out.as<unsigned long long>()
+                             : g.d_counters.as<unsigned long long>();
+  if (p.page_mode) {
     d.tile_cnt = b->d_ptile_cnt.as<uint32_t>();
     d.tile_start = b->d_ptile_start.as<uint64_t>();
     d.totals = reinterpret_cast<const uint64_t*>(static_cast<const char*>(b->d_page_out.p) + b->po_totals);
     d.page_docs = reinterpret_cast<uint32_t*>(static_cast<char*>(b->d_page_out.p) + b->po_docs);
     d.page_stride = b->doc_page_stride;
   }
-  d.bounds = score_mode ? d.counters + static_cast<size_t>(n) * 8 : nullptr;
+  d.bounds = p.score_mode ? d.counters + static_cast<size_t>(n) * 8 : nullptr;
 #ifdef MGX_ABLATION
   d.debug_skip = std::getenv("MGX_DEBUG_SKIP") ? static_cast<uint32_t>(atoi(std::getenv("MGX_DEBUG_SKIP"))) : 0u;
 #endif
-  if (score_mode) {
-    uint32_t max_needed = 1, max_limit = 1;
-    for (const DevQuery& q : dq) {
-      max_needed = std::max(max_needed, q.needed);
-      max_limit = std::max(max_limit, q.limit);
-    }
-    const size_t n_lists_total = n_lists_all;
-    d.cand_stride = max_needed;
-    b->top_stride = max_needed;
-    b->page_stride = max_limit;
-    MGX_HIP(b->d_cand_keys.Alloc(n_lists_total * max_needed * 8));
-    MGX_HIP(b->d_cand_docs.Alloc(n_lists_total * max_needed * 4));
-    MGX_HIP(b->d_cand_n.Alloc(n_lists_total * 4));
+  if (p.score_mode) {
+    const size_t n_lists = p.list_begin[n], max_needed = p.max_needed;
+    d.cand_stride = b->top_stride = p.max_needed;
+    b->page_stride = p.max_limit;
+    MGX_HIP(b->d_cand_keys.Alloc(n_lists * max_needed * 8));
+    MGX_HIP(b->d_cand_docs.Alloc(n_lists * max_needed * 4));
+    MGX_HIP(b->d_cand_n.Alloc(n_lists * 4));
     {
       const size_t elems = static_cast<size_t>(n) * max_needed + n;
       b->ex_off32 = elems * 8;
@@ -2456,7 +2490,7 @@ static int UploadGroup(mgx_batch* b, mgx_batch::Group& g, uint32_t mode, const s
     d.cand_keys = b->d_cand_keys.as<uint64_t>();
     d.cand_docs = b->d_cand_docs.as<uint32_t>();
     d.cand_n = b->d_cand_n.as<uint32_t>();
-  } else if (!df_mode && !page_mode) {
+  } else if (!p.df_mode && !p.page_mode) {
     const size_t tiles = b->idx->dev.n_tiles;
     MGX_HIP(b->d_rbits.Alloc(static_cast<size_t>(n) * tiles * kWordsPerTile * 8));
     MGX_HIP(b->d_tile_cnt.Alloc(static_cast<size_t>(n) * tiles * 4));
@@ -2470,49 +2504,71 @@ static int UploadGroup(mgx_batch* b, mgx_batch::Group& g, uint32_t mode, const s
     d.rbits = b->d_rbits.as<uint64_t>();
     d.tile_cnt = b->d_tile_cnt.as<uint32_t>();
   }
-  if (score_mode && !wave_tables.empty()) {
-    MGX_HIP(Upload(g.d_tables, wave_tables.data(), wave_tables.size()));
+  if (p.score_mode && !p.wave_tables.empty()) {
+    MGX_HIP(Upload(g.d_tables, p.wave_tables.data(), p.wave_tables.size()));
     d.wave_tables = g.d_tables.as<uint64_t>();
   }
+  if (!p.fastq.empty()) MGX_HIP(Upload(g.d_fast_queries, p.fastq.data(), p.fastq.size()));
   d.fast_queries = g.d_fast_queries.as<DevFastQuery>();
   d.dev_index = b->idx->d_dev_index.as<DevIndex>();
-  for (int t = 0; t < kFastMaxScore; ++t) {
-    g.dev_fast[t] = d;
-    g.dev_fast[t].items = g.d_items_fast[t].as<DevItem>();
-    g.dev_fast[t].n_items = static_cast<uint32_t>(items_fast[t].size());
+  for (int t = 0; t < kFastMaxScore; ++t) MGX_HIP(MakeRoute(g.fast[t], d, p.fast[t]));
+  MGX_HIP(MakeRoute(g.wave_lists, d, p.wave_lists));
+  MGX_HIP(MakeRoute(g.cand, d, p.cand));
+  MGX_HIP(MakeRoute(g.merge, d, p.merge));
+  if (p.page_mode && !p.cand.empty()) {
+    std::vector<uint8_t> skip(n, 0);
+    for (uint32_t i = 0; i < n; ++i) skip[i] = p.route[i] == Route::kCand ? 1 : 0;
+    MGX_HIP(Upload(g.d_cand_skip, skip.data(), skip.size()));
   }
-  g.dev_merge = d;
-  g.dev_merge.items = g.d_items_merge.as<DevItem>();
-  g.dev_merge.n_items = static_cast<uint32_t>(items_merge.size());
-  g.dev_cand = d;
-  g.dev_cand.items = g.d_items_cand.as<DevItem>();
-  g.dev_cand.n_items = static_cast<uint32_t>(items_cand.size());
-  g.dev_wave = d;
-  g.dev_wave.items = g.d_items_wave.as<DevItem>();
-  g.dev_wave.n_items = g.n_items_wave;
-  g.dev_wave_lists = d;
-  g.dev_wave_lists.items = g.d_items_wave_lists.as<DevItem>();
-  g.dev_wave_lists.n_items = static_cast<uint32_t>(items_wave_lists.size());
-  if (page_mode) {
+  MGX_HIP(MakeRoute(g.block, d, p.block));
+  MGX_HIP(MakeRoute(g.wave, d, p.wave));
+  MGX_HIP(Upload(g.d_list_begin, p.list_begin.data(), p.list_begin.size()));
+  if (p.page_mode) {
+    // the page pass: one item per query (cand_kernel writes its own pages); kOpVerifyFuzzy queries last in page_block,
+    // on the general kernel's FZ launch
     std::vector<DevItem> pw, pb;
     for (uint32_t i = 0; i < n; ++i)
-      if (on_wave[i] != 4 && specs[g.qids[i]].fz_distance == 0)
-        (on_wave[i] ? pw : pb).push_back(DevItem{i, 0, 0, 0});  // (cand_kernel writes its own pages)
+      if (p.route[i] != Route::kCand && specs[g.qids[i]].fz_distance == 0)
+        (p.route[i] == Route::kWave ? pw : pb).push_back(DevItem{i, 0, 0, 0});
     g.n_page_fz = 0;
-    for (uint32_t i = 0; i < n; ++i)  // (kOpVerifyFuzzy: general kernel, FZ launch)
+    for (uint32_t i = 0; i < n; ++i)
       if (specs[g.qids[i]].fz_distance != 0) {
         pb.push_back(DevItem{i, 0, 0, 0});
         ++g.n_page_fz;
       }
-    MGX_HIP(Upload(g.d_pq_wave, pw.data(), pw.size()));
-    MGX_HIP(Upload(g.d_pq_block, pb.data(), pb.size()));
-    g.dev_page_wave = d;
-    g.dev_page_wave.items = g.d_pq_wave.as<DevItem>();
-    g.dev_page_wave.n_items = static_cast<uint32_t>(pw.size());
-    g.dev_page_block = d;
-    g.dev_page_block.items = g.d_pq_block.as<DevItem>();
-    g.dev_page_block.n_items = static_cast<uint32_t>(pb.size());
+    MGX_HIP(MakeRoute(g.page_wave, d, pw));
+    MGX_HIP(MakeRoute(g.page_block, d, pb));
   }
+  return MGX_OK;
+}
+
+// Plans one group of the batch (the queries of one mode) and ships its tables: query layout, each query's route, the
+// work items and their launch order, then one descriptor per launch.
+static int UploadGroup(mgx_batch* b, Group& g, uint32_t mode, const std::vector<QuerySpec>& specs) {
+  GroupPlan p(static_cast<uint32_t>(g.qids.size()), mode);
+  if (p.n == 0) return MGX_OK;
+  const PathSwitches sw;
+  SectionTimer sec;
+  if (const int rc = LayOutQueries(b, g, specs, p)) return rc;
+  sec.Mark(0);
+  if (const int rc = ChooseRoutes(b, g, specs, sw, p)) return rc;
+  sec.Mark(1);
+  if (const int rc = UploadTables(b, g, p, sec)) return rc;
+  sec.Mark(3);
+  CutItems(b, g, specs, p);
+  sec.Mark(4);
+  if (const int rc = ScheduleItems(b, g, specs, p)) return rc;
+  sec.Mark(5);
+  if (const int rc = UploadItems(b, g, specs, p)) return rc;
+  sec.Mark(6);
+  if (std::getenv("MGX_VERBOSE"))
+    fprintf(stderr,
+            "[mgx] %s group: %u queries; fast path %zu items (lds %u B, ring %u), wave kernel %zu items (lds %u B), "
+            "block kernel %zu items (lds %u B), candidate-driven %zu queries, list merge %zu items\n",
+            p.score_mode ? "score" : p.page_mode ? "docid-page" : p.df_mode ? "df" : "bitmap", p.n,
+            p.fast[0].size() + p.fast[1].size() + p.fast[2].size() + p.fast[3].size() + p.fast[4].size(),
+            g.fplan.bytes, g.fplan.ring, p.wave.size() + p.wave_lists.size(), g.wplan.bytes, p.block.size(),
+            g.plan.bytes, p.cand.size(), p.merge.size());
   return MGX_OK;
 }
 
@@ -2796,8 +2852,8 @@ static int CountDfImpl(mgx_batch* b, hipStream_t s) {
     if (rc) return rc;
   }
   MGX_HIP(hipMemsetAsync(g.d_counters.p, 0, g.d_counters.bytes, s));
-  MGX_LAUNCH(LaunchWaveCount(idx->dev, g.dev_wave, g.wplan, true, s));
-  MGX_LAUNCH(LaunchTileEval(kModeTextDf, idx->dev, g.dev, g.plan, s, g.n_items_plain));
+  MGX_LAUNCH(LaunchWaveCount(idx->dev, g.wave.dev, g.wplan, true, s));
+  MGX_LAUNCH(LaunchTileEval(kModeTextDf, idx->dev, g.block.dev, g.plan, s, g.n_items_plain));
   // counter slot 5 of every df query (or the cached local count) -> the local array and the buffer ranks all-reduce
   MGX_LAUNCH(LaunchGatherDf(g.d_counters.as<unsigned long long>(), b->d_text_df_known.as<uint64_t>(),
                             static_cast<uint32_t>(g.qids.size()), b->d_text_df_local.as<uint64_t>(),
@@ -2814,6 +2870,18 @@ struct SeedGather {
   void* user = nullptr;
 };
 static int SeedBoundExchange(mgx_batch* b, mgx_batch::Group& g, const SeedGather& sg, hipStream_t s);
+
+// Fork of the side stream (idx->side_stream): it waits for what `s` has queued so far. A group joins it by recording
+// res->join_ev on the side stream after its side launches, and `s` waits for that event where the group needs them.
+static int ForkSide(mgx_batch* b, hipStream_t s) {
+  if (!b->res->fork_ev) {
+    MGX_HIP(hipEventCreateWithFlags(&b->res->fork_ev, hipEventDisableTiming));
+    MGX_HIP(hipEventCreateWithFlags(&b->res->join_ev, hipEventDisableTiming));
+  }
+  MGX_HIP(hipEventRecord(b->res->fork_ev, s));
+  MGX_HIP(hipStreamWaitEvent(b->idx->side_stream, b->res->fork_ev, 0));
+  return MGX_OK;
+}
 
 static int ExecuteImpl(mgx_batch* b, hipStream_t s, const SeedGather* sg = nullptr) {
   mgx_index* idx = b->idx;
@@ -2885,31 +2953,26 @@ static int ExecuteImpl(mgx_batch* b, hipStream_t s, const SeedGather* sg = nullp
       if (idx->chain_ev && idx->chain_ev != b->res->main_ev) MGX_HIP(hipStreamWaitEvent(s, idx->chain_ev, 0));
     }
     uint32_t n_fast = 0;
-    for (int t = 0; t < kFastMaxScore; ++t) n_fast += g.dev_fast[t].n_items;
-    const bool main_work = n_fast != 0 || g.n_items_wave != 0 || g.dev_merge.n_items != 0;
-    const bool side_work = g.n_items != 0 || g.dev_wave_lists.n_items != 0 || g.dev_cand.n_items != 0;
+    for (int t = 0; t < kFastMaxScore; ++t) n_fast += g.fast[t].dev.n_items;
+    const bool main_work = n_fast != 0 || g.wave.dev.n_items != 0 || g.merge.dev.n_items != 0;
+    const bool side_work = g.block.dev.n_items != 0 || g.wave_lists.dev.n_items != 0 || g.cand.dev.n_items != 0;
     hipStream_t side = s;
     if (main_work && side_work) {
       // fork: the (small) shares of the general kernel and of the list-operand plan run on the side stream while the
       // main launch fills the chip
-      if (!b->res->fork_ev) {
-        MGX_HIP(hipEventCreateWithFlags(&b->res->fork_ev, hipEventDisableTiming));
-        MGX_HIP(hipEventCreateWithFlags(&b->res->join_ev, hipEventDisableTiming));
-      }
-      MGX_HIP(hipEventRecord(b->res->fork_ev, s));
-      MGX_HIP(hipStreamWaitEvent(idx->side_stream, b->res->fork_ev, 0));
+      if (const int rc = ForkSide(b, s)) return rc;
       side = idx->side_stream;
     }
-    MGX_LAUNCH(LaunchCand(kModeScore, idx->dev, g.dev_cand, g.cand_leaves, g.cand_instr, g.cand_cap, side));
-    MGX_LAUNCH(LaunchWaveScore(idx->dev, g.dev_wave_lists, g.wplan_lists, side));
-    MGX_LAUNCH(LaunchTileEval(kModeScore, idx->dev, g.dev, g.plan, side, g.n_items_plain, g.n_items_fz));
+    MGX_LAUNCH(LaunchCand(kModeScore, idx->dev, g.cand.dev, g.cand_leaves, g.cand_instr, g.cand_cap, side));
+    MGX_LAUNCH(LaunchWaveScore(idx->dev, g.wave_lists.dev, g.wplan_lists, side));
+    MGX_LAUNCH(LaunchTileEval(kModeScore, idx->dev, g.block.dev, g.plan, side, g.n_items_plain, g.n_items_fz));
     // (both conditions are the same on every rank: the collective is entered by all or by none)
     static const uint64_t kMinShardDocs = std::getenv("MGX_SEED_EXCHANGE_MIN_DOCS") ? static_cast<uint64_t>(atoll(std::getenv("MGX_SEED_EXCHANGE_MIN_DOCS"))) : 1000000ull;
     if (sg && sg->fn && g.seed_k != 0 && g.seed_table_docs / static_cast<uint64_t>(sg->world) >= kMinShardDocs) {
       // doc-range shards: a shard's own matches give a weak bound (a 1.25M-doc shard scores 22 % of its matches where
       // the whole table scores 7 %); the seeds of ALL shards together are a sample of the whole table
       for (int t = 0; t < kFastMaxScore; ++t) {
-        DevBatch seeds = g.dev_fast[t];
+        DevBatch seeds = g.fast[t].dev;
         seeds.n_items = g.n_seed_fast[t];
         MGX_LAUNCH(LaunchBitmapScore(static_cast<uint32_t>(t + 1), idx->dev, seeds, g.fplan, s));
       }
@@ -2918,17 +2981,17 @@ static int ExecuteImpl(mgx_batch* b, hipStream_t s, const SeedGather* sg = nullp
         if (rc) return rc;
       }
       for (int t = 0; t < kFastMaxScore; ++t) {
-        DevBatch rest = g.dev_fast[t];
+        DevBatch rest = g.fast[t].dev;
         rest.items += g.n_seed_fast[t];
         rest.n_items -= g.n_seed_fast[t];
         MGX_LAUNCH(LaunchBitmapScore(static_cast<uint32_t>(t + 1), idx->dev, rest, g.fplan, s));
       }
     } else {
       for (int t = 0; t < kFastMaxScore; ++t)
-        MGX_LAUNCH(LaunchBitmapScore(static_cast<uint32_t>(t + 1), idx->dev, g.dev_fast[t], g.fplan, s));
+        MGX_LAUNCH(LaunchBitmapScore(static_cast<uint32_t>(t + 1), idx->dev, g.fast[t].dev, g.fplan, s));
     }
-    MGX_LAUNCH(LaunchWaveScore(idx->dev, g.dev_wave, g.wplan, s));
-    MGX_LAUNCH(LaunchMergeScore(idx->dev, g.dev_merge, g.merge_leaves, g.merge_instr, g.merge_ops, g.merge_cap, s));
+    MGX_LAUNCH(LaunchWaveScore(idx->dev, g.wave.dev, g.wplan, s));
+    MGX_LAUNCH(LaunchMergeScore(idx->dev, g.merge.dev, g.merge_leaves, g.merge_instr, g.merge_ops, g.merge_cap, s));
     if (side != s) {
       MGX_HIP(hipEventRecord(b->res->join_ev, side));
       MGX_HIP(hipStreamWaitEvent(s, b->res->join_ev, 0));
@@ -2956,7 +3019,7 @@ static int ExecuteImpl(mgx_batch* b, hipStream_t s, const SeedGather* sg = nullp
     if (b->timing && !timed) {
       MGX_HIP(hipEventRecord(ev0, s));
     }
-    MGX_LAUNCH(LaunchTileEval(kModeBitmap, idx->dev, g.dev, g.plan, s, g.n_items_plain, g.n_items_fz));
+    MGX_LAUNCH(LaunchTileEval(kModeBitmap, idx->dev, g.block.dev, g.plan, s, g.n_items_plain, g.n_items_fz));
     if (b->timing && !timed) {
       MGX_HIP(hipEventRecord(ev1, s));
       timed = true;
@@ -2973,28 +3036,23 @@ static int ExecuteImpl(mgx_batch* b, hipStream_t s, const SeedGather* sg = nullp
     }
     // candidate-driven queries (selective: a sparse list drives) beside the tile passes, on the side stream: they write
     // their totals and pages themselves
-    const bool cand_side = g.dev_cand.n_items != 0 && (g.dev_wave.n_items != 0 || g.n_items != 0) && b->res_owned;
+    const bool cand_side = g.cand.dev.n_items != 0 && (g.wave.dev.n_items != 0 || g.block.dev.n_items != 0) && b->res_owned;
     if (cand_side) {
-      if (!b->res->fork_ev) {
-        MGX_HIP(hipEventCreateWithFlags(&b->res->fork_ev, hipEventDisableTiming));
-        MGX_HIP(hipEventCreateWithFlags(&b->res->join_ev, hipEventDisableTiming));
-      }
-      MGX_HIP(hipEventRecord(b->res->fork_ev, s));
-      MGX_HIP(hipStreamWaitEvent(idx->side_stream, b->res->fork_ev, 0));
-      MGX_LAUNCH(LaunchCand(kModeDocPage, idx->dev, g.dev_cand, g.cand_leaves, g.cand_instr, 0, idx->side_stream));
+      if (const int rc = ForkSide(b, s)) return rc;
+      MGX_LAUNCH(LaunchCand(kModeDocPage, idx->dev, g.cand.dev, g.cand_leaves, g.cand_instr, 0, idx->side_stream));
       MGX_HIP(hipEventRecord(b->res->join_ev, idx->side_stream));
     }
-    MGX_LAUNCH(LaunchWaveCount(idx->dev, g.dev_wave, g.wplan, false, s));
-    MGX_LAUNCH(LaunchTileEval(kModeDocCount, idx->dev, g.dev, g.plan, s, g.n_items_plain, g.n_items_fz));
+    MGX_LAUNCH(LaunchWaveCount(idx->dev, g.wave.dev, g.wplan, false, s));
+    MGX_LAUNCH(LaunchTileEval(kModeDocCount, idx->dev, g.block.dev, g.plan, s, g.n_items_plain, g.n_items_fz));
     if (b->timing && !timed) {
       MGX_HIP(hipEventRecord(ev1, s));
       timed = true;
     }
     MGX_LAUNCH(LaunchScanTiles(g.dev.tile_cnt, n, idx->dev.n_tiles, b->d_ptile_start.as<uint64_t>(),
                                const_cast<uint64_t*>(g.dev.totals), s, g.d_cand_skip.as<uint8_t>()));
-    if (!cand_side) MGX_LAUNCH(LaunchCand(kModeDocPage, idx->dev, g.dev_cand, g.cand_leaves, g.cand_instr, 0, s));
-    MGX_LAUNCH(LaunchWavePage(idx->dev, g.dev_page_wave, g.wplan, s));
-    MGX_LAUNCH(LaunchTileEval(kModeDocPage, idx->dev, g.dev_page_block, g.plan, s, 0xFFFFFFFFu, g.n_page_fz));
+    if (!cand_side) MGX_LAUNCH(LaunchCand(kModeDocPage, idx->dev, g.cand.dev, g.cand_leaves, g.cand_instr, 0, s));
+    MGX_LAUNCH(LaunchWavePage(idx->dev, g.page_wave.dev, g.wplan, s));
+    MGX_LAUNCH(LaunchTileEval(kModeDocPage, idx->dev, g.page_block.dev, g.plan, s, 0xFFFFFFFFu, g.n_page_fz));
     if (cand_side) MGX_HIP(hipStreamWaitEvent(s, b->res->join_ev, 0));
   }
   if (b->timing) {
@@ -3458,7 +3516,7 @@ int mgx_batch_reset(mgx_batch* batch, const mgx_query* queries, uint32_t n_queri
         const double per = static_cast<double>(period);
         fprintf(stderr, "[mgx] reset x%llu: CompileQuery loop %.3f ms, reset + PrepareInto %.3f ms per batch\n",
                 static_cast<unsigned long long>(period), us_compile.exchange(0) / (per * 1e3), us_into.exchange(0) / (per * 1e3));
-        for (int k = 0; k < 8; ++k)
+        for (int k = 0; k < mgx::kSections; ++k)
           fprintf(stderr, "[mgx]   %-24s %.3f ms\n", mgx::kSectionNames[k], mgx::g_section_us[k].exchange(0) / (per * 1e6));
       }
     }
