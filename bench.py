@@ -11,9 +11,15 @@ The index is resident in HBM; the query strings are resident in host memory (the
 `value` is that end-to-end rate. The kernel-replay rate of round 1 (prepared batches re-executed) is reported beside it
 as `replay_qps`, and the dominant kernel's duration comes from HIP events around it in the replay loop.
 
-    python bench.py --gpus 1 --steps 200 --warmup 20
+A plain run sets up, runs the replay loop (the timed steps have always followed it), warms up, times the steps, writes
+--dump-outputs and prints the line. `--full` adds what runs after the timed steps and fills the fields that are null
+without it: the other operating points of the executor (`other_operating_points`), this box's measured read bandwidth
+(`roofline.peak_measured_read`), the CPU baseline with its parity check of the timed rows (`cpu_baseline`) and, with
+8 GPUs, the configs[3] block (`config3_100M_docs_8_gpus`).
+
+    python bench.py --gpus 1 --steps 200 --warmup 20 [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
-        bench.py --gpus N --steps K --warmup W
+        bench.py --gpus N --steps K --warmup W [--full]
 
 N > 1 is STRONG scaling: the same 10M-doc table is cut into N contiguous doc-range shards, one per rank; every rank
 runs the whole batch on its shard, per-shard top-k lists are exchanged (RCCL all-gather) and merged.
@@ -242,7 +248,7 @@ def dump_outputs(path, totals, n_docs, docs, scores):
         np.save(os.path.join(path, name + ".npy"), np.asarray(a, dtype=np.float64))
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
@@ -250,7 +256,14 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="after the timed steps, write the last step's results (totals, n_docs, docs, scores) as "
                          "DIR/<name>.npy, float64; the inputs are seeded, so runs with the same arguments compare")
-    args = ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline does not need: other operating points, "
+                         "measured read bandwidth, CPU baseline + parity, configs[3] with 8 GPUs")
+    return ap.parse_args(argv)
+
+
+def main():
+    args = parse_args()
 
     import torch
     import torch.distributed as dist
@@ -319,7 +332,9 @@ def main():
 
     # ---------------------------------------------------------------------------------------------------------------
     # (1) replay loop: 4 prepared batches re-executed — isolates the device side; the dominant kernel is timed by HIP
-    #     events on its launch stream, algorithmic bytes come from the fetched match counts
+    #     events on its launch stream, algorithmic bytes come from the fetched match counts. A plain run keeps it too: it
+    #     costs ~0.2 s, and the timed steps have always run after it — without it they read ~4 % faster (same box,
+    #     interleaved runs), so the headline would no longer compare with earlier ones.
     # ---------------------------------------------------------------------------------------------------------------
     replay_q = [[mg.engine.Query(t, sort_score=by_score, limit=10) for t in tb] for tb in term_batches[:4]]
     batches = [table.prepare(qs) for qs in replay_q]
@@ -356,7 +371,7 @@ def main():
     alg = [sum(x[i] for x in per_batch) / len(per_batch) for i in range(3)]
     alg_total = sum(alg)
     achieved = alg_total / (k_ms * 1e-3) / 1e9 if k_ms > 0 else 0.0
-    results0 = batches[0].fetch() if rank == 0 else None
+    results0 = batches[0].fetch() if rank == 0 and args.full else None  # (the replay path's rows: --full's parity check)
 
     # ---------------------------------------------------------------------------------------------------------------
     # (2) the timed region: fresh batches end to end in C++; N > 1 adds the RCCL exchange inside the same C++ executor
@@ -469,11 +484,11 @@ def main():
         elapsed = max(float(x.item()) for x in every)
 
     # ---------------------------------------------------------------------------------------------------------------
-    # (3) other operating points of the same executor (short passes AFTER the timed region; never the headline): the
-    #     metric is queries/s AND p50 batch latency, and the number of batches in flight trades one for the other
+    # (3) --full: other operating points of the same executor (short passes AFTER the timed region; never the headline):
+    #     the metric is queries/s AND p50 batch latency, and the number of batches in flight trades one for the other
     # ---------------------------------------------------------------------------------------------------------------
-    operating_points = []
-    if (not exchange) and rank == 0 and not os.environ.get("MGX_BENCH_NO_POINTS"):
+    operating_points = [] if args.full else None
+    if args.full and (not exchange) and rank == 0 and not os.environ.get("MGX_BENCH_NO_POINTS"):
         for d2, fifo2 in ((1, True), (2, True), (4, False)):
             if d2 == depth and fifo2 == fifo:
                 continue
@@ -496,16 +511,16 @@ def main():
             del ex2
         table.index.device_index.set_batch_order(fifo)
 
-    # second denominator: this box's streaming-read bandwidth, measured in the same job (read-only kernel, 2 GiB)
+    # --full: second denominator: this box's streaming-read bandwidth, measured in the same job (read-only kernel, 2 GiB)
     measured_peak = None
-    if rank == 0:
+    if args.full and rank == 0:
         import ctypes
         gbs = ctypes.c_double(0.0)
         if mg._capi.load().mgxt_measure_read_bandwidth(local_rank, 2 << 30, 5, ctypes.byref(gbs)) == 0:
             measured_peak = gbs.value
 
     cpu = None
-    if rank == 0 and world == 1 and cpu_seconds > 0:
+    if args.full and rank == 0 and world == 1 and cpu_seconds > 0:
         # the rows checked against the oracle are the ones the TIMED C++ executor returned for distinct batch 0 (and, beside
         # them, the Python replay path's: both must agree with the oracle bit for bit)
         def gpu_rows(i):
@@ -522,14 +537,14 @@ def main():
         cpu["parity_rows_from"] = "the timed C++ executor (search_pipeline::BatchExecutor)" if kept0 else "the replay path"
 
     # ---------------------------------------------------------------------------------------------------------------
-    # (4) N = 8 only: BASELINE.json configs[3] beside the strong-scaling line — 100M docs doc-range-sharded 12.5M per rank,
-    #     batch 1024 x 3-term AND + BM25 top-100, RCCL top-k merge (each rank generates only its own shard). A second block
-    #     of the same JSON line; the headline above stays configs[1].
+    # (4) --full, N = 8 only: BASELINE.json configs[3] beside the strong-scaling line — 100M docs doc-range-sharded
+    #     12.5M per rank, batch 1024 x 3-term AND + BM25 top-100, RCCL top-k merge (each rank generates only its own
+    #     shard). A second block of the same JSON line; the headline above stays configs[1].
     # ---------------------------------------------------------------------------------------------------------------
     index_bytes_hbm = table.index.device_index.memory_bytes()
     shard_grams, shard_postings = cols.n_grams, cols.n_postings
     config3 = None
-    want_cfg3 = os.environ.get("MGX_BENCH_CFG3", "1" if world == 8 else "0") != "0"
+    want_cfg3 = args.full and os.environ.get("MGX_BENCH_CFG3", "1" if world == 8 else "0") != "0"
     if want_cfg3 and cxx_exchange and by_score:
         try:
             t_c3 = time.perf_counter()
@@ -613,6 +628,7 @@ def main():
         line = {
             "metric": "queries/sec + p50 latency, 10M-doc bigram index, batch=1024 3-term AND",
             "value": qps, "unit": "queries/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": 1e3 * elapsed / args.steps, "p50_ms": 1e3 * statistics.median(lat),
             "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "u32 set algebra + f64 BM25",
             "data": "synthetic",
