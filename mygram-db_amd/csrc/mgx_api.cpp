@@ -1803,14 +1803,14 @@ struct mgx_batch {
   uint32_t top_stride = 0, page_stride = 0;
   bool merged_shards = false;
   // bitmap group outputs
-  DevBuf d_rbits, d_tile_cnt, d_tile_start, d_totals, d_take, d_out_off, d_reverse, d_out;
+  DevBuf d_rbits, d_tile_cnt, d_tile_start, d_totals, d_take, d_out_off, d_reverse;
   // mutable tables (mgx_batch_merge_local): the bitmap group's sizes are known only at fetch time, so the merge of that
   // group runs inside mgx_batch_fetch(primary). merge_other: on the primary, the batch whose bitmap-group queries the
   // fetch merges in; merged_away: on that other batch, its bitmap-group pages went into the primary's result.
   mgx_batch* merge_other = nullptr;
   bool merged_away = false;
   hipStream_t merge_stream = nullptr;
-  DevBuf d_merge;  // scratch of the merged fetch: runs, keys, page, run descriptors (grown, never shrunk)
+  DevBuf d_merge;  // scratch of the bitmap group's fetch: runs, keys, page, run descriptors (grown, never shrunk)
   // docid-page group (kModeDocPage): per-tile counts / rank offsets, and one packed result block
   // [counters n*8 u64 | totals n u64 | page docs n*stride u32] mirrored in pinned host memory
   Group page;
@@ -3081,34 +3081,37 @@ static std::vector<double> DeepIdfs(const mgx_batch* b, const QuerySpec& sp) {
   return idfs;
 }
 
-// The bitmap group of a mutable table's primary batch, merged with the other batch's (mgx_batch_merge_local): for every
-// query the table-wide total and exactly the page an index built from the table's current documents returns.
-//   - one synchronisation brings both indexes' totals; each side then materialises what the page can need
-//     (min(total, limit) in page order for docid pages, every match for limit 0 and for deep SORT _score);
-//   - deep SORT _score: each side scores its matches with its own index's columns on local slots, then the delta's
-//     slots become table ids, and each side's (key, docid') run is sorted by the bitonic network;
-//   - rank_merge_kernel cuts every query's page from the two sorted, disjoint runs, in one launch.
-// Everything lives in the batch's d_merge scratch.
-struct MergedPages {
+// The bitmap group (limit 0, docid pages past 16384, deep SORT _score): for every query its total and its page, from
+// one index, or on a mutable table's primary batch from two (mgx_batch_merge_local: merge_other, the delta's batch)
+// with exactly the page an index built from the table's current documents returns.
+//   - one synchronisation brings the funnel counters and every side's totals; each side then materialises what the page
+//     can need (min(total, limit) in page order for docid pages, every match for limit 0 and for deep SORT _score);
+//   - deep SORT _score: each side scores its matches with its own index's columns on local slots; when two sides merge,
+//     the delta's slots then become table ids; each side's (key, docid') run is sorted by the bitonic network;
+//   - rank_merge_kernel cuts every query's page from its sorted, disjoint runs (one per side), in one launch.
+// Everything lives in the batch's d_merge scratch. On the delta's batch of a merge (merged_away) every page is empty:
+// the primary's fetch returned them.
+struct BitmapPages {
   std::vector<uint64_t> total, page_off, page_n;
   std::vector<uint32_t> docs;
-  std::vector<double> scores;
+  std::vector<double> scores;  // (deep SORT _score pages only)
 };
 
 static uint64_t Align8(uint64_t x) { return (x + 7) & ~7ull; }
 
-static int FetchBitmapMerged(mgx_batch* a, MergedPages* m) {
-  mgx_batch* b = a->merge_other;
-  mgx_batch* const side[2] = {a, b};
-  hipStream_t s = a->merge_stream;
+static int FetchBitmapPages(mgx_batch* a, BitmapPages* m) {
+  mgx_batch* const side[2] = {a, a->merge_other};
+  const int n_side = a->merge_other ? 2 : 1;
+  hipStream_t s = n_side == 2 ? a->merge_stream : a->last_stream;
   mgx_batch::Group& g = a->bitmap;
   const size_t n = g.qids.size();
-  for (mgx_batch* x : side)
-    if (x->last_stream != s) MGX_HIP(hipStreamSynchronize(x->last_stream));
-  // ---- the one synchronisation of the group: counters of the primary, totals of both ----
+  for (int k = 0; k < n_side; ++k)
+    if (side[k]->last_stream != s) MGX_HIP(hipStreamSynchronize(side[k]->last_stream));
+  // ---- the one synchronisation of the group: counters of the primary, totals of every side ----
   std::vector<uint64_t> tot[2] = {std::vector<uint64_t>(n), std::vector<uint64_t>(n)};
   MGX_HIP(hipMemcpyAsync(g.h_counters.data(), g.d_counters.p, n * 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-  for (int k = 0; k < 2; ++k) MGX_HIP(hipMemcpyAsync(tot[k].data(), side[k]->d_totals.p, n * 8, hipMemcpyDeviceToHost, s));
+  for (int k = 0; k < n_side; ++k)
+    MGX_HIP(hipMemcpyAsync(tot[k].data(), side[k]->d_totals.p, n * 8, hipMemcpyDeviceToHost, s));
   MGX_HIP(hipStreamSynchronize(s));
   // ---- sizes and the scratch layout ----
   m->total.resize(n);
@@ -3130,7 +3133,7 @@ static int FetchBitmapMerged(mgx_batch* a, MergedPages* m) {
   uint64_t at[2] = {0, 0}, n_scores = 0, n_keys = 0, pages = 0, elems = 0;
   for (size_t i = 0; i < n; ++i) {
     const QuerySpec& sp = a->specs[g.qids[i]];
-    const uint64_t t = tot[0][i] + tot[1][i];
+    const uint64_t t = a->merged_away ? 0 : tot[0][i] + tot[1][i];  // (merged_away: sizes the empty page only)
     uint64_t lo = 0, hi = 0;
     if (sp.deep_score) {
       lo = std::min<uint64_t>(sp.offset, t);
@@ -3138,7 +3141,8 @@ static int FetchBitmapMerged(mgx_batch* a, MergedPages* m) {
     } else {
       hi = sp.limit == 0 ? t : std::min<uint64_t>(t, sp.limit);  // (docid order: no offset, see Compile)
     }
-    m->total[i] = t;
+    // one index reports the funnel's count (slot 4) like the other groups; a merge, the table-wide sum
+    m->total[i] = n_side == 2 ? t : g.h_counters[i * 8 + 4];
     m->page_off[i] = pages;
     m->page_n[i] = hi - lo;
     pages += hi - lo;
@@ -3148,7 +3152,7 @@ static int FetchBitmapMerged(mgx_batch* a, MergedPages* m) {
     r.lo = static_cast<uint32_t>(lo);
     r.hi = static_cast<uint32_t>(hi);
     r.out_off = m->page_off[i];
-    for (int k = 0; k < 2; ++k) {
+    for (int k = 0; k < n_side; ++k) {
       // a docid page needs each side's first hi ids in page order; a score page needs every match
       take[k][i] = hi == lo ? 0 : sp.deep_score ? tot[k][i] : std::min<uint64_t>(tot[k][i], hi);
       off[k][i] = at[k];
@@ -3168,11 +3172,12 @@ static int FetchBitmapMerged(mgx_batch* a, MergedPages* m) {
       }
     }
     r.a_n = static_cast<uint32_t>(take[0][i]);
-    r.b_n = static_cast<uint32_t>(take[1][i]);
+    r.b_n = static_cast<uint32_t>(take[1][i]);  // (one index: 0, so an element's rank is its index in its own run)
     run_start[i] = elems;
     elems += take[0][i] + take[1][i];
   }
   run_start[n] = elems;
+  if (elems == 0) return MGX_OK;  // every page is empty
   if (elems > 0xFFFFFFFFull || pages > 0xFFFFFFFFull || n_keys > 0xFFFFFFFFull)
     return Fail(MGX_ERR_OUT_OF_RANGE, "batch result exceeds 2^32 doc ids");
   for (size_t i = 0; i < n; ++i) {
@@ -3208,7 +3213,7 @@ static int FetchBitmapMerged(mgx_batch* a, MergedPages* m) {
   double* pscores = reinterpret_cast<double*>(base + o_pscores);
   // ---- each side materialises its part (expand_kernel, page order: ascending, or descending for reverse docid pages)
   std::vector<uint64_t> out_off[2];
-  for (int k = 0; k < 2; ++k) {
+  for (int k = 0; k < n_side; ++k) {
     mgx_batch* x = side[k];
     out_off[k] = off[k];
     if (k == 1)
@@ -3224,7 +3229,7 @@ static int FetchBitmapMerged(mgx_batch* a, MergedPages* m) {
   const uint32_t* d_terms = reinterpret_cast<const uint32_t*>(base + o_terms);
   const double* d_idfs = reinterpret_cast<const double*>(base + o_idfs);
   for (size_t i = 0; i < n; ++i)
-    for (int k = 0; k < 2; ++k) {
+    for (int k = 0; k < n_side; ++k) {
       if (n2[k][i] == 0) continue;
       mgx_batch* x = side[k];
       const QuerySpec& ks = x->specs[g.qids[i]];
@@ -3233,32 +3238,34 @@ static int FetchBitmapMerged(mgx_batch* a, MergedPages* m) {
                                             x->d_patterns.as<uint8_t>(), x->d_text_terms.as<DevTextTerm>(), ks.k1,
                                             ks.b, ks.avgdl, scores + soff[k][i], s));
     }
-  // ---- local slots -> table ids (a delta index numbers its documents in ascending table-id order) ----
-  for (int k = 0; k < 2; ++k) {
-    const mgx_index* ix = side[k]->idx;
-    if (ix->d_doc_map.p && at[k])
-      MGX_LAUNCH(LaunchRemapDocs(docs + (k == 0 ? 0 : at[0]), at[k], ix->d_doc_map.as<uint32_t>(), ix->dev.first_doc_id,
-                                 ix->dev.n_docs, s));
-  }
+  // ---- a merge: local slots -> table ids (a delta index numbers its documents in ascending table-id order; one index's
+  // fetch returns its own ids) ----
+  if (n_side == 2)
+    for (int k = 0; k < 2; ++k) {
+      const mgx_index* ix = side[k]->idx;
+      if (ix->d_doc_map.p && at[k])
+        MGX_LAUNCH(LaunchRemapDocs(docs + (k == 0 ? 0 : at[0]), at[k], ix->d_doc_map.as<uint32_t>(), ix->dev.first_doc_id,
+                                   ix->dev.n_docs, s));
+    }
   // ---- deep SORT _score: (key, docid') runs, each sorted best first (padding (0, 0) sorts to the tail) ----
   if (n_keys) {
     MGX_HIP(hipMemsetAsync(keys, 0, n_keys * 8, s));
     MGX_HIP(hipMemsetAsync(dprime, 0, n_keys * 4, s));
   }
   for (size_t i = 0; i < n; ++i)
-    for (int k = 0; k < 2; ++k) {
+    for (int k = 0; k < n_side; ++k) {
       if (n2[k][i] == 0) continue;
       MGX_LAUNCH(LaunchMakeSortKeys(docs + out_off[k][i], scores + soff[k][i], take[k][i], runs[i].descending,
                                     keys + koff[k][i], dprime + koff[k][i], s));
       MGX_LAUNCH(LaunchSortPairs(keys + koff[k][i], dprime + koff[k][i], n2[k][i], s));
     }
-  // ---- every query's page from its two runs ----
+  // ---- every query's page from its runs ----
   MGX_LAUNCH(LaunchRankMerge(reinterpret_cast<const DevMergeRun*>(base), reinterpret_cast<const uint64_t*>(base + o_start),
                              static_cast<uint32_t>(n), elems, docs, keys, dprime, pdocs, pscores, s));
   m->docs.resize(pages);
-  m->scores.resize(pages);
-  if (pages) {
-    MGX_HIP(hipMemcpyAsync(m->docs.data(), pdocs, pages * 4, hipMemcpyDeviceToHost, s));
+  if (pages) MGX_HIP(hipMemcpyAsync(m->docs.data(), pdocs, pages * 4, hipMemcpyDeviceToHost, s));
+  if (pages && n_keys) {  // (scores: a deep SORT _score page is in the batch)
+    m->scores.resize(pages);
     MGX_HIP(hipMemcpyAsync(m->scores.data(), pscores, pages * 8, hipMemcpyDeviceToHost, s));
   }
   MGX_HIP(hipStreamSynchronize(s));
@@ -3309,96 +3316,11 @@ static int FetchImpl(mgx_batch* b, mgx_result_view* out) {
     page_docs = reinterpret_cast<const uint32_t*>(h + b->so_docs);
     page_n = reinterpret_cast<const uint32_t*>(h + b->so_n);
   }
-  // ---- bitmap group: totals -> page sizes -> expand ----
-  std::vector<uint64_t> totals, take, out_off;
-  std::vector<uint32_t> bm_docs;
-  std::vector<std::vector<uint32_t>> deep_docs;
-  std::vector<std::vector<double>> deep_scores;
-  MergedPages merged;
-  const bool bm_merged = b->merge_other != nullptr && !b->bitmap.qids.empty();
-  if (bm_merged) {
-    int rc = FetchBitmapMerged(b, &merged);
+  // ---- bitmap group: totals -> page sizes -> pages ----
+  BitmapPages bm;
+  if (!b->bitmap.qids.empty()) {
+    int rc = FetchBitmapPages(b, &bm);
     if (rc) return rc;
-  } else if (!b->bitmap.qids.empty()) {
-    mgx_batch::Group& g = b->bitmap;
-    const size_t n = g.qids.size();
-    MGX_HIP(hipStreamSynchronize(s));  // (this group's sizes make a host round trip)
-    totals.resize(n);
-    take.resize(n);
-    out_off.resize(n);
-    MGX_HIP(hipMemcpy(g.h_counters.data(), g.d_counters.p, n * 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    MGX_HIP(hipMemcpy(totals.data(), b->d_totals.p, n * 8, hipMemcpyDeviceToHost));
-    uint64_t at = 0;
-    for (size_t i = 0; i < n; ++i) {
-      const QuerySpec& sp = b->specs[g.qids[i]];
-      take[i] = b->merged_away                   ? 0  // (the primary's fetch returned these pages, merged)
-                : (sp.limit == 0 || sp.deep_score) ? totals[i]
-                                                   : std::min<uint64_t>(totals[i], sp.limit);
-      out_off[i] = at;
-      at += take[i];
-    }
-    if (at > 0xFFFFFFFFull) return Fail(MGX_ERR_OUT_OF_RANGE, "batch result exceeds 2^32 doc ids");
-    bm_docs.resize(at);
-    if (at) {
-      if (b->d_out.bytes < at * 4) MGX_HIP(b->d_out.Alloc(at * 4));
-      MGX_HIP(hipMemcpyAsync(b->d_take.p, take.data(), n * 8, hipMemcpyHostToDevice, s));
-      MGX_HIP(hipMemcpyAsync(b->d_out_off.p, out_off.data(), n * 8, hipMemcpyHostToDevice, s));
-      MGX_LAUNCH(LaunchExpand(g.dev.rbits, b->d_tile_start.as<uint64_t>(), b->d_totals.as<uint64_t>(),
-                              b->d_take.as<uint64_t>(), b->d_out_off.as<uint64_t>(), b->d_reverse.as<uint32_t>(),
-                              static_cast<uint32_t>(n), idx->dev.n_tiles, idx->dev.first_doc_id,
-                              b->d_out.as<uint32_t>(), s));
-      MGX_HIP(hipMemcpyAsync(bm_docs.data(), b->d_out.p, at * 4, hipMemcpyDeviceToHost, s));
-      MGX_HIP(hipStreamSynchronize(s));
-    }
-    // deep SORT _score pages: BM25Scorer::ScoreDocuments over every match, ResultSorter::SortByScore by a full sort
-    deep_docs.assign(n, {});
-    deep_scores.assign(n, {});
-    for (size_t i = 0; i < n; ++i) {
-      const QuerySpec& sp = b->specs[g.qids[i]];
-      if (!sp.deep_score || take[i] == 0) continue;
-      const uint64_t m = take[i];
-      const uint32_t lo = static_cast<uint32_t>(std::min<uint64_t>(sp.offset, m));
-      const uint32_t hi = sp.limit == 0 ? static_cast<uint32_t>(m)
-                                        : static_cast<uint32_t>(std::min<uint64_t>(static_cast<uint64_t>(lo) + sp.limit, m));
-      if (hi == lo) continue;
-      uint64_t n2 = 2048;
-      while (n2 < m) n2 <<= 1;
-      const uint32_t* cand = b->d_out.as<uint32_t>() + out_off[i];
-      DevBuf d_g, d_i, d_sc, d_k, d_d, d_pd, d_ps;
-      MGX_HIP(Upload(d_g, sp.deep_grams.data(), sp.deep_grams.size()));
-      if (sp.text_terms.empty()) {
-        MGX_HIP(Upload(d_i, sp.deep_idfs.data(), sp.deep_idfs.size()));
-      } else {
-        const std::vector<double> idfs = DeepIdfs(b, sp);
-        MGX_HIP(Upload(d_i, idfs.data(), idfs.size()));
-      }
-      MGX_HIP(d_sc.Alloc(m * 8));
-      MGX_HIP(d_k.Alloc(n2 * 8));
-      MGX_HIP(d_d.Alloc(n2 * 4));
-      MGX_HIP(d_pd.Alloc(static_cast<size_t>(hi - lo) * 4));
-      MGX_HIP(d_ps.Alloc(static_cast<size_t>(hi - lo) * 8));
-      if (sp.text_terms.empty())
-        MGX_LAUNCH(LaunchScoreCandidates(idx->dev, cand, m, d_g.as<uint32_t>(), d_i.as<double>(),
-                                         static_cast<uint32_t>(sp.deep_grams.size()), sp.k1, sp.b, sp.avgdl,
-                                         d_sc.as<double>(), s));
-      else  // text-level scored terms: tf counted in the doc text, summed in scored-term order like the fused path
-        MGX_LAUNCH(LaunchScoreCandidatesMixed(idx->dev, cand, m, d_g.as<uint32_t>(), d_i.as<double>(),
-                                              static_cast<uint32_t>(sp.deep_grams.size()), b->d_patterns.as<uint8_t>(),
-                                              b->d_text_terms.as<DevTextTerm>(), sp.k1, sp.b, sp.avgdl,
-                                              d_sc.as<double>(), s));
-      MGX_HIP(hipMemsetAsync(d_k.as<uint64_t>() + m, 0, (n2 - m) * 8, s));
-      MGX_HIP(hipMemsetAsync(d_d.as<uint32_t>() + m, 0, (n2 - m) * 4, s));
-      MGX_LAUNCH(LaunchMakeSortKeys(cand, d_sc.as<double>(), m, sp.reverse ? 1 : 0, d_k.as<uint64_t>(),
-                                    d_d.as<uint32_t>(), s));
-      MGX_LAUNCH(LaunchSortPairs(d_k.as<uint64_t>(), d_d.as<uint32_t>(), n2, s));
-      MGX_LAUNCH(LaunchSortPage(d_k.as<uint64_t>(), d_d.as<uint32_t>(), lo, hi, sp.reverse ? 1 : 0,
-                                d_pd.as<uint32_t>(), d_ps.as<double>(), s));
-      deep_docs[i].resize(hi - lo);
-      deep_scores[i].resize(hi - lo);
-      MGX_HIP(hipMemcpyAsync(deep_docs[i].data(), d_pd.p, static_cast<size_t>(hi - lo) * 4, hipMemcpyDeviceToHost, s));
-      MGX_HIP(hipMemcpyAsync(deep_scores[i].data(), d_ps.p, static_cast<size_t>(hi - lo) * 8, hipMemcpyDeviceToHost, s));
-      MGX_HIP(hipStreamSynchronize(s));
-    }
   }
   const uint32_t* dp_docs = nullptr;
   const unsigned long long* dp_totals = nullptr;
@@ -3429,12 +3351,10 @@ static int FetchImpl(mgx_batch* b, mgx_result_view* out) {
     r.total = c[4];
     if (sc && b->merged_shards) r.total = override_tot[gi];
     if (pg && b->merged_shards) r.total = dp_totals[gi];
-    if (!sc && !pg && bm_merged) r.total = merged.total[gi];
-    r.n_docs = sc                         ? page_n[gi]
-               : pg                       ? static_cast<uint32_t>(std::min<uint64_t>(r.total, b->specs[qi].limit))
-               : bm_merged                ? static_cast<uint32_t>(merged.page_n[gi])
-               : b->specs[qi].deep_score ? static_cast<uint32_t>(deep_docs[gi].size())
-                                          : static_cast<uint32_t>(take[gi]);
+    if (!sc && !pg) r.total = bm.total[gi];
+    r.n_docs = sc   ? page_n[gi]
+               : pg ? static_cast<uint32_t>(std::min<uint64_t>(r.total, b->specs[qi].limit))
+                    : static_cast<uint32_t>(bm.page_n[gi]);
     r.docs_begin = static_cast<uint32_t>(n_out);
     n_out += r.n_docs;
   }
@@ -3453,16 +3373,10 @@ static int FetchImpl(mgx_batch* b, mgx_result_view* out) {
                   r.n_docs * sizeof(double));
     } else if (mode == kModeDocPage) {
       std::memcpy(dst, dp_docs + static_cast<size_t>(gi) * b->doc_page_stride, r.n_docs * sizeof(uint32_t));
-    } else if (bm_merged) {
-      std::memcpy(dst, merged.docs.data() + merged.page_off[gi], r.n_docs * sizeof(uint32_t));
-      if (b->specs[qi].deep_score)
-        std::memcpy(b->h_scores.data() + r.docs_begin, merged.scores.data() + merged.page_off[gi],
-                    r.n_docs * sizeof(double));
-    } else if (b->specs[qi].deep_score) {
-      std::memcpy(dst, deep_docs[gi].data(), r.n_docs * sizeof(uint32_t));
-      std::memcpy(b->h_scores.data() + r.docs_begin, deep_scores[gi].data(), r.n_docs * sizeof(double));
     } else {
-      std::memcpy(dst, bm_docs.data() + out_off[gi], r.n_docs * sizeof(uint32_t));
+      std::memcpy(dst, bm.docs.data() + bm.page_off[gi], r.n_docs * sizeof(uint32_t));
+      if (b->specs[qi].deep_score)
+        std::memcpy(b->h_scores.data() + r.docs_begin, bm.scores.data() + bm.page_off[gi], r.n_docs * sizeof(double));
     }
   }
   out->n_queries = b->n_queries;
@@ -4372,8 +4286,9 @@ int mgx_score_documents(mgx_index* idx, const uint32_t* candidates, uint64_t n_c
   if (!idx || (n_cand && (!candidates || !scores_out)) || (n_terms && (!gram_ids || !idfs)))
     return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_score_documents: null argument");
   if (!idx->can_score) return mgx::Fail(MGX_ERR_NOT_IMPLEMENTED, "index was created without tf/doc_len columns");
+  // (an id with bit 31 set would read as a text-level term (kDeepText): nothing bounds n_grams below 2^31)
   for (uint32_t i = 0; i < n_terms; ++i)
-    if (gram_ids[i] != mgx::kNoRow && gram_ids[i] >= idx->n_grams)
+    if (gram_ids[i] != mgx::kNoRow && (gram_ids[i] >= idx->n_grams || (gram_ids[i] & mgx::kDeepText) != 0))
       return mgx::Fail(MGX_ERR_OUT_OF_RANGE, "mgx_score_documents: unknown gram id");
   if (n_cand == 0) return MGX_OK;
   try {
@@ -4388,8 +4303,9 @@ int mgx_score_documents(mgx_index* idx, const uint32_t* candidates, uint64_t n_c
     MGX_HIP(mgx::Upload(d_i, idfs, n_terms));
     MGX_HIP(d_s.Alloc(n_cand * 8));
     MGX_HIP(lease.Ship(stream));
-    MGX_LAUNCH(mgx::LaunchScoreCandidates(idx->dev, d_c.as<uint32_t>(), n_cand, d_g.as<uint32_t>(), d_i.as<double>(),
-                                          n_terms, k1, b, avg_doc_length, d_s.as<double>(), stream));
+    MGX_LAUNCH(mgx::LaunchScoreCandidatesMixed(idx->dev, d_c.as<uint32_t>(), n_cand, d_g.as<uint32_t>(),
+                                               d_i.as<double>(), n_terms, nullptr, nullptr, k1, b, avg_doc_length,
+                                               d_s.as<double>(), stream));
     MGX_HIP(hipMemcpyAsync(scores_out, d_s.p, n_cand * 8, hipMemcpyDeviceToHost, stream));
     MGX_HIP(hipStreamSynchronize(stream));
     return MGX_OK;

@@ -3619,44 +3619,6 @@ __global__ void retain_kernel(DevIndex ix, const uint32_t* __restrict__ cand, ui
   keep[i] = ok ? 1 : 0;
 }
 
-// BM25Scorer::ScoreDocuments for single-gram terms over explicit candidates (bm25_scorer.cpp:71-91).
-__global__ void score_candidates_kernel(DevIndex ix, const uint32_t* __restrict__ cand, uint64_t n_cand,
-                                        const uint32_t* __restrict__ grams, const double* __restrict__ idfs,
-                                        uint32_t n_terms, double k1, double b, double one_minus_b, double k1_plus_1,
-                                        double avgdl_clamped, double* __restrict__ scores) {
-  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (i >= n_cand) return;
-  const uint32_t d = cand[i];
-  double score = 0.0;
-  if (d >= ix.first_doc_id && static_cast<uint64_t>(d) - ix.first_doc_id < ix.n_docs) {
-    const uint32_t slot = d - ix.first_doc_id;
-    const uint32_t dli = ix.doc_len[slot];
-    if (dli > 0) {  // empty / missing text => 0.0
-      const double dl = static_cast<double>(dli);
-      const double length_norm = one_minus_b + b * dl / avgdl_clamped;
-      for (uint32_t t = 0; t < n_terms; ++t) {
-        const uint32_t g = grams[t];
-        if (g == kNoRow) continue;  // term unknown to the index: tf = 0 everywhere
-        uint64_t lo = ix.offsets[g], hi = ix.offsets[g + 1];
-        const uint32_t row = ix.skip_row[g];
-        if (row != kNoRow) {
-          const uint32_t* r = ix.tile_off + static_cast<uint64_t>(row) * (ix.n_tiles + 1);
-          hi = lo + r[(slot >> kTileShift) + 1];
-          lo = lo + r[slot >> kTileShift];
-        }
-        const uint64_t p = lower_bound_u32(ix.docids, lo, hi, d);
-        if (p < hi && ix.docids[p] == d) {
-          const double tf = static_cast<double>(posting_tf(ix, p));
-          const double numerator = tf * k1_plus_1;
-          const double denominator = tf + k1 * length_norm;
-          score += idfs[t] * numerator / denominator;
-        }
-      }
-    }
-  }
-  scores[i] = score;
-}
-
 // BM25Scorer::ScoreDocuments as the reference runs it — every term's tf counted in the doc text (bm25_scorer.cpp:71-91)
 // — for terms of any length. One thread per candidate.
 __global__ void score_candidates_text_kernel(DevIndex ix, const uint32_t* __restrict__ cand, uint64_t n_cand,
@@ -4448,17 +4410,6 @@ int LaunchRetain(const DevIndex& ix, const uint32_t* cand, uint64_t n_cand, cons
   return 0;
 }
 
-int LaunchScoreCandidates(const DevIndex& ix, const uint32_t* cand, uint64_t n_cand, const uint32_t* grams,
-                          const double* idfs, uint32_t n_terms, double k1, double b, double avgdl, double* scores,
-                          hipStream_t s) {
-  if (n_cand == 0) return 0;
-  const double avg = avgdl > 1.0 ? avgdl : 1.0;
-  hipLaunchKernelGGL(score_candidates_kernel, dim3(static_cast<uint32_t>((n_cand + 255) / 256)), dim3(256), 0, s, ix,
-                     cand, n_cand, grams, idfs, n_terms, k1, b, 1.0 - b, k1 + 1.0, avg, scores);
-  MGX_KCHECK();
-  return 0;
-}
-
 int LaunchScoreCandidatesText(const DevIndex& ix, const uint32_t* cand, uint64_t n_cand, const uint8_t* term_bytes,
                               const uint32_t* term_off, const double* idfs, uint32_t n_terms, double k1, double b,
                               double avgdl, double* scores, hipStream_t s) {
@@ -4539,12 +4490,13 @@ int LaunchSortByScore(const uint32_t* docs, const double* scores, uint64_t n, in
 
 
 // ---------------------------------------------------------------------------------------------------------------
-// merged bitmap-group pages of a mutable table (main index + delta index, mgx_batch_merge_local)
+// bitmap-group pages: one index, or a mutable table's main + delta index merged (mgx_batch_merge_local)
 // ---------------------------------------------------------------------------------------------------------------
 
 // Deep SORT _score: BM25Scorer::ScoreDocuments (bm25_scorer.cpp:71-91) over explicit candidates with the scored terms of
 // the fused path — a gram term takes tf from its posting, a text-level term (kDeepText | t) counts it in the doc text —
 // summed in scored-term order, so the result equals the fused kernel's to the last bit. One thread per candidate.
+// mgx_score_documents runs it with gram terms only (no patterns, no text terms).
 __global__ void score_candidates_mixed_kernel(DevIndex ix, const uint32_t* __restrict__ cand, uint64_t n_cand,
                                               const uint32_t* __restrict__ terms, const double* __restrict__ idfs,
                                               uint32_t n_terms, const uint8_t* __restrict__ patterns,

@@ -68,9 +68,6 @@ int LaunchExpand(const uint64_t* rbits, const uint64_t* tile_start, const uint64
                  uint32_t first_doc_id, uint32_t* out, hipStream_t s);
 int LaunchRetain(const DevIndex& ix, const uint32_t* cand, uint64_t n_cand, const uint32_t* grams, uint32_t n_grams,
                  uint8_t* keep, hipStream_t s);
-int LaunchScoreCandidates(const DevIndex& ix, const uint32_t* cand, uint64_t n_cand, const uint32_t* grams,
-                          const double* idfs, uint32_t n_terms, double k1, double b, double avgdl, double* scores,
-                          hipStream_t s);
 int LaunchScoreCandidatesText(const DevIndex& ix, const uint32_t* cand, uint64_t n_cand, const uint8_t* term_bytes,
                               const uint32_t* term_off, const double* idfs, uint32_t n_terms, double k1, double b,
                               double avgdl, double* scores, hipStream_t s);
@@ -82,7 +79,7 @@ int LaunchSortPage(const uint64_t* keys, const uint32_t* dprime, uint32_t lo, ui
                    uint32_t* out_docs, double* out_scores, hipStream_t s);
 int LaunchMakeSortKeys(const uint32_t* docs, const double* scores, uint64_t n, int descending, uint64_t* keys,
                        uint32_t* dprime, hipStream_t s);
-// merged bitmap-group pages of a mutable table (mgx_batch_merge_local)
+// bitmap-group pages (one index, or merged with a delta: mgx_batch_merge_local); the scorer also serves mgx_score_documents
 int LaunchScoreCandidatesMixed(const DevIndex& ix, const uint32_t* cand, uint64_t n_cand, const uint32_t* terms,
                                const double* idfs, uint32_t n_terms, const uint8_t* patterns,
                                const DevTextTerm* text_terms, double k1, double b, double avgdl, double* scores,
