@@ -2561,14 +2561,18 @@ static int UploadGroup(mgx_batch* b, Group& g, uint32_t mode, const std::vector<
   sec.Mark(5);
   if (const int rc = UploadItems(b, g, specs, p)) return rc;
   sec.Mark(6);
-  if (std::getenv("MGX_VERBOSE"))
+  if (std::getenv("MGX_VERBOSE")) {
+    size_t fast_queries = 0;
+    for (Route r : p.route) fast_queries += r == Route::kFast ? 1 : 0;
     fprintf(stderr,
-            "[mgx] %s group: %u queries; fast path %zu items (lds %u B, ring %u), wave kernel %zu items (lds %u B), "
-            "block kernel %zu items (lds %u B), candidate-driven %zu queries, list merge %zu items\n",
+            "[mgx] %s group: %u queries; fast path %zu items (%zu queries, lds %u B, ring %u), wave kernel %zu items "
+            "(lds %u B, lists %zu), block kernel %zu items (lds %u B), candidate-driven %zu queries, list merge %zu "
+            "items\n",
             p.score_mode ? "score" : p.page_mode ? "docid-page" : p.df_mode ? "df" : "bitmap", p.n,
-            p.fast[0].size() + p.fast[1].size() + p.fast[2].size() + p.fast[3].size() + p.fast[4].size(),
-            g.fplan.bytes, g.fplan.ring, p.wave.size() + p.wave_lists.size(), g.wplan.bytes, p.block.size(),
-            g.plan.bytes, p.cand.size(), p.merge.size());
+            p.fast[0].size() + p.fast[1].size() + p.fast[2].size() + p.fast[3].size() + p.fast[4].size(), fast_queries,
+            g.fplan.bytes, g.fplan.ring, p.wave.size() + p.wave_lists.size(), g.wplan.bytes, p.wave_lists.size(),
+            p.block.size(), g.plan.bytes, p.cand.size(), p.merge.size());
+  }
   return MGX_OK;
 }
 

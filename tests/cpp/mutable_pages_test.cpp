@@ -1,7 +1,8 @@
 // mutable_pages_test.cpp — queries without a page bound on a table with a delta index, through
 // search_pipeline::ExecuteBatch: limit 0 (the full result vector), docid pages past 16384, deep SORT _score pages, on
-// term, expression (ast) and FUZZY queries with and without verify_text. The bar: a changed table returns what an Index
-// built from the same current documents returns (docs, totals, scores bit for bit). Needs a GPU; built and run by
+// term, expression (ast) and FUZZY queries with and without verify_text; the SORT _score pages (bounded, deep, limit 0)
+// once more at two BM25 parameter sets other than the defaults. The bar: a changed table returns what an Index built from
+// the same current documents returns (docs, totals, scores bit for bit). Needs a GPU; built and run by
 // tests/test_gpu_mutable_pages_cpp.py.
 #include <cstdint>
 #include <cstdio>
@@ -106,6 +107,24 @@ static std::vector<BatchQuery> Queries() {
   return qs;
 }
 
+// Every SORT _score query of Queries() plus bounded pages, at (k1, b) (BatchQuery::bm25).
+static std::vector<BatchQuery> ScoredAt(double k1, double b) {
+  std::vector<BatchQuery> qs;
+  for (BatchQuery& q : Queries())
+    if (q.sort_by_score) qs.push_back(std::move(q));
+  for (SortOrder o : {SortOrder::ASC, SortOrder::DESC}) {
+    qs.push_back(Terms({"gamma", "ta"}, true, o, 10));
+    qs.push_back(Terms({"ta", "ma"}, true, o, 100, 7));
+    qs.push_back(Terms({"alpha", "ta", "ma"}, true, o, 1));
+    qs.push_back(Terms({"zzqx", "ta"}, true, o, 10));
+  }
+  for (BatchQuery& q : qs) {
+    q.bm25.k1 = k1;
+    q.bm25.b = b;
+  }
+  return qs;
+}
+
 static bool SamePage(const BatchResult& a, const BatchResult& b) {
   return a.results == b.results && a.scores == b.scores && a.total == b.total;
 }
@@ -134,6 +153,27 @@ static void Compare(Index& table, const std::map<DocId, std::string>& docs, cons
     nonempty += (*got)[i].results.empty() ? 0 : 1;
   }
   EXPECT(nonempty + 2 >= qs.size());  // (every shape returns a page; zzqx may be absent from the delta after compaction)
+  // the scored pages at parameters other than the defaults: the table's statistics (main + delta) and the merge of main
+  // and delta pages carry k1 and b through
+  for (const auto& kb : {std::make_pair(0.3, 1.0), std::make_pair(20.0, 0.0)}) {
+    const std::vector<BatchQuery> sq = ScoredAt(kb.first, kb.second);
+    auto g = ExecuteBatch(table, sq);
+    auto w = ExecuteBatch(fresh, sq);
+    auto d = ExecuteBatch(table, ScoredAt(1.2, 0.75));
+    EXPECT(g.has_value() && w.has_value() && d.has_value());
+    if (!g || !w || !d) continue;
+    size_t differ = 0;
+    for (size_t i = 0; i < sq.size(); ++i) {
+      const bool same = SamePage((*g)[i], (*w)[i]);
+      EXPECT(same);
+      if (!same)
+        std::printf("  %s: k1 %g b %g: query %zu differs: total %llu/%llu, %zu/%zu docs\n", round, kb.first, kb.second, i,
+                    static_cast<unsigned long long>((*g)[i].total), static_cast<unsigned long long>((*w)[i].total),
+                    (*g)[i].results.size(), (*w)[i].results.size());
+      differ += (*g)[i].scores != (*d)[i].scores ? 1 : 0;
+    }
+    EXPECT(differ + 2 >= sq.size());  // (the parameters reached the device: scores other than the defaults' ones)
+  }
   EXPECT((*want)[0].results.size() == (*want)[0].total && (*want)[0].total > 1000);  // limit 0: the full vector
   // a limit-0 query's funnel counters equal those of the same query with limit 10, on the same table
   std::vector<BatchQuery> pair = {Terms({"alpha"}, false, SortOrder::ASC, 0), Terms({"alpha"}, false, SortOrder::ASC, 10)};

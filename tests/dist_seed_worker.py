@@ -58,6 +58,29 @@ def main():
         assert np.array_equal(g.scores, w.scores), q.terms
         hits += w.total > 0
     assert hits > 300
+    # away from the default BM25 parameters: the seeds' keys and the exchanged bounds are scores at (k1, b); the
+    # unsharded index answers the same, and on rank 0 a sample is held against the oracle at those parameters too
+    qs2 = [Q(q.terms, sort_score=True, limit=q.limit, offset=q.offset, descending=q.descending,
+             k1=(2.0, 0.3, 20.0)[i % 3], b=(0.3, 1.0, 0.0)[i % 3]) for i, q in enumerate(qs)]
+    batch2 = table.prepare(qs2)
+    table.run(batch2)
+    got2 = batch2.fetch()
+    want2 = whole.search_batch(qs2)
+    for q, g, w in zip(qs2, got2, want2):
+        assert g.total == w.total, (q.terms, q.k1, q.b, g.total, w.total)
+        assert g.docs.tolist() == w.docs.tolist(), (q.terms, q.k1, q.b, q.limit, q.offset, q.descending)
+        assert np.array_equal(g.scores, w.scores), (q.terms, q.k1, q.b)
+    if rank == 0:
+        from oracle import oracle as O
+        c = whole.columns
+        o_idx = O.Index.from_csr(2, 0, True, c.key_bytes, c.key_off, c.offsets, c.docids)
+        o_store = O.DocumentStore.from_arrays(whole.corpus.text_bytes, whole.corpus.text_off)
+        for q, g in list(zip(qs2, got2))[:12]:
+            total, docs, scores = O.search_scored(o_idx, o_store, [O.normalize_text(t) for t in q.terms],
+                                                  whole.total_docs, whole.avg_doc_length, q.k1, q.b, q.descending,
+                                                  q.limit, q.offset)
+            assert g.total == total and g.docs.tolist() == docs.tolist(), (q.terms, q.k1, q.b)
+            assert np.array_equal(g.scores, scores), (q.terms, q.k1, q.b)
     print("ok")
 
 

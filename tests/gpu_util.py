@@ -21,13 +21,17 @@ def densify(docs):
 class Pair:
     """The same index on the device (mg.Index) and in the oracle."""
 
-    def __init__(self, docs=None, corpus=None, first_doc_id=1, ngram=2, kanji=0, cross=True, dense_threshold=0.0):
+    def __init__(self, docs=None, corpus=None, first_doc_id=1, ngram=2, kanji=0, cross=True, dense_threshold=0.0,
+                 total_docs=None, avg_doc_length=None):
+        """total_docs / avg_doc_length: BM25 statistics other than the index's own (a shard scores with the table's),
+        used by the device index and the oracle alike; None keeps the index's own."""
         if corpus is None:
             first_doc_id, texts = densify(docs)
             corpus = mg.Corpus.from_texts(texts)
         self.corpus = corpus
         self.dev = mg.Index(corpus=corpus, first_doc_id=first_doc_id, ngram_size=ngram, kanji_ngram_size=kanji,
-                            cross_boundary=cross, dense_threshold=dense_threshold)
+                            cross_boundary=cross, dense_threshold=dense_threshold, total_docs=total_docs,
+                            avg_doc_length=avg_doc_length)
         c = self.dev.columns
         # the oracle adopts the CSR arrays; tests/test_host_cpu.py pins those arrays to the oracle's own text-level build
         self.oidx = O.Index.from_csr(ngram, kanji, cross, c.key_bytes, c.key_off, c.offsets, c.docids)
@@ -41,6 +45,10 @@ class Pair:
                     self.ostore.add(first_doc_id + i, t)
         self.N, self.total_len = c.bm25_doc_count, c.bm25_total_len
         self.avgdl = c.avg_doc_length()
+        if total_docs is not None:
+            self.N = total_docs
+        if avg_doc_length is not None:
+            self.avgdl = avg_doc_length
         self.filters = {}  # bitmap id -> sorted docids
 
     def add_filter(self, docids):

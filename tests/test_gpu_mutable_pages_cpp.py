@@ -1,5 +1,6 @@
 """-m gpu: builds tests/cpp/mutable_pages_test.cpp (queries without a page bound — limit 0, docid pages past 16384, deep
-SORT _score — on a table with a delta index, through search_pipeline::ExecuteBatch: term, expression and FUZZY queries)
+SORT _score — on a table with a delta index, through search_pipeline::ExecuteBatch: term, expression and FUZZY queries;
+the SORT _score pages also at two (k1, b) pairs other than the defaults)
 against libmygram_shim.so + libmygram_gpu.so and runs it."""
 import os
 import subprocess
