@@ -3103,6 +3103,19 @@ struct BitmapPages {
 
 static uint64_t Align8(uint64_t x) { return (x + 7) & ~7ull; }
 
+// One scored run as (key, docid') pairs sorted best first by the bitonic network: keys/dprime[0, n) from docs and
+// scores, [n, n2) padding (0, 0) that sorts to the tail (n2: a power of two, at least one LDS run).
+static int SortRun(const uint32_t* docs, const double* scores, uint64_t n, uint64_t n2, int descending, uint64_t* keys,
+                   uint32_t* dprime, hipStream_t s) {
+  if (n2 > n) {
+    MGX_HIP(hipMemsetAsync(keys + n, 0, (n2 - n) * 8, s));
+    MGX_HIP(hipMemsetAsync(dprime + n, 0, (n2 - n) * 4, s));
+  }
+  MGX_LAUNCH(LaunchMakeSortKeys(docs, scores, n, descending, keys, dprime, s));
+  MGX_LAUNCH(LaunchSortPairs(keys, dprime, n2, s));
+  return MGX_OK;
+}
+
 static int FetchBitmapPages(mgx_batch* a, BitmapPages* m) {
   mgx_batch* const side[2] = {a, a->merge_other};
   const int n_side = a->merge_other ? 2 : 1;
@@ -3165,7 +3178,7 @@ static int FetchBitmapPages(mgx_batch* a, BitmapPages* m) {
         const QuerySpec& ks = side[k]->specs[g.qids[i]];
         soff[k][i] = n_scores;
         n_scores += take[k][i];
-        n2[k][i] = 2048;  // (LaunchSortPairs: a power of two, at least one LDS run)
+        n2[k][i] = 2048;  // (SortRun: a power of two, at least one LDS run)
         while (n2[k][i] < take[k][i]) n2[k][i] <<= 1;
         koff[k][i] = n_keys;
         n_keys += n2[k][i];
@@ -3251,17 +3264,13 @@ static int FetchBitmapPages(mgx_batch* a, BitmapPages* m) {
         MGX_LAUNCH(LaunchRemapDocs(docs + (k == 0 ? 0 : at[0]), at[k], ix->d_doc_map.as<uint32_t>(), ix->dev.first_doc_id,
                                    ix->dev.n_docs, s));
     }
-  // ---- deep SORT _score: (key, docid') runs, each sorted best first (padding (0, 0) sorts to the tail) ----
-  if (n_keys) {
-    MGX_HIP(hipMemsetAsync(keys, 0, n_keys * 8, s));
-    MGX_HIP(hipMemsetAsync(dprime, 0, n_keys * 4, s));
-  }
+  // ---- deep SORT _score: (key, docid') runs, each sorted best first ----
   for (size_t i = 0; i < n; ++i)
     for (int k = 0; k < n_side; ++k) {
       if (n2[k][i] == 0) continue;
-      MGX_LAUNCH(LaunchMakeSortKeys(docs + out_off[k][i], scores + soff[k][i], take[k][i], runs[i].descending,
-                                    keys + koff[k][i], dprime + koff[k][i], s));
-      MGX_LAUNCH(LaunchSortPairs(keys + koff[k][i], dprime + koff[k][i], n2[k][i], s));
+      const int rc = SortRun(docs + out_off[k][i], scores + soff[k][i], take[k][i], n2[k][i], runs[i].descending,
+                             keys + koff[k][i], dprime + koff[k][i], s);
+      if (rc) return rc;
     }
   // ---- every query's page from its runs ----
   MGX_LAUNCH(LaunchRankMerge(reinterpret_cast<const DevMergeRun*>(base), reinterpret_cast<const uint64_t*>(base + o_start),
@@ -3989,6 +3998,8 @@ void mgx_batch_destroy(mgx_batch* batch) {
   delete batch;
 }
 
+}  // extern "C"
+
 // =================================================================================================================
 // single operators
 // =================================================================================================================
@@ -3998,6 +4009,7 @@ namespace {
 struct SingleLease {
   mgx_index* idx;
   std::unique_ptr<mgx::BatchResources> res;
+  hipStream_t stream = nullptr;
   explicit SingleLease(mgx_index* i) : idx(i) {
     {
       std::lock_guard<std::mutex> lock(idx->pool_mu);
@@ -4013,60 +4025,113 @@ struct SingleLease {
     std::lock_guard<std::mutex> lock(idx->pool_mu);
     if (idx->single_pool.size() < 64) idx->single_pool.push_back(std::move(res));
   }
-  hipError_t Stream(hipStream_t* s) {
+  hipError_t OpenStream() {
     if (!res->stream) {
       const hipError_t e = hipStreamCreateWithFlags(&res->stream, hipStreamNonBlocking);
       if (e != hipSuccess) return e;
     }
-    *s = res->stream;
+    stream = res->stream;
     return hipSuccess;
   }
   // ships what Upload() staged in the lease's pinned mirror (calls that do not go through a batch's execute)
-  hipError_t Ship(hipStream_t s) {
+  hipError_t Ship() {
     for (const mgx::Arena::Chunk& c : res->upload.chunks)
       if (c.used) {
-        const hipError_t e = hipMemcpyAsync(c.dev, c.host, c.used, hipMemcpyHostToDevice, s);
+        const hipError_t e = hipMemcpyAsync(c.dev, c.host, c.used, hipMemcpyHostToDevice, stream);
         if (e != hipSuccess) return e;
       }
     res->uploaded = true;
     return hipSuccess;
   }
+  // copies a result back to the host behind the call's kernels and waits for it
+  hipError_t CopyBack(void* host, const void* dev, size_t bytes) {
+    const hipError_t e = hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, stream);
+    return e != hipSuccess ? e : hipStreamSynchronize(stream);
+  }
 };
-}  // namespace
 
-static int RunSingle(mgx_index* idx, mgx::QuerySpec&& spec, uint32_t** out_docs, uint64_t* out_n) {
-  *out_docs = nullptr;
-  *out_n = 0;
+// Every single operator's failure handling: an exception out of `body` becomes MGX_ERR_INTERNAL "<name>: <what>".
+template <class Body>
+int Guarded(const char* name, Body&& body) {
+  try {
+    return body();
+  } catch (const std::exception& e) {
+    return mgx::Fail(MGX_ERR_INTERNAL, std::string(name) + ": " + e.what());
+  }
+}
+
+// body(lease) on the index's device with a lease and its open stream. arenas: DevBuf::Alloc / Upload in `body` draw
+// from the lease's arenas (uploads go out with lease.Ship()); otherwise from their own hipMalloc (a batch run on the
+// lease takes the lease's resources itself, as mgx_batch::res).
+template <class Body>
+int WithLease(mgx_index* idx, const char* name, bool arenas, Body&& body) {
+  return Guarded(name, [&] {
+    MGX_HIP(hipSetDevice(idx->device));
+    SingleLease lease(idx);
+    MGX_HIP(lease.OpenStream());
+    mgx::ResourceScope scope(arenas ? lease.res.get() : nullptr);
+    return body(lease);
+  });
+}
+
+// Prepares and executes one compiled query as a batch of one on the lease.
+int ExecuteSingle(SingleLease& lease, mgx::QuerySpec&& spec, mgx_batch* b) {
   std::vector<mgx::QuerySpec> specs;
   specs.push_back(std::move(spec));
-  MGX_HIP(hipSetDevice(idx->device));
-  SingleLease lease(idx);
-  hipStream_t stream = nullptr;
-  MGX_HIP(lease.Stream(&stream));
-  mgx_batch batch_obj;
-  mgx_batch* b = &batch_obj;
   b->res = lease.res.get();
-  int rc = mgx::PrepareInto(b, idx, std::move(specs));
-  if (rc) return rc;
-  rc = mgx::ExecuteImpl(b, stream);
-  if (rc) return rc;
-  mgx_result_view v{};
-  rc = mgx::FetchImpl(b, &v);
-  if (rc) return rc;
-  const uint32_t n = v.queries[0].n_docs;
-  uint32_t* o = static_cast<uint32_t*>(std::malloc((n ? n : 1) * sizeof(uint32_t)));
-  if (!o) return mgx::Fail(MGX_ERR_INTERNAL, "out of host memory");
-  if (n) std::memcpy(o, v.docs, n * sizeof(uint32_t));
-  *out_docs = o;
-  *out_n = n;
+  const int rc = mgx::PrepareInto(b, lease.idx, std::move(specs));
+  return rc ? rc : mgx::ExecuteImpl(b, lease.stream);
+}
+
+// mgx_and / mgx_or / mgx_not / mgx_threshold: emit(c, q) compiles the query (nonzero: its argument error); within the
+// leaf limit it runs as a batch of one, and *out_docs (malloc) gets its ids.
+template <class Emit>
+int RunSingle(mgx_index* idx, const char* name, uint32_t** out_docs, uint64_t* out_n, Emit&& emit) {
+  return Guarded(name, [&] {
+    mgx::QuerySpec q;
+    mgx::Compiler c{idx, &q, 0};
+    const int rc = emit(c, q);
+    if (rc) return rc;
+    if (q.leaves.size() > mgx::kMaxLeaves)
+      return mgx::Fail(MGX_ERR_NOT_IMPLEMENTED, std::string(name) + ": more than 192 lists");
+    return WithLease(idx, name, false, [&](SingleLease& lease) {
+      mgx_batch b;
+      int rc = ExecuteSingle(lease, std::move(q), &b);
+      if (rc) return rc;
+      mgx_result_view v{};
+      rc = mgx::FetchImpl(&b, &v);
+      if (rc) return rc;
+      const uint32_t n = v.queries[0].n_docs;
+      uint32_t* o = static_cast<uint32_t*>(std::malloc((n ? n : 1) * sizeof(uint32_t)));
+      if (!o) return mgx::Fail(MGX_ERR_INTERNAL, "out of host memory");
+      if (n) std::memcpy(o, v.docs, n * sizeof(uint32_t));
+      *out_docs = o;
+      *out_n = n;
+      return MGX_OK;
+    });
+  });
+}
+
+// out-parameters cleared, then the arguments of every operator on gram ids checked
+int CheckSingle(const char* name, const mgx_index* idx, const uint32_t* g, uint32_t n, uint32_t** out_docs,
+                uint64_t* out_n) {
+  if (out_docs) *out_docs = nullptr;
+  if (out_n) *out_n = 0;
+  if (!idx || !out_docs || !out_n) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, std::string(name) + ": null argument");
+  if (n && !g) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, std::string(name) + ": null gram ids");
+  for (uint32_t i = 0; i < n; ++i)
+    if (g[i] >= idx->n_grams) return mgx::Fail(MGX_ERR_OUT_OF_RANGE, std::string(name) + ": unknown gram id");
   return MGX_OK;
 }
+}  // namespace
+
+extern "C" {
 
 int mgx_facet_counts(mgx_index* idx, const mgx_query* query, uint32_t column_id, uint64_t* counts_out, uint64_t* matched) {
   if (matched) *matched = 0;
   if (!idx || !query || !counts_out || !matched)
     return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_facet_counts: null argument");
-  try {
+  return WithLease(idx, "mgx_facet_counts", false, [&](SingleLease& lease) {
     // the search part as a materialising query: the result bitmap of every tile, then a histogram of the column's value
     // ids over it (what roaring_bitmap_and_cardinality per value bitmap adds up to, filter_index.cpp:300-306)
     mgx_query q = *query;
@@ -4088,101 +4153,60 @@ int mgx_facet_counts(mgx_index* idx, const mgx_query* query, uint32_t column_id,
     }
     const mgx_index::FilterColumn& col = *colp;
     if (!col.d_value_ids.p) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_facet_counts: the column was added without value ids");
-    std::vector<mgx::QuerySpec> specs;
-    specs.push_back(std::move(spec));
-    MGX_HIP(hipSetDevice(idx->device));
-    SingleLease lease(idx);
-    hipStream_t stream = nullptr;
-    MGX_HIP(lease.Stream(&stream));
-    mgx_batch batch_obj;
-    mgx_batch* b = &batch_obj;
-    b->res = lease.res.get();
-    rc = mgx::PrepareInto(b, idx, std::move(specs));
+    mgx_batch b;
+    rc = ExecuteSingle(lease, std::move(spec), &b);
     if (rc) return rc;
-    rc = mgx::ExecuteImpl(b, stream);
-    if (rc) return rc;
-    if (b->bitmap.qids.size() != 1) return mgx::Fail(MGX_ERR_INTERNAL, "mgx_facet_counts: the query did not compile to a result bitmap");
-    DevBuf d_counts;
-    {
-      mgx::ResourceScope none(nullptr);
-      MGX_HIP(d_counts.Alloc(std::max<size_t>(col.n_values, 1) * sizeof(unsigned long long)));
-    }
-    MGX_HIP(hipMemsetAsync(d_counts.p, 0, d_counts.bytes, stream));
-    MGX_LAUNCH(mgx::LaunchFacetCount(b->d_rbits.as<uint64_t>(), idx->dev.n_tiles * mgx::kWordsPerTile,
+    if (b.bitmap.qids.size() != 1) return mgx::Fail(MGX_ERR_INTERNAL, "mgx_facet_counts: the query did not compile to a result bitmap");
+    DevBuf d_counts;  // (own memory: no arena scope here)
+    MGX_HIP(d_counts.Alloc(std::max<size_t>(col.n_values, 1) * sizeof(unsigned long long)));
+    MGX_HIP(hipMemsetAsync(d_counts.p, 0, d_counts.bytes, lease.stream));
+    MGX_LAUNCH(mgx::LaunchFacetCount(b.d_rbits.as<uint64_t>(), idx->dev.n_tiles * mgx::kWordsPerTile,
                                      col.d_value_ids.as<uint32_t>(), idx->dev.n_docs, col.n_values,
-                                     d_counts.as<unsigned long long>(), stream));
+                                     d_counts.as<unsigned long long>(), lease.stream));
     uint64_t total = 0;
     if (col.n_values)
-      MGX_HIP(hipMemcpyAsync(counts_out, d_counts.p, static_cast<size_t>(col.n_values) * 8, hipMemcpyDeviceToHost, stream));
-    MGX_HIP(hipMemcpyAsync(&total, b->d_totals.p, 8, hipMemcpyDeviceToHost, stream));
-    MGX_HIP(hipStreamSynchronize(stream));
+      MGX_HIP(hipMemcpyAsync(counts_out, d_counts.p, static_cast<size_t>(col.n_values) * 8, hipMemcpyDeviceToHost,
+                             lease.stream));
+    MGX_HIP(lease.CopyBack(&total, b.d_totals.p, 8));
     *matched = total;
     return MGX_OK;
-  } catch (const std::exception& e) {
-    return mgx::Fail(MGX_ERR_INTERNAL, std::string("mgx_facet_counts: ") + e.what());
-  }
+  });
 }
-
-static int CheckGrams(const mgx_index* idx, const uint32_t* g, uint32_t n, const char* what) {
-  if (n && !g) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, std::string(what) + ": null gram ids");
-  for (uint32_t i = 0; i < n; ++i)
-    if (g[i] >= idx->n_grams) return mgx::Fail(MGX_ERR_OUT_OF_RANGE, std::string(what) + ": unknown gram id");
-  return MGX_OK;
-}
-
-#define MGX_SINGLE_PROLOGUE(name)                                                                    \
-  if (out_docs) *out_docs = nullptr;                                                                 \
-  if (out_n) *out_n = 0;                                                                             \
-  if (!idx || !out_docs || !out_n) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, name ": null argument"); \
-  {                                                                                                  \
-    int rc_ = CheckGrams(idx, gram_ids, n, name);                                                    \
-    if (rc_) return rc_;                                                                             \
-  }
 
 int mgx_and(mgx_index* idx, const uint32_t* gram_ids, uint32_t n, uint64_t limit, int reverse, uint32_t** out_docs,
             uint64_t* out_n) {
-  MGX_SINGLE_PROLOGUE("mgx_and");
+  if (int rc = CheckSingle("mgx_and", idx, gram_ids, n, out_docs, out_n)) return rc;
   if (n == 0) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_and: no grams (the caller returns {} for empty terms)");
   if (limit > 0xFFFFFFFFull) limit = 0;
-  try {
-    mgx::QuerySpec q;
-    mgx::Compiler c{idx, &q, 0};
+  return RunSingle(idx, "mgx_and", out_docs, out_n, [&](mgx::Compiler& c, mgx::QuerySpec& q) {
     c.Emit(mgx::kOpLoad, c.GramLeaf(gram_ids[0]));
     for (uint32_t i = 1; i < n; ++i) c.Emit(mgx::kOpAnd, c.GramLeaf(gram_ids[i]));
-    if (q.leaves.size() > mgx::kMaxLeaves) return mgx::Fail(MGX_ERR_NOT_IMPLEMENTED, "mgx_and: more than 192 lists");
     q.limit = static_cast<uint32_t>(limit);
     q.reverse = reverse ? 1 : 0;
-    return RunSingle(idx, std::move(q), out_docs, out_n);
-  } catch (const std::exception& e) {
-    return mgx::Fail(MGX_ERR_INTERNAL, std::string("mgx_and: ") + e.what());
-  }
+    return MGX_OK;
+  });
 }
 
 int mgx_or(mgx_index* idx, const uint32_t* gram_ids, uint32_t n, uint32_t** out_docs, uint64_t* out_n) {
-  MGX_SINGLE_PROLOGUE("mgx_or");
+  if (int rc = CheckSingle("mgx_or", idx, gram_ids, n, out_docs, out_n)) return rc;
   if (n == 0) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_or: no grams");
-  try {
-    mgx::QuerySpec q;
-    mgx::Compiler c{idx, &q, 0};
+  return RunSingle(idx, "mgx_or", out_docs, out_n, [&](mgx::Compiler& c, mgx::QuerySpec&) {
     c.Emit(mgx::kOpLoad, c.GramLeaf(gram_ids[0]));
     for (uint32_t i = 1; i < n; ++i) c.Emit(mgx::kOpOr, c.GramLeaf(gram_ids[i]));
-    if (q.leaves.size() > mgx::kMaxLeaves) return mgx::Fail(MGX_ERR_NOT_IMPLEMENTED, "mgx_or: more than 192 lists");
-    return RunSingle(idx, std::move(q), out_docs, out_n);
-  } catch (const std::exception& e) {
-    return mgx::Fail(MGX_ERR_INTERNAL, std::string("mgx_or: ") + e.what());
-  }
+    return MGX_OK;
+  });
 }
 
 int mgx_not(mgx_index* idx, const uint32_t* all_docs, uint64_t n_all, const uint32_t* gram_ids, uint32_t n,
             uint32_t** out_docs, uint64_t* out_n) {
-  MGX_SINGLE_PROLOGUE("mgx_not");
+  if (int rc = CheckSingle("mgx_not", idx, gram_ids, n, out_docs, out_n)) return rc;
   if (n_all && !all_docs) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_not: null all_docs");
   if (n_all > 0xFFFFFFFFull) return mgx::Fail(MGX_ERR_OUT_OF_RANGE, "mgx_not: too many docs");
-  try {
-    mgx::QuerySpec q;
-    mgx::Compiler c{idx, &q, 0};
-    // ids outside the index range cannot be in any posting list: they pass through untouched, in order
-    std::vector<uint32_t> below, above;
+  // ids outside the index range cannot be in any posting list: they pass through untouched, in order
+  std::vector<uint32_t> below, above;
+  uint32_t* mid = nullptr;
+  uint64_t n_mid = 0;
+  const int rc = RunSingle(idx, "mgx_not", &mid, &n_mid, [&](mgx::Compiler& c, mgx::QuerySpec& q) {
     const uint64_t lo = idx->dev.first_doc_id, hi = lo + idx->dev.n_docs;
     for (uint64_t i = 0; i < n_all; ++i) {
       if (i && all_docs[i] <= all_docs[i - 1])
@@ -4200,76 +4224,59 @@ int mgx_not(mgx_index* idx, const uint32_t* all_docs, uint64_t n_all, const uint
     q.leaves.push_back(lf);
     c.Emit(mgx::kOpLoad, 0);
     for (uint32_t i = 0; i < n; ++i) c.Emit(mgx::kOpAndNot, c.GramLeaf(gram_ids[i]));
-    if (q.leaves.size() > mgx::kMaxLeaves) return mgx::Fail(MGX_ERR_NOT_IMPLEMENTED, "mgx_not: more than 192 lists");
-    uint32_t* mid = nullptr;
-    uint64_t n_mid = 0;
-    int rc = RunSingle(idx, std::move(q), &mid, &n_mid);
-    if (rc) return rc;
-    if (below.empty() && above.empty()) {
-      *out_docs = mid;
-      *out_n = n_mid;
-      return MGX_OK;
-    }
-    const uint64_t tot = below.size() + n_mid + above.size();
-    uint32_t* o = static_cast<uint32_t*>(std::malloc((tot ? tot : 1) * 4));
-    if (!o) {
-      std::free(mid);
-      return mgx::Fail(MGX_ERR_INTERNAL, "out of host memory");
-    }
-    std::copy(below.begin(), below.end(), o);
-    std::copy(mid, mid + n_mid, o + below.size());
-    std::copy(above.begin(), above.end(), o + below.size() + n_mid);
-    std::free(mid);
-    *out_docs = o;
-    *out_n = tot;
     return MGX_OK;
-  } catch (const std::exception& e) {
-    return mgx::Fail(MGX_ERR_INTERNAL, std::string("mgx_not: ") + e.what());
+  });
+  if (rc) return rc;
+  if (below.empty() && above.empty()) {
+    *out_docs = mid;
+    *out_n = n_mid;
+    return MGX_OK;
   }
+  const uint64_t tot = below.size() + n_mid + above.size();
+  uint32_t* o = static_cast<uint32_t*>(std::malloc((tot ? tot : 1) * 4));
+  if (!o) {
+    std::free(mid);
+    return mgx::Fail(MGX_ERR_INTERNAL, "out of host memory");
+  }
+  std::copy(below.begin(), below.end(), o);
+  std::copy(mid, mid + n_mid, o + below.size());
+  std::copy(above.begin(), above.end(), o + below.size() + n_mid);
+  std::free(mid);
+  *out_docs = o;
+  *out_n = tot;
+  return MGX_OK;
 }
 
 int mgx_threshold(mgx_index* idx, const uint32_t* gram_ids, uint32_t n, uint32_t threshold, uint32_t** out_docs,
                   uint64_t* out_n) {
-  MGX_SINGLE_PROLOGUE("mgx_threshold");
+  if (int rc = CheckSingle("mgx_threshold", idx, gram_ids, n, out_docs, out_n)) return rc;
   if (n == 0 || threshold == 0 || threshold > n)
     return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_threshold: need 1 <= threshold <= number of distinct grams");
   if (n > 127) return mgx::Fail(MGX_ERR_OUT_OF_RANGE, "mgx_threshold: more than 127 grams");
-  try {
-    mgx::QuerySpec q;
-    mgx::Compiler c{idx, &q, 0};
+  return RunSingle(idx, "mgx_threshold", out_docs, out_n, [&](mgx::Compiler& c, mgx::QuerySpec& q) {
     c.Emit(mgx::kOpThreshBegin);
     for (uint32_t i = 0; i < n; ++i) c.Emit(mgx::kOpThreshAdd, c.GramLeaf(gram_ids[i]));
     c.Emit(mgx::kOpThreshEnd, threshold);
     if (q.leaves.size() != n) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_threshold: grams must be distinct");
-    if (q.leaves.size() > mgx::kMaxLeaves)
-      return mgx::Fail(MGX_ERR_NOT_IMPLEMENTED, "mgx_threshold: more than 192 lists");
-    return RunSingle(idx, std::move(q), out_docs, out_n);
-  } catch (const std::exception& e) {
-    return mgx::Fail(MGX_ERR_INTERNAL, std::string("mgx_threshold: ") + e.what());
-  }
+    return MGX_OK;
+  });
 }
 
 int mgx_retain(mgx_index* idx, const uint32_t* candidates, uint64_t n_cand, const uint32_t* gram_ids, uint32_t n,
                uint32_t** out_docs, uint64_t* out_n) {
-  MGX_SINGLE_PROLOGUE("mgx_retain");
+  if (int rc = CheckSingle("mgx_retain", idx, gram_ids, n, out_docs, out_n)) return rc;
   if (n_cand && !candidates) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_retain: null candidates");
-  try {
-    MGX_HIP(hipSetDevice(idx->device));
-    SingleLease lease(idx);
-    hipStream_t stream = nullptr;
-    MGX_HIP(lease.Stream(&stream));
-    mgx::ResourceScope scope(lease.res.get());
+  return WithLease(idx, "mgx_retain", true, [&](SingleLease& lease) {
     std::vector<uint8_t> keep(n_cand, 1);
     if (n_cand && n) {
       DevBuf d_c, d_g, d_k;
       MGX_HIP(mgx::Upload(d_c, candidates, n_cand));
       MGX_HIP(mgx::Upload(d_g, gram_ids, n));
       MGX_HIP(d_k.Alloc(n_cand));
-      MGX_HIP(lease.Ship(stream));
+      MGX_HIP(lease.Ship());
       MGX_LAUNCH(mgx::LaunchRetain(idx->dev, d_c.as<uint32_t>(), n_cand, d_g.as<uint32_t>(), n, d_k.as<uint8_t>(),
-                                   stream));
-      MGX_HIP(hipMemcpyAsync(keep.data(), d_k.p, n_cand, hipMemcpyDeviceToHost, stream));
-      MGX_HIP(hipStreamSynchronize(stream));
+                                   lease.stream));
+      MGX_HIP(lease.CopyBack(keep.data(), d_k.p, n_cand));
     }
     uint32_t* o = static_cast<uint32_t*>(std::malloc((n_cand ? n_cand : 1) * 4));
     if (!o) return mgx::Fail(MGX_ERR_INTERNAL, "out of host memory");
@@ -4279,9 +4286,7 @@ int mgx_retain(mgx_index* idx, const uint32_t* candidates, uint64_t n_cand, cons
     *out_docs = o;
     *out_n = k;
     return MGX_OK;
-  } catch (const std::exception& e) {
-    return mgx::Fail(MGX_ERR_INTERNAL, std::string("mgx_retain: ") + e.what());
-  }
+  });
 }
 
 int mgx_score_documents(mgx_index* idx, const uint32_t* candidates, uint64_t n_cand, const uint32_t* gram_ids,
@@ -4295,27 +4300,19 @@ int mgx_score_documents(mgx_index* idx, const uint32_t* candidates, uint64_t n_c
     if (gram_ids[i] != mgx::kNoRow && (gram_ids[i] >= idx->n_grams || (gram_ids[i] & mgx::kDeepText) != 0))
       return mgx::Fail(MGX_ERR_OUT_OF_RANGE, "mgx_score_documents: unknown gram id");
   if (n_cand == 0) return MGX_OK;
-  try {
-    MGX_HIP(hipSetDevice(idx->device));
-    SingleLease lease(idx);
-    hipStream_t stream = nullptr;
-    MGX_HIP(lease.Stream(&stream));
-    mgx::ResourceScope scope(lease.res.get());
+  return WithLease(idx, "mgx_score_documents", true, [&](SingleLease& lease) {
     DevBuf d_c, d_g, d_i, d_s;
     MGX_HIP(mgx::Upload(d_c, candidates, n_cand));
     MGX_HIP(mgx::Upload(d_g, gram_ids, n_terms));
     MGX_HIP(mgx::Upload(d_i, idfs, n_terms));
     MGX_HIP(d_s.Alloc(n_cand * 8));
-    MGX_HIP(lease.Ship(stream));
+    MGX_HIP(lease.Ship());
     MGX_LAUNCH(mgx::LaunchScoreCandidatesMixed(idx->dev, d_c.as<uint32_t>(), n_cand, d_g.as<uint32_t>(),
                                                d_i.as<double>(), n_terms, nullptr, nullptr, k1, b, avg_doc_length,
-                                               d_s.as<double>(), stream));
-    MGX_HIP(hipMemcpyAsync(scores_out, d_s.p, n_cand * 8, hipMemcpyDeviceToHost, stream));
-    MGX_HIP(hipStreamSynchronize(stream));
+                                               d_s.as<double>(), lease.stream));
+    MGX_HIP(lease.CopyBack(scores_out, d_s.p, n_cand * 8));
     return MGX_OK;
-  } catch (const std::exception& e) {
-    return mgx::Fail(MGX_ERR_INTERNAL, std::string("mgx_score_documents: ") + e.what());
-  }
+  });
 }
 
 int mgx_score_documents_text(mgx_index* idx, const uint32_t* candidates, uint64_t n_cand, const uint8_t* term_bytes,
@@ -4330,28 +4327,30 @@ int mgx_score_documents_text(mgx_index* idx, const uint32_t* candidates, uint64_
   if (n_terms && term_off[n_terms] > term_off[0] && !term_bytes)
     return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_score_documents_text: null term bytes");
   if (n_cand == 0) return MGX_OK;
-  try {
-    MGX_HIP(hipSetDevice(idx->device));
-    SingleLease lease(idx);
-    hipStream_t stream = nullptr;
-    MGX_HIP(lease.Stream(&stream));
-    mgx::ResourceScope scope(lease.res.get());
-    DevBuf d_c, d_t, d_o, d_i, d_s;
+  return WithLease(idx, "mgx_score_documents_text", true, [&](SingleLease& lease) {
+    // the mixed scorer with text-level terms only: term t is kDeepText | t, its bytes at term_off[t] - term_off[0]
+    std::vector<uint32_t> terms(n_terms);
+    std::vector<mgx::DevTextTerm> text_terms(n_terms);
+    for (uint32_t t = 0; t < n_terms; ++t) {
+      terms[t] = mgx::kDeepText | t;
+      text_terms[t] = {term_off[t] - term_off[0], term_off[t + 1] - term_off[t]};
+    }
+    const uint64_t n_bytes = n_terms ? term_off[n_terms] - term_off[0] : 0;
+    DevBuf d_c, d_t, d_p, d_tt, d_i, d_s;
     MGX_HIP(mgx::Upload(d_c, candidates, n_cand));
-    MGX_HIP(mgx::Upload(d_t, term_bytes, n_terms ? term_off[n_terms] : 0, 16));
-    MGX_HIP(mgx::Upload(d_o, term_off, n_terms + 1));
+    MGX_HIP(mgx::Upload(d_t, terms.data(), n_terms));
+    MGX_HIP(mgx::Upload(d_p, n_bytes ? term_bytes + term_off[0] : term_bytes, n_bytes, 16));
+    MGX_HIP(mgx::Upload(d_tt, text_terms.data(), n_terms));
     MGX_HIP(mgx::Upload(d_i, idfs, n_terms));
     MGX_HIP(d_s.Alloc(n_cand * 8));
-    MGX_HIP(lease.Ship(stream));
-    MGX_LAUNCH(mgx::LaunchScoreCandidatesText(idx->dev, d_c.as<uint32_t>(), n_cand, d_t.as<uint8_t>(),
-                                              d_o.as<uint32_t>(), d_i.as<double>(), n_terms, k1, b, avg_doc_length,
-                                              d_s.as<double>(), stream));
-    MGX_HIP(hipMemcpyAsync(scores_out, d_s.p, n_cand * 8, hipMemcpyDeviceToHost, stream));
-    MGX_HIP(hipStreamSynchronize(stream));
+    MGX_HIP(lease.Ship());
+    MGX_LAUNCH(mgx::LaunchScoreCandidatesMixed(idx->dev, d_c.as<uint32_t>(), n_cand, d_t.as<uint32_t>(),
+                                               d_i.as<double>(), n_terms, d_p.as<uint8_t>(),
+                                               d_tt.as<mgx::DevTextTerm>(), k1, b, avg_doc_length, d_s.as<double>(),
+                                               lease.stream));
+    MGX_HIP(lease.CopyBack(scores_out, d_s.p, n_cand * 8));
     return MGX_OK;
-  } catch (const std::exception& e) {
-    return mgx::Fail(MGX_ERR_INTERNAL, std::string("mgx_score_documents_text: ") + e.what());
-  }
+  });
 }
 
 int mgx_sort_by_score(mgx_index* idx, const uint32_t* results, const double* scores, uint64_t n, int descending,
@@ -4366,119 +4365,94 @@ int mgx_sort_by_score(mgx_index* idx, const uint32_t* results, const double* sco
   // (owned here until the call has succeeded: out-parameters stay NULL/0 on every failure path)
   std::unique_ptr<uint32_t, void (*)(void*)> page(
       static_cast<uint32_t*>(std::malloc(((end - start) ? (end - start) : 1) * 4)), std::free);
-  uint32_t* o = page.get();
-  if (!o) return mgx::Fail(MGX_ERR_INTERNAL, "out of host memory");
-  auto succeed = [&]() {
-    *out_docs = page.release();
-    *out_n = end - start;
-    return MGX_OK;
-  };
-  if (end == start) return succeed();
-  const bool bounded_page = limit != 0 && static_cast<uint64_t>(offset) + limit <= mgx::kMaxNeeded;
-  if (n > 4096 && !(bounded_page && n > 65536)) {
-    // the full-sort fallback (result_sorter.cpp:661-716 sorts whatever it is given; deep OFFSETs are benchmarked,
-    // docs/releases/v1.3.5.md:238): every pair sorted best first by the bitonic network, then the page is cut out
-    try {
-      MGX_HIP(hipSetDevice(idx->device));
-      SingleLease lease(idx);
-      hipStream_t stream = nullptr;
-      MGX_HIP(lease.Stream(&stream));
-      mgx::ResourceScope scope(lease.res.get());
-      uint64_t n2 = 2048;
-      while (n2 < n) n2 <<= 1;
-      DevBuf d_r, d_s, d_k, d_d, d_o;
+  if (!page) return mgx::Fail(MGX_ERR_INTERNAL, "out of host memory");
+  if (end > start) {
+    const bool bounded_page = limit != 0 && static_cast<uint64_t>(offset) + limit <= mgx::kMaxNeeded;
+    const int rc = WithLease(idx, "mgx_sort_by_score", true, [&](SingleLease& lease) {
+      const hipStream_t stream = lease.stream;
+      DevBuf d_r, d_s, d_o;
       MGX_HIP(mgx::Upload(d_r, results, n));
       MGX_HIP(mgx::Upload(d_s, scores, n));
-      MGX_HIP(d_k.Alloc(n2 * 8));
-      MGX_HIP(d_d.Alloc(n2 * 4));
-      MGX_HIP(d_o.Alloc((end - start) * 4));
-      MGX_HIP(hipMemsetAsync(d_k.as<uint64_t>() + n, 0, (n2 - n) * 8, stream));
-      MGX_HIP(hipMemsetAsync(d_d.as<uint32_t>() + n, 0, (n2 - n) * 4, stream));
-      MGX_HIP(lease.Ship(stream));
-      MGX_LAUNCH(mgx::LaunchMakeSortKeys(d_r.as<uint32_t>(), d_s.as<double>(), n, descending, d_k.as<uint64_t>(),
-                                         d_d.as<uint32_t>(), stream));
-      MGX_LAUNCH(mgx::LaunchSortPairs(d_k.as<uint64_t>(), d_d.as<uint32_t>(), n2, stream));
-      MGX_LAUNCH(mgx::LaunchSortPage(d_k.as<uint64_t>(), d_d.as<uint32_t>(), static_cast<uint32_t>(start),
-                                     static_cast<uint32_t>(end), descending, d_o.as<uint32_t>(), nullptr, stream));
-      MGX_HIP(hipMemcpyAsync(o, d_o.p, (end - start) * 4, hipMemcpyDeviceToHost, stream));
-      MGX_HIP(hipStreamSynchronize(stream));
-      return succeed();
-    } catch (const std::exception& e) {
-      return mgx::Fail(MGX_ERR_INTERNAL, std::string("mgx_sort_by_score: ") + e.what());
-    }
+      if (n > 4096 && !(bounded_page && n > 65536)) {
+        // the full-sort fallback (result_sorter.cpp:661-716 sorts whatever it is given; deep OFFSETs are benchmarked,
+        // docs/releases/v1.3.5.md:238): every pair sorted best first by the bitonic network, then the page is cut out
+        // of the one sorted run by rank_merge_kernel (an element's rank is its index in the run)
+        uint64_t n2 = 2048;
+        while (n2 < n) n2 <<= 1;
+        mgx::DevMergeRun run{};
+        run.kind = mgx::kMergeScore;
+        run.descending = descending ? 1u : 0u;
+        run.a_n = static_cast<uint32_t>(n);
+        run.lo = static_cast<uint32_t>(start);
+        run.hi = static_cast<uint32_t>(end);
+        const uint64_t run_start[2] = {0, n};
+        DevBuf d_run, d_start, d_k, d_d, d_ps;
+        MGX_HIP(mgx::Upload(d_run, &run, 1));
+        MGX_HIP(mgx::Upload(d_start, run_start, 2));
+        MGX_HIP(d_k.Alloc(n2 * 8));
+        MGX_HIP(d_d.Alloc(n2 * 4));
+        MGX_HIP(d_o.Alloc((end - start) * 4));
+        MGX_HIP(d_ps.Alloc((end - start) * 8));  // (the page's scores: written, not returned)
+        MGX_HIP(lease.Ship());
+        const int rc = mgx::SortRun(d_r.as<uint32_t>(), d_s.as<double>(), n, n2, descending, d_k.as<uint64_t>(),
+                                    d_d.as<uint32_t>(), stream);
+        if (rc) return rc;
+        MGX_LAUNCH(mgx::LaunchRankMerge(d_run.as<mgx::DevMergeRun>(), d_start.as<uint64_t>(), 1, n, nullptr,
+                                        d_k.as<uint64_t>(), d_d.as<uint32_t>(), d_o.as<uint32_t>(), d_ps.as<double>(),
+                                        stream));
+      } else if (n > 65536) {
+        // long arrays: per-wave top-(offset+limit) over strided shares, then the merge kernel of the batch path
+        const uint32_t needed = static_cast<uint32_t>(std::min<uint64_t>(static_cast<uint64_t>(offset) + limit, n));
+        uint32_t cap = 64;
+        while (cap < needed) cap <<= 1;
+        const uint32_t n_blocks = static_cast<uint32_t>(std::min<uint64_t>(256, (n + 16383) / 16384));
+        const uint32_t n_lists = n_blocks * (mgx::kBlock / 64);
+        mgx::DevQuery q{};
+        q.needed = needed;
+        q.cap = cap;
+        q.limit = limit;
+        q.offset = offset;
+        q.descending = descending ? 1 : 0;
+        const uint32_t zero = 0;
+        DevBuf d_k, d_d, d_ck, d_cd, d_cn, d_q, d_id, d_ps, d_pn;
+        MGX_HIP(mgx::Upload(d_q, &q, 1));
+        MGX_HIP(mgx::Upload(d_id, &zero, 1));
+        MGX_HIP(d_k.Alloc(n * 8));
+        MGX_HIP(d_d.Alloc(n * 4));
+        MGX_HIP(d_ck.Alloc(static_cast<size_t>(n_lists) * needed * 8));
+        MGX_HIP(d_cd.Alloc(static_cast<size_t>(n_lists) * needed * 4));
+        MGX_HIP(d_cn.Alloc(static_cast<size_t>(n_lists) * 4));
+        MGX_HIP(d_o.Alloc(static_cast<size_t>(limit) * 4));
+        MGX_HIP(d_ps.Alloc(static_cast<size_t>(limit) * 8));
+        MGX_HIP(d_pn.Alloc(4));
+        MGX_HIP(lease.Ship());
+        MGX_LAUNCH(mgx::LaunchMakeSortKeys(d_r.as<uint32_t>(), d_s.as<double>(), n, descending, d_k.as<uint64_t>(),
+                                           d_d.as<uint32_t>(), stream));
+        MGX_LAUNCH(mgx::LaunchTopKScan(d_k.as<uint64_t>(), d_d.as<uint32_t>(), n, needed, cap, descending, n_blocks,
+                                       d_ck.as<uint64_t>(), d_cd.as<uint32_t>(), d_cn.as<uint32_t>(), stream));
+        MGX_LAUNCH(mgx::LaunchMergeTopK(d_q.as<mgx::DevQuery>(), d_id.as<uint32_t>(), 1, n_lists, d_ck.as<uint64_t>(),
+                                        d_cd.as<uint32_t>(), d_cn.as<uint32_t>(), /*kq=*/0, /*kj=*/needed,
+                                        /*dj=*/needed, /*cq=*/0, /*cj=*/1, nullptr, nullptr, nullptr, 0,
+                                        d_o.as<uint32_t>(), d_ps.as<double>(), d_pn.as<uint32_t>(), limit, nullptr,
+                                        nullptr, nullptr, stream));
+      } else {
+        DevBuf d_k, d_d;
+        MGX_HIP(d_k.Alloc(n * 8));
+        MGX_HIP(d_d.Alloc(n * 4));
+        MGX_HIP(d_o.Alloc((end - start) * 4));
+        MGX_HIP(lease.Ship());
+        MGX_LAUNCH(mgx::LaunchSortByScore(d_r.as<uint32_t>(), d_s.as<double>(), n, descending,
+                                          static_cast<uint32_t>(start), static_cast<uint32_t>(end), d_k.as<uint64_t>(),
+                                          d_d.as<uint32_t>(), d_o.as<uint32_t>(), stream));
+      }
+      MGX_HIP(lease.CopyBack(page.get(), d_o.p, (end - start) * 4));
+      return MGX_OK;
+    });
+    if (rc) return rc;
   }
-  if (n > 65536) {
-    // long arrays: per-wave top-(offset+limit) over strided shares, then the merge kernel of the batch path
-    try {
-      MGX_HIP(hipSetDevice(idx->device));
-      SingleLease lease(idx);
-      hipStream_t stream = nullptr;
-      MGX_HIP(lease.Stream(&stream));
-      mgx::ResourceScope scope(lease.res.get());
-      const uint32_t needed = static_cast<uint32_t>(std::min<uint64_t>(static_cast<uint64_t>(offset) + limit, n));
-      uint32_t cap = 64;
-      while (cap < needed) cap <<= 1;
-      const uint32_t n_blocks = static_cast<uint32_t>(std::min<uint64_t>(256, (n + 16383) / 16384));
-      const uint32_t n_lists = n_blocks * (mgx::kBlock / 64);
-      mgx::DevQuery q{};
-      q.needed = needed;
-      q.cap = cap;
-      q.limit = limit;
-      q.offset = offset;
-      q.descending = descending ? 1 : 0;
-      const uint32_t zero = 0;
-      DevBuf d_r, d_s, d_k, d_d, d_ck, d_cd, d_cn, d_q, d_id, d_o, d_ps, d_pn;
-      MGX_HIP(mgx::Upload(d_r, results, n));
-      MGX_HIP(mgx::Upload(d_s, scores, n));
-      MGX_HIP(mgx::Upload(d_q, &q, 1));
-      MGX_HIP(mgx::Upload(d_id, &zero, 1));
-      MGX_HIP(d_k.Alloc(n * 8));
-      MGX_HIP(d_d.Alloc(n * 4));
-      MGX_HIP(d_ck.Alloc(static_cast<size_t>(n_lists) * needed * 8));
-      MGX_HIP(d_cd.Alloc(static_cast<size_t>(n_lists) * needed * 4));
-      MGX_HIP(d_cn.Alloc(static_cast<size_t>(n_lists) * 4));
-      MGX_HIP(d_o.Alloc(static_cast<size_t>(limit) * 4));
-      MGX_HIP(d_ps.Alloc(static_cast<size_t>(limit) * 8));
-      MGX_HIP(d_pn.Alloc(4));
-      MGX_HIP(lease.Ship(stream));
-      MGX_LAUNCH(mgx::LaunchMakeSortKeys(d_r.as<uint32_t>(), d_s.as<double>(), n, descending, d_k.as<uint64_t>(),
-                                         d_d.as<uint32_t>(), stream));
-      MGX_LAUNCH(mgx::LaunchTopKScan(d_k.as<uint64_t>(), d_d.as<uint32_t>(), n, needed, cap, descending, n_blocks,
-                                     d_ck.as<uint64_t>(), d_cd.as<uint32_t>(), d_cn.as<uint32_t>(), stream));
-      MGX_LAUNCH(mgx::LaunchMergeTopK(d_q.as<mgx::DevQuery>(), d_id.as<uint32_t>(), 1, n_lists, d_ck.as<uint64_t>(),
-                                      d_cd.as<uint32_t>(), d_cn.as<uint32_t>(), /*kq=*/0, /*kj=*/needed, /*dj=*/needed,
-                                      /*cq=*/0, /*cj=*/1, nullptr, nullptr, nullptr, 0, d_o.as<uint32_t>(),
-                                      d_ps.as<double>(), d_pn.as<uint32_t>(), limit, nullptr, nullptr, nullptr,
-                                      stream));
-      MGX_HIP(hipMemcpyAsync(o, d_o.p, (end - start) * 4, hipMemcpyDeviceToHost, stream));
-      MGX_HIP(hipStreamSynchronize(stream));
-      return succeed();
-    } catch (const std::exception& e) {
-      return mgx::Fail(MGX_ERR_INTERNAL, std::string("mgx_sort_by_score: ") + e.what());
-    }
-  }
-  try {
-    MGX_HIP(hipSetDevice(idx->device));
-    SingleLease lease(idx);
-    hipStream_t stream = nullptr;
-    MGX_HIP(lease.Stream(&stream));
-    mgx::ResourceScope scope(lease.res.get());
-    DevBuf d_r, d_s, d_k, d_d, d_o;
-    MGX_HIP(mgx::Upload(d_r, results, n));
-    MGX_HIP(mgx::Upload(d_s, scores, n));
-    MGX_HIP(d_k.Alloc(n * 8));
-    MGX_HIP(d_d.Alloc(n * 4));
-    MGX_HIP(d_o.Alloc((end - start) * 4));
-    MGX_HIP(lease.Ship(stream));
-    MGX_LAUNCH(mgx::LaunchSortByScore(d_r.as<uint32_t>(), d_s.as<double>(), n, descending,
-                                      static_cast<uint32_t>(start), static_cast<uint32_t>(end), d_k.as<uint64_t>(),
-                                      d_d.as<uint32_t>(), d_o.as<uint32_t>(), stream));
-    MGX_HIP(hipMemcpyAsync(o, d_o.p, (end - start) * 4, hipMemcpyDeviceToHost, stream));
-    MGX_HIP(hipStreamSynchronize(stream));
-    return succeed();
-  } catch (const std::exception& e) {
-    return mgx::Fail(MGX_ERR_INTERNAL, std::string("mgx_sort_by_score: ") + e.what());
-  }
+  *out_docs = page.release();
+  *out_n = end - start;
+  return MGX_OK;
 }
 
 }  // extern "C"

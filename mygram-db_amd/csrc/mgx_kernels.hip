@@ -1533,9 +1533,9 @@ __device__ __forceinline__ void wave_fetch_operand(const DevIndex& ix, const Dev
   }
 }
 
-// exact tf of gram `g` in the doc at `slot` (the nibble saturated, or the gram has no nibble row because its list is
-// sparse): binary search of the tile's posting segment; 0 when the doc lacks the gram
-__device__ __forceinline__ uint32_t exact_tf(const DevIndex& ix, uint32_t g, uint32_t row, uint32_t slot) {
+// the doc at `slot` in gram `g`'s posting list: binary search of its tile's segment (row: the gram's skip row); false
+// when the doc lacks the gram, else p = its posting's position
+__device__ __forceinline__ bool find_posting(const DevIndex& ix, uint32_t g, uint32_t row, uint32_t slot, uint64_t& p) {
   const uint32_t tile = slot >> kTileShift;
   const uint64_t l0 = ix.offsets[g];
   uint64_t lo = l0, hi = ix.offsets[g + 1];
@@ -1545,8 +1545,15 @@ __device__ __forceinline__ uint32_t exact_tf(const DevIndex& ix, uint32_t g, uin
     lo = l0 + r[tile];
   }
   const uint32_t d = ix.first_doc_id + slot;
-  const uint64_t p = lower_bound_u32(ix.docids, lo, hi, d);
-  return (p < hi && ix.docids[p] == d) ? posting_tf(ix, p) : 0u;
+  p = lower_bound_u32(ix.docids, lo, hi, d);
+  return p < hi && ix.docids[p] == d;
+}
+
+// exact tf of gram `g` in the doc at `slot` (the nibble saturated, or the gram has no nibble row because its list is
+// sparse); 0 when the doc lacks the gram
+__device__ __forceinline__ uint32_t exact_tf(const DevIndex& ix, uint32_t g, uint32_t row, uint32_t slot) {
+  uint64_t p;
+  return find_posting(ix, g, row, slot, p) ? posting_tf(ix, p) : 0u;
 }
 
 __device__ __forceinline__ void wave_score_body(const DevIndex ix, const DevBatch bt, const WavePlan plan) {
@@ -3603,51 +3610,10 @@ __global__ void retain_kernel(DevIndex ix, const uint32_t* __restrict__ cand, ui
   if (i >= n_cand) return;
   const uint32_t d = cand[i];
   bool ok = d >= ix.first_doc_id && static_cast<uint64_t>(d) - ix.first_doc_id < ix.n_docs;
-  for (uint32_t t = 0; ok && t < n_grams; ++t) {
-    const uint32_t g = grams[t];
-    uint64_t lo = ix.offsets[g], hi = ix.offsets[g + 1];
-    const uint32_t row = ix.skip_row[g];
-    if (row != kNoRow) {
-      const uint32_t tile = (d - ix.first_doc_id) >> kTileShift;
-      const uint32_t* r = ix.tile_off + static_cast<uint64_t>(row) * (ix.n_tiles + 1);
-      hi = lo + r[tile + 1];
-      lo = lo + r[tile];
-    }
-    const uint64_t p = lower_bound_u32(ix.docids, lo, hi, d);
-    ok = p < hi && ix.docids[p] == d;
-  }
+  uint64_t p;
+  for (uint32_t t = 0; ok && t < n_grams; ++t)
+    ok = find_posting(ix, grams[t], ix.skip_row[grams[t]], d - ix.first_doc_id, p);
   keep[i] = ok ? 1 : 0;
-}
-
-// BM25Scorer::ScoreDocuments as the reference runs it — every term's tf counted in the doc text (bm25_scorer.cpp:71-91)
-// — for terms of any length. One thread per candidate.
-__global__ void score_candidates_text_kernel(DevIndex ix, const uint32_t* __restrict__ cand, uint64_t n_cand,
-                                             const uint8_t* __restrict__ term_bytes,
-                                             const uint32_t* __restrict__ term_off, const double* __restrict__ idfs,
-                                             uint32_t n_terms, double k1, double b, double one_minus_b,
-                                             double k1_plus_1, double avgdl_clamped, double* __restrict__ scores) {
-  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (i >= n_cand) return;
-  const uint32_t d = cand[i];
-  double score = 0.0;
-  if (d >= ix.first_doc_id && static_cast<uint64_t>(d) - ix.first_doc_id < ix.n_docs) {
-    const uint32_t slot = d - ix.first_doc_id;
-    const uint64_t t0 = ix.text_off[slot], t1 = ix.text_off[slot + 1];
-    if (t1 > t0) {  // empty / missing text => 0.0
-      const double dl = static_cast<double>(ix.doc_len[slot]);
-      const double length_norm = one_minus_b + b * dl / avgdl_clamped;
-      for (uint32_t t = 0; t < n_terms; ++t) {
-        const double tf = static_cast<double>(text_count_occurrences(
-            ix.text, t0, t1, text_pattern(term_bytes + term_off[t], term_off[t + 1] - term_off[t]), false));
-        if (tf > 0.0) {
-          const double numerator = tf * k1_plus_1;
-          const double denominator = tf + k1 * length_norm;
-          score += idfs[t] * numerator / denominator;
-        }
-      }
-    }
-  }
-  scores[i] = score;
 }
 
 // (key, docid') pairs for ResultSorter::SortByScore on arbitrary inputs, and the trivial one-list "merge" input.
@@ -3740,16 +3706,6 @@ __global__ void sort_global_kernel(uint64_t* __restrict__ keys, uint32_t* __rest
     keys[i] = kl; docs[i] = dl;
     keys[l] = ki; docs[l] = di;
   }
-}
-
-// page[i] = docid of rank lo + i, scores likewise (scores may be null)
-__global__ void sort_page_kernel(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ dprime, uint32_t lo,
-                                 uint32_t hi, int descending, uint32_t* __restrict__ out_docs,
-                                 double* __restrict__ out_scores) {
-  const uint32_t i = lo + blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= hi) return;
-  out_docs[i - lo] = descending ? dprime[i] : ~dprime[i];
-  if (out_scores) out_scores[i - lo] = key_score(keys[i], descending != 0);
 }
 
 // SortByScore over an arbitrarily long (key, docid') array when only a bounded page is wanted: every wave keeps the
@@ -4410,17 +4366,6 @@ int LaunchRetain(const DevIndex& ix, const uint32_t* cand, uint64_t n_cand, cons
   return 0;
 }
 
-int LaunchScoreCandidatesText(const DevIndex& ix, const uint32_t* cand, uint64_t n_cand, const uint8_t* term_bytes,
-                              const uint32_t* term_off, const double* idfs, uint32_t n_terms, double k1, double b,
-                              double avgdl, double* scores, hipStream_t s) {
-  if (n_cand == 0) return 0;
-  const double avg = avgdl > 1.0 ? avgdl : 1.0;
-  hipLaunchKernelGGL(score_candidates_text_kernel, dim3(static_cast<uint32_t>((n_cand + 255) / 256)), dim3(256), 0, s,
-                     ix, cand, n_cand, term_bytes, term_off, idfs, n_terms, k1, b, 1.0 - b, k1 + 1.0, avg, scores);
-  MGX_KCHECK();
-  return 0;
-}
-
 // keys/dprime: the (key, docid') pairs of make_sort_keys_kernel. Returns the number of candidate lists written
 // (negative: a HIP error code negated).
 int LaunchTopKScan(const uint64_t* keys, const uint32_t* dprime, uint64_t n, uint32_t needed, uint32_t cap,
@@ -4457,15 +4402,6 @@ int LaunchSortPairs(uint64_t* keys, uint32_t* dprime, uint64_t n_pow2, hipStream
   return 0;
 }
 
-int LaunchSortPage(const uint64_t* keys, const uint32_t* dprime, uint32_t lo, uint32_t hi, int descending,
-                   uint32_t* out_docs, double* out_scores, hipStream_t s) {
-  if (hi <= lo) return 0;
-  hipLaunchKernelGGL(sort_page_kernel, dim3((hi - lo + 255) / 256), dim3(256), 0, s, keys, dprime, lo, hi, descending,
-                     out_docs, out_scores);
-  MGX_KCHECK();
-  return 0;
-}
-
 int LaunchMakeSortKeys(const uint32_t* docs, const double* scores, uint64_t n, int descending, uint64_t* keys,
                        uint32_t* dprime, hipStream_t s) {
   if (n == 0) return 0;
@@ -4496,7 +4432,9 @@ int LaunchSortByScore(const uint32_t* docs, const double* scores, uint64_t n, in
 // Deep SORT _score: BM25Scorer::ScoreDocuments (bm25_scorer.cpp:71-91) over explicit candidates with the scored terms of
 // the fused path — a gram term takes tf from its posting, a text-level term (kDeepText | t) counts it in the doc text —
 // summed in scored-term order, so the result equals the fused kernel's to the last bit. One thread per candidate.
-// mgx_score_documents runs it with gram terms only (no patterns, no text terms).
+// mgx_score_documents runs it with gram terms only (no patterns, no text terms), mgx_score_documents_text with
+// text-level terms only. A doc of length 0 has no grams; its text-level terms are still counted (an empty text has no
+// occurrence).
 __global__ void score_candidates_mixed_kernel(DevIndex ix, const uint32_t* __restrict__ cand, uint64_t n_cand,
                                               const uint32_t* __restrict__ terms, const double* __restrict__ idfs,
                                               uint32_t n_terms, const uint8_t* __restrict__ patterns,
@@ -4510,33 +4448,25 @@ __global__ void score_candidates_mixed_kernel(DevIndex ix, const uint32_t* __res
   if (d >= ix.first_doc_id && static_cast<uint64_t>(d) - ix.first_doc_id < ix.n_docs) {
     const uint32_t slot = d - ix.first_doc_id;
     const uint32_t dli = ix.doc_len[slot];
-    if (dli > 0) {  // empty / missing text => 0.0
-      const double dl = static_cast<double>(dli);
-      const double length_norm = one_minus_b + b * dl / avgdl_clamped;
-      for (uint32_t t = 0; t < n_terms; ++t) {
-        const uint32_t g = terms[t];
-        if (g == kNoRow) continue;  // term unknown to the index: tf = 0 everywhere
-        double tf = 0.0;
-        if (g & kDeepText) {
-          const DevTextTerm tt = text_terms[g & ~kDeepText];
-          tf = static_cast<double>(text_count_occurrences(ix.text, ix.text_off[slot], ix.text_off[slot + 1],
-                                                          text_pattern(patterns + tt.pat_off, tt.pat_len), false));
-        } else {
-          uint64_t lo = ix.offsets[g], hi = ix.offsets[g + 1];
-          const uint32_t row = ix.skip_row[g];
-          if (row != kNoRow) {
-            const uint32_t* r = ix.tile_off + static_cast<uint64_t>(row) * (ix.n_tiles + 1);
-            hi = lo + r[(slot >> kTileShift) + 1];
-            lo = lo + r[slot >> kTileShift];
-          }
-          const uint64_t p = lower_bound_u32(ix.docids, lo, hi, d);
-          if (p < hi && ix.docids[p] == d) tf = static_cast<double>(posting_tf(ix, p));
-        }
-        if (tf > 0.0) {
-          const double numerator = tf * k1_plus_1;
-          const double denominator = tf + k1 * length_norm;
-          score += idfs[t] * numerator / denominator;
-        }
+    // the doc's text for text-level terms (no text attached: gram terms only)
+    const uint64_t t0 = ix.text ? ix.text_off[slot] : 0, t1 = ix.text ? ix.text_off[slot + 1] : 0;
+    const double dl = static_cast<double>(dli);
+    const double length_norm = one_minus_b + b * dl / avgdl_clamped;
+    for (uint32_t t = 0; t < n_terms; ++t) {
+      const uint32_t g = terms[t];
+      if (g == kNoRow) continue;  // term unknown to the index: tf = 0 everywhere
+      double tf = 0.0;
+      if (g & kDeepText) {
+        const DevTextTerm tt = text_terms[g & ~kDeepText];
+        tf = static_cast<double>(
+            text_count_occurrences(ix.text, t0, t1, text_pattern(patterns + tt.pat_off, tt.pat_len), false));
+      } else if (dli > 0) {
+        tf = static_cast<double>(exact_tf(ix, g, ix.skip_row[g], slot));
+      }
+      if (tf > 0.0) {
+        const double numerator = tf * k1_plus_1;
+        const double denominator = tf + k1 * length_norm;
+        score += idfs[t] * numerator / denominator;
       }
     }
   }

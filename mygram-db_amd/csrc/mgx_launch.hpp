@@ -68,18 +68,14 @@ int LaunchExpand(const uint64_t* rbits, const uint64_t* tile_start, const uint64
                  uint32_t first_doc_id, uint32_t* out, hipStream_t s);
 int LaunchRetain(const DevIndex& ix, const uint32_t* cand, uint64_t n_cand, const uint32_t* grams, uint32_t n_grams,
                  uint8_t* keep, hipStream_t s);
-int LaunchScoreCandidatesText(const DevIndex& ix, const uint32_t* cand, uint64_t n_cand, const uint8_t* term_bytes,
-                              const uint32_t* term_off, const double* idfs, uint32_t n_terms, double k1, double b,
-                              double avgdl, double* scores, hipStream_t s);
 int LaunchTopKScan(const uint64_t* keys, const uint32_t* dprime, uint64_t n, uint32_t needed, uint32_t cap,
                    int descending, uint32_t n_blocks, uint64_t* cand_keys, uint32_t* cand_docs, uint32_t* cand_n,
                    hipStream_t s);
 int LaunchSortPairs(uint64_t* keys, uint32_t* dprime, uint64_t n_pow2, hipStream_t s);
-int LaunchSortPage(const uint64_t* keys, const uint32_t* dprime, uint32_t lo, uint32_t hi, int descending,
-                   uint32_t* out_docs, double* out_scores, hipStream_t s);
 int LaunchMakeSortKeys(const uint32_t* docs, const double* scores, uint64_t n, int descending, uint64_t* keys,
                        uint32_t* dprime, hipStream_t s);
-// bitmap-group pages (one index, or merged with a delta: mgx_batch_merge_local); the scorer also serves mgx_score_documents
+// bitmap-group pages (one index, or merged with a delta: mgx_batch_merge_local); the scorer also serves
+// mgx_score_documents and mgx_score_documents_text, the page cut mgx_sort_by_score's full sort
 int LaunchScoreCandidatesMixed(const DevIndex& ix, const uint32_t* cand, uint64_t n_cand, const uint32_t* terms,
                                const double* idfs, uint32_t n_terms, const uint8_t* patterns,
                                const DevTextTerm* text_terms, double k1, double b, double avgdl, double* scores,

@@ -1430,6 +1430,20 @@ std::vector<DocId> FinishTopN(std::vector<DocId> all, size_t limit, bool reverse
   }
   return all;
 }
+
+// The tail of every single-operator call: call(&out, &n) runs the mgx_* operator; its ids, or on failure {} and its
+// error recorded for the index and the thread.
+template <class Call>
+std::vector<DocId> DeviceIds(std::string* last_error, Call&& call) {
+  uint32_t* out = nullptr;
+  uint64_t n = 0;
+  if (call(&out, &n) != MGX_OK) {
+    *last_error = mgx_last_error();
+    SetDeviceError(*last_error);
+    return {};
+  }
+  return Take(out, n);
+}
 }  // namespace
 
 std::vector<DocId> Index::SearchAnd(const std::vector<std::string>& terms, size_t limit, bool reverse) const {
@@ -1448,14 +1462,9 @@ std::vector<DocId> Index::SearchAnd(const std::vector<std::string>& terms, size_
     if (!impl_->Lookup(t, &id)) return {};  // :211-215 unknown term
     ids.push_back(id);
   }
-  uint32_t* out = nullptr;
-  uint64_t n = 0;
-  if (mgx_and(impl_->dev, ids.data(), static_cast<uint32_t>(ids.size()), limit, reverse ? 1 : 0, &out, &n) != MGX_OK) {
-    impl_->last_error = mgx_last_error();
-    SetDeviceError(impl_->last_error);
-    return {};
-  }
-  return Take(out, n);
+  return DeviceIds(&impl_->last_error, [&](uint32_t** out, uint64_t* n) {
+    return mgx_and(impl_->dev, ids.data(), static_cast<uint32_t>(ids.size()), limit, reverse ? 1 : 0, out, n);
+  });
 }
 
 std::vector<DocId> Index::SearchOr(const std::vector<std::string>& terms) const {  // index.cpp:418-448
@@ -1475,14 +1484,9 @@ std::vector<DocId> Index::SearchOr(const std::vector<std::string>& terms) const 
   std::sort(ids.begin(), ids.end());
   ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
   if (ids.empty()) return {};
-  uint32_t* out = nullptr;
-  uint64_t n = 0;
-  if (mgx_or(impl_->dev, ids.data(), static_cast<uint32_t>(ids.size()), &out, &n) != MGX_OK) {
-    impl_->last_error = mgx_last_error();
-    SetDeviceError(impl_->last_error);
-    return {};
-  }
-  return Take(out, n);
+  return DeviceIds(&impl_->last_error, [&](uint32_t** out, uint64_t* n) {
+    return mgx_or(impl_->dev, ids.data(), static_cast<uint32_t>(ids.size()), out, n);
+  });
 }
 
 std::vector<DocId> Index::SearchNot(const std::vector<DocId>& all_docs, const std::vector<std::string>& terms) const {
@@ -1514,15 +1518,10 @@ std::vector<DocId> Index::SearchNot(const std::vector<DocId>& all_docs, const st
   std::vector<DocId> distinct;
   if (repeats) std::unique_copy(all_docs.begin(), all_docs.end(), std::back_inserter(distinct));
   const std::vector<DocId>& in = repeats ? distinct : all_docs;
-  uint32_t* out = nullptr;
-  uint64_t n = 0;
-  if (mgx_not(impl_->dev, in.data(), in.size(), ids.data(), static_cast<uint32_t>(ids.size()), &out, &n) != MGX_OK) {
-    impl_->last_error = mgx_last_error();
-    SetDeviceError(impl_->last_error);
-    return {};
-  }
-  std::vector<DocId> kept = Take(out, n);
-  if (!repeats) return kept;
+  std::vector<DocId> kept = DeviceIds(&impl_->last_error, [&](uint32_t** out, uint64_t* n) {
+    return mgx_not(impl_->dev, in.data(), in.size(), ids.data(), static_cast<uint32_t>(ids.size()), out, n);
+  });
+  if (!repeats || !tl_device_error.empty()) return kept;  // (a device failure: {})
   std::vector<DocId> res;
   size_t k = 0;
   for (size_t i = 0; i < all_docs.size();) {
@@ -1555,15 +1554,10 @@ std::vector<DocId> Index::SearchByThreshold(const std::vector<std::string>& term
     if (impl_->Lookup(t, &id)) ids.push_back(id);  // missing lists do not count (:512-518)
   }
   if (ids.size() < threshold) return {};           // :521-523
-  uint32_t* out = nullptr;
-  uint64_t n = 0;
-  if (mgx_threshold(impl_->dev, ids.data(), static_cast<uint32_t>(ids.size()), static_cast<uint32_t>(threshold), &out,
-                    &n) != MGX_OK) {
-    impl_->last_error = mgx_last_error();
-    SetDeviceError(impl_->last_error);
-    return {};
-  }
-  return Take(out, n);
+  return DeviceIds(&impl_->last_error, [&](uint32_t** out, uint64_t* n) {
+    return mgx_threshold(impl_->dev, ids.data(), static_cast<uint32_t>(ids.size()), static_cast<uint32_t>(threshold),
+                         out, n);
+  });
 }
 
 std::vector<DocId> Index::FilterByNgrams(const std::vector<DocId>& candidates,
@@ -1606,15 +1600,10 @@ std::vector<DocId> Index::FilterByNgrams(const std::vector<DocId>& candidates,
     if (!impl_->Lookup(t, &id)) return {};  // :381-385
     ids.push_back(id);
   }
-  uint32_t* out = nullptr;
-  uint64_t n = 0;
-  if (mgx_retain(impl_->dev, candidates.data(), candidates.size(), ids.data(), static_cast<uint32_t>(ids.size()), &out,
-                 &n) != MGX_OK) {
-    impl_->last_error = mgx_last_error();
-    SetDeviceError(impl_->last_error);
-    return {};
-  }
-  return Take(out, n);
+  return DeviceIds(&impl_->last_error, [&](uint32_t** out, uint64_t* n) {
+    return mgx_retain(impl_->dev, candidates.data(), candidates.size(), ids.data(), static_cast<uint32_t>(ids.size()),
+                      out, n);
+  });
 }
 
 // ---- BM25Scorer ---------------------------------------------------------------------------------------------------

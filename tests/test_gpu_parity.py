@@ -254,6 +254,21 @@ def test_score_documents_unknown_and_textless_candidates():
     assert score[1] == 0.0 and score[-1] == 0.0
 
 
+def test_score_documents_text_empty_and_unknown_candidates():
+    # mgx_score_documents_text (terms that are not one n-gram: tf counted in the doc text) on candidates with empty
+    # text, ids outside the index and terms longer than some documents, against BM25Scorer::ScoreDocuments
+    texts = ["", "ab", "abcab abcab", "abc", "x abcabcabc ab", ""] * 400 + ["abcab " * 50]
+    p = Pair(docs=list(enumerate(texts, start=1)))
+    n = len(texts)
+    cand = np.asarray([1, 6, 2, 3, 0, 9_000_000, 4, 5, n + 1] + list(range(7, n + 1, 7)) + [n, 1], dtype=np.uint32)
+    for terms in (["abcab"], ["abcabcabc", "ab", "abcab"], ["zzzzz", "abcabcabcabcabcabc"]):
+        dfs = [sum(1 for t in texts if term in t) for term in terms]
+        want = O.score_documents(p.ostore, cand, terms, dfs, p.N, p.avgdl)
+        got = p.dev.score_documents(cand, terms, dfs, p.N, p.avgdl)
+        assert np.array_equal(got, want), terms
+    assert want[0] == 0.0 and got[0] == 0.0  # (the empty text)
+
+
 def test_ties_break_on_docid_both_directions(score_kernel):
     # every doc identical => all scores tie; DESC keeps larger docids first, ASC smaller first (result_sorter.cpp:681-686)
     p = Pair(docs=[(i, "abab cd") for i in range(1, 40_001)])
