@@ -7,7 +7,7 @@ LIB := mygram-db_amd/libmygram_gpu.so
 CXXFLAGS := -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wextra -Wno-unused-parameter -Iinclude
 HIPFLAGS := --offload-arch=$(ARCH) $(CXXFLAGS)
 
-OBJS := $(CSRC)/mgx_kernels.o $(CSRC)/mgx_api.o $(CSRC)/mgx_columns.o $(CSRC)/mgx_tools.o
+OBJS := $(CSRC)/mgx_kernels.o $(CSRC)/mgx_highlight.o $(CSRC)/mgx_api.o $(CSRC)/mgx_columns.o $(CSRC)/mgx_tools.o
 
 SHIM := mygram-db_amd/libmygram_shim.so
 
@@ -15,11 +15,14 @@ all: $(LIB) $(SHIM) oracle
 
 $(CSRC)/mgx_kernels.o: $(CSRC)/mgx_kernels.hip $(CSRC)/mgx_internal.hpp $(CSRC)/mgx_launch.hpp $(CSRC)/mgx_fuzzy.hpp $(CSRC)/mgx_text.hpp
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(CSRC)/mgx_api.o: $(CSRC)/mgx_api.cpp $(CSRC)/mgx_internal.hpp $(CSRC)/mgx_launch.hpp $(CSRC)/mgx_host.hpp include/mygram_gpu.h
+# the HIGHLIGHT kernel is a translation unit of its own: the code of every other kernel is compiled from unchanged input
+$(CSRC)/mgx_highlight.o: $(CSRC)/mgx_highlight.hip $(CSRC)/mgx_highlight.hpp $(CSRC)/mgx_internal.hpp $(CSRC)/mgx_launch.hpp
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+$(CSRC)/mgx_api.o: $(CSRC)/mgx_api.cpp $(CSRC)/mgx_internal.hpp $(CSRC)/mgx_launch.hpp $(CSRC)/mgx_host.hpp $(CSRC)/mgx_highlight.hpp include/mygram_gpu.h
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
 $(CSRC)/mgx_columns.o: $(CSRC)/mgx_columns.cpp $(CSRC)/mgx_host.hpp $(CSRC)/mgx_text.hpp include/mygram_gpu.h
 	g++ $(CXXFLAGS) -pthread -c $< -o $@
-$(CSRC)/mgx_tools.o: $(CSRC)/mgx_tools.cpp include/mygram_tools.h $(CSRC)/mgx_fuzzy.hpp $(CSRC)/mgx_text.hpp
+$(CSRC)/mgx_tools.o: $(CSRC)/mgx_tools.cpp include/mygram_tools.h $(CSRC)/mgx_fuzzy.hpp $(CSRC)/mgx_highlight.hpp $(CSRC)/mgx_text.hpp
 	g++ $(CXXFLAGS) -pthread -c $< -o $@
 
 $(LIB): $(OBJS)
@@ -32,7 +35,7 @@ ICU_OK := $(if $(MGX_NO_ICU),,$(shell printf '\043include <unicode/unorm2.h>\nin
 ICU_FLAGS := $(if $(ICU_OK),-DMGX_USE_ICU,)
 ICU_LIBS := $(if $(ICU_OK),-licui18n -licuuc,)
 SHIM_SRC := $(CSRC)/shim/mygram_shim.cpp $(CSRC)/shim/shim_capi.cpp $(CSRC)/shim/normalize.cpp
-$(SHIM): $(CSRC)/mgx_text.hpp $(SHIM_SRC) $(CSRC)/shim/mygram_shim.hpp include/mygram_shim_c.h include/mygram_gpu.h $(LIB)
+$(SHIM): $(CSRC)/mgx_text.hpp $(CSRC)/mgx_highlight.hpp $(SHIM_SRC) $(CSRC)/shim/mygram_shim.hpp include/mygram_shim_c.h include/mygram_gpu.h $(LIB)
 	g++ $(CXXFLAGS) $(ICU_FLAGS) -shared -o $@ $(SHIM_SRC) -Lmygram-db_amd -lmygram_gpu $(ICU_LIBS) -Wl,-rpath,'$$ORIGIN' -pthread
 
 oracle:
@@ -42,7 +45,7 @@ oracle:
 ablation:
 	$(HIPCC) $(HIPFLAGS) -DMGX_ABLATION -c $(CSRC)/mgx_kernels.hip -o /tmp/mgx_kernels_abl.o
 	$(HIPCC) $(HIPFLAGS) -DMGX_ABLATION -x hip -c $(CSRC)/mgx_api.cpp -o /tmp/mgx_api_abl.o
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o mygram-db_amd/libmygram_gpu_ablation.so /tmp/mgx_kernels_abl.o /tmp/mgx_api_abl.o $(CSRC)/mgx_columns.o $(CSRC)/mgx_tools.o -pthread
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o mygram-db_amd/libmygram_gpu_ablation.so /tmp/mgx_kernels_abl.o $(CSRC)/mgx_highlight.o /tmp/mgx_api_abl.o $(CSRC)/mgx_columns.o $(CSRC)/mgx_tools.o -pthread
 
 clean:
 	rm -f $(OBJS) $(LIB) $(SHIM)

@@ -376,6 +376,83 @@ int mgx_batch_stream(mgx_batch* batch, void** hip_stream);
 int mgx_batch_execute(mgx_batch* batch, void* hip_stream);
 /* Waits for the last execute and copies the (small) results to host memory owned by the batch. */
 int mgx_batch_fetch(mgx_batch* batch, mgx_result_view* out);
+/* ---- HIGHLIGHT (SEARCH ... HIGHLIGHT [TAG <open> <close>] [SNIPPET_LEN n] [MAX_FRAGMENTS n]: GenerateHighlightSnippets on
+ * the page, src/server/handlers/search_handler.cpp:473-482; query::Highlighter::Generate, src/query/highlighter.cpp:114-309)
+ * The snippet material of every page entry of the highlighted queries is produced ON THE DEVICE, by one more kernel on the
+ * batch's stream behind the kernel that finalises the page (after mgx_batch_execute's last kernel; on a table with a delta
+ * once more after mgx_batch_merge_local, where an entry's text comes from the index that holds the live document: the
+ * delta's doc map is searched first). It reads the page's doc ids from the device result block and its records ride the
+ * same event as the page. A batch without a highlighted query launches and copies nothing.
+ *
+ * mgx_batch_set_highlight attaches the requests to a prepared or reset batch, BEFORE its first execute; requests[i]
+ * belongs to query i (n_queries = the batch's); mgx_batch_reset drops them. `terms` is the query's already-built term list
+ * (search_pipeline::BuildHighlightTerms, search_pipeline.cpp:712-745: normalized, pieces added, sorted, deduplicated) as
+ * byte strings; empty terms are skipped as the reference skips them. max_text_bytes: the longest document text a page
+ * entry can have, 0 = the longest text of the batch's own index (a table with a delta passes the larger of the two,
+ * mgx_index_max_text_bytes).
+ * Refused: snippet_length outside 1..10000 or max_fragments outside 1..100 (the parser's ranges,
+ * query_parser_clauses.cpp:372-431) and more than MGX_HIGHLIGHT_MAX_TERMS terms: MGX_ERR_OUT_OF_RANGE; a highlighted query
+ * with limit 0 or offset + limit above 1024 (the fused top-k page bound; docid pages: limit above 1024):
+ * MGX_ERR_OUT_OF_RANGE; an index without mgx_index_attach_text: MGX_ERR_INVALID_ARGUMENT; a batch whose records could,
+ * in the worst case, exceed MGX_HIGHLIGHT_ARENA_CAP bytes: MGX_ERR_OUT_OF_RANGE (the message names the option to lower).
+ * The worst case of one entry is min(4 * snippet_length * max_fragments, max_text_bytes) text bytes, as many match spans
+ * as fit, and max_fragments windows. A sharded table (mgx_batch_exchange) cannot be highlighted: the page's texts live on
+ * other ranks (MGX_ERR_NOT_IMPLEMENTED from mgx_batch_export_topk / _export_buffer, mgx_batch_merge_shards,
+ * mgx_batch_exchange, mgx_batch_execute_gather and mgx_batch_execute_sharded, a host's own transport included).
+ *
+ * The texts are normalizer output, so valid UTF-8; a code point is a byte that is not 10xxxxxx. On other input the device
+ * stays inside the text's bounds and the record's capacities, and the snippet is unspecified. */
+#define MGX_HIGHLIGHT_ARENA_CAP (256ull << 20)
+#define MGX_HIGHLIGHT_MAX_TERMS 256u
+typedef struct mgx_highlight_request {
+  uint32_t enabled;        /* 0: the query is not highlighted (the other fields are ignored) */
+  uint32_t snippet_length; /* HighlightOptions::snippet_length (query_parser.h:158-163), code points per fragment */
+  uint32_t max_fragments;
+  uint32_t n_terms;
+  const uint8_t* const* terms; /* term t = terms[t][0 .. term_lens[t]) */
+  const uint32_t* term_lens;
+} mgx_highlight_request;
+int mgx_batch_set_highlight(mgx_batch* batch, const mgx_highlight_request* requests, uint32_t n_queries,
+                            uint32_t max_text_bytes);
+/* defer != 0: the batch's page is not final after mgx_batch_execute because mgx_batch_merge_local follows (the primary
+ * batch of a table with a delta): execute then leaves the highlight kernel and the copy of its records to the merge,
+ * which would otherwise repeat them. Call after mgx_batch_set_highlight; mgx_batch_reset clears it. */
+int mgx_batch_defer_highlight(mgx_batch* batch, int defer);
+/* What the host needs to render one page entry: the kept windows (byte ranges of the document, in order), the matches
+ * inside them (byte ranges of the document, ascending; spans [windows[i-1].span_end, windows[i].span_end) belong to
+ * window i and are clipped to it when rendered), and the windows' text (window i's bytes start at bytes + bytes_begin). */
+#define MGX_HL_LEADING_DOTS 1u  /* "..." before the first window */
+#define MGX_HL_TRAILING_DOTS 2u /* "..." after the last window */
+#define MGX_HL_OVERFLOW 4u      /* a capacity cut the record short (mgx_batch_fetch_highlight refuses such a batch) */
+typedef struct mgx_highlight_window {
+  uint32_t start, end; /* bytes of the document */
+  uint32_t span_end;
+  uint32_t bytes_begin;
+} mgx_highlight_window;
+typedef struct mgx_highlight_span {
+  uint32_t start, end;
+} mgx_highlight_span;
+typedef struct mgx_highlight_entry {
+  uint32_t n_windows, flags, n_spans, n_bytes;
+  const mgx_highlight_window* windows;
+  const mgx_highlight_span* spans;
+  const uint8_t* bytes;
+} mgx_highlight_entry;
+typedef struct mgx_highlight_view {
+  uint32_t n_entries; /* = the docs of the last mgx_batch_fetch; entry i belongs to mgx_result_view.docs[i] */
+  const mgx_highlight_entry* entries; /* queries that are not highlighted: all-zero entries */
+} mgx_highlight_view;
+/* After mgx_batch_fetch of the same execute: no further wait, no further copy. The view stays valid until the batch's
+ * next execute, reset or destroy. */
+int mgx_batch_fetch_highlight(mgx_batch* batch, mgx_highlight_view* out);
+/* The host's share: tags and "..." around the record's bytes (GenerateWithPositions' rendering loop,
+ * highlighter.cpp:188-222). Writes at most `cap` bytes to `out` and the snippet's full length to *out_len. Tags are at
+ * most 256 bytes each (query_parser.h:276), else MGX_ERR_OUT_OF_RANGE. */
+int mgx_highlight_render(const mgx_highlight_entry* entry, const uint8_t* open_tag, size_t open_len,
+                         const uint8_t* close_tag, size_t close_len, uint8_t* out, size_t cap, size_t* out_len);
+/* Length in bytes of the longest text attached to the index (0 without mgx_index_attach_text). */
+int mgx_index_max_text_bytes(const mgx_index* idx, uint32_t* out);
+
 /* Multi-GPU exchange (one rank per doc-range shard). The batch must be all MGX_SORT_SCORE, or all docid-ordered
  * pages (MGX_SORT_DOCID with 0 < limit <= 16384): a page is a best-first list under the key "doc id" (or its
  * complement for ascending order), so the same two calls serve both.

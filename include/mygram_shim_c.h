@@ -109,6 +109,20 @@ int mgxs_search(mgxs_table* table, uint32_t n_terms, const char* const* terms, u
                 uint32_t n_cond, const char* const* cond_columns, const uint32_t* cond_ops, const char* const* cond_values,
                 int sort_by_score, int descending, uint32_t limit, uint32_t offset, uint64_t* total, uint32_t* n_docs,
                 uint32_t* docs, double* scores /* may be NULL */);
+/* mgxs_search with HIGHLIGHT (BatchQuery::highlight: GenerateHighlightSnippets on the page, search_handler.cpp:473-482, on the
+ * device): the page's snippets, packed into `snippets`; doc k's snippet is snippets[snippet_off[k] .. snippet_off[k+1]).
+ * snippet_off has room for limit + 1 entries. Tags NUL-terminated, at most 256 bytes; snippet_length 1..10000,
+ * max_fragments 1..100. MGX_ERR_OUT_OF_RANGE when the snippets exceed snippets_cap. */
+int mgxs_search_highlight(mgxs_table* table, uint32_t n_terms, const char* const* terms, uint32_t n_not,
+                          const char* const* not_terms, int sort_by_score, int descending, uint32_t limit, uint32_t offset,
+                          const char* open_tag, const char* close_tag, uint32_t snippet_length, uint32_t max_fragments,
+                          uint64_t* total, uint32_t* n_docs, uint32_t* docs, double* scores /* may be NULL */,
+                          char* snippets, size_t snippets_cap, uint32_t* snippet_off);
+/* query::Highlighter::Generate on the host (the host build of the device's highlighter) over one normalized text; terms
+ * are byte strings. Writes at most cap bytes, the snippet's full length to *out_len. */
+int mgxs_highlight_generate(const char* text, size_t len, uint32_t n_terms, const char* const* terms, const size_t* term_lens,
+                            const char* open_tag, const char* close_tag, uint32_t snippet_length, uint32_t max_fragments,
+                            char* out, size_t cap, size_t* out_len);
 /* search_pipeline::ExecuteFacet (ExecuteFacetPipeline, src/server/search_pipeline.cpp:2061-2153): value counts of `column`
  * over the query's result set (no terms: every document), count descending, paged by offset then limit. counts has room
  * for `limit` entries, display_off for limit + 1; value k's printable form (DeserializeToDisplayString) is

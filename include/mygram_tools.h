@@ -38,6 +38,22 @@ void mgxt_fail_device_allocs(int after, int count);
 int mgxt_contains_fuzzy_match(const uint8_t* text, size_t text_len, const uint8_t* term, size_t term_len,
                               uint32_t max_distance);
 
+/* Test hooks: the host build of the highlighter the batch path runs on the device (highlight_kernel, one source for the
+ * window / merge / clamp / render rules: mygram-db_amd/csrc/mgx_highlight.hpp) — query::Highlighter::Generate and
+ * FindMatchPositions of the reference (src/query/highlighter.cpp:252-309) over one NORMALIZED text. Terms are byte
+ * strings: term t = terms[t][0 .. term_lens[t]). snippet_length 1..10000, max_fragments 1..100, tags <= 256 bytes (the
+ * parser's ranges), else MGX_ERR_OUT_OF_RANGE (3). The text must be valid UTF-8 (normalizer output); on other input the
+ * calls stay inside the buffers and the output is unspecified.
+ * mgxt_highlight_generate writes at most `cap` bytes of the snippet to `out` and its full length to *out_len.
+ * mgxt_highlight_match_positions writes at most `cap_pairs` (start, end) code-point pairs and their number to *n_pairs. */
+int mgxt_highlight_generate(const uint8_t* text, size_t text_len, const uint8_t* const* terms, const size_t* term_lens,
+                            uint32_t n_terms, uint32_t snippet_length, uint32_t max_fragments, const uint8_t* open_tag,
+                            size_t open_len, const uint8_t* close_tag, size_t close_len, uint8_t* out, size_t cap,
+                            size_t* out_len);
+int mgxt_highlight_match_positions(const uint8_t* text, size_t text_len, const uint8_t* const* terms,
+                                   const size_t* term_lens, uint32_t n_terms, uint32_t* out_pairs, size_t cap_pairs,
+                                   size_t* n_pairs);
+
 #ifdef __cplusplus
 }
 #endif

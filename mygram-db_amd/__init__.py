@@ -5,5 +5,5 @@ thin Python mirror of the reference's operator interface over that ABI, used by 
 driver. Import name: `mygram_db_amd` (the directory name has a hyphen; see load_package() in __graft_entry__.py).
 """
 from . import _capi, engine  # noqa: F401
-from .engine import (Columns, Corpus, DeviceIndex, Index, PreparedBatch, compute_idf,  # noqa: F401
+from .engine import (Columns, Corpus, DeviceIndex, Highlight, Index, PreparedBatch, compute_idf,  # noqa: F401
                      generate_query_ngrams)

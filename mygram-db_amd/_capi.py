@@ -33,6 +33,8 @@ EXPORTS = [
     "mgx_and", "mgx_or", "mgx_not", "mgx_threshold", "mgx_retain", "mgx_score_documents", "mgx_sort_by_score",
     "mgxt_corpus_generate", "mgxt_corpus_view", "mgxt_corpus_destroy", "mgxt_measure_read_bandwidth", "mgxt_fail_device_allocs",
     "mgxt_contains_fuzzy_match",
+    "mgx_batch_set_highlight", "mgx_batch_fetch_highlight", "mgx_highlight_render", "mgx_index_max_text_bytes", "mgx_batch_defer_highlight",
+    "mgxt_highlight_generate", "mgxt_highlight_match_positions",
 ]
 
 
@@ -115,6 +117,23 @@ class ResultView(C.Structure):
     _fields_ = [("n_queries", C.c_uint32), ("queries", C.POINTER(QueryResult)), ("docs", C.POINTER(C.c_uint32)),
                 ("scores", C.POINTER(C.c_double))]
 
+
+class HighlightRequest(C.Structure):
+    _fields_ = [("enabled", C.c_uint32), ("snippet_length", C.c_uint32), ("max_fragments", C.c_uint32),
+                ("n_terms", C.c_uint32), ("terms", C.POINTER(C.c_char_p)), ("term_lens", C.POINTER(C.c_uint32))]
+
+
+class HighlightEntry(C.Structure):
+    _fields_ = [("n_windows", C.c_uint32), ("flags", C.c_uint32), ("n_spans", C.c_uint32), ("n_bytes", C.c_uint32),
+                ("windows", C.c_void_p), ("spans", C.c_void_p), ("bytes", C.c_void_p)]
+
+
+class HighlightView(C.Structure):
+    _fields_ = [("n_entries", C.c_uint32), ("entries", C.POINTER(HighlightEntry))]
+
+
+HIGHLIGHT_ARENA_CAP = 256 << 20
+HIGHLIGHT_MAX_TERMS = 256
 
 _lib = None
 
@@ -200,6 +219,15 @@ def load():
     L.mgxt_fail_device_allocs.argtypes = [i32, i32]
     L.mgxt_fail_device_allocs.restype = None
     L.mgxt_contains_fuzzy_match.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, u32]
+    L.mgx_batch_set_highlight.argtypes = [vp, C.POINTER(HighlightRequest), u32, u32]
+    L.mgx_batch_fetch_highlight.argtypes = [vp, C.POINTER(HighlightView)]
+    L.mgx_highlight_render.argtypes = [C.POINTER(HighlightEntry), C.c_char_p, sz, C.c_char_p, sz, vp, sz, C.POINTER(sz)]
+    L.mgx_batch_defer_highlight.argtypes = [vp, i32]
+    L.mgx_index_max_text_bytes.argtypes = [vp, C.POINTER(u32)]
+    L.mgxt_highlight_generate.argtypes = [C.c_char_p, sz, C.POINTER(C.c_char_p), C.POINTER(sz), u32, u32, u32, C.c_char_p,
+                                          sz, C.c_char_p, sz, vp, sz, C.POINTER(sz)]
+    L.mgxt_highlight_match_positions.argtypes = [C.c_char_p, sz, C.POINTER(C.c_char_p), C.POINTER(sz), u32, vp, sz,
+                                                 C.POINTER(sz)]
     _lib = L
     return L
 

@@ -11,7 +11,7 @@ LIB_PATH = os.path.join(_HERE, "libmygram_shim.so")
 EXPORTS = ["mgxs_last_error", "mgxs_table_adopt", "mgxs_table_set_global_stats", "mgxs_table_destroy",
            "mgxs_table_set_normalization", "mgxs_table_set_absent_grams", "mgxs_normalize_uses_icu", "mgxs_normalize_text",
            "mgxs_executor_create", "mgxs_executor_create_sharded", "mgxs_executor_destroy", "mgxs_executor_warm",
-           "mgxs_submit", "mgxs_wait", "mgxs_table_from_dump", "mgxs_table_add_filter_column", "mgxs_search", "mgxs_facet",
+           "mgxs_submit", "mgxs_wait", "mgxs_table_from_dump", "mgxs_table_add_filter_column", "mgxs_search", "mgxs_facet", "mgxs_search_highlight", "mgxs_highlight_generate",
            "mgxs_table_add_document", "mgxs_table_update_document", "mgxs_table_remove_document", "mgxs_table_mutation_stats", "mgxs_table_compact", "mgxs_table_set_mutation_staleness", "mgxs_table_update_filters",
            "mgxs_batcher_create", "mgxs_batcher_destroy", "mgxs_batcher_search", "mgxs_batcher_stats"]
 _lib = None
@@ -50,6 +50,10 @@ def load():
     L.mgxs_table_add_filter_column.argtypes = [vp, C.c_char_p, i32, u64, vp, vp, vp]
     L.mgxs_table_from_dump.argtypes = [C.c_char_p, u64, C.c_char_p, i32, C.POINTER(vp)]
     L.mgxs_search.argtypes = [vp, u32, vp, u32, vp, u32, vp, vp, vp, i32, i32, u32, u32, C.POINTER(u64), C.POINTER(u32), vp, vp]
+    L.mgxs_search_highlight.argtypes = [vp, u32, vp, u32, vp, i32, i32, u32, u32, C.c_char_p, C.c_char_p, u32, u32,
+                                        C.POINTER(u64), C.POINTER(u32), vp, vp, vp, C.c_size_t, vp]
+    L.mgxs_highlight_generate.argtypes = [C.c_char_p, C.c_size_t, u32, vp, vp, C.c_char_p, C.c_char_p, u32, u32, vp,
+                                          C.c_size_t, C.POINTER(C.c_size_t)]
     L.mgxs_facet.argtypes = [vp, u32, vp, u32, vp, u32, vp, vp, vp, C.c_char_p, u32, u32, C.POINTER(u64), C.POINTER(u64),
                              C.POINTER(u32), vp, vp, C.c_size_t, vp]
     L.mgxs_table_add_document.argtypes = [vp, u32, C.c_char_p, C.c_size_t, u32, vp, vp, vp, vp]

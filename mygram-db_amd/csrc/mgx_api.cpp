@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "../../include/mygram_gpu.h"
+#include "mgx_highlight.hpp"
 #include "mgx_host.hpp"
 #include "mgx_internal.hpp"
 #include "mgx_launch.hpp"
@@ -137,8 +138,8 @@ struct Arena {
 struct BatchResources {
   Arena upload{true}, out{false};
   bool uploaded = false;
-  void* h_down[2] = {nullptr, nullptr};  // pinned result blocks (score group, docid-page group)
-  size_t h_down_cap[2] = {0, 0};
+  void* h_down[3] = {nullptr, nullptr, nullptr};  // pinned result blocks (score group, docid-page group, highlight records)
+  size_t h_down_cap[3] = {0, 0, 0};
   hipEvent_t fork_ev = nullptr, join_ev = nullptr;  // fork/join of the side-stream launch
   // A batch object is one pipeline slot: with a NULL stream argument it runs on its own non-blocking stream, and the
   // copy of its (small) result block to pinned memory is part of the execute, fenced by done_ev — so fetching batch i
@@ -287,6 +288,7 @@ struct mgx_index {
   mgx::DevIndex dev{};
   DevBuf d_offsets, d_docids, d_tf, d_doc_len, d_skip_row, d_tile_off, d_gram_bitmaps, d_filter_bitmaps;
   DevBuf d_text, d_text_off;  // mgx_index_attach_text
+  uint32_t max_text_bytes = 0;  // the longest attached text (sizes the highlight records)
   DevBuf d_dl8, d_tfnib, d_tf_ovf_pos, d_tf_ovf_val;
   DevBuf d_dev_index;  // `dev` in device memory: what out-of-line device functions take a pointer to (SyncDevIndex)
   std::vector<uint64_t> h_offsets;
@@ -927,7 +929,17 @@ int mgx_index_attach_text(mgx_index* idx, const uint8_t* text_bytes, const uint6
   MGX_HIP(mgx::Upload(idx->d_text_off, rel.data(), rel.size()));
   idx->dev.text = idx->d_text.as<uint8_t>();
   idx->dev.text_off = idx->d_text_off.as<uint64_t>();
+  uint64_t longest = 0;
+  for (uint64_t i = 0; i < n; ++i) longest = std::max<uint64_t>(longest, text_off[i + 1] - text_off[i]);
+  idx->max_text_bytes = static_cast<uint32_t>(longest);
   MGX_HIP(mgx::SyncDevIndex(idx));
+  return MGX_OK;
+}
+
+int mgx_index_max_text_bytes(const mgx_index* idx, uint32_t* out) {
+  if (out) *out = 0;
+  if (!idx || !out) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_index_max_text_bytes: null argument");
+  *out = idx->dev.text ? idx->max_text_bytes : 0;
   return MGX_OK;
 }
 
@@ -1818,6 +1830,21 @@ struct mgx_batch {
   void* h_page_out = nullptr;
   size_t po_totals = 0, po_docs = 0, po_bytes = 0;
   uint32_t doc_page_stride = 0;
+  // HIGHLIGHT (mgx_batch_set_highlight): the highlighted queries' descriptors, their terms, and the records the kernel
+  // fills, one per (highlighted query, page entry), copied to pinned memory behind the page
+  struct Highlight {
+    std::vector<mgx::DevHlQuery> queries;  // in batch order
+    std::vector<int32_t> of_query;         // batch query -> index into `queries`, or -1
+    DevBuf d_queries, d_terms, d_patterns, d_arena;
+    void* h_arena = nullptr;  // pinned (BatchResources)
+    size_t bytes = 0;
+    uint32_t n_entries = 0;
+    bool defer = false;  // mgx_batch_defer_highlight: mgx_batch_merge_local runs the kernel, execute does not
+    std::vector<mgx_highlight_entry> entries;  // of the last fetch
+    bool on() const { return !queries.empty(); }
+  };
+  Highlight hl;
+  bool fetched = false;  // mgx_batch_fetch assembled h_results for the last execute
   // host results
   std::vector<mgx_query_result> h_results;
   std::vector<uint32_t> h_docs;
@@ -2887,6 +2914,36 @@ static int ForkSide(mgx_batch* b, hipStream_t s) {
   return MGX_OK;
 }
 
+// HIGHLIGHT: the records of the highlighted queries' page entries, behind the kernel that finalised the page, and their
+// copy to pinned memory (the caller records the batch's done event after it). `mapped`: the index whose documents the
+// page names by table id through its doc map (the delta of a mutable table), `plain`: the index whose own ids it holds.
+static int RunHighlight(mgx_batch* b, hipStream_t s, bool merged, const mgx_index* mapped, const mgx_index* plain) {
+  mgx_batch::Highlight& h = b->hl;
+  DevHlBatch hb{};
+  hb.queries = h.d_queries.as<DevHlQuery>();
+  hb.n_queries = static_cast<uint32_t>(h.queries.size());
+  hb.n_entries = h.n_entries;
+  hb.terms = h.d_terms.as<DevHlTerm>();
+  hb.patterns = h.d_patterns.as<uint8_t>();
+  hb.arena = h.d_arena.as<uint8_t>();
+  auto source = [](const mgx_index* ix, bool with_map) {
+    DevHlSource src{};
+    if (!ix) return src;
+    src.text = ix->dev.text;
+    src.text_off = ix->dev.text_off;
+    src.doc_map = with_map ? ix->d_doc_map.as<uint32_t>() : nullptr;
+    src.first_doc_id = ix->dev.first_doc_id;
+    src.n_docs = ix->dev.n_docs;
+    return src;
+  };
+  hb.mapped = source(mapped, true);
+  hb.plain = source(plain, false);
+  hb.merged = merged ? 1u : 0u;
+  MGX_LAUNCH(LaunchHighlight(hb, s));
+  MGX_HIP(hipMemcpyAsync(h.h_arena, h.d_arena.p, h.bytes, hipMemcpyDeviceToHost, s));
+  return MGX_OK;
+}
+
 static int ExecuteImpl(mgx_batch* b, hipStream_t s, const SeedGather* sg = nullptr) {
   mgx_index* idx = b->idx;
   MGX_HIP(hipSetDevice(idx->device));
@@ -3067,11 +3124,16 @@ static int ExecuteImpl(mgx_batch* b, hipStream_t s, const SeedGather* sg = nullp
       (void)hipEventDestroy(ev1);
     }
   }
+  if (b->hl.on() && !b->hl.defer) {
+    const int rc = RunHighlight(b, s, /*merged=*/false, nullptr, idx);  // (a page of one index holds that index's own ids)
+    if (rc) return rc;
+  }
   {
     int rc = IssueResultCopy(b, s);
     if (rc) return rc;
   }
   b->executed = true;
+  b->fetched = false;
   b->last_stream = s;
   return MGX_OK;
 }
@@ -3396,6 +3458,7 @@ static int FetchImpl(mgx_batch* b, mgx_result_view* out) {
   out->queries = b->h_results.data();
   out->docs = b->h_docs.data();
   out->scores = b->h_scores.data();
+  b->fetched = true;
   return MGX_OK;
 }
 
@@ -3487,6 +3550,187 @@ int mgx_batch_fetch(mgx_batch* batch, mgx_result_view* out) {
   }
 }
 
+int mgx_batch_set_highlight(mgx_batch* batch, const mgx_highlight_request* requests, uint32_t n_queries,
+                            uint32_t max_text_bytes) {
+  namespace hl = mgx::highlight;
+  if (!batch || (n_queries && !requests)) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_batch_set_highlight: null argument");
+  if (!batch->res_owned) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_batch_set_highlight: not a prepared batch object");
+  if (n_queries != batch->n_queries)
+    return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_batch_set_highlight: one request per query of the batch");
+  if (batch->res->uploaded || batch->executed || batch->hl.on())
+    return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_batch_set_highlight: call it once, after prepare / reset and before the first execute");
+  try {
+    mgx_index* idx = batch->idx;
+    std::vector<mgx::DevHlQuery> queries;
+    std::vector<int32_t> of_query(n_queries, -1);
+    std::vector<mgx::DevHlTerm> terms;
+    std::string pool;
+    std::vector<uint32_t> pos_in_group(n_queries, 0);
+    for (size_t i = 0; i < batch->score.qids.size(); ++i) pos_in_group[batch->score.qids[i]] = static_cast<uint32_t>(i);
+    for (size_t i = 0; i < batch->page.qids.size(); ++i) pos_in_group[batch->page.qids[i]] = static_cast<uint32_t>(i);
+    const uint32_t longest = max_text_bytes ? max_text_bytes : idx->max_text_bytes;
+    uint64_t arena = 0;
+    uint32_t n_entries = 0;
+    for (uint32_t qi = 0; qi < n_queries; ++qi) {
+      const mgx_highlight_request& r = requests[qi];
+      if (!r.enabled) continue;
+      const std::string who = "mgx_batch_set_highlight: query " + std::to_string(qi) + ": ";
+      if (!idx->dev.text) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, who + "highlight without mgx_index_attach_text");
+      if (r.snippet_length < 1 || r.snippet_length > hl::kMaxSnippetLength)
+        return mgx::Fail(MGX_ERR_OUT_OF_RANGE, who + "snippet_length must be 1..10000");
+      if (r.max_fragments < 1 || r.max_fragments > hl::kMaxFragments)
+        return mgx::Fail(MGX_ERR_OUT_OF_RANGE, who + "max_fragments must be 1..100");
+      if (r.n_terms && (!r.terms || !r.term_lens)) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, who + "null term list");
+      const mgx::QuerySpec& sp = batch->specs[qi];
+      if (sp.limit == 0) return mgx::Fail(MGX_ERR_OUT_OF_RANGE, who + "a highlighted query needs a page (limit 0 returns every match)");
+      const bool score = sp.mode == mgx::kModeScore, page = sp.mode == mgx::kModeDocPage;
+      if ((!score && !page) || static_cast<uint64_t>(sp.offset) + sp.limit > mgx::kMaxNeeded)
+        return mgx::Fail(MGX_ERR_OUT_OF_RANGE, who + "a highlighted query's offset + limit must not exceed 1024");
+      mgx::DevHlQuery q{};
+      const uint32_t gi = pos_in_group[qi];
+      if (score) {
+        q.page_docs = batch->sc_docs() + static_cast<size_t>(gi) * batch->page_stride;
+        q.page_n = batch->sc_n() + gi;
+      } else {
+        q.page_docs = batch->page.dev.page_docs + static_cast<size_t>(gi) * batch->doc_page_stride;
+        q.total_exec = static_cast<const unsigned long long*>(batch->d_page_out.p) + static_cast<size_t>(gi) * 8 + 4;
+        q.total_merged = reinterpret_cast<const unsigned long long*>(batch->page.dev.totals) + gi;
+      }
+      q.limit = sp.limit;
+      q.entry_begin = n_entries;
+      q.snippet_length = r.snippet_length;
+      q.max_fragments = r.max_fragments;
+      q.term_begin = static_cast<uint32_t>(terms.size());
+      uint32_t shortest = 0xFFFFFFFFu;
+      for (uint32_t t = 0; t < r.n_terms; ++t) {
+        const uint32_t len = r.term_lens[t];
+        if (len == 0) continue;  // (highlighter.cpp:257-259)
+        if (!r.terms[t]) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, who + "null term");
+        if (len > longest) continue;  // longer than every text (:260-262)
+        terms.push_back(mgx::DevHlTerm{static_cast<uint32_t>(pool.size()), len, hl::CountCps(r.terms[t], len), 0});
+        pool.append(reinterpret_cast<const char*>(r.terms[t]), len);
+        shortest = std::min(shortest, len);
+      }
+      q.n_terms = static_cast<uint32_t>(terms.size()) - q.term_begin;
+      if (q.n_terms > MGX_HIGHLIGHT_MAX_TERMS)
+        return mgx::Fail(MGX_ERR_OUT_OF_RANGE, who + "more than 256 highlight terms");
+      if (pool.size() > 0x7FFFFFFFull) return mgx::Fail(MGX_ERR_OUT_OF_RANGE, who + "highlight terms exceed 2 GiB");
+      // worst case of one entry: its windows are disjoint pieces of one text, max_fragments of them, of snippet_length
+      // code points (4 bytes at most) each; a window of L code points holds at most L matches, and non-overlapping
+      // matches of terms of `shortest` bytes or more are at most text bytes / shortest
+      const uint64_t fl = static_cast<uint64_t>(r.snippet_length) * r.max_fragments;
+      q.byte_cap = static_cast<uint32_t>(std::min<uint64_t>(4 * fl, longest));
+      q.span_cap = q.n_terms ? static_cast<uint32_t>(std::min<uint64_t>(fl, longest / shortest)) : 0;
+      q.rec_off = arena;
+      q.rec_stride = sizeof(hl::Header) + sizeof(hl::Window) * q.max_fragments + sizeof(hl::Span) * q.span_cap +
+                     ((static_cast<uint64_t>(q.byte_cap) + 7) & ~7ull);
+      arena += q.rec_stride * q.limit;
+      if (arena > MGX_HIGHLIGHT_ARENA_CAP)
+        return mgx::Fail(MGX_ERR_OUT_OF_RANGE,
+                         "mgx_batch_set_highlight: the batch's highlight records can exceed MGX_HIGHLIGHT_ARENA_CAP (256 MiB) "
+                         "in the worst case; lower snippet_length (or max_fragments, or limit), or highlight fewer queries "
+                         "per batch (query " + std::to_string(qi) + " needs " + std::to_string(q.rec_stride) + " bytes per page entry)");
+      n_entries += q.limit;
+      of_query[qi] = static_cast<int32_t>(queries.size());
+      queries.push_back(q);
+    }
+    if (queries.empty()) return MGX_OK;  // nothing is highlighted: the batch launches and copies nothing new
+    mgx::ResourceScope scope(batch->res);
+    MGX_HIP(hipSetDevice(idx->device));
+    mgx_batch::Highlight& h = batch->hl;
+    MGX_HIP(mgx::Upload(h.d_queries, queries.data(), queries.size()));
+    MGX_HIP(mgx::Upload(h.d_terms, terms.data(), terms.size(), 1));
+    MGX_HIP(mgx::Upload(h.d_patterns, reinterpret_cast<const uint8_t*>(pool.data()), pool.size(), 16));
+    MGX_HIP(h.d_arena.Alloc(arena));
+    MGX_HIP(batch->res->Pinned(2, arena, &h.h_arena));
+    h.bytes = arena;
+    h.n_entries = n_entries;
+    h.of_query = std::move(of_query);
+    h.queries = std::move(queries);
+    return MGX_OK;
+  } catch (const std::exception& e) {
+    return mgx::Fail(MGX_ERR_INTERNAL, std::string("mgx_batch_set_highlight: ") + e.what());
+  }
+}
+
+int mgx_batch_defer_highlight(mgx_batch* batch, int defer) {
+  if (!batch) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_batch_defer_highlight: null batch");
+  batch->hl.defer = defer != 0;
+  return MGX_OK;
+}
+
+int mgx_batch_fetch_highlight(mgx_batch* batch, mgx_highlight_view* out) {
+  namespace hl = mgx::highlight;
+  if (out) std::memset(out, 0, sizeof(*out));
+  if (!batch || !out) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_batch_fetch_highlight: null argument");
+  if (!batch->executed || !batch->fetched)
+    return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_batch_fetch_highlight: call mgx_batch_fetch for this execute first");
+  try {
+    mgx_batch::Highlight& h = batch->hl;
+    h.entries.assign(batch->h_docs.size(), mgx_highlight_entry{});
+    for (uint32_t qi = 0; qi < batch->n_queries && h.on(); ++qi) {
+      if (h.of_query[qi] < 0) continue;
+      const mgx::DevHlQuery& q = h.queries[h.of_query[qi]];
+      const mgx_query_result& r = batch->h_results[qi];
+      for (uint32_t j = 0; j < r.n_docs && j < q.limit; ++j) {
+        const uint8_t* rec = static_cast<const uint8_t*>(h.h_arena) + q.rec_off + static_cast<uint64_t>(j) * q.rec_stride;
+        hl::Header head;
+        std::memcpy(&head, rec, sizeof(head));
+        if ((head.flags & hl::kFlagOverflow) || head.n_windows > q.max_fragments || head.n_spans > q.span_cap ||
+            head.n_bytes > q.byte_cap)
+          return mgx::Fail(MGX_ERR_OUT_OF_RANGE,
+                           "mgx_batch_fetch_highlight: a page entry's text is longer than the max_text_bytes the records "
+                           "were sized for (or is not valid UTF-8)");
+        mgx_highlight_entry& e = h.entries[r.docs_begin + j];
+        e.n_windows = head.n_windows;
+        e.flags = head.flags;
+        e.n_spans = head.n_spans;
+        e.n_bytes = head.n_bytes;
+        e.windows = reinterpret_cast<const mgx_highlight_window*>(rec + sizeof(hl::Header));
+        e.spans = reinterpret_cast<const mgx_highlight_span*>(rec + sizeof(hl::Header) + sizeof(hl::Window) * q.max_fragments);
+        e.bytes = reinterpret_cast<const uint8_t*>(e.spans) + sizeof(hl::Span) * q.span_cap;
+      }
+    }
+    out->n_entries = static_cast<uint32_t>(h.entries.size());
+    out->entries = h.entries.data();
+    return MGX_OK;
+  } catch (const std::exception& e) {
+    return mgx::Fail(MGX_ERR_INTERNAL, std::string("mgx_batch_fetch_highlight: ") + e.what());
+  }
+}
+
+static_assert(sizeof(mgx_highlight_window) == sizeof(mgx::highlight::Window) &&
+                  offsetof(mgx_highlight_window, start) == offsetof(mgx::highlight::Window, start) &&
+                  offsetof(mgx_highlight_window, end) == offsetof(mgx::highlight::Window, end) &&
+                  offsetof(mgx_highlight_window, span_end) == offsetof(mgx::highlight::Window, span_end) &&
+                  offsetof(mgx_highlight_window, bytes_begin) == offsetof(mgx::highlight::Window, aux) &&
+                  sizeof(mgx_highlight_span) == sizeof(mgx::highlight::Span) &&
+                  offsetof(mgx_highlight_span, start) == offsetof(mgx::highlight::Span, start) &&
+                  offsetof(mgx_highlight_span, end) == offsetof(mgx::highlight::Span, end),
+              "the ABI's record structs are the shared header's, field by field");
+
+int mgx_highlight_render(const mgx_highlight_entry* entry, const uint8_t* open_tag, size_t open_len,
+                         const uint8_t* close_tag, size_t close_len, uint8_t* out, size_t cap, size_t* out_len) {
+  namespace hl = mgx::highlight;
+  if (out_len) *out_len = 0;
+  if (!entry || !out_len || (cap && !out) || (open_len && !open_tag) || (close_len && !close_tag))
+    return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_highlight_render: null argument");
+  if (open_len > hl::kMaxTagBytes || close_len > hl::kMaxTagBytes)
+    return mgx::Fail(MGX_ERR_OUT_OF_RANGE, "mgx_highlight_render: a tag is at most 256 bytes");
+  if ((entry->n_windows && !entry->windows) || (entry->n_spans && !entry->spans) || (entry->n_bytes && !entry->bytes))
+    return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_highlight_render: null record array");
+  for (uint32_t i = 0; i < entry->n_windows; ++i) {  // every window's bytes lie inside the record's byte area
+    const mgx_highlight_window& w = entry->windows[i];
+    if (w.end < w.start || w.bytes_begin > entry->n_bytes || w.end - w.start > entry->n_bytes - w.bytes_begin)
+      return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_highlight_render: a window's bytes lie outside the record");
+  }
+  const hl::Header head{entry->n_windows, entry->flags, entry->n_spans, entry->n_bytes};
+  *out_len = hl::Render(head, reinterpret_cast<const hl::Window*>(entry->windows),
+                        reinterpret_cast<const hl::Span*>(entry->spans), entry->bytes, false, open_tag, open_len, close_tag,
+                        close_len, out, cap);
+  return MGX_OK;
+}
+
 int mgx_batch_count_df(mgx_batch* batch, void* hip_stream) {
   if (!batch) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_batch_count_df: null batch");
   try {
@@ -3521,6 +3765,7 @@ static int MergeGroup(mgx_batch* batch, bool pages, uint32_t n_shards, const uin
 int mgx_batch_export_topk(mgx_batch* batch, uint64_t* blob64, uint32_t* blob32, uint32_t* stride,
                           void* hip_stream) {
   if (!batch || !stride) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_batch_export_topk: null argument");
+  if (batch->hl.on()) return mgx::Fail(MGX_ERR_NOT_IMPLEMENTED, "mgx_batch_export_topk: highlight on a sharded table is not implemented: the page's texts live on other ranks");
   const bool pages = batch->score.qids.empty() && batch->bitmap.qids.empty() && !batch->page.qids.empty();
   if (!pages && (!batch->bitmap.qids.empty() || !batch->page.qids.empty() || batch->score.qids.empty()))
     return mgx::Fail(MGX_ERR_INVALID_ARGUMENT,
@@ -3560,6 +3805,8 @@ int mgx_batch_export_buffer(mgx_batch* batch, void** device_blob, uint64_t* byte
   if (offset32) *offset32 = 0;
   if (!batch || !device_blob || !bytes || !offset32)
     return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_batch_export_buffer: null argument");
+  if (batch->hl.on())
+    return mgx::Fail(MGX_ERR_NOT_IMPLEMENTED, "mgx_batch_export_buffer: highlight on a sharded table is not implemented: the page's texts live on other ranks");
   if (!batch->bitmap.qids.empty() || !batch->page.qids.empty() || batch->score.qids.empty()) return MGX_OK;  // none
   *device_blob = batch->d_export.p;
   *bytes = batch->ex_bytes;
@@ -3571,6 +3818,7 @@ int mgx_batch_merge_shards(mgx_batch* batch, uint32_t n_shards, const uint64_t* 
                            const uint32_t* blob32, uint64_t pitch32, void* hip_stream) {
   if (!batch || !blob64 || !blob32 || n_shards == 0)
     return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_batch_merge_shards: null argument");
+  if (batch->hl.on()) return mgx::Fail(MGX_ERR_NOT_IMPLEMENTED, "mgx_batch_merge_shards: highlight on a sharded table is not implemented: the page's texts live on other ranks");
   const bool pages = batch->score.qids.empty() && batch->bitmap.qids.empty() && !batch->page.qids.empty();
   if (!pages && (!batch->bitmap.qids.empty() || !batch->page.qids.empty() || batch->score.qids.empty()))
     return mgx::Fail(MGX_ERR_INVALID_ARGUMENT,
@@ -3687,12 +3935,13 @@ int mgx_batch_merge_local(mgx_batch* primary, mgx_batch* const* others, uint32_t
     void* recv = nullptr;
     MGX_HIP(primary->res->Exchange(1, need, &recv));
     char* g = static_cast<char*>(recv);
+    int rc = MGX_OK;
     for (int pass = 0; pass < 2; ++pass) {
       const bool pages = pass == 1;
       const uint32_t n = static_cast<uint32_t>(pages ? primary->page.qids.size() : primary->score.qids.size());
       if (n == 0) continue;
       uint32_t stride = 0;
-      int rc = ExportGroup(primary, pages, nullptr, nullptr, &stride, hip_stream);
+      rc = ExportGroup(primary, pages, nullptr, nullptr, &stride, hip_stream);
       if (rc) return rc;
       for (uint32_t j = 0; j < n_others; ++j) {
         uint32_t st = 0;
@@ -3720,6 +3969,22 @@ int mgx_batch_merge_local(mgx_batch* primary, mgx_batch* const* others, uint32_t
                       reinterpret_cast<const uint32_t*>(g + off32), bytes / 4, hip_stream);
       if (rc) return rc;
       g += bytes * (1ull + n_others);
+    }
+    if (primary->hl.on()) {
+      // the merged page names every document by its table id: the delta's through its doc map, the main index's own
+      const mgx_index* mapped = nullptr;
+      const mgx_index* plain = nullptr;
+      for (uint32_t j = 0; j <= n_others; ++j) {
+        const mgx_index* ix = (j == 0 ? primary : others[j - 1])->idx;
+        const mgx_index*& slot = ix->d_doc_map.p ? mapped : plain;
+        if (slot) return mgx::Fail(MGX_ERR_NOT_IMPLEMENTED, "mgx_batch_merge_local: highlight reads one main index and one delta");
+        slot = ix;
+      }
+      if ((mapped && !mapped->dev.text) || (plain && !plain->dev.text))
+        return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_batch_merge_local: highlight needs mgx_index_attach_text on every index");
+      rc = mgx::RunHighlight(primary, s, /*merged=*/true, mapped, plain);
+      if (rc) return rc;
+      MGX_HIP(hipEventRecord(primary->res->done_ev, s));  // (the records replace those of the primary's own page)
     }
     return MGX_OK;
   } catch (const std::exception& e) {
@@ -3849,6 +4114,7 @@ int mgx_batch_exchange_df(mgx_batch* batch, mgx_comm* comm, void* hip_stream) {
 
 int mgx_batch_exchange(mgx_batch* batch, mgx_comm* comm, void* hip_stream) {
   if (!batch || !comm) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_batch_exchange: null argument");
+  if (batch->hl.on()) return mgx::Fail(MGX_ERR_NOT_IMPLEMENTED, "mgx_batch_exchange: highlight on a sharded table is not implemented: the page's texts live on other ranks");
   if (!comm->comm) return mgx::Fail(MGX_ERR_INTERNAL, "mgx_batch_exchange: the communicator was aborted");
   if (batch->n_queries == 0) return MGX_OK;
   if (!batch->executed) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_batch_exchange: not executed");
@@ -3910,6 +4176,7 @@ static int RcclGather(void* user, const void* mine, void* all, uint64_t bytes, v
 
 int mgx_batch_execute_gather(mgx_batch* batch, int world, mgx_gather_fn gather, void* user, void* hip_stream) {
   if (!batch || !gather || world < 1) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_batch_execute_gather: bad argument");
+  if (batch->hl.on()) return mgx::Fail(MGX_ERR_NOT_IMPLEMENTED, "mgx_batch_execute_gather: highlight on a sharded table is not implemented: the page's texts live on other ranks");
   try {
     hipStream_t s = nullptr;
     int rc = mgx::BatchStream(batch, hip_stream, &s);

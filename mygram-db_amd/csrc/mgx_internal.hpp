@@ -264,6 +264,45 @@ struct DevBatch {
   uint32_t page_stride;
 };
 
+// ---- HIGHLIGHT (highlight_kernel, mgx_highlight.hip): one wave per (highlighted query, page entry) ------------------
+constexpr uint32_t kHlMaxTerms = 256;  // highlight terms of one query (each keeps one LDS word per wave)
+// Where a page's texts live: an index's resident texts by local slot. A delta index (mgx_index_set_doc_map) is looked up
+// by table id in its ascending doc map; the main index by doc id - first_doc_id.
+struct DevHlSource {
+  const uint8_t* text;       // null: no such source
+  const uint64_t* text_off;  // [n_docs + 1]
+  const uint32_t* doc_map;   // [n_docs] ascending table ids, or null
+  uint32_t first_doc_id, n_docs;
+};
+struct DevHlTerm {
+  uint32_t off, len;  // bytes in DevHlBatch::patterns; 1 <= len
+  uint32_t cps, pad;  // code points of the term
+};
+// One highlighted query. Its page is read where the batch's last kernel left it: `page_docs[j]`, j < the page's entry
+// count = *page_n (SORT _score), or min(*total, limit) of a docid page (total_exec after an execute, total_merged after
+// mgx_batch_merge_local). Entry j's record is at arena + rec_off + j * rec_stride:
+//   [Header | Window[win_cap] | Span[span_cap] | bytes[byte_cap]]
+struct DevHlQuery {
+  const uint32_t* page_docs;
+  const uint32_t* page_n;
+  const unsigned long long* total_exec;
+  const unsigned long long* total_merged;
+  uint32_t limit, entry_begin;
+  uint32_t snippet_length, max_fragments;
+  uint32_t term_begin, n_terms;
+  uint32_t span_cap, byte_cap;
+  uint64_t rec_off, rec_stride;
+};
+struct DevHlBatch {
+  const DevHlQuery* queries;
+  uint32_t n_queries, n_entries;
+  const DevHlTerm* terms;
+  const uint8_t* patterns;
+  uint8_t* arena;
+  DevHlSource mapped, plain;
+  uint32_t merged, pad;
+};
+
 // LDS bytes the tile kernel needs for a launch whose queries have at most these shapes.
 struct LdsPlan {
   uint32_t max_leaves, max_score, max_stack, max_instr, max_cap;

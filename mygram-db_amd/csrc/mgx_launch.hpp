@@ -87,5 +87,7 @@ int LaunchRankMerge(const DevMergeRun* runs, const uint64_t* run_start, uint32_t
                     double* out_scores, hipStream_t s);
 int LaunchSortByScore(const uint32_t* docs, const double* scores, uint64_t n, int descending, uint32_t lo,
                       uint32_t hi, uint64_t* keys_tmp, uint32_t* dprime_tmp, uint32_t* out, hipStream_t s);
+// HIGHLIGHT: one wave per (highlighted query, page entry), after the kernel that finalises the page (mgx_highlight.hip)
+int LaunchHighlight(const DevHlBatch& hb, hipStream_t s);
 
 }  // namespace mgx

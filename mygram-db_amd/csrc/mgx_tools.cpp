@@ -9,6 +9,7 @@
 
 #include "../../include/mygram_tools.h"
 #include "mgx_fuzzy.hpp"
+#include "mgx_highlight.hpp"
 
 namespace {
 
@@ -163,4 +164,81 @@ extern "C" int mgxt_contains_fuzzy_match(const uint8_t* text, size_t text_len, c
                                          uint32_t max_distance) {
   if ((text == nullptr && text_len != 0) || (term == nullptr && term_len != 0)) return -1;
   return mgx::fuzzy::ContainsFuzzyMatchD(text, text_len, term, term_len, max_distance);
+}
+
+// ---- highlighter: the host build of mgx_highlight.hpp ---------------------------------------------------------------
+namespace {
+
+namespace hl = mgx::highlight;
+
+bool HighlightTerms(const uint8_t* text, size_t text_len, const uint8_t* const* terms, const size_t* term_lens,
+                    uint32_t n_terms, std::vector<hl::Term>* out) {
+  if ((text == nullptr && text_len != 0) || (n_terms != 0 && (!terms || !term_lens)) || text_len > 0x7FFFFFFFu) return false;
+  for (uint32_t t = 0; t < n_terms; ++t) {
+    if (terms[t] == nullptr && term_lens[t] != 0) return false;
+    if (term_lens[t] == 0 || term_lens[t] > text_len) continue;  // (:257-262)
+    const uint32_t len = static_cast<uint32_t>(term_lens[t]);
+    out->push_back(hl::Term{terms[t], len, hl::CountCps(terms[t], len)});
+  }
+  return true;
+}
+
+}  // namespace
+
+extern "C" int mgxt_highlight_match_positions(const uint8_t* text, size_t text_len, const uint8_t* const* terms,
+                                              const size_t* term_lens, uint32_t n_terms, uint32_t* out_pairs,
+                                              size_t cap_pairs, size_t* n_pairs) {
+  if (n_pairs) *n_pairs = 0;
+  std::vector<hl::Term> tv;
+  if (!n_pairs || (cap_pairs != 0 && !out_pairs) || !HighlightTerms(text, text_len, terms, term_lens, n_terms, &tv)) return 2;
+  std::vector<uint32_t> scratch(tv.size() + 1);
+  hl::Scanner sc;
+  sc.Init(text, static_cast<uint32_t>(text_len), tv.data(), static_cast<uint32_t>(tv.size()), scratch.data());
+  size_t n = 0;
+  uint32_t ms, me, bs, be;
+  while (sc.Next(&ms, &me, &bs, &be)) {
+    if (n < cap_pairs) {
+      out_pairs[2 * n] = ms;
+      out_pairs[2 * n + 1] = me;
+    }
+    ++n;
+  }
+  *n_pairs = n;
+  return 0;
+}
+
+extern "C" int mgxt_highlight_generate(const uint8_t* text, size_t text_len, const uint8_t* const* terms,
+                                       const size_t* term_lens, uint32_t n_terms, uint32_t snippet_length,
+                                       uint32_t max_fragments, const uint8_t* open_tag, size_t open_len,
+                                       const uint8_t* close_tag, size_t close_len, uint8_t* out, size_t cap,
+                                       size_t* out_len) {
+  if (out_len) *out_len = 0;
+  std::vector<hl::Term> tv;
+  if (!out_len || (cap != 0 && !out) || (open_len != 0 && !open_tag) || (close_len != 0 && !close_tag) ||
+      !HighlightTerms(text, text_len, terms, term_lens, n_terms, &tv))
+    return 2;
+  if (snippet_length < 1 || snippet_length > hl::kMaxSnippetLength || max_fragments < 1 ||
+      max_fragments > hl::kMaxFragments || open_len > hl::kMaxTagBytes || close_len > hl::kMaxTagBytes)
+    return 3;
+  if (text_len == 0) return 0;  // an empty text gives an empty snippet (:301-305)
+  const uint32_t n = static_cast<uint32_t>(text_len);
+  std::vector<uint32_t> scratch(tv.size() + 1);
+  std::vector<hl::Window> win(max_fragments);
+  std::vector<hl::Span> spans;
+  // (a window of L code points holds at most L matches of one code point or more)
+  const size_t span_cap = std::min<size_t>(static_cast<size_t>(max_fragments) * snippet_length, text_len);
+  spans.resize(span_cap + 1);
+  hl::Scanner sc;
+  sc.Init(text, n, tv.data(), static_cast<uint32_t>(tv.size()), scratch.data());
+  hl::Builder bd;
+  bd.Init(snippet_length, max_fragments, win.data(), spans.data(), static_cast<uint32_t>(span_cap));
+  uint32_t ms, me, bs, be;
+  while (!bd.done && sc.Next(&ms, &me, &bs, &be)) bd.Feed(ms, me, bs, be, true);
+  const uint32_t total = bd.done ? hl::kNoTotal : hl::CountCps(text, text_len);
+  bd.Finish(total, true);
+  hl::FinalizeWindows(win.data(), bd.n_win, bd.matched, snippet_length, total, &bd.flags);
+  hl::Header h{bd.n_win, bd.flags, bd.n_spans, 0};
+  h.n_bytes = hl::WindowsToBytes(text, n, win.data(), bd.n_win);
+  *out_len = hl::Render(h, win.data(), spans.data(), text, true, open_tag, open_len, close_tag, close_len, out, cap);
+  return 0;
 }

@@ -2,6 +2,7 @@
 // Host-side rules are cited from the reference (paths relative to its tree); all posting work goes to the device.
 #include "mygram_shim.hpp"
 
+#include "../mgx_highlight.hpp"
 #include "../mgx_text.hpp"
 
 #include <algorithm>
@@ -1695,6 +1696,70 @@ Expected<std::vector<ScoredDoc>, Error> BM25Scorer::ScoreDocuments(const std::ve
 
 namespace query {
 
+namespace {
+namespace hl = mgx::highlight;
+// The terms FindMatchPositions scans for: empty ones and those longer than the text are skipped (highlighter.cpp:257-262).
+std::vector<hl::Term> HighlightScanTerms(std::string_view text, const std::vector<std::string>& search_terms) {
+  std::vector<hl::Term> tv;
+  for (const auto& t : search_terms) {
+    if (t.empty() || t.size() > text.size()) continue;
+    const auto* b = reinterpret_cast<const uint8_t*>(t.data());
+    tv.push_back(hl::Term{b, static_cast<uint32_t>(t.size()), hl::CountCps(b, t.size())});
+  }
+  return tv;
+}
+}  // namespace
+
+std::vector<std::pair<uint32_t, uint32_t>> Highlighter::FindMatchPositions(std::string_view normalized_text,
+                                                                           const std::vector<std::string>& search_terms) {
+  std::vector<std::pair<uint32_t, uint32_t>> positions;
+  if (normalized_text.size() > 0x7FFFFFFFu) return positions;
+  const std::vector<hl::Term> tv = HighlightScanTerms(normalized_text, search_terms);
+  std::vector<uint32_t> scratch(tv.size() + 1);
+  hl::Scanner sc;
+  sc.Init(reinterpret_cast<const uint8_t*>(normalized_text.data()), static_cast<uint32_t>(normalized_text.size()),
+          tv.data(), static_cast<uint32_t>(tv.size()), scratch.data());
+  uint32_t ms, me, bs, be;
+  while (sc.Next(&ms, &me, &bs, &be)) positions.emplace_back(ms, me);
+  return positions;
+}
+
+HighlightResult Highlighter::Generate(std::string_view normalized_text, const std::vector<std::string>& search_terms,
+                                      const HighlightOptions& options) {
+  HighlightResult result;
+  if (normalized_text.empty() || normalized_text.size() > 0x7FFFFFFFu) return result;  // (:301-305)
+  if (options.snippet_length < 1 || options.snippet_length > hl::kMaxSnippetLength || options.max_fragments < 1 ||
+      options.max_fragments > hl::kMaxFragments || options.open_tag.size() > hl::kMaxTagBytes ||
+      options.close_tag.size() > hl::kMaxTagBytes)
+    return result;
+  const auto* text = reinterpret_cast<const uint8_t*>(normalized_text.data());
+  const uint32_t n = static_cast<uint32_t>(normalized_text.size());
+  const std::vector<hl::Term> tv = HighlightScanTerms(normalized_text, search_terms);
+  std::vector<uint32_t> scratch(tv.size() + 1);
+  std::vector<hl::Window> win(options.max_fragments);
+  const size_t span_cap = std::min<size_t>(static_cast<size_t>(options.max_fragments) * options.snippet_length, n);
+  std::vector<hl::Span> spans(span_cap + 1);
+  hl::Scanner sc;
+  sc.Init(text, n, tv.data(), static_cast<uint32_t>(tv.size()), scratch.data());
+  hl::Builder bd;
+  bd.Init(options.snippet_length, options.max_fragments, win.data(), spans.data(), static_cast<uint32_t>(span_cap));
+  uint32_t ms, me, bs, be;
+  while (!bd.done && sc.Next(&ms, &me, &bs, &be)) bd.Feed(ms, me, bs, be, true);
+  const uint32_t total = bd.done ? hl::kNoTotal : hl::CountCps(text, n);
+  bd.Finish(total, true);
+  hl::FinalizeWindows(win.data(), bd.n_win, bd.matched, options.snippet_length, total, &bd.flags);
+  hl::Header h{bd.n_win, bd.flags, bd.n_spans, 0};
+  h.n_bytes = hl::WindowsToBytes(text, n, win.data(), bd.n_win);
+  const auto* ot = reinterpret_cast<const uint8_t*>(options.open_tag.data());
+  const auto* ct = reinterpret_cast<const uint8_t*>(options.close_tag.data());
+  const size_t len = hl::Render(h, win.data(), spans.data(), text, true, ot, options.open_tag.size(), ct,
+                                options.close_tag.size(), nullptr, 0);
+  result.snippet.resize(len);
+  hl::Render(h, win.data(), spans.data(), text, true, ot, options.open_tag.size(), ct, options.close_tag.size(),
+             reinterpret_cast<uint8_t*>(result.snippet.data()), len);
+  return result;
+}
+
 std::vector<DocId> ResultSorter::SortByScore(const index::Index& index, const std::vector<DocId>& results,
                                              const std::vector<double>& scores, SortOrder order, uint32_t limit,
                                              uint32_t offset) {
@@ -2307,6 +2372,7 @@ void Collect(const std::vector<PlannedQuery>& plans, const mgx_result_view& v, s
     o.total = 0;
     o.total_candidates = o.after_intersection = o.after_not = o.after_filters = 0;
     o.empty_term_detected = false;
+    o.snippets.clear();
     if (!plans[qi].on_device) {
       o.empty_term_detected = plans[qi].empty_term_detected;
       continue;
@@ -2330,7 +2396,133 @@ void Collect(const std::vector<PlannedQuery>& plans, const mgx_result_view& v, s
     o.scores.assign(v.scores + r.docs_begin, v.scores + r.docs_begin + r.n_docs);
   }
 }
+
+// ---- HIGHLIGHT -------------------------------------------------------------------------------------------------------
+// The requests of one batch's device queries (mgx_batch_set_highlight) and everything they point at.
+struct HighlightRequests {
+  std::vector<mgx_highlight_request> reqs;
+  std::vector<std::vector<std::string>> terms;
+  std::vector<std::vector<const uint8_t*>> ptrs;
+  std::vector<std::vector<uint32_t>> lens;
+};
+
+bool AnyHighlight(const std::vector<BatchQuery>& queries) {
+  for (const auto& q : queries)
+    if (q.highlight) return true;
+  return false;
+}
+
+void CollectScoringLeaves(const query::QueryNode& node, bool under_not, std::vector<std::string>* out) {
+  // CollectAstScoringTerms, search_pipeline.cpp:232-254
+  if (node.type == query::NodeType::TERM) {
+    if (!under_not) out->push_back(node.term);
+    return;
+  }
+  for (const auto& c : node.children)
+    if (c) CollectScoringLeaves(*c, under_not || node.type == query::NodeType::NOT, out);
+}
+
+// After prepare / reset and before the execute. `delta`: the table's delta index (its texts can be the longest).
+Error AttachHighlight(const index::Index& index, const index::Index* delta, const std::vector<BatchQuery>& queries,
+                    const std::vector<PlannedQuery>& plans, mgx_batch* batch, HighlightRequests* h) {
+  h->reqs.clear();
+  if (!AnyHighlight(queries)) return Error{ErrorCode::kSuccess, ""};
+  size_t n_dev = 0;
+  for (const auto& p : plans) n_dev += p.on_device ? 1 : 0;
+  h->reqs.assign(n_dev, mgx_highlight_request{});
+  h->terms.resize(n_dev);
+  h->ptrs.resize(n_dev);
+  h->lens.resize(n_dev);
+  size_t k = 0;
+  for (size_t qi = 0; qi < queries.size(); ++qi) {
+    if (!plans[qi].on_device) continue;
+    const BatchQuery& q = queries[qi];
+    const size_t at = k++;
+    if (!q.highlight) continue;
+    std::vector<std::string> all;
+    if (q.ast) CollectScoringLeaves(*q.ast, false, &all);
+    all.insert(all.end(), q.terms.begin(), q.terms.end());
+    h->terms[at] = BuildHighlightTerms(all, &index);
+    h->ptrs[at].clear();
+    h->lens[at].clear();
+    for (const std::string& t : h->terms[at]) {
+      h->ptrs[at].push_back(reinterpret_cast<const uint8_t*>(t.data()));
+      h->lens[at].push_back(static_cast<uint32_t>(t.size()));
+    }
+    mgx_highlight_request& r = h->reqs[at];
+    r.enabled = 1;
+    r.snippet_length = q.highlight->snippet_length;
+    r.max_fragments = q.highlight->max_fragments;
+    r.n_terms = static_cast<uint32_t>(h->terms[at].size());
+    r.terms = h->ptrs[at].data();
+    r.term_lens = h->lens[at].data();
+    if (q.highlight->open_tag.size() > 256 || q.highlight->close_tag.size() > 256)  // query_parser.h:276
+      return MakeError(ErrorCode::kOutOfRange, "highlight: a tag is at most 256 bytes");
+  }
+  uint32_t longest = 0, dl = 0;
+  (void)mgx_index_max_text_bytes(index.impl()->dev, &longest);
+  if (delta != nullptr && delta->impl()->dev != nullptr) {
+    (void)mgx_index_max_text_bytes(delta->impl()->dev, &dl);
+    longest = std::max(longest, dl);
+  }
+  int rc = mgx_batch_set_highlight(batch, h->reqs.data(), static_cast<uint32_t>(h->reqs.size()), longest);
+  // (with a delta the page is final only after mgx_batch_merge_local: the kernel runs once, there)
+  if (rc == MGX_OK && delta != nullptr) rc = mgx_batch_defer_highlight(batch, 1);
+  return rc == MGX_OK ? Error{ErrorCode::kSuccess, ""} : MakeError(static_cast<ErrorCode>(rc), mgx_last_error());
+}
+
+// After mgx_batch_fetch: the snippets of the highlighted queries' pages (the host adds tags and "...").
+int CollectSnippets(const std::vector<BatchQuery>& queries, const std::vector<PlannedQuery>& plans, mgx_batch* batch,
+                    const mgx_result_view& v, std::vector<BatchResult>* out) {
+  if (!AnyHighlight(queries) || batch == nullptr || v.queries == nullptr) return MGX_OK;
+  mgx_highlight_view hv{};
+  int rc = mgx_batch_fetch_highlight(batch, &hv);
+  if (rc != MGX_OK) return rc;
+  size_t k = 0;
+  for (size_t qi = 0; qi < plans.size(); ++qi) {
+    if (!plans[qi].on_device) continue;
+    const mgx_query_result& r = v.queries[k++];
+    if (!queries[qi].highlight) continue;
+    const query::HighlightOptions& o = *queries[qi].highlight;
+    std::vector<std::string>& sn = (*out)[qi].snippets;
+    sn.resize(r.n_docs);  // (strings a caller hands back keep their storage: WaitInto)
+    for (uint32_t j = 0; j < r.n_docs; ++j) {
+      const mgx_highlight_entry& e = hv.entries[r.docs_begin + j];
+      const size_t cap = e.n_bytes + static_cast<size_t>(e.n_spans) * (o.open_tag.size() + o.close_tag.size()) +
+                         3 * (static_cast<size_t>(e.n_windows) + 1);
+      sn[j].resize(cap);
+      size_t len = 0;
+      rc = mgx_highlight_render(&e, reinterpret_cast<const uint8_t*>(o.open_tag.data()), o.open_tag.size(),
+                                reinterpret_cast<const uint8_t*>(o.close_tag.data()), o.close_tag.size(),
+                                reinterpret_cast<uint8_t*>(sn[j].data()), cap, &len);
+      if (rc != MGX_OK) return rc;
+      sn[j].resize(std::min(len, cap));
+    }
+  }
+  return MGX_OK;
+}
 }  // namespace
+
+std::vector<std::string> BuildHighlightTerms(const std::vector<std::string>& search_terms, const index::Index* index) {
+  std::vector<std::string> terms;
+  terms.reserve(search_terms.size());
+  for (const auto& term : search_terms) {
+    std::string normalized = index != nullptr ? index->NormalizeText(term) : term;
+    if (normalized.empty()) continue;
+    terms.push_back(normalized);
+    size_t i = 0;
+    const auto space = [](char c) { return c == ' ' || (c >= '\t' && c <= '\r'); };  // what `stream >> piece` skips
+    while (i < normalized.size()) {
+      while (i < normalized.size() && space(normalized[i])) ++i;
+      size_t j = i;
+      while (j < normalized.size() && !space(normalized[j])) ++j;
+      if (j > i && j - i != normalized.size()) terms.push_back(normalized.substr(i, j - i));
+      i = j;
+    }
+  }
+  DeduplicateSorted(terms);
+  return terms;
+}
 
 namespace {
 // A mutable table's delta index as the device holds it now (nullptr: none). ApplyMutations has run.
@@ -2403,6 +2595,11 @@ Expected<std::vector<BatchResult>, Error> ExecuteBatch(const index::Index& index
   int rc = mgx_batch_prepare(im->dev, mq.data(), static_cast<uint32_t>(mq.size()), &batch);
   if (rc != MGX_OK) return MakeUnexpected(MakeError(static_cast<ErrorCode>(rc), mgx_last_error()));
   std::unique_ptr<mgx_batch, void (*)(mgx_batch*)> guard(batch, mgx_batch_destroy);
+  HighlightRequests hreq;
+  {
+    const Error he = AttachHighlight(index, delta.get(), queries, plans, batch, &hreq);
+    if (he.code() != ErrorCode::kSuccess) return MakeUnexpected(he);
+  }
   if (delta) {
     mgx_batch* dbatch = nullptr;
     rc = mgx_batch_prepare(delta->impl()->dev, dq.data(), static_cast<uint32_t>(dq.size()), &dbatch);
@@ -2417,6 +2614,8 @@ Expected<std::vector<BatchResult>, Error> ExecuteBatch(const index::Index& index
     if (rc == MGX_OK) rc = mgx_batch_fetch(dbatch, &dv);
     if (rc != MGX_OK) return MakeUnexpected(MakeError(static_cast<ErrorCode>(rc), mgx_last_error()));
     Collect(plans, v, &out, &dv);
+    rc = CollectSnippets(queries, plans, batch, v, &out);
+    if (rc != MGX_OK) return MakeUnexpected(MakeError(static_cast<ErrorCode>(rc), mgx_last_error()));
     return out;
   }
   rc = mgx_batch_execute(batch, nullptr);
@@ -2424,6 +2623,8 @@ Expected<std::vector<BatchResult>, Error> ExecuteBatch(const index::Index& index
   rc = mgx_batch_fetch(batch, &v);
   if (rc != MGX_OK) return MakeUnexpected(MakeError(static_cast<ErrorCode>(rc), mgx_last_error()));
   Collect(plans, v, &out);
+  rc = CollectSnippets(queries, plans, batch, v, &out);
+  if (rc != MGX_OK) return MakeUnexpected(MakeError(static_cast<ErrorCode>(rc), mgx_last_error()));
   return out;
 }
 
@@ -2559,6 +2760,7 @@ struct BatchExecutor::Impl {
     std::shared_ptr<index::Index> delta, dbatch_index;
     std::vector<PlannedQuery> dplans;
     std::vector<mgx_query> dq;
+    HighlightRequests hreq;  // mgx_batch_set_highlight of this batch (storage re-used from batch to batch)
     mgx_batch* dbatch = nullptr;
     uint64_t total_docs = 0;  // BM25Stats the batch is planned with (a mutable table's change between batches)
     double avgdl = 0.0;
@@ -2650,6 +2852,8 @@ struct BatchExecutor::Impl {
       slot->error = MakeError(static_cast<ErrorCode>(rc), mgx_last_error());
       return;
     }
+    slot->error = AttachHighlight(index, slot->delta.get(), slot->queries, slot->plans, slot->batch, &slot->hreq);
+    if (slot->error.code() != ErrorCode::kSuccess) return;
     if (slot->dbatch && slot->dbatch_index != slot->delta) {  // the delta index was rebuilt (or went away)
       mgx_batch_destroy(slot->dbatch);
       slot->dbatch = nullptr;
@@ -2869,6 +3073,10 @@ Expected<uint64_t, Error> BatchExecutor::Submit(std::vector<BatchQuery>&& querie
     impl_->total_docs = impl_->index.Bm25DocCount();
     impl_->avgdl = impl_->index.Bm25AvgDocLength();
   }
+  if (impl_->opt.comm && AnyHighlight(queries))
+    return MakeUnexpected(MakeError(ErrorCode::kNotImplemented,
+                                    "highlight on a sharded table (Options::comm) is not implemented: the page's texts "
+                                    "live on other ranks"));
   Impl::Slot* slot = nullptr;
   {
     std::lock_guard<std::mutex> lock(impl_->mu);
@@ -2959,6 +3167,15 @@ Error BatchExecutor::WaitInto(uint64_t ticket, std::vector<BatchResult>* results
     }
   }
   Collect(s->plans, v, &out, s->delta ? &dv : nullptr);
+  if (!s->mq.empty()) {
+    const int rc = CollectSnippets(s->queries, s->plans, s->batch, v, &out);
+    if (rc != MGX_OK) {
+      const Error e = MakeError(static_cast<ErrorCode>(rc), mgx_last_error());
+      lock.lock();
+      s->state = Impl::kFree;
+      return e;
+    }
+  }
   s->timing.wait_ms = std::chrono::duration<double, std::milli>(Impl::clock::now() - t0).count();
   if (timing) *timing = s->timing;
   lock.lock();

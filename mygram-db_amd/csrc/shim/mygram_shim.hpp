@@ -26,6 +26,7 @@
 #include <chrono>
 #include <cstdint>
 #include <memory>
+#include <optional>
 #include <string>
 #include <unordered_map>
 #include <string_view>
@@ -353,6 +354,29 @@ struct QueryNode {
   explicit QueryNode(NodeType node_type) : type(node_type) {}
 };
 
+// query::HighlightOptions (src/query/query_parser.h:158-163): SEARCH ... HIGHLIGHT [TAG <open> <close>] [SNIPPET_LEN n]
+// [MAX_FRAGMENTS n]. The parser's ranges: snippet_length 1..10000, max_fragments 1..100, tags of 256 bytes at most
+// (query_parser_clauses.cpp:372-431, query_parser.h:276).
+struct HighlightOptions {
+  std::string open_tag = "<em>";
+  std::string close_tag = "</em>";
+  uint32_t snippet_length = 100;
+  uint32_t max_fragments = 3;
+};
+struct HighlightResult {  // src/query/highlighter.h:30-32
+  std::string snippet;
+};
+// query::Highlighter (src/query/highlighter.h; impl highlighter.cpp:252-309) over a NORMALIZED text, on the host: the
+// host build of the source the device's highlight_kernel compiles (csrc/mgx_highlight.hpp). GenerateOriginal is not
+// provided: the project holds normalized texts only. Options outside the parser's ranges give an empty snippet.
+class Highlighter {
+ public:
+  static HighlightResult Generate(std::string_view normalized_text, const std::vector<std::string>& search_terms,
+                                  const HighlightOptions& options);
+  static std::vector<std::pair<uint32_t, uint32_t>> FindMatchPositions(std::string_view normalized_text,
+                                                                       const std::vector<std::string>& search_terms);
+};
+
 class ResultSorter {
  public:
   // src/query/result_sorter.h:75-76. Runs on the device of `index` (any finalised index: only its stream is used).
@@ -401,7 +425,18 @@ struct BatchQuery {
   uint32_t limit = 100;                // api.default_limit (src/config/config.h:61)
   uint32_t offset = 0;
   index::BM25Params bm25;
+  // HIGHLIGHT: GenerateHighlightSnippets on the page (src/server/handlers/search_handler.cpp:473-482), on the device
+  // behind the kernel that finalises the page (mgx_batch_set_highlight). The terms are the reference's all_search_terms
+  // (`terms`, or the tree's TERM leaves that are not under a NOT, search_pipeline.cpp:1812-1816, 1848-1853) through
+  // BuildHighlightTerms. Needs limit > 0 and offset + limit <= 1024 (docid pages: limit <= 1024, the offset is the
+  // caller's cut); refused (kNotImplemented) on a sharded executor (Options::comm): the page's texts live on other ranks.
+  std::optional<query::HighlightOptions> highlight;
 };
+
+// search_pipeline::BuildHighlightTerms (src/server/search_pipeline.cpp:712-745) without the synonym branch: normalize
+// (index == nullptr: the terms are normalized already), skip empty terms, add the whitespace-separated pieces, sort and
+// dedupe.
+std::vector<std::string> BuildHighlightTerms(const std::vector<std::string>& search_terms, const index::Index* index);
 
 // SearchPipelineResult (src/server/search_pipeline.h:58-65) plus the page the handler would format.
 struct BatchResult {
@@ -410,6 +445,7 @@ struct BatchResult {
   uint64_t total = 0;                  // results.size() before pagination
   size_t total_candidates = 0, after_intersection = 0, after_not = 0, after_filters = 0;
   bool empty_term_detected = false;
+  std::vector<std::string> snippets;   // parallel to results when the query asked for highlight, else empty
 };
 
 // N queries planned like ExecuteFullPipeline's regular branch (GenerateTermInfos with df, sort by estimated size,

@@ -444,6 +444,61 @@ int mgxs_search(mgxs_table* table, uint32_t n_terms, const char* const* terms, u
   }
 }
 
+int mgxs_search_highlight(mgxs_table* table, uint32_t n_terms, const char* const* terms, uint32_t n_not,
+                          const char* const* not_terms, int sort_by_score, int descending, uint32_t limit, uint32_t offset,
+                          const char* open_tag, const char* close_tag, uint32_t snippet_length, uint32_t max_fragments,
+                          uint64_t* total, uint32_t* n_docs, uint32_t* docs, double* scores, char* snippets,
+                          size_t snippets_cap, uint32_t* snippet_off) {
+  if (!table || !total || !n_docs || !open_tag || !close_tag || !snippet_off || (limit && !docs) || (snippets_cap && !snippets))
+    return Fail(MGX_ERR_INVALID_ARGUMENT, "mgxs_search_highlight: null argument");
+  try {
+    BatchQuery q = MakeQuery(n_terms, terms, n_not, not_terms, 0, nullptr, nullptr, nullptr, sort_by_score, descending,
+                             limit, offset);
+    q.highlight = mygramdb::query::HighlightOptions{open_tag, close_tag, snippet_length, max_fragments};
+    auto r = mygramdb::search_pipeline::ExecuteBatch(*table->index, {q});
+    if (!r) return Fail(static_cast<int>(r.error().code()), r.error().message());
+    const auto& res = (*r)[0];
+    *total = res.total;
+    const size_t n = limit ? std::min<size_t>(res.results.size(), limit) : 0;
+    *n_docs = static_cast<uint32_t>(n);
+    size_t at = 0;
+    for (size_t k = 0; k < n; ++k) {
+      docs[k] = res.results[k];
+      if (scores) scores[k] = k < res.scores.size() ? res.scores[k] : 0.0;
+      snippet_off[k] = static_cast<uint32_t>(at);
+      const std::string& sn = res.snippets[k];
+      if (at + sn.size() > snippets_cap) return Fail(MGX_ERR_OUT_OF_RANGE, "mgxs_search_highlight: snippet buffer too small");
+      std::memcpy(snippets + at, sn.data(), sn.size());
+      at += sn.size();
+    }
+    snippet_off[n] = static_cast<uint32_t>(at);
+    return MGX_OK;
+  } catch (const std::exception& e) {
+    return Fail(MGX_ERR_INTERNAL, e.what());
+  }
+}
+
+int mgxs_highlight_generate(const char* text, size_t len, uint32_t n_terms, const char* const* terms, const size_t* term_lens,
+                            const char* open_tag, const char* close_tag, uint32_t snippet_length, uint32_t max_fragments,
+                            char* out, size_t cap, size_t* out_len) {
+  if ((len && !text) || (n_terms && (!terms || !term_lens)) || !open_tag || !close_tag || !out_len || (cap && !out))
+    return Fail(MGX_ERR_INVALID_ARGUMENT, "mgxs_highlight_generate: null argument");
+  try {
+    std::vector<std::string> tv;
+    for (uint32_t t = 0; t < n_terms; ++t) tv.emplace_back(terms[t] ? terms[t] : "", term_lens[t]);
+    const mygramdb::query::HighlightOptions o{open_tag, close_tag, snippet_length, max_fragments};
+    if (snippet_length < 1 || snippet_length > 10000 || max_fragments < 1 || max_fragments > 100 ||
+        o.open_tag.size() > 256 || o.close_tag.size() > 256)
+      return Fail(MGX_ERR_OUT_OF_RANGE, "mgxs_highlight_generate: option outside the parser's range");
+    const auto r = mygramdb::query::Highlighter::Generate(std::string_view(text ? text : "", len), tv, o);
+    *out_len = r.snippet.size();
+    std::memcpy(out, r.snippet.data(), std::min(cap, r.snippet.size()));
+    return MGX_OK;
+  } catch (const std::exception& e) {
+    return Fail(MGX_ERR_INTERNAL, e.what());
+  }
+}
+
 int mgxs_facet(mgxs_table* table, uint32_t n_terms, const char* const* terms, uint32_t n_not, const char* const* not_terms,
                uint32_t n_cond, const char* const* cond_columns, const uint32_t* cond_ops, const char* const* cond_values,
                const char* column, uint32_t limit, uint32_t offset, uint64_t* matched, uint64_t* total_values,

@@ -308,11 +308,34 @@ class DeviceIndex:
 # queries
 # --------------------------------------------------------------------------------------------------------------------
 
+class Highlight:
+    """query::HighlightOptions (src/query/query_parser.h:158-163): SEARCH ... HIGHLIGHT [TAG <open> <close>]
+    [SNIPPET_LEN n] [MAX_FRAGMENTS n]."""
+
+    def __init__(self, open_tag="<em>", close_tag="</em>", snippet_length=100, max_fragments=3):
+        self.open_tag, self.close_tag = open_tag, close_tag
+        self.snippet_length, self.max_fragments = snippet_length, max_fragments
+
+
+def build_highlight_terms(normalized_terms):
+    """search_pipeline::BuildHighlightTerms (search_pipeline.cpp:712-745) without the synonym branch, over terms that
+    are normalized already: skip empty terms, add the whitespace-separated pieces, sort bytewise and dedupe."""
+    out = set()
+    for t in normalized_terms:
+        b = t.encode("utf-8") if isinstance(t, str) else bytes(t)
+        if not b:
+            continue
+        out.add(b)
+        for piece in b.split():  # bytes.split(): ' ', \t, \n, \v, \f, \r — what `stream >> piece` skips
+            out.add(piece)
+    return sorted(out)
+
+
 class Query:
     """The parts of query::Query (src/query/query_parser.h:207-243) the hot path consumes."""
 
     def __init__(self, terms=(), not_terms=(), filters=(), sort_score=False, limit=100, offset=0, descending=True,
-                 k1=1.2, b=0.75, fuzzy=0, expr=None, universe=None, verify_text=False):
+                 k1=1.2, b=0.75, fuzzy=0, expr=None, universe=None, verify_text=False, highlight=None):
         """`expr`: boolean tree over term strings instead of the plain AND of `terms` (query::QueryNode):
         "term" | ("and", e, ...) | ("or", e, ...) | ("not", e). `universe` = (first_doc_id, count) of the NOT universe
         (DocumentStore::GetAllDocIds); None = every slot of the index."""
@@ -323,6 +346,9 @@ class Query:
         # queries with an uncovered mixed-script fragment are post-filtered by exact text regardless (:858-866)
         self.verify_text = verify_text
         self.expr, self.universe = expr, universe
+        # highlight: None / False = off; True = default options; or a Highlight. SearchResult.snippets then holds one
+        # snippet per returned doc (GenerateHighlightSnippets on the page, search_handler.cpp:473-482)
+        self.highlight = Highlight() if highlight is True else (highlight or None)
         if expr is not None and not self.terms:
             seen = []
 
@@ -345,7 +371,7 @@ class TermInfo:
 
 class SearchResult:
     __slots__ = ("total", "docs", "scores", "total_candidates", "after_intersection", "after_not", "after_filters",
-                 "empty_term_detected", "term_order")
+                 "empty_term_detected", "term_order", "snippets")
 
     def __init__(self):
         self.total = 0
@@ -354,6 +380,7 @@ class SearchResult:
         self.total_candidates = self.after_intersection = self.after_not = self.after_filters = 0
         self.empty_term_detected = False
         self.term_order = []
+        self.snippets = []  # bytes per returned doc, when the query asked for highlight
 
 
 def _take_u32(ptr, n):
@@ -362,10 +389,23 @@ def _take_u32(ptr, n):
     return out.astype(np.uint32)
 
 
+def _render_snippet(entry, opts):
+    """mgx_highlight_render: tags and "..." around one page entry's record."""
+    open_tag = opts.open_tag.encode("utf-8") if isinstance(opts.open_tag, str) else bytes(opts.open_tag)
+    close_tag = opts.close_tag.encode("utf-8") if isinstance(opts.close_tag, str) else bytes(opts.close_tag)
+    cap = entry.n_bytes + entry.n_spans * (len(open_tag) + len(close_tag)) + 3 * (entry.n_windows + 1)
+    buf = C.create_string_buffer(max(cap, 1))
+    n = C.c_size_t(0)
+    check(load().mgx_highlight_render(C.byref(entry), open_tag, len(open_tag), close_tag, len(close_tag), buf, cap,
+                                      C.byref(n)))
+    assert n.value <= cap
+    return buf.raw[:n.value]
+
+
 class PreparedBatch:
     """mgx_batch: a compiled, device-resident batch of queries that can be executed repeatedly."""
 
-    def __init__(self, index, cqueries, keep, shells, orders):
+    def __init__(self, index, cqueries, keep, shells, orders, highlights=None):
         self.index, self._keep, self._shells, self._orders = index, keep, shells, orders
         self.n = len(cqueries)
         self._h = None
@@ -374,13 +414,30 @@ class PreparedBatch:
             arr = (_capi.Query * self.n)(*cqueries)
             check(load().mgx_batch_prepare(index.device_index._h, arr, self.n, C.byref(h)))
             self._h = h
+        self._set_highlight(highlights)
+
+    def _set_highlight(self, highlights):
+        """mgx_batch_set_highlight: highlights[i] = None or (Highlight, term list as bytes) of device query i."""
+        self._highlights = highlights if highlights and any(h is not None for h in highlights) else None
+        if not self._highlights or not self._h:
+            return
+        reqs = (_capi.HighlightRequest * self.n)()
+        for i, h in enumerate(self._highlights):
+            if h is None:
+                continue
+            opts, terms = h
+            arr = (C.c_char_p * max(len(terms), 1))(*terms)
+            lens = (C.c_uint32 * max(len(terms), 1))(*[len(t) for t in terms])
+            self._keep.extend([arr, lens])
+            reqs[i] = _capi.HighlightRequest(1, opts.snippet_length, opts.max_fragments, len(terms), arr, lens)
+        check(load().mgx_batch_set_highlight(self._h, reqs, self.n, 0))
 
     def __del__(self):
         if getattr(self, "_h", None):
             load().mgx_batch_destroy(self._h)
             self._h = None
 
-    def reset(self, cqueries, keep, shells, orders):
+    def reset(self, cqueries, keep, shells, orders, highlights=None):
         """mgx_batch_reset: the same batch object (device arenas, pinned result block) for a new set of queries."""
         self._keep, self._shells, self._orders = keep, shells, orders
         self.n = len(cqueries)
@@ -392,6 +449,7 @@ class PreparedBatch:
             self._h = h
         else:
             check(load().mgx_batch_reset(self._h, arr, self.n))
+        self._set_highlight(highlights)
 
     def execute(self, stream=None):
         if self._h:
@@ -426,8 +484,11 @@ class PreparedBatch:
     def fetch(self):
         """-> list[SearchResult] in the order the queries were given (host-resolved queries included)."""
         v = _capi.ResultView()
+        hv = _capi.HighlightView()
         if self._h:
             check(load().mgx_batch_fetch(self._h, C.byref(v)))
+            if self._highlights:
+                check(load().mgx_batch_fetch_highlight(self._h, C.byref(hv)))
         out = []
         k = 0
         for qi, shell in enumerate(self._shells):
@@ -444,6 +505,9 @@ class PreparedBatch:
             if r.n_docs:
                 s.docs = np.ctypeslib.as_array(v.docs, shape=(r.docs_begin + r.n_docs,))[r.docs_begin:].copy()
                 s.scores = np.ctypeslib.as_array(v.scores, shape=(r.docs_begin + r.n_docs,))[r.docs_begin:].copy()
+            if self._highlights and self._highlights[k - 1] is not None:
+                opts = self._highlights[k - 1][0]
+                s.snippets = [_render_snippet(hv.entries[r.docs_begin + j], opts) for j in range(r.n_docs)]
             out.append(s)
         return out
 
@@ -787,9 +851,28 @@ class Index:
     def prepare(self, queries, into=None):
         """Compiles queries the way ExecuteFullPipeline's regular branch plans them (search_pipeline.cpp:2002-2030,
         Execute :795-869) and uploads them as one batch. `into`: a PreparedBatch to re-use (mgx_batch_reset)."""
-        cqueries, keep, shells, orders = [], [], [], []
+        cqueries, keep, shells, orders, highlights = [], [], [], [], []
         for q in queries:
             tis = [self.term_info(t, q.fuzzy) for t in q.terms]
+            hl = None
+            if q.highlight is not None:
+                # the reference's all_search_terms: search_text + and_terms; the CollectAstScoringTerms leaves of an
+                # expression (search_pipeline.cpp:1812-1816, 1848-1853); a FUZZY query's terms as given
+                self.ensure_text()
+                by_term = {t.term: t.normalized for t in tis}
+                names = []
+                if q.expr is not None:
+                    def leaves(e, under_not):
+                        if isinstance(e, str):
+                            if not under_not:
+                                names.append(e)
+                            return
+                        for c in e[1:]:
+                            leaves(c, under_not or e[0] == "not")
+                    leaves(q.expr, False)
+                else:
+                    names = list(q.terms)
+                hl = (q.highlight, build_highlight_terms([by_term[t] for t in names]))
             if q.fuzzy:
                 # ExecuteWithFuzzy (search_pipeline.cpp:1659-1744): terms in the order given (no size sort); a term
                 # without n-grams ends the query; per term "at least theta of its known grams", AND across terms
@@ -859,6 +942,7 @@ class Index:
                     cq.score_terms = sc.ctypes.data if len(sc) else C.cast(cterms, C.c_void_p).value  # (non-NULL: "none")
                     cq.n_score_terms = len(sc)
                 cqueries.append(cq)
+                highlights.append(hl)
                 shells.append(None)
                 continue
             if q.expr is not None:
@@ -981,13 +1065,14 @@ class Index:
                 if q.universe is not None:
                     cq.universe_first, cq.universe_count = q.universe
             cqueries.append(cq)
+            highlights.append(hl)
             shells.append(None)
         if into == "raw":  # (facet: the compiled C queries themselves)
             return cqueries, keep, shells
         if into is not None:
-            into.reset(cqueries, keep, shells, orders)
+            into.reset(cqueries, keep, shells, orders, highlights)
             return into
-        return PreparedBatch(self, cqueries, keep, shells, orders)
+        return PreparedBatch(self, cqueries, keep, shells, orders, highlights)
 
     def facet_counts(self, query, column_id, n_values):
         """mgx_facet_counts: (matched documents, counts per value id) of the query's whole result set."""
