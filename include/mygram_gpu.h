@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define MGX_ABI_VERSION 4U
+#define MGX_ABI_VERSION 5U
 
 /* Values of mygram::utils::ErrorCode used on this path (src/utils/error.h:37-48,100). */
 #define MGX_OK 0
@@ -278,6 +278,26 @@ typedef struct mgx_filter {
   uint32_t negate;    /* 0: EQ (AND), 1: NE (ANDNOT) — search_pipeline.cpp:1196-1237 */
 } mgx_filter;
 
+/* One FilterCondition evaluated by the batch itself: the doc set mgx_index_filter_compare(column_id, op, literal_bits,
+ * eq_epsilon, null_matches, never_matches) would register, bit for bit, but held in a row of an arena the BATCH OBJECT
+ * owns — no row of the index's filter pool, no synchronisation at planning time. Every execute of the batch starts
+ * with one launch (filter_compare_batch_kernel) that evaluates the batch's distinct conditions (two conditions are the
+ * same when every field but `negate` is equal) against the resident typed columns; the arena is kept across
+ * mgx_batch_reset and grows only when a batch holds more distinct conditions than any before it. A batch whose
+ * distinct conditions would need more than MGX_CONDITION_ARENA_MAX_BYTES of rows (one row = the index's filter row:
+ * n_docs bits rounded up to 16384-doc tiles, plus padding) is refused with MGX_ERR_OUT_OF_RANGE. */
+#define MGX_CONDITION_ARENA_MAX_BYTES (1ull << 30)
+typedef struct mgx_condition {
+  uint32_t column_id;    /* from mgx_index_add_filter_column; unknown: MGX_ERR_OUT_OF_RANGE */
+  uint32_t op;           /* MGX_CMP_*; unknown: MGX_ERR_INVALID_ARGUMENT */
+  uint64_t literal_bits; /* as mgx_index_filter_compare */
+  double eq_epsilon;
+  uint32_t null_matches; /* as mgx_index_filter_compare */
+  uint32_t never_matches;
+  uint32_t negate;       /* as mgx_filter.negate: 1 = ANDNOT the set */
+  uint32_t reserved;     /* 0 */
+} mgx_condition;
+
 /* Boolean expression over the positive terms (query::QueryNode, src/query/query_ast.h:52-83), in POSTFIX order.
  * Evaluated like EvaluateBooleanAstExpanded (src/server/search_pipeline.cpp:327-378): TERM = the term's doc set,
  * AND = intersection of its children, OR = union, NOT = universe minus child, where the universe is
@@ -339,6 +359,11 @@ typedef struct mgx_query {
    * mgx_index_attach_text. after_filters still counts the docs before this filter, `total` those after it. The query
    * runs on the general kernel, in a launch of its own. */
   uint32_t fuzzy_verify_distance;
+  /* FILTER conditions the batch evaluates itself (mgx_condition), applied after `filters` in the same funnel step
+   * (after_filters counts the docs that passed both). n_filters + n_conditions <= MGX_MAX_TERMS, else
+   * MGX_ERR_OUT_OF_RANGE. NULL / 0: none — the batch then launches and allocates nothing for them. */
+  const mgx_condition* conditions;
+  uint32_t n_conditions;
 } mgx_query;
 
 typedef struct mgx_batch mgx_batch;

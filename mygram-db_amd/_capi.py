@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # MGX_LIBRARY: tools only (e.g. the -DMGX_ABLATION build of `make ablation`); the product is libmygram_gpu.so
 LIB_PATH = os.environ.get("MGX_LIBRARY") or os.path.join(_HERE, "libmygram_gpu.so")
 
-ABI_VERSION = 4
+ABI_VERSION = 5
 GRAM_ABSENT = 0xFFFFFFFF
 SORT_DOCID, SORT_SCORE = 0, 1
 
@@ -74,6 +74,12 @@ class Filter(C.Structure):
     _fields_ = [("bitmap_id", C.c_uint32), ("negate", C.c_uint32)]
 
 
+class Condition(C.Structure):
+    _fields_ = [("column_id", C.c_uint32), ("op", C.c_uint32), ("literal_bits", C.c_uint64), ("eq_epsilon", C.c_double),
+                ("null_matches", C.c_uint32), ("never_matches", C.c_uint32), ("negate", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
 class Query(C.Structure):
     _fields_ = [("terms", C.c_void_p), ("n_terms", C.c_uint32), ("not_terms", C.c_void_p),
                 ("n_not_terms", C.c_uint32), ("filters", C.c_void_p), ("n_filters", C.c_uint32),
@@ -81,7 +87,8 @@ class Query(C.Structure):
                 ("k1", C.c_double), ("b", C.c_double), ("total_docs", C.c_uint64), ("avg_doc_length", C.c_double),
                 ("expr", C.c_void_p), ("n_expr", C.c_uint32), ("universe_first", C.c_uint32),
                 ("universe_count", C.c_uint64), ("exact_text", C.c_uint32), ("score_terms", C.c_void_p),
-                ("n_score_terms", C.c_uint32), ("fuzzy_verify_distance", C.c_uint32)]
+                ("n_score_terms", C.c_uint32), ("fuzzy_verify_distance", C.c_uint32),
+                ("conditions", C.c_void_p), ("n_conditions", C.c_uint32)]
 
 
 class DumpView(C.Structure):
@@ -133,6 +140,7 @@ class HighlightView(C.Structure):
 
 
 HIGHLIGHT_ARENA_CAP = 256 << 20
+CONDITION_ARENA_MAX_BYTES = 1 << 30
 HIGHLIGHT_MAX_TERMS = 256
 
 _lib = None

@@ -24,6 +24,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <tuple>
 #include <unordered_map>
 #include <vector>
 
@@ -165,7 +166,24 @@ struct BatchResources {
     *out_ptr = xchg[which];
     return hipSuccess;
   }
+  // The rows the batch's own FILTER conditions are evaluated into (mgx_query.conditions): grown when a batch needs more
+  // rows than any before it, never shrunk, kept across mgx_batch_reset like the arenas.
+  void* cond = nullptr;
+  size_t cond_cap = 0;
+  hipError_t Conditions(size_t bytes, void** out_ptr) {
+    if (cond_cap < bytes) {
+      if (cond) (void)hipFree(cond);
+      cond = nullptr;
+      cond_cap = 0;
+      hipError_t e = DeviceMalloc(&cond, bytes);
+      if (e != hipSuccess) return e;
+      cond_cap = bytes;
+    }
+    *out_ptr = cond;
+    return hipSuccess;
+  }
   ~BatchResources() {
+    if (cond) (void)hipFree(cond);
     for (void* x : xchg)
       if (x) (void)hipFree(x);
     if (stream) (void)hipStreamDestroy(stream);
@@ -300,6 +318,7 @@ struct mgx_index {
     DevBuf d_values, d_null, d_value_ids;
   };
   std::vector<std::unique_ptr<FilterColumn>> filter_columns;
+  std::atomic<uint32_t> n_filter_columns{0};  // = filter_columns.size(), for readers that hold no lock (CompileQuery)
   std::vector<DevBuf> retired_filter_pools;
   uint64_t n_grams = 0;
   bool can_score = false;
@@ -991,6 +1010,7 @@ int mgx_index_add_filter_column(mgx_index* idx, const mgx_filter_column_desc* d,
     if (d->is_null) MGX_HIP(mgx::Upload(col->d_null, d->is_null, n));
     if (d->value_ids) MGX_HIP(mgx::Upload(col->d_value_ids, d->value_ids, n));
     idx->filter_columns.push_back(std::move(col));
+    idx->n_filter_columns.store(static_cast<uint32_t>(idx->filter_columns.size()), std::memory_order_release);
     *out_column_id = static_cast<uint32_t>(idx->filter_columns.size() - 1);
     return MGX_OK;
   } catch (const std::exception& e) {
@@ -1262,6 +1282,7 @@ struct QuerySpec {
   std::vector<uint32_t> prog;
   std::vector<DevScoreTerm> score;
   std::vector<uint32_t> explicit_ids;  // for kLeafExplicit leaves (offsets are relative to this vector)
+  std::vector<mgx_condition> conds;    // for kLeafCondBitmap leaves (a = index here until LayOutConditions gives them rows)
   uint32_t mode = kModeBitmap;
   uint32_t limit = 0, offset = 0, reverse = 0;
   uint32_t stack_depth = 0;
@@ -1295,6 +1316,7 @@ struct QuerySpec {
     prog.clear();
     score.clear();
     explicit_ids.clear();
+    conds.clear();
     text_terms.clear();
     verify_patterns.clear();
     deep_score = false;
@@ -1438,6 +1460,16 @@ static int CompileQuery(const mgx_index* idx, const mgx_query& in, QuerySpec* ou
   if (in.n_terms == 0 || !in.terms) return Fail(MGX_ERR_INVALID_ARGUMENT, "query without positive terms");
   if (in.n_terms > MGX_MAX_TERMS || in.n_not_terms > MGX_MAX_TERMS || in.n_filters > MGX_MAX_TERMS)
     return Fail(MGX_ERR_OUT_OF_RANGE, "more than 64 terms / NOT terms / filters (query_parser.h:270-272)");
+  if (static_cast<uint64_t>(in.n_filters) + in.n_conditions > MGX_MAX_TERMS)
+    return Fail(MGX_ERR_OUT_OF_RANGE, "more than 64 filters and conditions together (query_parser.h:270-272)");
+  if (in.n_conditions != 0) {
+    if (!in.conditions) return Fail(MGX_ERR_INVALID_ARGUMENT, "n_conditions without conditions");
+    const uint32_t n_columns = idx->n_filter_columns.load(std::memory_order_acquire);
+    for (uint32_t i = 0; i < in.n_conditions; ++i) {
+      if (in.conditions[i].op > MGX_CMP_GE) return Fail(MGX_ERR_INVALID_ARGUMENT, "condition: unknown operator");
+      if (in.conditions[i].column_id >= n_columns) return Fail(MGX_ERR_OUT_OF_RANGE, "condition: unknown filter column");
+    }
+  }
   Compiler c{idx, out, 0};
   for (uint32_t i = 0; i < in.n_terms; ++i) {
     int rc = ValidateTerm(idx, in.terms[i], "term");
@@ -1591,6 +1623,17 @@ static int CompileQuery(const mgx_index* idx, const mgx_query& in, QuerySpec* ou
     const uint32_t id = static_cast<uint32_t>(out->leaves.size());
     out->leaves.push_back(lf);
     c.Emit(in.filters[i].negate ? kOpAndNot : kOpAnd, id);
+  }
+  for (uint32_t i = 0; i < in.n_conditions; ++i) {  // a filter row in all but where it lives: the batch's own arena
+    DevLeaf lf{};
+    lf.score_slot = kNoSlot;
+    lf.row = kNoRow;
+    lf.kind = kLeafCondBitmap;
+    lf.a = static_cast<uint32_t>(out->conds.size());
+    out->conds.push_back(in.conditions[i]);
+    const uint32_t id = static_cast<uint32_t>(out->leaves.size());
+    out->leaves.push_back(lf);
+    c.Emit(in.conditions[i].negate ? kOpAndNot : kOpAnd, id);
   }
   c.Emit(kOpCount, 3);
   if (in.fuzzy_verify_distance != 0) {
@@ -1791,6 +1834,11 @@ struct mgx_batch {
   std::vector<uint64_t> text_df_known;      // per text term: its cached LOCAL df, or ~0ull (the df query then counts it)
   std::vector<std::string> text_df_key;     // per text term: the cache key
   std::vector<double> h_text_idf;
+  // the batch's distinct conditions, sorted by column, and the columns' groups (filter_compare_batch_kernel); their rows
+  // live in res->cond
+  DevBuf d_cond_groups, d_conds;
+  uint32_t n_cond_groups = 0;
+  uint64_t* cond_arena = nullptr;
   bool df_ready = false;  // mgx_batch_count_df ran (and the caller summed the counts) for the next execute
   // score group outputs
   DevBuf d_cand_keys, d_cand_docs, d_cand_n;
@@ -1996,7 +2044,7 @@ static int LayOutQueries(mgx_batch* b, Group& g, const std::vector<QuerySpec>& s
 }
 
 // Fast path: the query's resolved bitmap_score_kernel descriptor; false when the query does not fit the path.
-static bool ResolveFast(mgx_index* idx, const QuerySpec& s, const DevQuery& q, DevFastQuery* out) {
+static bool ResolveFast(mgx_index* idx, const uint64_t* cond_arena, const QuerySpec& s, const DevQuery& q, DevFastQuery* out) {
   DevFastQuery& f = *out;
   for (uint32_t ins : s.prog) {
     const uint32_t op = ins >> 24, arg = ins & 0xFFFFFFu;
@@ -2016,6 +2064,9 @@ static bool ResolveFast(mgx_index* idx, const QuerySpec& s, const DevQuery& q, D
       o.base = static_cast<uint64_t>(lf.b) * idx->dev.fb_row_stride * 8;
       stride = idx->dev.fb_tile_stride * 8;
       o.code |= 16u;
+    } else if (lf.kind == kLeafCondBitmap) {  // the batch's arena stays where it is for as long as the batch is prepared
+      o.base = reinterpret_cast<uint64_t>(cond_arena + static_cast<uint64_t>(lf.b) * idx->dev.fb_row_stride);
+      stride = idx->dev.fb_tile_stride * 8;
     } else {
       return false;
     }
@@ -2094,11 +2145,11 @@ static void RouteCandMerge(mgx_batch* b, Group& g, const std::vector<QuerySpec>&
       }
       if ((op == kOpLoad) != (pc == 0) || (op != kOpLoad && op != kOpAnd && op != kOpAndNot)) { ok = false; break; }
       const DevLeaf& lf = s.leaves[arg];
-      if (lf.kind != kLeafList && lf.kind != kLeafGramBitmap && lf.kind != kLeafFilterBitmap) { ok = false; break; }
+      if (lf.kind != kLeafList && lf.kind != kLeafGramBitmap && !IsFilterKind(lf.kind)) { ok = false; break; }
       if (lf.kind == kLeafList) longest_list = std::max<uint64_t>(longest_list, idx->h_offsets[lf.a + 1] - idx->h_offsets[lf.a]);
       // any positive gram loaded before the first COUNT makes every counter a count of candidates; the smallest of them
       // drives (with terms in the reference's order that is the smallest gram of the whole query)
-      if (op == kOpAndNot || lf.kind == kLeafFilterBitmap || counted) continue;
+      if (op == kOpAndNot || IsFilterKind(lf.kind) || counted) continue;
       const uint64_t sz = idx->h_offsets[lf.a + 1] - idx->h_offsets[lf.a];
       if (sz < best) {
         best = sz;
@@ -2164,7 +2215,7 @@ static int ChooseRoutes(mgx_batch* b, Group& g, const std::vector<QuerySpec>& sp
       if (p.dq[i].cap > 128) continue;
       if (have_params && (Bits(s.k1) != Bits(pk1) || Bits(s.b) != Bits(pb) || Bits(s.avgdl) != Bits(pavg))) continue;
       DevFastQuery f{};
-      if (!ResolveFast(idx, s, p.dq[i], &f)) continue;
+      if (!ResolveFast(idx, b->cond_arena, s, p.dq[i], &f)) continue;
       if (!have_params) {
         pk1 = s.k1;
         pb = s.b;
@@ -2538,6 +2589,7 @@ static int UploadItems(mgx_batch* b, Group& g, const std::vector<QuerySpec>& spe
   if (!p.fastq.empty()) MGX_HIP(Upload(g.d_fast_queries, p.fastq.data(), p.fastq.size()));
   d.fast_queries = g.d_fast_queries.as<DevFastQuery>();
   d.dev_index = b->idx->d_dev_index.as<DevIndex>();
+  d.cond_bitmaps = b->cond_arena;
   for (int t = 0; t < kFastMaxScore; ++t) MGX_HIP(MakeRoute(g.fast[t], d, p.fast[t]));
   MGX_HIP(MakeRoute(g.wave_lists, d, p.wave_lists));
   MGX_HIP(MakeRoute(g.cand, d, p.cand));
@@ -2698,6 +2750,72 @@ static int CompileAll(const mgx_index* idx, const mgx_query* queries, uint32_t n
   return pool.rc;
 }
 
+// The batch's FILTER conditions (mgx_query.conditions): every distinct one (all fields but `negate`) gets one row of the
+// batch's condition arena, its operands get that row, and the descriptors the first launch of every execute reads —
+// the conditions sorted by column, one group per column — go into the upload arena. Nothing here touches the device
+// beyond growing the arena when this batch holds more distinct conditions than any before it.
+static int LayOutConditions(mgx_batch* b) {
+  mgx_index* idx = b->idx;
+  size_t n_refs = 0;
+  for (const QuerySpec& s : b->specs) n_refs += s.conds.size();
+  if (n_refs == 0) return MGX_OK;
+  using Key = std::tuple<uint32_t, uint32_t, uint64_t, uint64_t, uint32_t, uint32_t>;  // column first: the map is the kernel's order
+  std::map<Key, uint32_t> rows;
+  for (QuerySpec& s : b->specs)
+    for (DevLeaf& lf : s.leaves) {
+      if (lf.kind != kLeafCondBitmap) continue;
+      const mgx_condition& c = s.conds[lf.a];
+      const Key key{c.column_id, c.op, c.literal_bits, Bits(c.eq_epsilon), c.null_matches ? 1u : 0u, c.never_matches ? 1u : 0u};
+      lf.b = rows.emplace(key, static_cast<uint32_t>(rows.size())).first->second;
+      lf.a = 0;
+    }
+  const uint64_t row_bytes = idx->dev.fb_row_stride * sizeof(uint64_t);
+  if (idx->dev.fb_row_stride % kCondBlockWords != 0)  // (the condition pass covers a row in whole workgroups)
+    return Fail(MGX_ERR_INTERNAL, "filter row stride is not a multiple of the condition pass's block");
+  if (rows.size() * row_bytes > MGX_CONDITION_ARENA_MAX_BYTES)
+    return Fail(MGX_ERR_OUT_OF_RANGE, "the batch holds " + std::to_string(rows.size()) + " distinct conditions of " +
+                                          std::to_string(row_bytes) + " bytes each: more than the " +
+                                          std::to_string(MGX_CONDITION_ARENA_MAX_BYTES) +
+                                          " bytes (MGX_CONDITION_ARENA_MAX_BYTES) a batch's condition arena may take");
+  void* arena = nullptr;
+  MGX_HIP(b->res->Conditions(rows.size() * row_bytes, &arena));
+  b->cond_arena = static_cast<uint64_t*>(arena);
+  std::vector<DevCondition> conds;
+  std::vector<DevCondGroup> groups;
+  conds.reserve(rows.size());
+  {
+    std::lock_guard<std::mutex> lock(idx->mu);  // (columns are added under mu; the objects themselves never move)
+    uint32_t last_column = 0;
+    for (const auto& kv : rows) {
+      const uint32_t column = std::get<0>(kv.first);
+      if (groups.empty() || column != last_column) {
+        last_column = column;
+        const mgx_index::FilterColumn& col = *idx->filter_columns[column];
+        DevCondGroup g{};
+        g.values = col.d_values.as<uint64_t>();
+        g.is_null = col.d_null.as<uint8_t>();
+        g.value_class = col.value_class;
+        g.cond_begin = g.cond_end = static_cast<uint32_t>(conds.size());
+        groups.push_back(g);
+      }
+      DevCondition d{};
+      d.literal = std::get<2>(kv.first);
+      __builtin_memcpy(&d.eq_epsilon, &std::get<3>(kv.first), 8);
+      d.op = std::get<1>(kv.first);
+      d.null_matches = std::get<4>(kv.first);
+      d.never_matches = std::get<5>(kv.first);
+      d.row = kv.second;
+      conds.push_back(d);
+      groups.back().cond_end = static_cast<uint32_t>(conds.size());
+    }
+  }
+  if (groups.size() > 65535) return Fail(MGX_ERR_OUT_OF_RANGE, "conditions on more than 65535 columns in one batch");
+  MGX_HIP(Upload(b->d_conds, conds.data(), conds.size()));
+  MGX_HIP(Upload(b->d_cond_groups, groups.data(), groups.size()));
+  b->n_cond_groups = static_cast<uint32_t>(groups.size());
+  return MGX_OK;
+}
+
 // Compiles `specs` into batch object `b` (fresh, or just emptied by ResetBatch): every device array comes from the
 // batch's arenas, nothing is copied to the device here — the first execute ships the upload arena.
 static int PrepareInto(mgx_batch* b, mgx_index* idx, std::vector<QuerySpec>&& specs) {
@@ -2710,6 +2828,7 @@ static int PrepareInto(mgx_batch* b, mgx_index* idx, std::vector<QuerySpec>&& sp
     (m == kModeScore ? b->score : m == kModeDocPage ? b->page : b->bitmap).qids.push_back(i);
   }
   MGX_HIP(hipSetDevice(idx->device));
+  if (const int rc = LayOutConditions(b)) return rc;
   // text-level scored terms: number them across the batch, pool their bytes, and give each one a df query
   {
     std::string pool;
@@ -2951,6 +3070,9 @@ static int ExecuteImpl(mgx_batch* b, hipStream_t s, const SeedGather* sg = nullp
     int rc = EnsureUploaded(b, s);
     if (rc) return rc;
   }
+  // the batch's own conditions into their arena rows, before anything reads an operand: one launch, none without conditions
+  MGX_LAUNCH(LaunchFilterCompareBatch(b->d_cond_groups.as<DevCondGroup>(), b->n_cond_groups, b->d_conds.as<DevCondition>(),
+                                      idx->dev.n_docs, idx->dev.fb_row_stride, b->cond_arena, s));
   b->merged_shards = false;
   b->merge_other = nullptr;
   b->merged_away = false;

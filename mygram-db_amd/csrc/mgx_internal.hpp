@@ -34,7 +34,10 @@ enum LeafKind : uint32_t {
   kLeafFilterBitmap = 2,  // b = row in filter_bitmaps
   kLeafRange = 3,         // a = first local slot, b = one past the last local slot
   kLeafExplicit = 4,      // a = offset, b = length of an ascending docid list in the batch's explicit pool
+  kLeafCondBitmap = 5,    // b = row in the batch's condition arena (DevBatch::cond_bitmaps): a filter row in all but its base
 };
+// a filter-row operand: a row of the index's pool or of the batch's condition arena (same tile and row strides)
+inline constexpr bool IsFilterKind(uint32_t kind) { return kind == kLeafFilterBitmap || kind == kLeafCondBitmap; }
 
 struct DevLeaf {
   uint32_t kind, a, b;
@@ -177,6 +180,7 @@ constexpr int kFastWaves = kFastBlock / 64;
 enum FastOpKind : uint32_t { kFastOr = 0, kFastAnd = 1, kFastAndNot = 2 };  // (LOAD = OR into the empty accumulator)
 struct FastOp {
   uint64_t base;         // address of the operand's words of tile 0; filter bitmaps: byte offset from DevIndex::filter_bitmaps
+                         // (a row of the batch's condition arena never moves while the batch lives: its address)
   uint32_t tile_stride;  // bytes from one tile's 2 KiB of this row to the next tile's
   uint32_t code;         // kind | (relative-to-filter-base flag << 4) | (funnel counter mask counted AFTER this op << 8)
 };
@@ -229,6 +233,22 @@ struct DevItem {
   uint32_t query, tile_begin, n_tiles, list;
 };
 
+// ---- batch conditions (filter_compare_batch_kernel): the batch's distinct FILTER conditions, sorted by column ----------
+struct DevCondition {
+  uint64_t literal;
+  double eq_epsilon;
+  uint32_t op, null_matches, never_matches;
+  uint32_t row;  // row of the batch's condition arena the condition's doc set is written to
+};
+struct DevCondGroup {  // the conditions [cond_begin, cond_end) compare against one column
+  const uint64_t* values;
+  const uint8_t* is_null;  // or null: the column has no NULLs
+  uint32_t value_class, cond_begin, cond_end, pad;
+};
+static_assert(sizeof(DevCondition) % 8 == 0 && sizeof(DevCondGroup) % 8 == 0, "read with scalar loads");
+constexpr uint32_t kCondWordsPerWave = 8;  // consecutive 64-doc words one wave evaluates: a 64-byte store per row
+constexpr uint32_t kCondBlockWords = kCondWordsPerWave * (kBlock / 64);
+
 struct DevBatch {
   const DevItem* items;
   uint32_t n_items;
@@ -253,6 +273,7 @@ struct DevBatch {
   const uint64_t* wave_tables;  // [n_queries][kWaveScoreSlots] addresses of the scored terms' pool tables (wave kernel)
   const DevFastQuery* fast_queries;  // [n_queries] resolved descriptors of the fast-path queries (others: unused rows)
   const struct DevIndex* dev_index;  // the index's descriptor in device memory (out-of-line cold paths take a pointer)
+  const uint64_t* cond_bitmaps;  // the batch's condition arena (kLeafCondBitmap rows; DevIndex::fb_*_stride), or null
   uint32_t debug_skip;   // -DMGX_ABLATION builds only (MGX_DEBUG_SKIP: 1 = no scoring, 2 = no enumeration + scoring); 0 otherwise
   // bitmap mode
   uint64_t* rbits;       // [n_bitmap_queries][n_tiles][256]

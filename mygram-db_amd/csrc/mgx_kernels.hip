@@ -81,6 +81,12 @@ __device__ __forceinline__ uint64_t lower_bound_u32(const uint32_t* __restrict__
 
 // tf of posting p: the byte column, or — where the byte is saturated — the side table of true counts
 // (CountTermOccurrences has no ceiling, bm25_scorer.cpp:27-45; a doc that repeats a gram 300 times must score as such)
+// The pool a filter-row operand lives in: the index's filter rows, or the batch's condition arena (kLeafCondBitmap); both
+// have the index's fb_tile_stride / fb_row_stride. The operand's kind is wave-uniform, so this is a scalar select.
+__device__ __forceinline__ const uint64_t* filter_rows(const DevIndex& ix, const uint64_t* cond_bitmaps, uint32_t kind) {
+  return kind == kLeafCondBitmap ? cond_bitmaps : ix.filter_bitmaps;
+}
+
 __device__ __forceinline__ uint32_t posting_tf(const DevIndex& ix, uint64_t p) {
   uint32_t v = ix.tf[p];
   if (v == 255u && ix.n_tf_ovf != 0) {
@@ -624,7 +630,7 @@ __device__ __noinline__ uint32_t tile_jump_setup(const uint32_t* prog, uint32_t 
       if ((op == kOpLoad || op == kOpAnd || op == kOpOr || op == kOpAndNot || op == kOpThreshAdd) && arg == tid) my_ref = true;
     }
     const DevLeaf lf = leaf[tid];
-    blocks = my_ref && (lf.kind == kLeafGramBitmap || lf.kind == kLeafFilterBitmap || (lf.kind == kLeafRange && lf.b > lf.a));
+    blocks = my_ref && (lf.kind == kLeafGramBitmap || IsFilterKind(lf.kind) || (lf.kind == kLeafRange && lf.b > lf.a));
     my_req = ((req_mask[tid >> 6] >> (tid & 63u)) & 1ull) && (walked || (lf.kind == kLeafList && has_off_row));
     absent_possible = my_ref && (lf.kind == kLeafList || lf.kind == kLeafExplicit || lf.kind == kLeafRange);
   }
@@ -1002,7 +1008,8 @@ __device__ __forceinline__ void tile_eval_body(const DevIndex& ix, const DevBatc
     // this thread's 64-bit word of a bitmap-form operand (dense gram, filter, slot range), straight from HBM
     auto direct_word = [&](const DevLeaf lf) -> uint64_t {
       if (lf.kind == kLeafGramBitmap) return ix.gram_bitmaps[tile * ix.gb_tile_stride + lf.b * ix.gb_row_stride + tid];
-      if (lf.kind == kLeafFilterBitmap) return ix.filter_bitmaps[tile * ix.fb_tile_stride + lf.b * ix.fb_row_stride + tid];
+      if (IsFilterKind(lf.kind))
+        return filter_rows(ix, bt.cond_bitmaps, lf.kind)[tile * ix.fb_tile_stride + lf.b * ix.fb_row_stride + tid];
       if (lf.kind == kLeafRange) {
         // slots [a, b) of the shard; this thread's word covers slots [s0, s0+64)
         const uint64_t s0 = static_cast<uint64_t>(tile) * kTileDocs + static_cast<uint64_t>(tid) * 64;
@@ -1481,10 +1488,10 @@ __device__ __forceinline__ void wave_fetch_operand(const DevIndex& ix, const Dev
                                                    uint64_t (&w)[4], uint32_t* seg_rel) {
   const uint32_t lane = lane_id();
   *seg_rel = 0;
-  if (lf.kind == kLeafGramBitmap || lf.kind == kLeafFilterBitmap) {
+  if (lf.kind == kLeafGramBitmap || IsFilterKind(lf.kind)) {
     const uint64_t* rowp = lf.kind == kLeafGramBitmap
                                ? ix.gram_bitmaps + tile * ix.gb_tile_stride + lf.b * ix.gb_row_stride + lane * 4
-                               : ix.filter_bitmaps + tile * ix.fb_tile_stride + lf.b * ix.fb_row_stride + lane * 4;
+                               : filter_rows(ix, bt.cond_bitmaps, lf.kind) + tile * ix.fb_tile_stride + lf.b * ix.fb_row_stride + lane * 4;
     const uint4 v0 = *reinterpret_cast<const uint4*>(rowp);
     const uint4 v1 = *reinterpret_cast<const uint4*>(rowp + 2);
     w[0] = (static_cast<uint64_t>(v0.y) << 32) | v0.x;
@@ -2403,7 +2410,7 @@ __device__ __forceinline__ void wave_operand_words(const DevIndex& ix, const Dev
   } else {  // gram or filter bitmap
     const uint64_t* rowp = lf.kind == kLeafGramBitmap
                                ? ix.gram_bitmaps + tile * ix.gb_tile_stride + lf.b * ix.gb_row_stride + lane * 4
-                               : ix.filter_bitmaps + tile * ix.fb_tile_stride + lf.b * ix.fb_row_stride + lane * 4;
+                               : filter_rows(ix, bt.cond_bitmaps, lf.kind) + tile * ix.fb_tile_stride + lf.b * ix.fb_row_stride + lane * 4;
     const uint4 v0 = *reinterpret_cast<const uint4*>(rowp);
     const uint4 v1 = *reinterpret_cast<const uint4*>(rowp + 2);
     w[0] = (static_cast<uint64_t>(v0.y) << 32) | v0.x;
@@ -2661,12 +2668,13 @@ uint32_t CandLdsBytes(uint32_t max_leaves, uint32_t max_instr, uint32_t max_cap)
 }
 
 // Is the doc at `slot` (tile `tile`, doc id `d`) a member of operand `lf`?
-__device__ __forceinline__ bool cand_member(const DevIndex& ix, const DevLeaf lf, uint32_t d, uint32_t slot, uint32_t tile) {
-  if (lf.kind == kLeafGramBitmap || lf.kind == kLeafFilterBitmap) {
+__device__ __forceinline__ bool cand_member(const DevIndex& ix, const uint64_t* cond_bitmaps, const DevLeaf lf, uint32_t d,
+                                            uint32_t slot, uint32_t tile) {
+  if (lf.kind == kLeafGramBitmap || IsFilterKind(lf.kind)) {
     const uint32_t w = (slot & (kTileDocs - 1)) >> 6;
     const uint64_t* wp = lf.kind == kLeafGramBitmap
                              ? ix.gram_bitmaps + tile * ix.gb_tile_stride + lf.b * ix.gb_row_stride + w
-                             : ix.filter_bitmaps + tile * ix.fb_tile_stride + lf.b * ix.fb_row_stride + w;
+                             : filter_rows(ix, cond_bitmaps, lf.kind) + tile * ix.fb_tile_stride + lf.b * ix.fb_row_stride + w;
     return ((*wp >> (slot & 63)) & 1ull) != 0;
   }
   if (lf.kind == kLeafList) {
@@ -2686,7 +2694,7 @@ __device__ __forceinline__ bool cand_member(const DevIndex& ix, const DevLeaf lf
 
 // The flat program on kCandU candidates per lane (alive[u]: the lane holds a posting of the driver). On return alive[u]
 // marks the survivors; the funnel counts of the wave are added to cnt[0..3].
-__device__ __forceinline__ void cand_run_program(const DevIndex& ix, const DevLeaf* leaf, const uint32_t* prog,
+__device__ __forceinline__ void cand_run_program(const DevIndex& ix, const uint64_t* cond_bitmaps, const DevLeaf* leaf, const uint32_t* prog,
                                                  uint32_t n_instr, uint32_t driver_leaf, bool (&alive)[kCandU],
                                                  const uint32_t (&d)[kCandU], uint32_t (&cnt)[4]) {
   for (uint32_t pc = 0; pc < n_instr; ++pc) {
@@ -2714,7 +2722,7 @@ __device__ __forceinline__ void cand_run_program(const DevIndex& ix, const DevLe
 #pragma unroll
     for (int u = 0; u < kCandU; ++u) {  // (the probes of the lane's candidates are independent loads: in flight together)
       const uint32_t slot = d[u] - ix.first_doc_id;
-      in[u] = alive[u] && cand_member(ix, lf, d[u], slot, slot >> kTileShift);
+      in[u] = alive[u] && cand_member(ix, cond_bitmaps, lf, d[u], slot, slot >> kTileShift);
     }
 #pragma unroll
     for (int u = 0; u < kCandU; ++u) alive[u] = op == kOpAndNot ? (alive[u] && !in[u]) : in[u];
@@ -2777,7 +2785,7 @@ __global__ __launch_bounds__(kCandBlock) void cand_kernel(DevIndex ix, DevBatch 
       alive[u] = p < wb;
       d[u] = alive[u] ? ix.docids[p] : ix.first_doc_id;
     }
-    cand_run_program(ix, leaf, prog, q.n_instr, driver_leaf, alive, d, cnt);
+    cand_run_program(ix, bt.cond_bitmaps, leaf, prog, q.n_instr, driver_leaf, alive, d, cnt);
 #pragma unroll
     for (int u = 0; u < kCandU; ++u) {
       const uint64_t amask = __ballot(alive[u]);
@@ -2896,7 +2904,7 @@ __global__ __launch_bounds__(kCandBlock) void cand_kernel(DevIndex ix, DevBatch 
       alive[u] = p < wb;
       d[u] = alive[u] ? ix.docids[p] : ix.first_doc_id;
     }
-    cand_run_program(ix, leaf, prog, q.n_instr, driver_leaf, alive, d, dummy);
+    cand_run_program(ix, bt.cond_bitmaps, leaf, prog, q.n_instr, driver_leaf, alive, d, dummy);
 #pragma unroll
     for (int u = 0; u < kCandU; ++u) {
       const uint64_t amask = __ballot(alive[u]);
@@ -3082,7 +3090,7 @@ __global__ __launch_bounds__(kMergeBlock) void merge_score_kernel(DevIndex ix, D
       } else {  // bitmap-form gram or filter: the tile's 2 KiB row
         const uint64_t* rowp = lf.kind == kLeafGramBitmap
                                    ? ix.gram_bitmaps + tile * ix.gb_tile_stride + lf.b * ix.gb_row_stride + lane * 4
-                                   : ix.filter_bitmaps + tile * ix.fb_tile_stride + lf.b * ix.fb_row_stride + lane * 4;
+                                   : filter_rows(ix, bt.cond_bitmaps, lf.kind) + tile * ix.fb_tile_stride + lf.b * ix.fb_row_stride + lane * 4;
         const uint4 v0 = *reinterpret_cast<const uint4*>(rowp);
         const uint4 v1 = *reinterpret_cast<const uint4*>(rowp + 2);
         *reinterpret_cast<uint4*>(b + lane * 4) = v0;
@@ -4080,6 +4088,32 @@ int LaunchBuildContribTables(const TableJob* jobs, uint32_t n_jobs, uint32_t tab
 //     (":invalid number -> false" for every non-NULL doc);
 //   * the EQ bitmap of the FilterIndex path (BuildTypeUnionBitmap, :1021-1094): op EQ, eq_epsilon 0 (doubles by their
 //     bits, as the serialized keys compare), null_matches 0.
+// The comparison itself, shared by both kernels below: does a doc (NULL or holding `v`) belong to the condition's set?
+__device__ __forceinline__ bool filter_condition_holds(bool is_null, uint64_t v, uint32_t value_class, uint32_t op,
+                                                       uint64_t literal, double eq_epsilon, uint32_t null_matches,
+                                                       uint32_t never_matches) {
+  if (is_null) return null_matches != 0;
+  if (never_matches != 0) return false;
+  bool lt, gt, le, ge, eq, ne;
+  if (value_class == 0) {  // signed
+    const long long a = static_cast<long long>(v), b = static_cast<long long>(literal);
+    lt = a < b; gt = a > b; le = a <= b; ge = a >= b; eq = a == b; ne = a != b;
+  } else if (value_class == 1) {  // unsigned / string rank
+    lt = v < literal; gt = v > literal; le = v <= literal; ge = v >= literal; eq = v == literal; ne = v != literal;
+  } else {  // double: CompareDoubleValues (comparison_utils.h:56-70), or the exact key comparison of the bitmap path
+    const double a = __longlong_as_double(static_cast<long long>(v)), b = __longlong_as_double(static_cast<long long>(literal));
+    lt = a < b; gt = a > b; le = a <= b; ge = a >= b;
+    if (eq_epsilon > 0.0) {
+      eq = fabs(a - b) < eq_epsilon;
+      ne = fabs(a - b) >= eq_epsilon;
+    } else {
+      eq = v == literal;
+      ne = !eq;
+    }
+  }
+  return op == 0u ? eq : op == 1u ? ne : op == 2u ? lt : op == 3u ? le : op == 4u ? gt : ge;
+}
+
 // One thread per doc, one ballot per 64 docs: coalesced 8-byte loads, one 8-byte store per wave.
 __global__ __launch_bounds__(256) void filter_compare_kernel(const uint64_t* __restrict__ values,
                                                              const uint8_t* __restrict__ is_null, uint32_t n_docs,
@@ -4089,32 +4123,57 @@ __global__ __launch_bounds__(256) void filter_compare_kernel(const uint64_t* __r
   const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
   bool m = false;
   if (slot < n_docs) {
-    if (is_null != nullptr && is_null[slot] != 0) {
-      m = null_matches != 0;
-    } else if (never_matches == 0) {
-      const uint64_t v = values[slot];
-      bool lt, gt, le, ge, eq, ne;
-      if (value_class == 0) {  // signed
-        const long long a = static_cast<long long>(v), b = static_cast<long long>(literal);
-        lt = a < b; gt = a > b; le = a <= b; ge = a >= b; eq = a == b; ne = a != b;
-      } else if (value_class == 1) {  // unsigned / string rank
-        lt = v < literal; gt = v > literal; le = v <= literal; ge = v >= literal; eq = v == literal; ne = v != literal;
-      } else {  // double: CompareDoubleValues (comparison_utils.h:56-70), or the exact key comparison of the bitmap path
-        const double a = __longlong_as_double(static_cast<long long>(v)), b = __longlong_as_double(static_cast<long long>(literal));
-        lt = a < b; gt = a > b; le = a <= b; ge = a >= b;
-        if (eq_epsilon > 0.0) {
-          eq = fabs(a - b) < eq_epsilon;
-          ne = fabs(a - b) >= eq_epsilon;
-        } else {
-          eq = v == literal;
-          ne = !eq;
-        }
-      }
-      m = op == 0u ? eq : op == 1u ? ne : op == 2u ? lt : op == 3u ? le : op == 4u ? gt : ge;
-    }
+    const bool nul = is_null != nullptr && is_null[slot] != 0;
+    const uint64_t v = (nul || never_matches != 0) ? 0ull : values[slot];
+    m = filter_condition_holds(nul, v, value_class, op, literal, eq_epsilon, null_matches, never_matches);
   }
   const uint64_t mask = __ballot(m);
   if ((threadIdx.x & 63) == 0 && slot < ((n_docs + 63u) & ~63u)) dst[slot >> 6] = mask;
+}
+
+// The conditions a BATCH brings along (mgx_query.conditions), all of them in one launch at the head of every execute:
+// blockIdx.y = a column with its conditions (DevCondGroup), blockIdx.x = kCondBlockWords consecutive words of the rows.
+// A wave holds its kCondWordsPerWave x 64 docs' values and NULL bytes in registers (read once, coalesced) and walks the
+// column's conditions: the descriptors are wave-uniform (scalar loads), each ballot is one 64-bit word of the
+// condition's row, and lane k keeps word k, so that a row receives one contiguous 64-byte vector store per wave. The
+// grid covers the whole row stride: bits at and past n_docs and the stride's padding words are written as zero, so a
+// row is fully defined by every execute, whatever the arena held before.
+__global__ __launch_bounds__(kBlock) void filter_compare_batch_kernel(const DevCondGroup* __restrict__ groups,
+                                                                      const DevCondition* __restrict__ conds,
+                                                                      uint32_t n_docs, uint64_t row_stride,
+                                                                      uint64_t* __restrict__ arena) {
+  const DevCondGroup g = groups[blockIdx.y];
+  const uint32_t lane = lane_id();
+  const uint32_t word0 = blockIdx.x * kCondBlockWords + wave_id() * kCondWordsPerWave;  // < row_stride (a multiple of 32)
+  uint64_t v[kCondWordsPerWave];
+  bool nul[kCondWordsPerWave], live[kCondWordsPerWave];
+#pragma unroll
+  for (uint32_t k = 0; k < kCondWordsPerWave; ++k) {
+    const uint64_t slot = static_cast<uint64_t>(word0 + k) * 64 + lane;
+    live[k] = slot < n_docs;
+    nul[k] = live[k] && g.is_null != nullptr && g.is_null[slot] != 0;
+    v[k] = live[k] ? g.values[slot] : 0ull;
+  }
+  for (uint32_t c = g.cond_begin; c < g.cond_end; ++c) {
+    const DevCondition cd = conds[c];
+    uint64_t mine = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < kCondWordsPerWave; ++k) {
+      const uint64_t mask = __ballot(live[k] && filter_condition_holds(nul[k], v[k], g.value_class, cd.op, cd.literal,
+                                                                      cd.eq_epsilon, cd.null_matches, cd.never_matches));
+      if (lane == k) mine = mask;
+    }
+    if (lane < kCondWordsPerWave) arena[static_cast<uint64_t>(cd.row) * row_stride + word0 + lane] = mine;
+  }
+}
+
+int LaunchFilterCompareBatch(const DevCondGroup* groups, uint32_t n_groups, const DevCondition* conds, uint32_t n_docs,
+                             uint64_t row_stride, uint64_t* arena, hipStream_t s) {
+  if (n_groups == 0) return 0;
+  hipLaunchKernelGGL(filter_compare_batch_kernel, dim3(static_cast<uint32_t>(row_stride / kCondBlockWords), n_groups),
+                     dim3(kBlock), 0, s, groups, conds, n_docs, row_stride, arena);
+  MGX_KCHECK();
+  return 0;
 }
 
 int LaunchFilterCompare(const uint64_t* values, const uint8_t* is_null, uint32_t n_docs, uint32_t value_class, uint32_t op,

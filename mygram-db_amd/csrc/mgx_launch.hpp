@@ -51,6 +51,10 @@ int LaunchBuildContribTables(const TableJob* jobs, uint32_t n_jobs, uint32_t tab
 int LaunchFilterCompare(const uint64_t* values, const uint8_t* is_null, uint32_t n_docs, uint32_t value_class, uint32_t op,
                         uint64_t literal, double eq_epsilon, uint32_t null_matches, uint32_t never_matches, uint64_t* dst,
                         hipStream_t s);
+// every distinct condition of a batch into its row of the batch's condition arena: one launch (row_stride, in words, is a
+// multiple of kCondBlockWords; the arena holds a row for every DevCondition::row)
+int LaunchFilterCompareBatch(const DevCondGroup* groups, uint32_t n_groups, const DevCondition* conds, uint32_t n_docs,
+                             uint64_t row_stride, uint64_t* arena, hipStream_t s);
 int LaunchFacetCount(const uint64_t* rbits, uint32_t n_words, const uint32_t* value_ids, uint32_t n_docs, uint32_t n_values,
                      unsigned long long* counts, hipStream_t s);
 int LaunchUpdateBitmap(uint64_t* row, const uint32_t* slots, uint32_t n_set, uint32_t n_total, hipStream_t s);

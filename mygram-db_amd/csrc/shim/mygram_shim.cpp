@@ -1128,6 +1128,12 @@ uint32_t FilterClassOf(size_t type) {  // MGX_FC_* of a FilterValue alternative
 }
 }  // namespace
 
+uint64_t Index::DeviceMemoryBytes() const {
+  uint64_t n = 0;
+  if (impl_->dev == nullptr || mgx_index_memory_bytes(impl_->dev, &n) != MGX_OK) return 0;
+  return n;
+}
+
 std::string Index::AddFilterColumn(const std::string& name, const std::vector<storage::FilterValue>& values) const {
   Finalize();
   Impl* im = impl_.get();
@@ -1885,6 +1891,7 @@ struct PlannedQuery {
   std::vector<IdVec> ids;       // (reserved before the first mgx_term points into it: elements must not move)
   std::vector<TermInfo> tis;    // scratch of PlanQuery, kept for its storage
   std::vector<mgx_filter> filters;
+  std::vector<mgx_condition> conditions;  // FILTER conditions the batch evaluates itself (ResolveCondition's routing)
   std::vector<mgx_expr_token> expr;
   std::vector<uint32_t> score_list;  // mgx_query::score_terms of expression / FUZZY queries
   bool has_score_list = false;
@@ -1901,6 +1908,7 @@ struct PlannedQuery {
     ids.clear();
     tis.clear();
     filters.clear();
+    conditions.clear();
     expr.clear();
     score_list.clear();
     has_score_list = false;
@@ -1976,8 +1984,10 @@ bool ParseWhole(const std::string& s, T* out) {  // std::from_chars over the who
 
 struct ResolvedFilter {
   bool skip = false;     // the condition holds for every document
+  bool is_condition = false;  // `condition` travels with the batch (mgx_query.conditions); otherwise row `bitmap` of the index
   uint32_t bitmap = 0;
   bool negate = false;
+  mgx_condition condition{};
 };
 
 // One FilterCondition against the table's columns. bitmap_mode: every condition of the query is EQ / NE (the FilterIndex
@@ -1989,24 +1999,10 @@ std::string ResolveCondition(const index::Index& index, const query::FilterCondi
   index::Index::Impl* im = index.impl();
   std::lock_guard<std::mutex> lock(im->filter_mu);
   const index::Index::Impl::FilterColumn* col = im->ResolveColumn(cond.column);
-  std::string key;
-  key.push_back(bitmap_mode ? 'b' : 'f');
-  key.push_back(static_cast<char>('0' + static_cast<int>(cond.op)));
-  key += col ? col->name : std::string("\x01") + cond.column;
-  key.push_back('\0');
-  key += cond.value;
-  const auto hit = im->condition_cache.find(key);
-  if (hit != im->condition_cache.end()) {
-    out->bitmap = hit->second.first;
-    out->negate = hit->second.second;
-    out->skip = hit->second.first == 0xFFFFFFFFu;
-    return "";
-  }
   auto remember = [&](uint32_t bitmap, bool negate, bool skip) {
     out->bitmap = bitmap;
     out->negate = negate;
     out->skip = skip;
-    im->condition_cache.emplace(key, std::make_pair(skip ? 0xFFFFFFFFu : bitmap, negate));
   };
   auto empty_bitmap = [&](uint32_t* id) -> std::string {
     if (!im->have_empty_bitmap) {
@@ -2094,28 +2090,71 @@ std::string ResolveCondition(const index::Index& index, const query::FilterCondi
     }
   }
   uint32_t id = 0;
-  if (bitmap_mode) {
-    // EQ: AND the union of the literal's interpretations; NE: ANDNOT it (NULL documents are in no value bitmap: they
-    // pass NE, fail EQ). No interpretation in this column's type: the union is empty.
-    if (!valid) {
-      if (is_ne) {
-        remember(0, false, true);
-        return "";
-      }
-      const std::string err = empty_bitmap(&id);
-      if (!err.empty()) return err;
-      remember(id, false, false);
+  // EQ: AND the union of the literal's interpretations; NE: ANDNOT it (NULL documents are in no value bitmap: they
+  // pass NE, fail EQ). No interpretation in this column's type: the union is empty.
+  if (bitmap_mode && !valid) {
+    if (is_ne) {
+      remember(0, false, true);
       return "";
     }
-    if (mgx_index_filter_compare(im->dev, col->device_id, MGX_CMP_EQ, lit, 0.0, 0, 0, &id) != MGX_OK) return mgx_last_error();
-    remember(id, is_ne, false);
+    const std::string err = empty_bitmap(&id);
+    if (!err.empty()) return err;
+    remember(id, false, false);
     return "";
   }
-  // per-document semantics: the set of documents that PASS the condition, ANDed
-  const uint32_t dev_op = is_ne ? static_cast<uint32_t>(MGX_CMP_NE) : op;
-  if (mgx_index_filter_compare(im->dev, col->device_id, dev_op, lit, eps, is_ne ? 1 : 0, valid ? 0 : 1, &id) != MGX_OK)
+  // The condition as the device evaluates it. bitmap path: the EQ set, ANDed or (NE) ANDNOTed; per-document path: the set
+  // of documents that PASS the condition, ANDed.
+  mgx_condition c{};
+  c.column_id = col->device_id;
+  c.literal_bits = lit;
+  if (bitmap_mode) {
+    c.op = MGX_CMP_EQ;
+    c.negate = is_ne ? 1u : 0u;
+  } else {
+    c.op = is_ne ? static_cast<uint32_t>(MGX_CMP_NE) : op;
+    c.eq_epsilon = eps;
+    c.null_matches = is_ne ? 1u : 0u;
+    c.never_matches = valid ? 0u : 1u;
+  }
+  // Routing. A persistent row of the index only where the column's cardinality bounds how many there can be: = / != against
+  // a value the column's dictionary holds. Everything else — every range operator, a literal no document holds (request
+  // ids, timestamps) — travels with the batch as a condition: planning it touches no device state and leaves nothing behind.
+  bool in_dict = false;
+  if (valid && (cond.op == query::FilterOp::EQ || is_ne)) {
+    if (type == 11) {
+      in_dict = lit != ~0ull;
+    } else {
+      const storage::FilterValue fv = index::FilterValueFromBits(type, lit, col->dict);
+      bool ordered = true;
+      if (type == 12) {
+        double d;
+        std::memcpy(&d, &lit, 8);
+        ordered = d == d;  // (NaN orders against nothing: no dictionary search)
+      }
+      in_dict = ordered && index::WidenFilterValue(fv) == lit && std::binary_search(col->dict.begin(), col->dict.end(), fv);
+    }
+  }
+  if (!in_dict) {
+    out->is_condition = true;
+    out->condition = c;
+    return "";
+  }
+  std::string key;
+  key.push_back(bitmap_mode ? 'b' : 'f');
+  key.push_back(static_cast<char>('0' + static_cast<int>(cond.op)));  // (= and != share the EQ set on the bitmap path, not `negate`)
+  key += col->name;
+  key.push_back('\0');
+  key.append(reinterpret_cast<const char*>(&lit), 8);
+  const auto hit = im->condition_cache.find(key);
+  if (hit != im->condition_cache.end()) {
+    remember(hit->second.first, hit->second.second, false);
+    return "";
+  }
+  if (mgx_index_filter_compare(im->dev, c.column_id, c.op, c.literal_bits, c.eq_epsilon, static_cast<int>(c.null_matches),
+                               static_cast<int>(c.never_matches), &id) != MGX_OK)
     return mgx_last_error();
-  remember(id, false, false);
+  remember(id, c.negate != 0, false);
+  im->condition_cache.emplace(key, std::make_pair(id, c.negate != 0));
   return "";
 }
 
@@ -2135,9 +2174,11 @@ void PlanQuery(const index::Index& index, const BatchQuery& q, uint64_t total_do
         p->error_message = err;
         return false;
       }
-      if (!rf.skip) p->filters.push_back(mgx_filter{rf.bitmap, rf.negate ? 1u : 0u});
+      if (rf.skip) continue;
+      if (rf.is_condition) p->conditions.push_back(rf.condition);
+      else p->filters.push_back(mgx_filter{rf.bitmap, rf.negate ? 1u : 0u});
     }
-    if (p->filters.size() > MGX_MAX_TERMS) {
+    if (p->filters.size() + p->conditions.size() > MGX_MAX_TERMS) {
       p->error = ErrorCode::kInvalidArgument;
       p->error_message = "more than 64 filters in one query";
       return false;
@@ -2152,6 +2193,8 @@ void PlanQuery(const index::Index& index, const BatchQuery& q, uint64_t total_do
     m.n_not_terms = static_cast<uint32_t>(p->not_terms.size());
     m.filters = p->filters.data();
     m.n_filters = static_cast<uint32_t>(p->filters.size());
+    m.conditions = p->conditions.data();
+    m.n_conditions = static_cast<uint32_t>(p->conditions.size());
     m.sort = sort;
     m.limit = q.limit;
     m.reverse = q.order == query::SortOrder::DESC ? 1 : 0;

@@ -188,6 +188,9 @@ class Index {
     uint64_t epoch = 0;            // times the device state was brought up to date
   };
   [[nodiscard]] MutationStats GetMutationStats() const;
+  // mgx_index_memory_bytes of the main device index (0 before it is built): what the index itself keeps in HBM — the
+  // rows of cached FILTER conditions among it, not the arenas of batch objects
+  [[nodiscard]] uint64_t DeviceMemoryBytes() const;
   // Brings the device state up to date with the recorded changes (every query entry point calls it). "" or an error.
   // With a staleness bound set (below) the entry points' calls do nothing until the bound has passed since the last
   // application; force = true applies now.

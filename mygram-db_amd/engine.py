@@ -291,13 +291,17 @@ class DeviceIndex:
         check(load().mgx_index_add_filter_column(self._h, C.byref(d), C.byref(out)))
         return int(out.value)
 
+    @staticmethod
+    def literal_bits(literal):
+        """A condition's literal (a python int or float in the column's class) as the ABI's 64-bit pattern."""
+        if isinstance(literal, float):
+            return int(np.float64(literal).view(np.uint64))
+        return int(literal) & 0xFFFFFFFFFFFFFFFF
+
     def filter_compare(self, column_id, op, literal, eq_epsilon=0.0, null_matches=False, never_matches=False):
         """mgx_index_filter_compare -> filter bitmap id. op: 0 = , 1 != , 2 < , 3 <= , 4 > , 5 >= ; literal: a python int or
         float in the column's class."""
-        if isinstance(literal, float):
-            bits = int(np.float64(literal).view(np.uint64))
-        else:
-            bits = int(literal) & 0xFFFFFFFFFFFFFFFF
+        bits = self.literal_bits(literal)
         out = C.c_uint32()
         check(load().mgx_index_filter_compare(self._h, column_id, op, bits, float(eq_epsilon), int(null_matches),
                                               int(never_matches), C.byref(out)))
@@ -335,11 +339,15 @@ class Query:
     """The parts of query::Query (src/query/query_parser.h:207-243) the hot path consumes."""
 
     def __init__(self, terms=(), not_terms=(), filters=(), sort_score=False, limit=100, offset=0, descending=True,
-                 k1=1.2, b=0.75, fuzzy=0, expr=None, universe=None, verify_text=False, highlight=None):
+                 k1=1.2, b=0.75, fuzzy=0, expr=None, universe=None, verify_text=False, highlight=None, conditions=()):
         """`expr`: boolean tree over term strings instead of the plain AND of `terms` (query::QueryNode):
         "term" | ("and", e, ...) | ("or", e, ...) | ("not", e). `universe` = (first_doc_id, count) of the NOT universe
         (DocumentStore::GetAllDocIds); None = every slot of the index."""
         self.terms, self.not_terms, self.filters = list(terms), list(not_terms), list(filters)
+        # conditions: FILTER conditions the batch evaluates itself (mgx_condition), each (column_id, op, literal,
+        # eq_epsilon=0.0, null_matches=False, never_matches=False, negate=False) with op and literal as in
+        # DeviceIndex.filter_compare — no filter row is registered for them
+        self.conditions = list(conditions)
         self.sort_score, self.limit, self.offset, self.descending = sort_score, limit, offset, descending
         self.k1, self.b, self.fuzzy = k1, b, fuzzy
         # verify_text: the caller's memory.verify_text decision (ShouldApplyVerifyText, search_pipeline.cpp:42-66);
@@ -361,6 +369,21 @@ class Query:
                         walk(c)
             walk(expr)
             self.terms = seen
+
+
+def _set_conditions(cq, q, keep):
+    """q.conditions -> cq.conditions / n_conditions (mgx_condition array, kept alive in `keep`)."""
+    if not q.conditions:
+        return
+    cc = (_capi.Condition * len(q.conditions))()
+    for j, cond in enumerate(q.conditions):
+        column_id, op, literal = cond[:3]
+        eps, null_matches, never_matches, negate = (tuple(cond[3:]) + (0.0, False, False, False)[len(cond) - 3:])[:4]
+        cc[j] = _capi.Condition(int(column_id), int(op), DeviceIndex.literal_bits(literal), float(eps), int(bool(null_matches)),
+                                int(bool(never_matches)), int(bool(negate)), 0)
+    keep.append(cc)
+    cq.conditions = C.cast(cc, C.c_void_p)
+    cq.n_conditions = len(q.conditions)
 
 
 class TermInfo:
@@ -934,6 +957,7 @@ class Index:
                                  C.cast(cf, C.c_void_p), len(q.filters),
                                  _capi.SORT_SCORE if q.sort_score else _capi.SORT_DOCID, q.limit, q.offset,
                                  int(q.descending), q.k1, q.b, self.total_docs, self.avg_doc_length)
+                _set_conditions(cq, q, keep)
                 if q.verify_text:
                     cq.fuzzy_verify_distance = q.fuzzy
                 if q.sort_score:
@@ -1054,6 +1078,7 @@ class Index:
                              _capi.SORT_SCORE if q.sort_score else _capi.SORT_DOCID, q.limit, q.offset,
                              int(q.descending), q.k1, q.b, self.total_docs, self.avg_doc_length)
             cq.exact_text = int(exact)
+            _set_conditions(cq, q, keep)
             if expr_tokens is not None and q.sort_score:
                 sc = np.asarray(expr_scored, dtype=np.uint32)
                 keep.append(sc)

@@ -5,6 +5,7 @@
     python tools/bench_configs.py cfg5 [--docs 12500000] [--batch 8192] [--steps 10]
     python tools/bench_configs.py cfg3 [--docs 1000000]  [--batch 4096] [--steps 10]
     python tools/bench_configs.py cfg4 | cfg2doc | text2
+    python tools/bench_configs.py range [--via conditions|rows]   (FILTER <int column> >= <a fresh literal per query and step>)
 """
 import argparse
 import json
@@ -153,21 +154,72 @@ def score5(mg, args):
     return idx, qs, {"workload": "%d docs, bigram, batch %d x 4- and 5-term AND + BM25 top-10" % (args.docs, args.batch)}
 
 
+def range_filter(mg, args):
+    """The bench.py batch (1024 x 3-term AND by df + BM25 top-10) with FILTER created_at >= <literal> on every query, a
+    distinct literal per query and per step: every step is a freshly prepared batch. --via conditions: the batch brings
+    the conditions along (Query(conditions=...)); --via rows: every literal becomes a persistent row of the index first
+    (DeviceIndex.filter_compare), which is how such a query was served before batch conditions existed. Prints queries/s
+    over prepare + execute + fetch and mgx_index_memory_bytes before and after the run."""
+    import torch
+    corpus = mg.Corpus.synthetic(args.docs, seed=42)
+    idx = mg.Index(corpus=corpus, ngram_size=2)
+    c = idx.columns
+    sizes = np.diff(c.offsets.astype(np.int64))
+    cand = [g for g in range(c.n_grams) if b" " not in c.gram(g)]
+    w = sizes[cand].astype(np.float64)
+    w /= w.sum()
+    rng = np.random.default_rng(42)
+    span = 1 << 30
+    col = idx.device_index.add_filter_column(rng.integers(0, span, size=c.n_docs, dtype=np.int64))
+    terms = [[c.gram(cand[i]).decode() for i in rng.choice(len(cand), size=3, replace=False, p=w)] for _ in range(args.batch)]
+    need = args.batch * (args.steps + args.warmup)
+    lits = rng.permutation(np.unique(rng.integers(0, span, size=2 * need))[:need]).reshape(args.steps + args.warmup, args.batch)
+
+    def queries(step):
+        if args.via == "rows":
+            return [mg.engine.Query(t, filters=[(idx.device_index.filter_compare(col, 5, int(v)), False)], sort_score=True, limit=10)
+                    for t, v in zip(terms, lits[step])]
+        return [mg.engine.Query(t, conditions=[(col, 5, int(v))], sort_score=True, limit=10) for t, v in zip(terms, lits[step])]
+
+    before = idx.device_index.memory_bytes()
+    batch, t0 = None, 0.0
+    for step in range(args.warmup + args.steps):
+        if step == args.warmup:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+        batch = idx.prepare(queries(step), into=batch)
+        batch.execute()
+        batch.fetch_raw()
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    after = idx.device_index.memory_bytes()
+    res = batch.fetch()
+    print(json.dumps({"metric": "queries/sec", "value": args.batch * args.steps / dt, "unit": "queries/s",
+                      "ms_per_step": 1e3 * dt / args.steps, "steps": args.steps, "config": {
+                          "workload": "range: %d docs, bigram, batch %d x 3-term AND + BM25 top-10 + FILTER int column >= literal, "
+                                      "a fresh literal per query and step, via %s" % (args.docs, args.batch, args.via),
+                          "index_bytes_before": before, "index_bytes_after": after, "index_bytes_growth": after - before,
+                          "distinct_literals": int(lits.size), "mean_total": float(np.mean([r.total for r in res]))}}))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("config", choices=["cfg3", "cfg4", "cfg5", "cfg2doc", "text2", "score5"])
+    ap.add_argument("config", choices=["cfg3", "cfg4", "cfg5", "cfg2doc", "text2", "score5", "range"])
+    ap.add_argument("--via", choices=["conditions", "rows"], default="conditions", help="range: how the conditions are served")
     ap.add_argument("--docs", type=int, default=0)
     ap.add_argument("--batch", type=int, default=0)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--check", type=int, default=0, help="sample this many queries of the batch against the CPU oracle")
     args = ap.parse_args()
-    args.docs = args.docs or {"cfg3": 1_000_000, "cfg5": 12_500_000, "cfg2doc": 10_000_000, "text2": 2_000_000, "cfg4": 12_500_000, "score5": 10_000_000}[args.config]
-    args.batch = args.batch or {"cfg3": 4096, "cfg5": 8192, "cfg2doc": 1024, "text2": 1024, "cfg4": 1024, "score5": 1024}[args.config]
+    args.docs = args.docs or {"cfg3": 1_000_000, "cfg5": 12_500_000, "cfg2doc": 10_000_000, "text2": 2_000_000, "cfg4": 12_500_000, "score5": 10_000_000, "range": 10_000_000}[args.config]
+    args.batch = args.batch or {"cfg3": 4096, "cfg5": 8192, "cfg2doc": 1024, "text2": 1024, "cfg4": 1024, "score5": 1024, "range": 1024}[args.config]
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("needs an MI355X")
     mg = entry.load_package()
+    if args.config == "range":
+        return range_filter(mg, args)
     t0 = time.perf_counter()
     idx, qs, cfg = {"cfg3": cfg3, "cfg5": cfg5, "cfg2doc": cfg2doc, "text2": text2, "cfg4": cfg4, "score5": score5}[args.config](mg, args)
     batch = idx.prepare(qs)
