@@ -426,7 +426,8 @@ std::unique_ptr<Index> Index::FromDump(const void* data, size_t len, const std::
         im->exists_bits[i >> 6] |= 1ull << (i & 63);
       }
     im->has_gaps = true;
-    if (mgx_index_add_filter_bitmap(im->dev, existing.data(), existing.size(), &im->exists_bitmap) != MGX_OK)
+    if (mgx_index_add_filter_bitmap(im->dev, existing.data(), existing.size(), &im->exists_bitmap) != MGX_OK ||
+        mgx_index_set_live_bitmap(im->dev, im->exists_bitmap, MGX_LIVE_BITMAPS_CLEAN) != MGX_OK)
       return fail(mgx_last_error());
   }
   g_last_finalized.store(idx.get());
@@ -1036,7 +1037,8 @@ std::string Index::Compact() const {
   if (mgx_index_attach_text(dev2, bytes.data(), off.data()) != MGX_OK) return fail(mgx_last_error());
   const bool gaps = existing.size() != n2;
   uint32_t exists_bitmap = 0;
-  if (gaps && mgx_index_add_filter_bitmap(dev2, existing.data(), existing.size(), &exists_bitmap) != MGX_OK)
+  if (gaps && (mgx_index_add_filter_bitmap(dev2, existing.data(), existing.size(), &exists_bitmap) != MGX_OK ||
+               mgx_index_set_live_bitmap(dev2, exists_bitmap, MGX_LIVE_BITMAPS_CLEAN) != MGX_OK))
     return fail(mgx_last_error());
   // what the re-added filter columns need of the old state
   const std::vector<uint64_t> old_live = m.main_live;
@@ -1246,8 +1248,12 @@ std::string Index::Finalize() const {
             std::chrono::duration<double, std::milli>(tb2 - tb1).count(),
             std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tb2).count());
   // DocumentStore::GetAllDocIds (the NOT universe of boolean expressions) is the set of ids that were added
+  // As the index's live row it is ANDed into every query before the first funnel counter (a gap holds no posting, so the
+  // bitmap forms are clean by construction): a NOT node's complement, total_candidates, after_intersection and after_not
+  // count stored documents only, as ExecuteWithBooleanAst's all_docs does (search_pipeline.cpp:1469, :1477).
   if (impl_->has_gaps &&
-      mgx_index_add_filter_bitmap(impl_->dev, existing.data(), existing.size(), &impl_->exists_bitmap) != MGX_OK)
+      (mgx_index_add_filter_bitmap(impl_->dev, existing.data(), existing.size(), &impl_->exists_bitmap) != MGX_OK ||
+       mgx_index_set_live_bitmap(impl_->dev, impl_->exists_bitmap, MGX_LIVE_BITMAPS_CLEAN) != MGX_OK))
     impl_->last_error = mgx_last_error();
   pending_columns_ready_ = !impl_->pending_filters.empty();
   return impl_->last_error;
@@ -2292,7 +2298,7 @@ void PlanQuery(const index::Index& index, const BatchQuery& q, uint64_t total_do
     }
     if (!add_not_terms()) return;
     if (!add_filters()) return;
-    if (im->has_gaps) p->filters.push_back(mgx_filter{im->exists_bitmap, 0u});  // NOT universe = added ids
+    // (NOT universe = added ids: a table with gaps carries its exists bitmap as the device index's live row)
     finish(q.sort_by_score ? MGX_SORT_SCORE : MGX_SORT_DOCID);
     p->q.offset = q.sort_by_score ? q.offset : 0;
     p->q.expr = p->expr.data();

@@ -896,7 +896,7 @@ class Index:
                 else:
                     names = list(q.terms)
                 hl = (q.highlight, build_highlight_terms([by_term[t] for t in names]))
-            if q.fuzzy:
+            if q.fuzzy and q.expr is None:
                 # ExecuteWithFuzzy (search_pipeline.cpp:1659-1744): terms in the order given (no size sort); a term
                 # without n-grams ends the query; per term "at least theta of its known grams", AND across terms
                 order = list(range(len(tis)))
@@ -983,12 +983,20 @@ class Index:
                 # ExecuteWithBooleanAst (search_pipeline.cpp:1408-1578): a term with an unknown gram is an empty
                 # doc set inside the tree, not the end of the query
                 toks = []
+                if q.fuzzy:
+                    # FUZZY d over an expression: every leaf is fuzzy_term_search (search_pipeline.cpp:1424-1445) — a
+                    # leaf without n-grams is the empty set (:1431-1433), any other "at least theta of its known grams"
+                    # (Index::SearchByThreshold); the scored terms stay the exact terms
+                    def leaf_empty(t):
+                        return not t.grams or t.fuzzy_empty or not t.fuzzy_ids
+                else:
+                    def leaf_empty(t):
+                        return t.estimated_size in (0, None)
 
                 def emit(e):
                     if isinstance(e, str):
                         i = q.terms.index(e)
-                        toks.append((_capi.EXPR_EMPTY, 0) if tis[i].estimated_size in (0, None)
-                                    else (_capi.EXPR_TERM, i))
+                        toks.append((_capi.EXPR_EMPTY, 0) if leaf_empty(tis[i]) else (_capi.EXPR_TERM, i))
                         return
                     for c in e[1:]:
                         emit(c)
@@ -1013,14 +1021,16 @@ class Index:
                 collect(q.expr, False)
                 # placeholder grams for EMPTY leaves so that every mgx_term stays well-formed
                 for t in tis:
-                    if t.estimated_size in (0, None):
-                        t.gram_ids = [0]
+                    if leaf_empty(t):
+                        t.gram_ids, t.threshold = [0], 0
+                    elif q.fuzzy:
+                        t.gram_ids = t.fuzzy_ids
             elif any(t.estimated_size in (0, None) and (t.grams or not t.normalized) for t in tis):
                 shell.empty_term_detected = True  # Execute :804-810
                 shells.append(shell)
                 continue
-            if any(not t.grams for t in tis) and (q.expr is not None or q.fuzzy):
-                raise _capi.MgxError(4, "a term shorter than one n-gram inside an expression / FUZZY query "
+            if any(not t.grams for t in tis) and q.expr is not None and (not q.fuzzy or q.sort_score):
+                raise _capi.MgxError(4, "a term shorter than one n-gram inside an expression "
                                         "(SearchNormalizedSubstring) is not on the device path")
             exact = q.expr is None and (q.verify_text or any(
                 has_uncovered_hybrid_fragment(t.normalized, self.ngram_size, self.kanji_ngram_size, self.cross_boundary)
@@ -1033,7 +1043,7 @@ class Index:
                 keep.append(ids)
                 thr = t.threshold if (q.fuzzy and t.threshold < len(ids)) else 0
                 idf, text_ptr, text_len = 0.0, None, 0
-                if exact or not t.grams:
+                if exact or (not t.grams and q.expr is None):
                     # (no grams at all: a term shorter than one n-gram — the device scans the texts for it,
                     # query::SearchNormalizedSubstring, src/query/substring_search.h:24-42)
                     self.ensure_text()

@@ -1393,14 +1393,15 @@ int orc_execute_fuzzy(const orc_index* idx, const orc_docstore* ds, const uint8_
     results = r2;
   }
   out->after_filters = results.n;
-  if (verify_text && results.n > 0 && ds != NULL) { /* PostFilterByFuzzyText :1746-1757 */
+  if (verify_text && results.n > 0 && ds != NULL) { /* PostFilterByFuzzyText :1746-1755: text.find(term) || fuzzy */
     size_t w = 0;
     for (size_t r = 0; r < results.n; ++r) {
       size_t tl;
       const uint8_t* tx = docstore_text(ds, results.v[r], &tl);
       int all = tx != NULL;
       for (size_t i = 0; all && i < n_terms; ++i)
-        all = orc_contains_fuzzy_match(tx, tl, tis[i].normalized, tis[i].normalized_len, max_distance);
+        all = bytes_find(tx, tl, tis[i].normalized, tis[i].normalized_len, 0) != (size_t)-1 || /* :1752, exact first */
+              orc_contains_fuzzy_match(tx, tl, tis[i].normalized, tis[i].normalized_len, max_distance);
       if (all) results.v[w++] = results.v[r];
     }
     results.n = w;
@@ -1430,6 +1431,249 @@ done:
   out->results = results.v ? results.v : u32_dup(NULL, 0);
   out->n_results = results.n;
   out->n_terms = n_terms;
+  return 0;
+}
+
+/* ---- boolean expression (ExecuteWithBooleanAst) ---------------------------------------------------------------- */
+
+typedef struct {
+  const orc_index* idx;
+  const orc_docstore* ds;
+  const orc_ast_node* nodes;
+  size_t n_nodes;
+  const uint32_t* kids;
+  const uint8_t* leaf_bytes;
+  const uint32_t* leaf_off;
+  size_t n_leaves;
+  int ngram_size, kanji_ngram_size, cross_boundary;
+  int fuzzy; /* fuzzy_max_distance.has_value() */
+  uint32_t max_distance;
+  const uint32_t* all_docs;
+  size_t n_all;
+} ast_ctx;
+
+/* regular_term_search :1446-1455: GenerateTermInfos({term}) then SearchTermDocuments (:438-446). */
+static u32vec ast_regular_term_search(const ast_ctx* c, const uint8_t* term, size_t len) {
+  term_info ti;
+  make_term_info(c->idx, c->ds, term, len, c->ngram_size, c->kanji_ngram_size, c->cross_boundary, 0, &ti);
+  u32vec out = search_term_documents(c->idx, c->ds, &ti);
+  free_term_info(&ti);
+  return out;
+}
+
+/* fuzzy_term_search :1424-1445: a term without n-grams is the empty set (:1431-1433); n_eff :1434-1441; theta
+ * :1442-1443; Index::SearchByThreshold :1444. */
+static u32vec ast_fuzzy_term_search(const ast_ctx* c, const uint8_t* term, size_t len) {
+  u32vec out = {0};
+  term_info ti;
+  make_term_info(c->idx, c->ds, term, len, c->ngram_size, c->kanji_ngram_size, c->cross_boundary, 0, &ti);
+  if (ti.ngrams.count != 0) {
+    int n_eff = c->ngram_size > 0 ? c->ngram_size : 2;
+    if (c->kanji_ngram_size > 0) {
+      size_t short_count = 0;
+      for (size_t g = 0; g < ti.ngrams.count; ++g)
+        if (ti.ngrams.off[g + 1] - ti.ngrams.off[g] <= 3) ++short_count;
+      if (short_count > ti.ngrams.count / 2) n_eff = c->kanji_ngram_size;
+    }
+    size_t drop = (size_t)c->max_distance * (size_t)n_eff;
+    size_t theta = ti.ngrams.count > drop ? ti.ngrams.count - drop : 1;
+    out.v = orc_search_by_threshold(c->idx, ti.ngrams.bytes, ti.ngrams.off, ti.ngrams.count, theta, &out.n);
+    out.cap = out.n;
+  }
+  free_term_info(&ti);
+  return out;
+}
+
+static u32vec ast_term_search(const ast_ctx* c, const uint8_t* term, size_t len) {
+  return c->fuzzy ? ast_fuzzy_term_search(c, term, len) : ast_regular_term_search(c, term, len);
+}
+
+static int ast_node_ok(const ast_ctx* c, uint32_t ni) {
+  if (ni == ORC_AST_NULL) return 1;
+  if (ni >= c->n_nodes) return 0;
+  const orc_ast_node* n = &c->nodes[ni];
+  if (n->type == ORC_AST_TERM) return n->term < c->n_leaves;
+  if (n->type > ORC_AST_NOT) return 0;
+  for (uint32_t k = 0; k < n->n_kids; ++k) {
+    uint32_t kid = c->kids[n->first_kid + k];
+    /* children follow their parent in the array: no cycles, the recursion ends */
+    if (kid != ORC_AST_NULL && (kid <= ni || !ast_node_ok(c, kid))) return 0;
+  }
+  return 1;
+}
+
+/* ContainsAstNot :224-230 */
+static int ast_contains_not(const ast_ctx* c, uint32_t ni) {
+  const orc_ast_node* n = &c->nodes[ni];
+  if (n->type == ORC_AST_NOT) return 1;
+  if (n->type == ORC_AST_TERM) return 0;
+  for (uint32_t k = 0; k < n->n_kids; ++k) {
+    uint32_t kid = c->kids[n->first_kid + k];
+    if (kid != ORC_AST_NULL && ast_contains_not(c, kid)) return 1;
+  }
+  return 0;
+}
+
+/* EvaluateBooleanAstExpanded :327-378 */
+static u32vec ast_evaluate(const ast_ctx* c, uint32_t ni) {
+  const orc_ast_node* n = &c->nodes[ni];
+  u32vec result = {0};
+  switch (n->type) {
+    case ORC_AST_TERM: /* :331-332 */
+      return ast_term_search(c, c->leaf_bytes + c->leaf_off[n->term], c->leaf_off[n->term + 1] - c->leaf_off[n->term]);
+    case ORC_AST_AND: { /* :333-355 */
+      int first = 1;
+      for (uint32_t k = 0; k < n->n_kids; ++k) {
+        uint32_t kid = c->kids[n->first_kid + k];
+        if (kid == ORC_AST_NULL) { /* :337-339 */
+          free(result.v);
+          memset(&result, 0, sizeof(result));
+          return result;
+        }
+        u32vec child = ast_evaluate(c, kid);
+        if (first) {
+          result = child;
+          first = 0;
+        } else {
+          u32vec inter = set_intersection_u32(result.v, result.n, child.v, child.n);
+          free(child.v);
+          free(result.v);
+          result = inter;
+        }
+        if (result.n == 0) break; /* :350-352: the children after an empty partial result are not evaluated */
+      }
+      return result;
+    }
+    case ORC_AST_OR: /* :356-364 */
+      for (uint32_t k = 0; k < n->n_kids; ++k) {
+        uint32_t kid = c->kids[n->first_kid + k];
+        if (kid == ORC_AST_NULL) continue;
+        u32vec child = ast_evaluate(c, kid);
+        u32vec u = set_union_u32(result.v, result.n, child.v, child.n);
+        free(child.v);
+        free(result.v);
+        result = u;
+      }
+      return result;
+    default: { /* NOT :365-375: all_docs minus the child */
+      if (n->n_kids == 0 || c->kids[n->first_kid] == ORC_AST_NULL) {
+        result.v = u32_dup(c->all_docs, c->n_all);
+        result.n = result.cap = c->n_all;
+        return result;
+      }
+      u32vec excluded = ast_evaluate(c, c->kids[n->first_kid]);
+      result = set_difference_u32(c->all_docs, c->n_all, excluded.v, excluded.n);
+      free(excluded.v);
+      return result;
+    }
+  }
+}
+
+static void ast_collect(const orc_ast_node* nodes, const uint32_t* kids, uint32_t ni, int under_not, uint32_t* out,
+                        size_t cap, size_t* n) {
+  const orc_ast_node* nd = &nodes[ni];
+  if (nd->type == ORC_AST_TERM) { /* :242-247 */
+    if (!under_not) {
+      if (*n < cap) out[*n] = nd->term;
+      ++*n;
+    }
+    return;
+  }
+  for (uint32_t k = 0; k < nd->n_kids; ++k) { /* :233-240, :249-253 */
+    uint32_t kid = kids[nd->first_kid + k];
+    if (kid != ORC_AST_NULL) ast_collect(nodes, kids, kid, under_not || nd->type == ORC_AST_NOT, out, cap, n);
+  }
+}
+
+size_t orc_collect_ast_scoring_terms(const orc_ast_node* nodes, size_t n_nodes, const uint32_t* kids, uint32_t* out,
+                                     size_t cap) {
+  size_t n = 0;
+  if (n_nodes == 0) return 0;
+  ast_ctx c;
+  memset(&c, 0, sizeof(c));
+  c.nodes = nodes;
+  c.n_nodes = n_nodes;
+  c.kids = kids;
+  c.n_leaves = (size_t)-1;
+  if (!ast_node_ok(&c, 0)) return (size_t)-1;
+  ast_collect(nodes, kids, 0, 0, out, cap, &n);
+  return n;
+}
+
+int orc_execute_boolean_ast(const orc_index* idx, const orc_docstore* ds, const orc_ast_node* nodes, size_t n_nodes,
+                            const uint32_t* kids, const uint8_t* leaf_bytes, const uint32_t* leaf_off, size_t n_leaves,
+                            const uint8_t* and_bytes, const uint32_t* and_off, size_t n_and, const uint8_t* nb,
+                            const uint32_t* noff, size_t n_not, const orc_filter* filters, size_t n_filters,
+                            const uint32_t* all_docs, size_t n_all, int fuzzy, uint32_t max_distance, int ngram_size,
+                            int kanji_ngram_size, int cross_boundary, orc_pipeline_result* out) {
+  memset(out, 0, sizeof(*out));
+  ast_ctx c;
+  memset(&c, 0, sizeof(c));
+  c.idx = idx;
+  c.ds = ds;
+  c.nodes = nodes;
+  c.n_nodes = n_nodes;
+  c.kids = kids;
+  c.leaf_bytes = leaf_bytes;
+  c.leaf_off = leaf_off;
+  c.n_leaves = n_leaves;
+  c.ngram_size = ngram_size;
+  c.kanji_ngram_size = kanji_ngram_size;
+  c.cross_boundary = cross_boundary;
+  c.fuzzy = fuzzy;
+  c.max_distance = max_distance;
+  if (n_nodes == 0 || !ast_node_ok(&c, 0)) return 11;
+  /* :1469: the universe is fetched only for a tree that holds a NOT */
+  if (ast_contains_not(&c, 0)) {
+    c.all_docs = all_docs;
+    c.n_all = n_all;
+  }
+  u32vec results = ast_evaluate(&c, 0); /* :1470-1476 */
+  out->total_candidates = results.n;   /* :1477 */
+  for (size_t i = 0; i < n_and; ++i) { /* :1479-1500 */
+    u32vec ar = ast_term_search(&c, and_bytes + and_off[i], and_off[i + 1] - and_off[i]);
+    if (ar.n == 0) { /* :1488-1492: returns at once, after_intersection / after_not / after_filters stay 0 */
+      free(ar.v);
+      free(results.v);
+      memset(&results, 0, sizeof(results));
+      out->empty_term_detected = 1;
+      goto done;
+    }
+    u32vec inter = set_intersection_u32(results.v, results.n, ar.v, ar.n);
+    free(ar.v);
+    free(results.v);
+    results = inter;
+    if (results.n == 0) break; /* :1497-1499 */
+  }
+  out->after_intersection = results.n; /* :1501 */
+  /* ApplyNotAndFilters :472-485; ApplyNotFilter :871-932 without a synonym dictionary */
+  if (n_not > 0 && results.n > 0) {
+    u32vec excluded = {0};
+    for (size_t i = 0; i < n_not; ++i) {
+      u32vec td = ast_regular_term_search(&c, nb + noff[i], noff[i + 1] - noff[i]); /* :906-915 */
+      u32vec u = set_union_u32(excluded.v, excluded.n, td.v, td.n);
+      free(td.v);
+      free(excluded.v);
+      excluded = u;
+    }
+    if (excluded.n > 0) {
+      u32vec d = set_difference_u32(results.v, results.n, excluded.v, excluded.n);
+      free(results.v);
+      results = d;
+    }
+    free(excluded.v);
+  }
+  out->after_not = results.n; /* :480 */
+  for (size_t f = 0; f < n_filters; ++f) { /* :481-483, ApplyFiltersWithBitmap :1196-1237 */
+    u32vec r2 = filters[f].negate ? set_difference_u32(results.v, results.n, filters[f].docs, filters[f].n_docs)
+                                  : set_intersection_u32(results.v, results.n, filters[f].docs, filters[f].n_docs);
+    free(results.v);
+    results = r2;
+  }
+  out->after_filters = results.n; /* :484 */
+done:
+  out->results = results.v ? results.v : u32_dup(NULL, 0);
+  out->n_results = results.n;
   return 0;
 }
 

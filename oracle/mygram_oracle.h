@@ -170,6 +170,36 @@ int orc_execute_fuzzy(const orc_index* idx, const orc_docstore* ds, const uint8_
                       size_t n_terms, uint32_t max_distance, const uint8_t* not_bytes, const uint32_t* not_off,
                       size_t n_not, const orc_filter* filters, size_t n_filters, int ngram_size, int kanji_ngram_size,
                       int cross_boundary, int verify_text, orc_pipeline_result* out, uint64_t* thetas);
+/* ---- boolean expression --------------------------------------------------------------------------------------- */
+
+/* query::QueryNode (src/query/query_ast.h) as plain data: node 0 is the root; the children of node i are
+ * kids[first_kid .. first_kid + n_kids), each the index of a LATER node or ORC_AST_NULL (a null child); a TERM node
+ * names leaf string `term`. The tree crosses as a tree: nothing here reads a postfix program. */
+enum { ORC_AST_TERM = 0, ORC_AST_AND = 1, ORC_AST_OR = 2, ORC_AST_NOT = 3 };
+#define ORC_AST_NULL 0xFFFFFFFFu
+typedef struct orc_ast_node {
+  uint32_t type, term, first_kid, n_kids;
+} orc_ast_node;
+
+/* src/server/search_pipeline.cpp:1408-1504 ExecuteWithBooleanAst on the oracle's own index and set operations:
+ * EvaluateBooleanAstExpanded (:327-378, with its AND early exit on an empty partial result and NOT = all_docs minus the
+ * child), the regular_term_search leaf (:1446-1455) or, when `fuzzy`, the fuzzy_term_search leaf (:1424-1445: theta and
+ * the effective n-gram size per leaf, then SearchByThreshold); total_candidates (:1477); the and_terms loop with its
+ * empty_term_detected exit (:1479-1501); ApplyNotAndFilters (:472-485) with after_not and after_filters. all_docs =
+ * DocumentStore::GetAllDocIds(), ascending; read only when the tree holds a NOT (:1469).
+ * NOT restated: the synonym_term_search leaf (:1456-1467) and the verify_text post-filters (:1505-1578) — the device
+ * refuses synonym dictionaries and offers no verify_text for expressions, so nothing could be compared with them.
+ * Returns 0, or 11 for a malformed tree. term_order / term_df of `out` are not filled. */
+int orc_execute_boolean_ast(const orc_index* idx, const orc_docstore* ds, const orc_ast_node* nodes, size_t n_nodes,
+                            const uint32_t* kids, const uint8_t* leaf_bytes, const uint32_t* leaf_off, size_t n_leaves,
+                            const uint8_t* and_bytes, const uint32_t* and_off, size_t n_and, const uint8_t* not_bytes,
+                            const uint32_t* not_off, size_t n_not, const orc_filter* filters, size_t n_filters,
+                            const uint32_t* all_docs, size_t n_all, int fuzzy, uint32_t max_distance, int ngram_size,
+                            int kanji_ngram_size, int cross_boundary, orc_pipeline_result* out);
+/* src/server/search_pipeline.cpp:232-254 CollectAstScoringTerms: the leaf index of every TERM node that is not under a
+ * NOT, in tree order, repeats kept. Writes up to cap entries; returns how many there are ((size_t)-1: malformed tree). */
+size_t orc_collect_ast_scoring_terms(const orc_ast_node* nodes, size_t n_nodes, const uint32_t* kids, uint32_t* out,
+                                     size_t cap);
 /* PostFilterByText, src/server/search_pipeline.cpp:1239-1246 (terms already normalized); caller frees the result. */
 uint32_t* orc_post_filter_by_text(const orc_docstore* ds, const uint32_t* cand, size_t n_cand,
                                   const uint8_t* term_bytes, const uint32_t* term_off, size_t n_terms, size_t* out_n);

@@ -77,6 +77,12 @@ def lib():
     L.orc_execute_fuzzy.restype = C.c_int
     L.orc_execute_fuzzy.argtypes = [C.c_void_p, C.c_void_p, u8p, u32p, sz, C.c_uint32, u8p, u32p, sz, C.c_void_p, sz,
                                     C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.orc_execute_boolean_ast.restype = C.c_int
+    L.orc_execute_boolean_ast.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, sz, u32p, u8p, u32p, sz, u8p, u32p, sz,
+                                          u8p, u32p, sz, C.c_void_p, sz, u32p, sz, C.c_int, C.c_uint32, C.c_int,
+                                          C.c_int, C.c_int, C.c_void_p]
+    L.orc_collect_ast_scoring_terms.restype = sz
+    L.orc_collect_ast_scoring_terms.argtypes = [C.c_void_p, sz, u32p, u32p, sz]
     L.orc_post_filter_by_text.restype = C.POINTER(C.c_uint32)
     L.orc_post_filter_by_text.argtypes = [C.c_void_p, u32p, sz, u8p, u32p, sz, C.POINTER(sz)]
     L.orc_pipeline_result_free.argtypes = [C.c_void_p]
@@ -390,6 +396,83 @@ def execute_fuzzy(index, store, terms, max_distance, not_terms=(), filters=(), n
            "after_intersection": pr.after_intersection, "after_not": pr.after_not, "after_filters": pr.after_filters,
            "empty_term_detected": bool(pr.empty_term_detected), "exact_text_applied": bool(pr.exact_text_applied),
            "thetas": [int(t) for t in thetas[: len(terms)]]}
+    lib().orc_pipeline_result_free(C.byref(pr))
+    return out
+
+
+class _AstNode(C.Structure):
+    _fields_ = [("type", C.c_uint32), ("term", C.c_uint32), ("first_kid", C.c_uint32), ("n_kids", C.c_uint32)]
+
+
+_AST_TYPES = {"and": 1, "or": 2, "not": 3}
+_AST_NULL = 0xFFFFFFFF
+
+
+def _flatten_tree(tree):
+    """"term" | ("and", e, ...) | ("or", e, ...) | ("not", e) (None = a null child) -> (orc_ast_node array, kids,
+    leaf strings). Node 0 is the root, children are laid out after their parent, every TERM node has its own leaf."""
+    nodes, kids, leaves = [], [], []
+
+    def add(e):
+        ni = len(nodes)
+        if isinstance(e, (str, bytes)):
+            nodes.append([0, len(leaves), 0, 0])
+            leaves.append(e)
+            return ni
+        nodes.append([_AST_TYPES[e[0]], 0, 0, 0])
+        mine = [_AST_NULL if c is None else add(c) for c in e[1:]]
+        nodes[ni][2], nodes[ni][3] = len(kids), len(mine)
+        kids.extend(mine)
+        return ni
+
+    add(tree)
+    arr = (_AstNode * len(nodes))(*[_AstNode(*n) for n in nodes])
+    return arr, np.asarray(kids + [0], dtype=np.uint32), leaves
+
+
+def collect_ast_scoring_terms(tree):
+    """CollectAstScoringTerms, search_pipeline.cpp:232-254: the TERM leaves not under a NOT, in tree order, repeats
+    kept."""
+    arr, kids, leaves = _flatten_tree(tree)
+    out = np.zeros(max(len(leaves), 1), dtype=np.uint32)
+    n = lib().orc_collect_ast_scoring_terms(C.byref(arr), len(arr), kids.ctypes.data, out.ctypes.data, len(out))
+    if n > len(leaves):
+        raise ValueError("malformed expression tree")
+    return [leaves[i] for i in out[:n].tolist()]
+
+
+def execute_boolean_ast(index, store, tree, and_terms=(), not_terms=(), filters=(), all_docs=(), fuzzy=0,
+                        ngram_size=None, kanji_ngram_size=None, cross_boundary=None):
+    """search_pipeline::ExecuteWithBooleanAst (src/server/search_pipeline.cpp:1408-1504). tree: "term" | ("and", e, ...)
+    | ("or", e, ...) | ("not", e). all_docs = DocumentStore::GetAllDocIds() (ascending), the universe of NOT nodes.
+    fuzzy > 0: every leaf and every and_term is a FUZZY term of that distance. -> dict like execute() (no term_order)."""
+    arr, kids, leaves = _flatten_tree(tree)
+    lb, loff = pack_terms(leaves)
+    ab, aoff = pack_terms(and_terms)
+    nb, noff = pack_terms(not_terms)
+    keep = []
+    farr = (_Filter * max(len(filters), 1))()
+    for i, (docs, negate) in enumerate(filters):
+        a = np.ascontiguousarray(docs, dtype=np.uint32)
+        keep.append(a)
+        farr[i].docs, farr[i].n_docs, farr[i].negate = a.ctypes.data, len(a), int(negate)
+    universe = np.ascontiguousarray(all_docs, dtype=np.uint32)
+    pr = _PipelineResult()
+    rc = lib().orc_execute_boolean_ast(index._h, store._h if store is not None else None, C.byref(arr), len(arr),
+                                       kids.ctypes.data, lb.ctypes.data, loff.ctypes.data, len(leaves),
+                                       ab.ctypes.data, aoff.ctypes.data, len(and_terms), nb.ctypes.data,
+                                       noff.ctypes.data, len(not_terms), C.byref(farr), len(filters),
+                                       universe.ctypes.data, len(universe), int(fuzzy > 0), int(fuzzy),
+                                       index.ngram_size if ngram_size is None else ngram_size,
+                                       index.kanji_ngram_size if kanji_ngram_size is None else kanji_ngram_size,
+                                       int(index.cross_boundary if cross_boundary is None else cross_boundary),
+                                       C.byref(pr))
+    if rc != 0:
+        raise ValueError("orc_execute_boolean_ast rc=%d" % rc)
+    res = np.ctypeslib.as_array(pr.results, shape=(max(pr.n_results, 1),))[: pr.n_results].copy()
+    out = {"results": res.astype(np.uint32), "total_candidates": pr.total_candidates,
+           "after_intersection": pr.after_intersection, "after_not": pr.after_not, "after_filters": pr.after_filters,
+           "empty_term_detected": bool(pr.empty_term_detected)}
     lib().orc_pipeline_result_free(C.byref(pr))
     return out
 

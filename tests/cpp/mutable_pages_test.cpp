@@ -150,6 +150,20 @@ static void Compare(Index& table, const std::map<DocId, std::string>& docs, cons
       std::printf("  %s: query %zu differs: total %llu/%llu, %zu/%zu docs\n", round, i,
                   static_cast<unsigned long long>((*got)[i].total), static_cast<unsigned long long>((*want)[i].total),
                   (*got)[i].results.size(), (*want)[i].results.size());
+    // the four funnel counters too: the sum of the main index's and the delta's equals a fresh index's only when the
+    // main index counts live documents alone and both plan the terms in the order of the table's current posting sizes
+    const bool counters = SameCounters((*got)[i], (*want)[i]);
+    EXPECT(counters);
+    if (!counters)
+      std::printf("  %s: query %zu counters differ: %llu %llu %llu %llu / %llu %llu %llu %llu\n", round, i,
+                  static_cast<unsigned long long>((*got)[i].total_candidates),
+                  static_cast<unsigned long long>((*got)[i].after_intersection),
+                  static_cast<unsigned long long>((*got)[i].after_not),
+                  static_cast<unsigned long long>((*got)[i].after_filters),
+                  static_cast<unsigned long long>((*want)[i].total_candidates),
+                  static_cast<unsigned long long>((*want)[i].after_intersection),
+                  static_cast<unsigned long long>((*want)[i].after_not),
+                  static_cast<unsigned long long>((*want)[i].after_filters));
     nonempty += (*got)[i].results.empty() ? 0 : 1;
   }
   EXPECT(nonempty + 2 >= qs.size());  // (every shape returns a page; zzqx may be absent from the delta after compaction)

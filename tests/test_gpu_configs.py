@@ -59,17 +59,13 @@ def test_config2_shape_cjk_trigram_mixed_batch_4096():
     n_nonempty = 0
     for i in sample.tolist():
         q, g = qs[i], got[i]
-        if q.fuzzy:
-            r = O.execute_fuzzy(p.oidx, p.ostore, q.terms, q.fuzzy, ngram_size=3, kanji_ngram_size=3, cross_boundary=True)
-            res = r["results"]
-            page = res[::-1][:100]
-            assert g.total == len(res) and g.docs.tolist() == page.tolist(), (i, q.terms)
-        else:
-            total, page, _, r = p.oracle_query(q)
-            assert g.total == total and g.docs.tolist() == page.tolist(), (i, q.terms, q.not_terms, q.expr)
-            if q.expr is None and not r["empty_term_detected"]:
-                for k in ("total_candidates", "after_intersection", "after_not", "after_filters"):
-                    assert getattr(g, k) == r[k], (i, k)
+        # plain AND, expression and FUZZY queries alike: page, total and the four funnel counters against the oracle
+        total, want, _, r = p.oracle_query(q)
+        assert g.total == total and g.docs.tolist() == want.tolist(), (i, q.terms, q.not_terms, q.expr, q.fuzzy)
+        assert g.empty_term_detected == r["empty_term_detected"], (i, q.terms)
+        if not r["empty_term_detected"]:
+            for k in ("total_candidates", "after_intersection", "after_not", "after_filters"):
+                assert getattr(g, k) == r[k], (i, k, q.terms, q.expr, q.fuzzy)
         n_nonempty += g.total > 0
     assert n_nonempty > 100  # (terms are cut out of documents: most queries match something)
 

@@ -2,7 +2,8 @@
 branch produced the results (src/server/handlers/search_handler.cpp:405-470 after search_pipeline.cpp:1842-1954): the
 scored terms of an expression are its TERM leaves that are not under a NOT, in tree order, repeats kept
 (CollectAstScoringTerms :232-254; vector tests/server/search_pipeline_test.cpp:1350-1392: NOT terms are not scored); a
-FUZZY query scores its exact terms. Expected values come from the oracle's own pieces: the branch's result set, df per
+FUZZY query scores its exact terms. Expected values come from the oracle's own pieces: the branch's result set
+(ExecuteWithBooleanAst / ExecuteWithFuzzy restated in oracle/), the scored terms (its CollectAstScoringTerms), df per
 term as PopulateTermDocumentFrequency counts it, BM25Scorer::ScoreDocuments over those terms, ResultSorter::SortByScore."""
 import numpy as np
 import pytest
@@ -13,17 +14,6 @@ from pkg import mg
 
 pytestmark = pytest.mark.gpu
 Query = mg.engine.Query
-
-
-def _positive_leaves(e, under_not=False, out=None):
-    out = [] if out is None else out
-    if isinstance(e, str):
-        if not under_not:
-            out.append(e)
-        return out
-    for c in e[1:]:
-        _positive_leaves(c, under_not or e[0] == "not", out)
-    return out
 
 
 def _df(p, term):
@@ -46,7 +36,7 @@ def _check_expr(p, qs):
         total, _, _, _ = p.oracle_query(Query(expr=q.expr, not_terms=q.not_terms, filters=q.filters, limit=0))
         res = np.asarray(sorted(p.oracle_query(Query(expr=q.expr, not_terms=q.not_terms, filters=q.filters, limit=0,
                                                      descending=False))[1].tolist()), dtype=np.uint32)
-        page, scores = _expected_scored(p, res, _positive_leaves(q.expr), q)
+        page, scores = _expected_scored(p, res, O.collect_ast_scoring_terms(q.expr), q)
         assert g.total == total == len(res), q.expr
         assert g.docs.tolist() == page.tolist(), (q.expr, g.docs, page)
         assert np.array_equal(g.scores, scores), (q.expr, g.scores, scores)
