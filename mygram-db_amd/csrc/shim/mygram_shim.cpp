@@ -16,6 +16,7 @@
 #include <condition_variable>
 #include <deque>
 #include <functional>
+#include <future>
 #include <iterator>
 #include <map>
 #include <mutex>
@@ -210,7 +211,7 @@ struct Index::Impl {
   mutable bool has_gaps = false;       // ids inside [first, last] that were never added
   mutable uint32_t exists_bitmap = 0;  // filter bitmap of the ids that were (only when has_gaps)
 
-  mutable bool owns_handles = true;  // false: adopted (Index::Adopt)
+  bool internal = false;  // a delta index BuildDelta made: never the index the index-less SortByScore resolves to
   // doc-range shards: table-wide statistics (empty / 0: this index is the whole table)
   std::vector<uint64_t> global_sizes;
   uint64_t global_docs = 0;
@@ -229,18 +230,6 @@ struct Index::Impl {
     }
   };
   mutable std::shared_ptr<Handles> handles;
-  void Publish() const {
-    auto h = std::make_shared<Handles>();
-    h->cols = cols;
-    h->dev = dev;
-    h->owns = owns_handles;
-    handles = std::move(h);
-  }
-  ~Impl() {
-    if (handles) return;  // (the generation object destroys what it owns)
-    if (dev && owns_handles) mgx_index_destroy(dev);
-    if (cols && owns_handles) mgx_columns_destroy(cols);
-  }
   bool Lookup(std::string_view gram, uint32_t* id) const {
     int found = 0;
     if (!cols) return false;
@@ -280,28 +269,49 @@ struct Index::Impl {
   const Impl* fallback = nullptr;
 
   // ---- mutable tables: changes recorded after the index was built (all under mu) ------------------------------------------
+  // What one application works from: how much of the recorded state it covers. It reads that state and consumes nothing;
+  // CommitMutations does, once the device has taken it all.
+  struct Snapshot {
+    uint64_t recorded = 0;           // Mutable::recorded when it was taken
+    size_t n_clear = 0, n_dead = 0;  // the prefix of pending_clear / pending_dead_* it covers
+    bool delta_changed = false;      // the delta's documents changed since the last application
+    uint64_t main_docs = 0, main_len = 0;
+  };
+  struct BuiltDelta {
+    bool rebuilt = false;
+    std::shared_ptr<Index> delta;  // nullptr with rebuilt: the delta is empty now
+    std::shared_ptr<const std::vector<DocId>> ids;
+    std::string error;
+  };
   struct Mutable {
     bool active = false;  // a change was ever recorded (the bookkeeping below exists)
-    bool dirty = false;   // recorded changes the device has not seen
+    // every recording call bumps `recorded`; the device has seen the changes up to `applied` (behind: recorded != applied);
+    // delta_recorded is `recorded` as of the last change to delta_docs / delta_filters (the delta changed: > applied)
+    uint64_t recorded = 0, applied = 0, delta_recorded = 0;
+    void Record(bool delta) {
+      ++recorded;
+      if (delta) delta_recorded = recorded;
+    }
+    bool retry = false;  // the last application failed: the next entry point applies in its own call, whatever the bound
     std::vector<uint64_t> main_live;            // live documents of the main index, by slot
+    // append-only between applications (an application covers a prefix, CommitMutations erases it):
     std::vector<DocId> pending_clear;           // main documents removed / superseded since the last apply
     std::vector<uint32_t> pending_dead_grams;   // their distinct n-grams (main gram ids): one posting less each
     std::vector<DocId> pending_dead_docs;       // parallel to pending_dead_grams: the document of each posting
     std::map<DocId, std::string> delta_docs;    // documents of the delta index: table id -> normalized text
     std::map<DocId, storage::FilterMap> delta_filters;
-    bool delta_changed = false;
     uint64_t main_docs = 0, main_len = 0;       // BM25Stats share of the main index's live documents
     uint64_t removed = 0, epoch = 0;
     std::chrono::microseconds staleness{0};                 // SetMutationStaleness
     std::chrono::steady_clock::time_point last_apply{};     // when the device state was last brought up to date
     uint32_t live_bitmap = 0;
-    bool have_live = false;
+    bool have_live = false;                     // the device holds row live_bitmap (made by the first install, tried or done)
     std::vector<uint64_t> applied_live;         // main_live as of the last application: what the DEVICE's live row says
-    // background application (SetMutationStaleness > 0): a snapshot's delta is built by `builder` while queries keep
-    // running on the old state; the result waits (build_ready) for the next entry point to install it
-    std::thread builder;
-    bool build_running = false, build_ready = false;
-    std::shared_ptr<void> bg_snapshot, bg_built;  // (MutationSnapshot / BuiltDelta of the running build)
+    // background application (SetMutationStaleness > 0): the delta of build_snapshot is built by a thread of its own (it
+    // needs no lock: BuildDelta) while queries keep running on the old state; the first entry point that finds the future
+    // ready installs it
+    std::future<BuiltDelta> build;
+    Snapshot build_snapshot;
     std::shared_ptr<Index> delta;               // the delta index the device holds (nullptr: none)
     std::shared_ptr<const std::vector<DocId>> delta_ids;  // its doc map: local id - 1 -> table id, ascending
     std::vector<std::pair<uint32_t, uint64_t>> delta_contrib;  // (main gram id, the delta's posting count) inside global_sizes
@@ -334,6 +344,30 @@ struct Index::Impl {
   mutable std::map<DocId, storage::FilterMap> pending_filters;  // AddDocument(..., filters) before the first search
   mutable uint32_t empty_bitmap = 0;
   mutable bool have_empty_bitmap = false;
+
+  // One generation of the main index as BuildGeneration makes it, off to the side: nothing of an Impl refers to it until
+  // Install publishes all of it in one step (mu held; filter_mu is taken here, in the order every writer uses).
+  struct Generation {
+    std::shared_ptr<Handles> handles;
+    mgx_columns_view view{};
+    bool has_gaps = false;
+    uint32_t exists_bitmap = 0;
+    std::vector<uint64_t> exists_bits;
+    std::vector<FilterColumn> filter_columns;
+  };
+  void Install(Generation&& g) const {
+    std::lock_guard<std::mutex> fl(filter_mu);
+    handles = std::move(g.handles);
+    cols = handles->cols;
+    dev = handles->dev;
+    view = g.view;
+    has_gaps = g.has_gaps;
+    exists_bitmap = g.exists_bitmap;
+    exists_bits = std::move(g.exists_bits);
+    filter_columns = std::move(g.filter_columns);
+    condition_cache.clear();
+    have_empty_bitmap = false;
+  }
 
   // FilterIndex::ResolveColumnName (filter_index.cpp:122-147): exact name first, else the one unambiguous ASCII
   // case-insensitive match
@@ -368,8 +402,191 @@ Index::Index(int ngram_size, int kanji_ngram_size, double roaring_threshold, boo
   impl_->query_kanji = kanji_ngram_size;
 }
 
+namespace {
+storage::FilterValue FilterValueFromBits(size_t type, uint64_t w, const std::vector<storage::FilterValue>& dict) {
+  switch (type) {
+    case 1: return w != 0;
+    case 2: return static_cast<int8_t>(static_cast<int64_t>(w));
+    case 3: return static_cast<uint8_t>(w);
+    case 4: return static_cast<int16_t>(static_cast<int64_t>(w));
+    case 5: return static_cast<uint16_t>(w);
+    case 6: return static_cast<int32_t>(static_cast<int64_t>(w));
+    case 7: return static_cast<uint32_t>(w);
+    case 8: return static_cast<int64_t>(w);
+    case 9: return static_cast<uint64_t>(w);
+    case 10: return storage::TimeValue{static_cast<int64_t>(w)};
+    case 11: return w < dict.size() ? dict[w] : storage::FilterValue{};  // strings are stored as dictionary ranks
+    case 12: {
+      double d;
+      std::memcpy(&d, &w, 8);
+      return d;
+    }
+    default: return storage::FilterValue{};
+  }
+}
+
+// widened device value of a non-NULL FilterValue (strings: their dictionary rank, filled in by the caller)
+uint64_t WidenFilterValue(const storage::FilterValue& v) {
+  return std::visit(
+      [](const auto& val) -> uint64_t {
+        using T = std::decay_t<decltype(val)>;
+        if constexpr (std::is_same_v<T, std::monostate> || std::is_same_v<T, std::string>) return 0;
+        else if constexpr (std::is_same_v<T, storage::TimeValue>) return static_cast<uint64_t>(val.seconds);
+        else if constexpr (std::is_same_v<T, double>) {
+          uint64_t u;
+          std::memcpy(&u, &val, 8);
+          return u;
+        } else if constexpr (std::is_signed_v<T> || std::is_same_v<T, bool>) return static_cast<uint64_t>(static_cast<int64_t>(val));
+        else return static_cast<uint64_t>(val);
+      },
+      v);
+}
+uint32_t FilterClassOf(size_t type) {  // MGX_FC_* of a FilterValue alternative
+  switch (type) {
+    case 12: return MGX_FC_DOUBLE;
+    case 3: case 5: case 7: case 9: case 11: return MGX_FC_UNSIGNED;
+    default: return MGX_FC_SIGNED;  // bool, int8/16/32/64, TimeValue
+  }
+}
+
+// One filter column on a device index of n_docs doc slots: its dictionary and the device column. Touches no Impl.
+std::string BuildFilterColumn(mgx_index* dev, uint64_t n_docs, const std::string& name,
+                              const std::vector<storage::FilterValue>& values, Index::Impl::FilterColumn* out) {
+  if (values.size() != n_docs) return "AddFilterColumn: one value per doc slot of the index";
+  Index::Impl::FilterColumn col;
+  col.name = name;
+  for (const auto& v : values) {
+    if (v.index() == 0) continue;
+    if (col.type == 0) col.type = v.index();
+    if (v.index() != col.type) return "AddFilterColumn: the values of one column must hold one type";
+  }
+  std::vector<storage::FilterValue> nn;
+  for (const auto& v : values)
+    if (v.index() != 0) nn.push_back(v);
+  std::sort(nn.begin(), nn.end());
+  nn.erase(std::unique(nn.begin(), nn.end()), nn.end());
+  col.dict = std::move(nn);
+  const size_t n = values.size();
+  std::vector<uint64_t> wide(n, 0);
+  std::vector<uint8_t> nul(n, 0);
+  std::vector<uint32_t> ids(n, 0xFFFFFFFFu);
+  for (size_t i = 0; i < n; ++i) {
+    if (values[i].index() == 0) {
+      nul[i] = 1;
+      continue;
+    }
+    const auto it = std::lower_bound(col.dict.begin(), col.dict.end(), values[i]);
+    ids[i] = static_cast<uint32_t>(it - col.dict.begin());
+    wide[i] = col.type == 11 ? ids[i] : WidenFilterValue(values[i]);  // strings compare by their bytewise rank
+  }
+  mgx_filter_column_desc d{sizeof(mgx_filter_column_desc), MGX_ABI_VERSION, FilterClassOf(col.type),
+                           static_cast<uint32_t>(col.dict.size()), wide.data(), nul.data(), ids.data()};
+  if (mgx_index_add_filter_column(dev, &d, &col.device_id) != MGX_OK) return mgx_last_error();
+  *out = std::move(col);
+  return "";
+}
+
+// Filter values recorded per document as one value vector of n slots per column name: `names` first, then every other
+// name a document carries, in the order met. slot(doc) is the document's place in the vectors (>= n: it has none).
+using NamedValues = std::vector<std::pair<std::string, std::vector<storage::FilterValue>>>;
+template <class SlotOf>
+NamedValues ValuesByName(const std::map<DocId, storage::FilterMap>& filters, std::vector<std::string> names, uint64_t n,
+                         SlotOf slot) {
+  for (const auto& kv : filters)
+    for (const auto& f : kv.second)
+      if (std::find(names.begin(), names.end(), f.first) == names.end()) names.push_back(f.first);
+  NamedValues out;
+  for (auto& name : names) out.emplace_back(std::move(name), std::vector<storage::FilterValue>(n));
+  for (const auto& kv : filters) {
+    const uint64_t s = slot(kv.first);
+    if (s >= n) continue;
+    for (auto& col : out) {
+      const auto fv = kv.second.find(col.first);
+      if (fv != kv.second.end()) col.second[s] = fv->second;
+    }
+  }
+  return out;
+}
+
+// What a generation of the main index is built from.
+struct GenerationSpec {
+  int device = 0;
+  double dense_threshold = 0.0;
+  int ngram = 2, kanji = 1;
+  bool cross = true;
+  mgx_columns* cols = nullptr;          // column arrays that exist already (a dump's: taken over); else built from the texts
+  const uint8_t* text_bytes = nullptr;  // the texts by doc slot, 16 bytes of padding behind them (nullptr: none are kept)
+  const uint64_t* text_off = nullptr;
+  DocId first = 1;
+  uint64_t n = 0;
+  const std::vector<DocId>* existing = nullptr;  // the ids that exist, when some of [first, first + n) do not
+  const NamedValues* columns = nullptr;          // filter values by doc slot
+};
+
+// One generation of the main index: column arrays, device index, texts, the exists row, every filter column. It touches
+// no Impl (Impl::Install publishes the result); when it fails, what it made is freed and `out` is as it was.
+std::string BuildGeneration(const GenerationSpec& in, Index::Impl::Generation* out) {
+  static const bool kTrace = std::getenv("MGX_TRACE_HOST") != nullptr;
+  Index::Impl::Generation g;
+  g.handles = std::make_shared<Index::Impl::Handles>();  // (owns what follows: gone with `g` on every early return)
+  g.handles->cols = in.cols;
+  const auto t0 = std::chrono::steady_clock::now();
+  if (!g.handles->cols) {
+    mgx_build_params bp{sizeof(mgx_build_params), MGX_ABI_VERSION, in.ngram, in.kanji, in.cross ? 1 : 0, 0};
+    if (mgx_columns_build(&bp, in.text_bytes, in.text_off, in.first, in.n, &g.handles->cols) != MGX_OK) {
+      g.handles->cols = nullptr;
+      return mgx_last_error();
+    }
+  }
+  const auto t1 = std::chrono::steady_clock::now();
+  mgx_columns_view_get(g.handles->cols, &g.view);
+  const auto& v = g.view;
+  mgx_index_desc d{sizeof(mgx_index_desc), MGX_ABI_VERSION, in.device, 0, v.first_doc_id, v.n_docs, v.n_grams,
+                   v.offsets,               v.docids,        v.tf,      v.doc_len, in.dense_threshold,
+                   v.tf_overflow_pos,       v.tf_overflow_val, v.n_tf_overflow};
+  if (mgx_index_create(&d, &g.handles->dev) != MGX_OK) {
+    g.handles->dev = nullptr;
+    return mgx_last_error();
+  }
+  mgx_index* dev = g.handles->dev;
+  const auto t2 = std::chrono::steady_clock::now();
+  // the shim's Index is also the DocumentStore of the texts it was given: BM25 terms longer than one n-gram are
+  // counted in the text on the device
+  if (in.text_bytes && mgx_index_attach_text(dev, in.text_bytes, in.text_off) != MGX_OK) return mgx_last_error();
+  if (kTrace)
+    fprintf(stderr, "[shim] generation of %llu docs: columns %.2f ms, device index %.2f ms, texts %.2f ms\n",
+            static_cast<unsigned long long>(v.n_docs), std::chrono::duration<double, std::milli>(t1 - t0).count(),
+            std::chrono::duration<double, std::milli>(t2 - t1).count(),
+            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t2).count());
+  // DocumentStore::GetAllDocIds (the NOT universe of boolean expressions) is the set of ids that were added (deleted ids
+  // leave gaps in the range). As the index's live row it is ANDed into every query before the first funnel counter (a gap
+  // holds no posting, so the bitmap forms are clean by construction): a NOT node's complement, total_candidates,
+  // after_intersection and after_not count stored documents only, as ExecuteWithBooleanAst's all_docs does
+  // (search_pipeline.cpp:1469, :1477).
+  if (in.existing) {
+    g.has_gaps = true;
+    g.exists_bits.assign((v.n_docs + 63) / 64, 0);
+    for (DocId doc : *in.existing) {
+      const uint64_t slot = doc - v.first_doc_id;
+      g.exists_bits[slot >> 6] |= 1ull << (slot & 63);
+    }
+    if (mgx_index_add_filter_bitmap(dev, in.existing->data(), in.existing->size(), &g.exists_bitmap) != MGX_OK ||
+        mgx_index_set_live_bitmap(dev, g.exists_bitmap, MGX_LIVE_BITMAPS_CLEAN) != MGX_OK)
+      return mgx_last_error();
+  }
+  if (in.columns)
+    for (const auto& c : *in.columns) {
+      g.filter_columns.emplace_back();
+      const std::string err = BuildFilterColumn(dev, v.n_docs, c.first, c.second, &g.filter_columns.back());
+      if (!err.empty()) return err;
+    }
+  *out = std::move(g);
+  return "";
+}
+}  // namespace
+
 Index::~Index() {
-  if (impl_->mut.builder.joinable()) impl_->mut.builder.join();  // (a delta build in flight reads this object's configuration)
+  if (impl_->mut.build.valid()) impl_->mut.build.wait();  // (a delta build in flight reads this object's configuration)
   if (tl_last_index == this) tl_last_index = nullptr;
   const Index* me = this;
   g_last_finalized.compare_exchange_strong(me, nullptr);
@@ -379,12 +596,12 @@ std::unique_ptr<Index> Index::Adopt(mgx_columns* columns, mgx_index* device_inde
                                     int kanji_ngram_size, bool cross_boundary_ngrams) {
   auto idx = std::make_unique<Index>(ngram_size, kanji_ngram_size, 0.0, cross_boundary_ngrams);
   Impl* im = idx->impl_.get();
-  im->cols = columns;
-  im->dev = device_index;
-  im->owns_handles = false;
+  im->handles = std::make_shared<Impl::Handles>();
+  im->handles->cols = im->cols = columns;
+  im->handles->dev = im->dev = device_index;
+  im->handles->owns = false;
   im->finalized = true;
   if (mgx_columns_view_get(columns, &im->view) != MGX_OK) im->last_error = mgx_last_error();
-  im->Publish();
   g_last_finalized.store(idx.get());
   return idx;
 }
@@ -405,66 +622,54 @@ std::unique_ptr<Index> Index::FromDump(const void* data, size_t len, const std::
   auto idx = std::make_unique<Index>(info.ngram_size, info.kanji_ngram_size, 0.0, info.cross_boundary_ngrams != 0,
                                      info.normalize_nfkc != 0, std::string(info.normalize_width), info.normalize_lower != 0, device);
   Impl* im = idx->impl_.get();
-  if (mgx_dump_take_columns(dump, &im->cols) != MGX_OK || im->cols == nullptr) return fail(mgx_last_error());
-  mgx_columns_view_get(im->cols, &im->view);
-  const auto& cv = im->view;
   im->finalized = true;
-  if (cv.n_docs == 0) return fail("the dump's table holds no document");
-  mgx_index_desc d{sizeof(mgx_index_desc), MGX_ABI_VERSION, device, 0, cv.first_doc_id, cv.n_docs, cv.n_grams,
-                   cv.offsets,              cv.docids,       cv.tf,  cv.doc_len, 0.0,
-                   cv.tf_overflow_pos,      cv.tf_overflow_val, cv.n_tf_overflow};
-  if (mgx_index_create(&d, &im->dev) != MGX_OK) return fail(mgx_last_error());
-  im->Publish();
-  if (v.has_texts && mgx_index_attach_text(im->dev, v.text_bytes, v.text_off) != MGX_OK) return fail(mgx_last_error());
-  // DocumentStore::GetAllDocIds: the ids the store holds (deleted ids leave gaps in the range)
-  if (v.n_existing != v.n_docs) {
-    std::vector<DocId> existing;
-    im->exists_bits.assign((v.n_docs + 63) / 64, 0);
-    for (uint64_t i = 0; i < v.n_docs; ++i)
-      if (v.exists[i]) {
-        existing.push_back(v.first_doc_id + static_cast<DocId>(i));
-        im->exists_bits[i >> 6] |= 1ull << (i & 63);
-      }
-    im->has_gaps = true;
-    if (mgx_index_add_filter_bitmap(im->dev, existing.data(), existing.size(), &im->exists_bitmap) != MGX_OK ||
-        mgx_index_set_live_bitmap(im->dev, im->exists_bitmap, MGX_LIVE_BITMAPS_CLEAN) != MGX_OK)
-      return fail(mgx_last_error());
+  GenerationSpec spec;
+  spec.device = device;
+  if (mgx_dump_take_columns(dump, &spec.cols) != MGX_OK || spec.cols == nullptr) return fail(mgx_last_error());
+  mgx_columns_view cv{};
+  mgx_columns_view_get(spec.cols, &cv);
+  if (cv.n_docs == 0) {
+    mgx_columns_destroy(spec.cols);
+    return fail("the dump's table holds no document");
   }
-  g_last_finalized.store(idx.get());
+  if (v.has_texts) {
+    spec.text_bytes = v.text_bytes;
+    spec.text_off = v.text_off;
+  }
+  // DocumentStore::GetAllDocIds: the ids the store holds
+  std::vector<DocId> existing;
+  if (v.n_existing != v.n_docs) {
+    for (uint64_t i = 0; i < v.n_docs; ++i)
+      if (v.exists[i]) existing.push_back(v.first_doc_id + static_cast<DocId>(i));
+    spec.existing = &existing;
+  }
+  NamedValues columns;
   for (uint32_t c = 0; c < v.n_filter_columns; ++c) {
     mgx_dump_filter_column fc{};
-    if (mgx_dump_filter_column_get(dump, c, &fc) != MGX_OK) return fail(mgx_last_error());
+    if (mgx_dump_filter_column_get(dump, c, &fc) != MGX_OK) {
+      mgx_columns_destroy(spec.cols);
+      return fail(mgx_last_error());
+    }
     std::vector<storage::FilterValue> vals(v.n_docs);
     for (uint64_t i = 0; i < v.n_docs; ++i) {
       if (fc.is_null[i]) continue;
-      const uint64_t w = fc.values[i];
-      switch (fc.value_type) {
-        case 1: vals[i] = w != 0; break;
-        case 2: vals[i] = static_cast<int8_t>(static_cast<int64_t>(w)); break;
-        case 3: vals[i] = static_cast<uint8_t>(w); break;
-        case 4: vals[i] = static_cast<int16_t>(static_cast<int64_t>(w)); break;
-        case 5: vals[i] = static_cast<uint16_t>(w); break;
-        case 6: vals[i] = static_cast<int32_t>(static_cast<int64_t>(w)); break;
-        case 7: vals[i] = static_cast<uint32_t>(w); break;
-        case 8: vals[i] = static_cast<int64_t>(w); break;
-        case 9: vals[i] = static_cast<uint64_t>(w); break;
-        case 10: vals[i] = storage::TimeValue{static_cast<int64_t>(w)}; break;
-        case 11:
-          vals[i] = std::string(reinterpret_cast<const char*>(fc.string_bytes + fc.string_off[i]),
-                                static_cast<size_t>(fc.string_off[i + 1] - fc.string_off[i]));
-          break;
-        case 12: {
-          double dv;
-          std::memcpy(&dv, &w, 8);
-          vals[i] = dv;
-          break;
-        }
-        default: break;
-      }
+      if (fc.value_type == 11)  // (strings come from the dump's byte pool, not from a dictionary)
+        vals[i] = std::string(reinterpret_cast<const char*>(fc.string_bytes + fc.string_off[i]),
+                              static_cast<size_t>(fc.string_off[i + 1] - fc.string_off[i]));
+      else
+        vals[i] = FilterValueFromBits(fc.value_type, fc.values[i], {});
     }
-    const std::string err = idx->AddFilterColumn(fc.name, vals);
-    if (!err.empty()) return fail(err);
+    columns.emplace_back(fc.name, std::move(vals));
   }
+  spec.columns = &columns;
+  Impl::Generation gen;
+  const std::string err = BuildGeneration(spec, &gen);
+  if (!err.empty()) return fail(err);
+  {
+    std::lock_guard<std::mutex> lock(im->mu);
+    im->Install(std::move(gen));
+  }
+  g_last_finalized.store(idx.get());
   return idx;
 }
 
@@ -496,65 +701,38 @@ std::string EnsureMutable(Index::Impl* im) {
 }
 }  // namespace
 
-bool Index::AddDocument(DocId doc_id, std::string_view text) {
-  std::lock_guard<std::mutex> lock(impl_->mu);
-  if (impl_->finalized) {  // index.cpp:39-74 on a built index: the document joins the delta
-    const std::string err = EnsureMutable(impl_.get());
+namespace {
+// Both forms of AddDocument, in one critical section: the text and its filter values are recorded together or not at all.
+bool AddDocumentLocked(const Index& index, DocId doc_id, std::string_view text, const storage::FilterMap* filters) {
+  Index::Impl* im = index.impl();
+  std::lock_guard<std::mutex> lock(im->mu);
+  if (im->finalized) {  // index.cpp:39-74 on a built index: the document joins the delta
+    const std::string err = EnsureMutable(im);
     if (!err.empty()) {
-      impl_->last_error = "AddDocument: " + err;
+      im->last_error = "AddDocument: " + err;
       return false;
     }
-    if (impl_->LiveInMain(doc_id) || impl_->mut.delta_docs.count(doc_id)) {
-      impl_->last_error = "AddDocument: the document id is live (UpdateDocument changes a document's text)";
+    if (im->LiveInMain(doc_id) || im->mut.delta_docs.count(doc_id)) {
+      im->last_error = "AddDocument: the document id is live (UpdateDocument changes a document's text)";
       return false;
     }
-    impl_->mut.delta_docs[doc_id] = std::string(text);
-    impl_->mut.delta_changed = impl_->mut.dirty = true;
-    return !GenerateHybridNgrams(text, ngram_size_, kanji_ngram_size_, cross_boundary_).empty();
+    im->mut.delta_docs[doc_id] = std::string(text);
+    if (filters) im->mut.delta_filters[doc_id] = *filters;
+    im->mut.Record(/*delta=*/true);
+  } else {
+    im->pending[doc_id] = std::string(text);
+    if (filters) im->pending_filters[doc_id] = *filters;
   }
-  impl_->pending[doc_id] = std::string(text);
-  return !GenerateHybridNgrams(text, ngram_size_, kanji_ngram_size_, cross_boundary_).empty();  // index.cpp:39-74
+  return !GenerateHybridNgrams(text, index.GetNgramSize(), index.GetKanjiNgramSize(), index.GetCrossBoundaryNgrams()).empty();
 }
+}  // namespace
 
+bool Index::AddDocument(DocId doc_id, std::string_view text) { return AddDocumentLocked(*this, doc_id, text, nullptr); }
 bool Index::AddDocument(DocId doc_id, std::string_view text, const storage::FilterMap& filters) {
-  bool was_live = false;
-  {
-    std::lock_guard<std::mutex> lock(impl_->mu);
-    was_live = impl_->finalized && (impl_->LiveInMain(doc_id) || impl_->mut.delta_docs.count(doc_id) != 0);
-  }
-  const bool has_grams = AddDocument(doc_id, text);
-  std::lock_guard<std::mutex> lock(impl_->mu);
-  if (!impl_->finalized) {
-    impl_->pending_filters[doc_id] = filters;
-  } else if (!was_live && impl_->mut.delta_docs.count(doc_id)) {
-    impl_->mut.delta_filters[doc_id] = filters;
-  }
-  return has_grams;
+  return AddDocumentLocked(*this, doc_id, text, &filters);
 }
 
 namespace {
-storage::FilterValue FilterValueFromBits(size_t type, uint64_t w, const std::vector<storage::FilterValue>& dict) {
-  switch (type) {
-    case 1: return w != 0;
-    case 2: return static_cast<int8_t>(static_cast<int64_t>(w));
-    case 3: return static_cast<uint8_t>(w);
-    case 4: return static_cast<int16_t>(static_cast<int64_t>(w));
-    case 5: return static_cast<uint16_t>(w);
-    case 6: return static_cast<int32_t>(static_cast<int64_t>(w));
-    case 7: return static_cast<uint32_t>(w);
-    case 8: return static_cast<int64_t>(w);
-    case 9: return static_cast<uint64_t>(w);
-    case 10: return storage::TimeValue{static_cast<int64_t>(w)};
-    case 11: return w < dict.size() ? dict[w] : storage::FilterValue{};  // strings are stored as dictionary ranks
-    case 12: {
-      double d;
-      std::memcpy(&d, &w, 8);
-      return d;
-    }
-    default: return storage::FilterValue{};
-  }
-}
-
 // RemoveDocument's bookkeeping (index.cpp:148-197: every distinct n-gram of the text loses the posting). im->mu held.
 void RemoveLocked(const Index& index, Index::Impl* im, DocId doc_id, std::string_view text) {
   Index::Impl::Mutable& m = im->mut;
@@ -562,7 +740,7 @@ void RemoveLocked(const Index& index, Index::Impl* im, DocId doc_id, std::string
   if (it != m.delta_docs.end()) {
     m.delta_docs.erase(it);
     m.delta_filters.erase(doc_id);
-    m.delta_changed = m.dirty = true;
+    m.Record(/*delta=*/true);
     return;
   }
   if (!im->LiveInMain(doc_id)) return;  // not a document of the table
@@ -584,7 +762,7 @@ void RemoveLocked(const Index& index, Index::Impl* im, DocId doc_id, std::string
     m.main_len -= dl;
   }
   m.removed += 1;
-  m.dirty = true;
+  m.Record(/*delta=*/false);
 }
 }  // namespace
 
@@ -630,7 +808,7 @@ void Index::UpdateDocument(DocId doc_id, std::string_view old_text, std::string_
   RemoveLocked(*this, im, doc_id, old_text);
   im->mut.delta_docs[doc_id] = std::string(new_text);
   if (!keep.empty()) im->mut.delta_filters[doc_id] = std::move(keep);
-  im->mut.delta_changed = im->mut.dirty = true;
+  im->mut.Record(/*delta=*/true);
 }
 
 void Index::UpdateDocument(DocId doc_id, std::string_view old_text, std::string_view new_text,
@@ -646,7 +824,7 @@ void Index::UpdateDocument(DocId doc_id, std::string_view old_text, std::string_
   RemoveLocked(*this, im, doc_id, old_text);
   im->mut.delta_docs[doc_id] = std::string(new_text);
   im->mut.delta_filters[doc_id] = filters;
-  im->mut.delta_changed = im->mut.dirty = true;
+  im->mut.Record(/*delta=*/true);
 }
 
 bool Index::UpdateFilters(DocId doc_id, const storage::FilterMap& filters) {
@@ -660,7 +838,7 @@ bool Index::UpdateFilters(DocId doc_id, const storage::FilterMap& filters) {
   }
   if (im->mut.delta_docs.count(doc_id)) {
     im->mut.delta_filters[doc_id] = filters;
-    im->mut.delta_changed = im->mut.dirty = true;
+    im->mut.Record(/*delta=*/true);
     return true;
   }
   if (!im->LiveInMain(doc_id)) {
@@ -680,7 +858,7 @@ bool Index::UpdateFilters(DocId doc_id, const storage::FilterMap& filters) {
   RemoveLocked(*this, im, doc_id, text);
   im->mut.delta_docs[doc_id] = std::move(text);
   im->mut.delta_filters[doc_id] = filters;
-  im->mut.delta_changed = im->mut.dirty = true;
+  im->mut.Record(/*delta=*/true);
   return true;
 }
 
@@ -698,59 +876,42 @@ Index::MutationStats Index::GetMutationStats() const {
 // The recorded changes reach the device: live row, delta index, table-wide statistics. The caller guarantees that no
 // batch of this Index is being planned, compiled or run by another thread (header note).
 namespace {
-// What one application works from: everything recorded up to one moment, taken under the index lock.
-struct MutationSnapshot {
-  std::vector<DocId> clear, dead_docs;
-  std::vector<uint32_t> dead_grams;
-  bool delta_changed = false;
-  std::map<DocId, std::string> docs;  // (copies, only when the delta changed)
-  std::map<DocId, storage::FilterMap> filters;
-  std::vector<std::string> column_names;
-  uint64_t main_docs = 0, main_len = 0;
-};
-struct BuiltDelta {
-  bool rebuilt = false;
-  std::shared_ptr<Index> delta;  // nullptr with rebuilt: the delta is empty now
-  std::shared_ptr<const std::vector<DocId>> ids;
-  std::string error;
-};
+using Snapshot = Index::Impl::Snapshot;
+using BuiltDelta = Index::Impl::BuiltDelta;
 
-MutationSnapshot TakeSnapshot(Index::Impl* im) {  // im->mu held
-  Index::Impl::Mutable& m = im->mut;
-  MutationSnapshot snap;
-  snap.clear.swap(m.pending_clear);
-  snap.dead_docs.swap(m.pending_dead_docs);
-  snap.dead_grams.swap(m.pending_dead_grams);
-  snap.delta_changed = m.delta_changed;
-  if (m.delta_changed) {
-    snap.docs = m.delta_docs;
-    snap.filters = m.delta_filters;
-  }
+Snapshot TakeSnapshot(const Index::Impl::Mutable& m) {  // im->mu held
+  Snapshot snap;
+  snap.recorded = m.recorded;
+  snap.n_clear = m.pending_clear.size();
+  snap.n_dead = m.pending_dead_grams.size();
+  snap.delta_changed = m.delta_recorded > m.applied;
   snap.main_docs = m.main_docs;
   snap.main_len = m.main_len;
-  {
-    std::lock_guard<std::mutex> fl(im->filter_mu);
-    for (const auto& c : im->filter_columns) snap.column_names.push_back(c.name);
-  }
-  m.delta_changed = false;
-  m.dirty = false;
   return snap;
 }
 
-// The delta index of a snapshot: column build, device index, doc map, filter columns. Touches nothing of `self` that changes
+std::vector<std::string> ColumnNames(const Index::Impl* im) {
+  std::lock_guard<std::mutex> fl(im->filter_mu);
+  std::vector<std::string> names;
+  for (const auto& c : im->filter_columns) names.push_back(c.name);
+  return names;
+}
+
+// The delta index over `docs`: column build, device index, doc map, filter columns. Touches nothing of `self` that changes
 // (its configuration only), so it runs with or without the index lock — in a builder thread when changes may wait.
-BuiltDelta BuildDelta(const Index& self, const MutationSnapshot& snap) {
+BuiltDelta BuildDelta(const Index& self, const std::map<DocId, std::string>& docs,
+                      const std::map<DocId, storage::FilterMap>& filters, std::vector<std::string> column_names) {
   BuiltDelta out;
-  if (!snap.delta_changed) return out;
   out.rebuilt = true;
-  if (snap.docs.empty()) return out;
+  if (docs.empty()) return out;
   Index::Impl* im = self.impl();
   auto nd = std::make_shared<Index>(self.GetNgramSize(), im->query_kanji, im->dense_threshold, self.GetCrossBoundaryNgrams(),
                                     self.GetNormalizeNfkc(), self.GetNormalizeWidth(), self.GetNormalizeLower(), im->device);
+  nd->impl()->internal = true;
   std::vector<DocId> ids;
-  ids.reserve(snap.docs.size());
+  ids.reserve(docs.size());
   DocId local = 1;
-  for (const auto& kv : snap.docs) {  // (ascending table id -> ascending local id: rank order and ties are kept)
+  for (const auto& kv : docs) {  // (ascending table id -> ascending local id: rank order and ties are kept)
     nd->AddDocument(local++, kv.second);
     ids.push_back(kv.first);
   }
@@ -763,23 +924,12 @@ BuiltDelta BuildDelta(const Index& self, const MutationSnapshot& snap) {
     out.error = mgx_last_error();
     return out;
   }
-  std::vector<std::string> names = snap.column_names;
-  for (const auto& kv : snap.filters)
-    for (const auto& f : kv.second)
-      if (std::find(names.begin(), names.end(), f.first) == names.end()) names.push_back(f.first);
-  for (const auto& name : names) {
-    std::vector<storage::FilterValue> values(ids.size());
-    for (size_t i = 0; i < ids.size(); ++i) {
-      const auto fm = snap.filters.find(ids[i]);
-      if (fm == snap.filters.end()) continue;
-      const auto fv = fm->second.find(name);
-      if (fv != fm->second.end()) values[i] = fv->second;
-    }
-    const std::string ferr = nd->AddFilterColumn(name, values);
-    if (!ferr.empty()) {
-      out.error = ferr;
-      return out;
-    }
+  const NamedValues columns = ValuesByName(filters, std::move(column_names), ids.size(), [&](DocId doc) {
+    return static_cast<uint64_t>(std::lower_bound(ids.begin(), ids.end(), doc) - ids.begin());  // (every key is a delta document)
+  });
+  for (const auto& c : columns) {
+    out.error = nd->AddFilterColumn(c.first, c.second);
+    if (!out.error.empty()) return out;
   }
   nd->impl()->fallback = im;
   out.delta = std::move(nd);
@@ -787,19 +937,30 @@ BuiltDelta BuildDelta(const Index& self, const MutationSnapshot& snap) {
   return out;
 }
 
-// A snapshot and its delta reach the device: cleaned bitmaps, live row, the delta's handles, table-wide statistics. im->mu
-// held; no batch of this Index is planned, compiled or in flight (the callers' contract).
-std::string InstallMutations(Index::Impl* im, MutationSnapshot& snap, BuiltDelta& built) {
-  Index::Impl::Mutable& m = im->mut;
-  static const bool kTrace = std::getenv("MGX_TRACE_HOST") != nullptr;
-  auto t_prev = std::chrono::steady_clock::now();
-  m.last_apply = t_prev;
-  auto lap = [&](const char* what) {
+struct Laps {  // MGX_TRACE_HOST: what each part of an application took
+  std::chrono::steady_clock::time_point t_prev = std::chrono::steady_clock::now();
+  void operator()(const char* what) {
+    static const bool kTrace = std::getenv("MGX_TRACE_HOST") != nullptr;
     if (!kTrace) return;
     const auto t = std::chrono::steady_clock::now();
     fprintf(stderr, "[shim] ApplyMutations %s: %.2f ms\n", what, std::chrono::duration<double, std::milli>(t - t_prev).count());
     t_prev = t;
-  };
+  }
+};
+
+void ClearLive(std::vector<uint64_t>* live, DocId first, const std::vector<DocId>& docs, size_t n) {
+  for (size_t i = 0; i < n; ++i) {
+    const uint64_t slot = docs[i] - first;
+    (*live)[slot >> 6] &= ~(1ull << (slot & 63));
+  }
+}
+
+// Every device call of an application, and nothing else: the host's picture of the table changes in CommitMutations, which
+// runs only after this returned "". What the calls do to a device that has seen part of them already is nothing (they
+// clear bits that are cleared), so after a failure the same snapshot, or a later one, is simply installed again.
+// im->mu held; no batch of this Index is planned, compiled or in flight (the callers' contract).
+std::string InstallMutations(Index::Impl* im, const Snapshot& snap, const BuiltDelta& built, Laps& lap) {
+  Index::Impl::Mutable& m = im->mut;
   auto fail = [&](const std::string& msg) {
     im->last_error = "ApplyMutations: " + msg;
     return im->last_error;
@@ -808,37 +969,51 @@ std::string InstallMutations(Index::Impl* im, MutationSnapshot& snap, BuiltDelta
   if (mgx_index_synchronize(im->dev) != MGX_OK) return fail(mgx_last_error());
   // ---- the dead documents' postings leave the bitmap form of their dense grams (a query over bitmap-form grams then
   // needs no live-row operand), then their live bits go --------------------------------------------------------------
-  if (!snap.dead_grams.empty() &&
-      mgx_index_clear_postings(im->dev, snap.dead_docs.data(), snap.dead_grams.data(), snap.dead_grams.size()) != MGX_OK)
+  if (snap.n_dead > 0 &&
+      mgx_index_clear_postings(im->dev, m.pending_dead_docs.data(), m.pending_dead_grams.data(), snap.n_dead) != MGX_OK)
     return fail(mgx_last_error());
-  for (DocId d : snap.clear) {
-    const uint64_t slot = d - im->view.first_doc_id;
-    m.applied_live[slot >> 6] &= ~(1ull << (slot & 63));
-  }
   // ---- the live row of the main index ---------------------------------------------------------------------------------
   if (!m.have_live) {
+    std::vector<uint64_t> bits = m.applied_live;
+    ClearLive(&bits, im->view.first_doc_id, m.pending_clear, snap.n_clear);
     std::vector<DocId> live;
     live.reserve(im->view.n_docs);
     for (uint64_t slot = 0; slot < im->view.n_docs; ++slot)
-      if ((m.applied_live[slot >> 6] >> (slot & 63)) & 1) live.push_back(im->view.first_doc_id + static_cast<DocId>(slot));
+      if ((bits[slot >> 6] >> (slot & 63)) & 1) live.push_back(im->view.first_doc_id + static_cast<DocId>(slot));
     if (mgx_index_add_filter_bitmap(im->dev, live.data(), live.size(), &m.live_bitmap) != MGX_OK) return fail(mgx_last_error());
-    if (mgx_index_set_live_bitmap(im->dev, m.live_bitmap, MGX_LIVE_BITMAPS_CLEAN) != MGX_OK) return fail(mgx_last_error());
-    m.have_live = true;
-    im->has_gaps = false;  // (the live row is also the NOT universe: ids never added are not in it)
-  } else if (!snap.clear.empty()) {
-    if (mgx_index_update_filter_bitmap(im->dev, m.live_bitmap, nullptr, 0, snap.clear.data(), snap.clear.size()) != MGX_OK)
+    m.have_live = true;  // (a fact about the device, not about the table: a retry updates this row, it makes no second one)
+  } else if (snap.n_clear > 0) {
+    if (mgx_index_update_filter_bitmap(im->dev, m.live_bitmap, nullptr, 0, m.pending_clear.data(), snap.n_clear) != MGX_OK)
       return fail(mgx_last_error());
   }
+  if (mgx_index_set_live_bitmap(im->dev, m.live_bitmap, MGX_LIVE_BITMAPS_CLEAN) != MGX_OK) return fail(mgx_last_error());
   lap("sync + live row + cleaned bitmaps");
+  // ---- the statistics tables of both indexes go: the next batch computes them from what the commit publishes -------------
+  const Index* delta = built.rebuilt ? built.delta.get() : m.delta.get();
+  if (delta && mgx_index_invalidate_statistics(delta->impl()->dev) != MGX_OK) return fail(mgx_last_error());
+  if (mgx_index_invalidate_statistics(im->dev) != MGX_OK) return fail(mgx_last_error());
+  return "";
+}
+
+// The one place recorded changes are marked applied: the covered prefix of the pending lists goes (what a writer appended
+// behind it while a background build ran stays), the delta's handles and the table-wide statistics of both indexes are
+// published. Host work only, nothing here fails. im->mu held, InstallMutations(snap, built) returned "".
+void CommitMutations(Index::Impl* im, const Snapshot& snap, BuiltDelta&& built, Laps& lap) {
+  Index::Impl::Mutable& m = im->mut;
+  ClearLive(&m.applied_live, im->view.first_doc_id, m.pending_clear, snap.n_clear);
+  im->has_gaps = false;  // (the live row is also the NOT universe: ids never added are not in it)
   // ---- posting sizes: the main index's live postings, then the delta's on top -------------------------------------------
   for (const auto& c : m.delta_contrib) im->global_sizes[c.first] -= c.second;
   m.delta_contrib.clear();
-  for (uint32_t gid : snap.dead_grams)
-    if (im->global_sizes[gid] > 0) im->global_sizes[gid] -= 1;
+  for (size_t i = 0; i < snap.n_dead; ++i)
+    if (im->global_sizes[m.pending_dead_grams[i]] > 0) im->global_sizes[m.pending_dead_grams[i]] -= 1;
+  m.pending_clear.erase(m.pending_clear.begin(), m.pending_clear.begin() + static_cast<std::ptrdiff_t>(snap.n_clear));
+  m.pending_dead_docs.erase(m.pending_dead_docs.begin(), m.pending_dead_docs.begin() + static_cast<std::ptrdiff_t>(snap.n_dead));
+  m.pending_dead_grams.erase(m.pending_dead_grams.begin(), m.pending_dead_grams.begin() + static_cast<std::ptrdiff_t>(snap.n_dead));
   // ---- the delta index ------------------------------------------------------------------------------------------------
   if (built.rebuilt) {
-    m.delta = built.delta;
-    m.delta_ids = built.ids;
+    m.delta = std::move(built.delta);
+    m.delta_ids = std::move(built.ids);
   }
   lap("delta index handles");
   // ---- table-wide statistics in both ------------------------------------------------------------------------------------
@@ -871,12 +1046,71 @@ std::string InstallMutations(Index::Impl* im, MutationSnapshot& snap, BuiltDelta
     dm->global_sizes = std::move(delta_sizes);
     dm->global_docs = im->global_docs;
     dm->global_avgdl = im->global_avgdl;
-    if (mgx_index_invalidate_statistics(dm->dev) != MGX_OK) return fail(mgx_last_error());
   }
-  if (mgx_index_invalidate_statistics(im->dev) != MGX_OK) return fail(mgx_last_error());
   lap("statistics");
+  m.applied = snap.recorded;
+  m.retry = false;
   m.epoch += 1;
-  return "";
+  m.last_apply = std::chrono::steady_clock::now();
+}
+
+// What an entry point would do about the recorded changes now (im->mu held): nothing; kick a background build of them
+// (nothing changes on the device yet); or install — something changes on the device in this call, so nothing of the
+// caller may be being planned or compiled meanwhile. With no staleness bound, the first time, when forced and after a
+// failed application, everything recorded so far is applied by the call itself.
+enum class MutationStep { kNothing, kKick, kInstall };
+MutationStep NextMutationStep(const Index::Impl::Mutable& m, bool force) {
+  const bool immediate = force || m.retry || m.staleness.count() == 0 || m.epoch == 0;
+  if (m.build.valid()) {  // a build is under way: its result is installed once it is there (a forced call waits for it)
+    const bool ready = m.build.wait_for(std::chrono::seconds(0)) == std::future_status::ready;
+    return immediate || ready ? MutationStep::kInstall : MutationStep::kNothing;
+  }
+  if (m.recorded == m.applied) return MutationStep::kNothing;
+  if (immediate) return MutationStep::kInstall;
+  return std::chrono::steady_clock::now() - m.last_apply >= m.staleness ? MutationStep::kKick : MutationStep::kNothing;
+}
+
+// With no staleness bound (and always the first time): snapshot, build, install, commit — in this call, under the lock (a
+// writer thread recording a change meanwhile waits, and is not marked applied). With a bound: the snapshot's delta is
+// built by a thread while queries keep running on the old state, and installed by the first entry point that finds it
+// ready — the stall a steady writer causes is the few milliseconds of the installation, not the delta build. im->mu held.
+std::string ApplyLocked(const Index& self, bool force) {
+  Index::Impl* im = self.impl();
+  Index::Impl::Mutable& m = im->mut;
+  for (;;) {
+    switch (NextMutationStep(m, force)) {
+      case MutationStep::kNothing: return "";
+      case MutationStep::kKick: {
+        m.build_snapshot = TakeSnapshot(m);
+        const bool changed = m.build_snapshot.delta_changed;  // (false: removals only, nothing to copy or build)
+        m.build = std::async(std::launch::async, [&self, changed, docs = changed ? m.delta_docs : decltype(m.delta_docs)(),
+                                                  filters = changed ? m.delta_filters : decltype(m.delta_filters)(),
+                                                  names = ColumnNames(im)] {
+          pthread_setname_np(pthread_self(), "mgx-delta");
+          return changed ? BuildDelta(self, docs, filters, names) : BuiltDelta{};
+        });
+        return "";
+      }
+      case MutationStep::kInstall: {
+        Snapshot snap;
+        BuiltDelta built;
+        if (m.build.valid()) {
+          snap = m.build_snapshot;
+          built = m.build.get();
+        } else {
+          snap = TakeSnapshot(m);
+          if (snap.delta_changed) built = BuildDelta(self, m.delta_docs, m.delta_filters, ColumnNames(im));
+        }
+        Laps lap;
+        const std::string err = InstallMutations(im, snap, built, lap);
+        if (!err.empty()) {
+          m.retry = true;
+          return err;
+        }
+        CommitMutations(im, snap, std::move(built), lap);
+      }
+    }
+  }
 }
 }  // namespace
 
@@ -885,72 +1119,28 @@ void Index::SetMutationStaleness(std::chrono::microseconds max_staleness) {
   impl_->mut.staleness = max_staleness;
 }
 
-// With no staleness bound (and always the first time): snapshot, build, install — in this call, under the lock. With a
-// bound: the snapshot's delta is built by a thread while queries keep running on the old state, and installed by the first
-// entry point that finds it ready — the stall a steady writer causes is the few milliseconds of the installation, not the
-// delta build.
 std::string Index::ApplyMutations(bool force) const {
-  Impl* im = impl_.get();
-  std::unique_lock<std::mutex> lock(im->mu);
-  Impl::Mutable& m = im->mut;
-  if (m.staleness.count() == 0) force = true;  // (no bound: every change recorded before this call is applied by it)
-  auto install_background = [&]() -> std::string {
-    if (m.builder.joinable()) {
-      lock.unlock();  // (the builder takes the lock to publish its result)
-      m.builder.join();
-      lock.lock();
-    }
-    auto snap = std::static_pointer_cast<MutationSnapshot>(m.bg_snapshot);
-    auto built = std::static_pointer_cast<BuiltDelta>(m.bg_built);
-    m.bg_snapshot.reset();
-    m.bg_built.reset();
-    m.build_running = m.build_ready = false;
-    return snap && built ? InstallMutations(im, *snap, *built) : std::string();
-  };
-  if (m.build_running && (m.build_ready || force)) {
-    const std::string e = install_background();
-    if (!e.empty()) return e;
-  }
-  if (m.build_running) return "";  // (a build is under way: its result is installed by a later call)
-  if (!m.dirty) return "";
-  const auto now = std::chrono::steady_clock::now();
-  const bool background = !force && m.staleness.count() > 0 && m.epoch > 0;
-  if (background && now - m.last_apply < m.staleness) return "";
-  if (background) {
-    auto snap = std::make_shared<MutationSnapshot>(TakeSnapshot(im));
-    m.bg_snapshot = snap;
-    m.build_running = true;
-    m.build_ready = false;
-    const Index* self = this;
-    m.builder = std::thread([self, im, snap] {
-      pthread_setname_np(pthread_self(), "mgx-delta");
-      auto built = std::make_shared<BuiltDelta>(BuildDelta(*self, *snap));
-      std::lock_guard<std::mutex> l(im->mu);
-      im->mut.bg_built = built;
-      im->mut.build_ready = true;
-    });
-    return "";
-  }
-  MutationSnapshot snap = TakeSnapshot(im);
-  // (the lock stays held through the build: a writer thread recording a change meanwhile waits, and is not marked applied)
-  BuiltDelta built = BuildDelta(*this, snap);
-  return InstallMutations(im, snap, built);
+  std::lock_guard<std::mutex> lock(impl_->mu);
+  return ApplyLocked(*this, force);
 }
 
 // The main index rebuilt from the table's current documents: live documents of the old main index (their texts come back
-// from the device, where BM25 keeps them) + the delta's. Same quiescence contract as ApplyMutations. Batch objects an
-// executor compiled on the old device index stay valid until that executor lets go of them (Impl::Handles).
+// from the device, where BM25 keeps them) + the delta's. The index lock is held from the forced application to the swap:
+// the new generation, filter columns included, is built off to the side and published in one step, so a writer or another
+// thread's ApplyMutations sees the table before or after the compaction, and a failure leaves it as it was, still serving.
+// Batch objects an executor compiled on the old device index stay valid until that executor lets go of them
+// (Impl::Handles).
 std::string Index::Compact() const {
   Finalize();
   FlushPendingFilterColumns();
-  {
-    const std::string e = ApplyMutations(/*force=*/true);
-    if (!e.empty()) return e;
-  }
   Impl* im = impl_.get();
-  std::unique_lock<std::mutex> lock(im->mu);
+  std::lock_guard<std::mutex> lock(im->mu);
   Impl::Mutable& m = im->mut;
   if (!m.active) return "";  // the table never changed
+  {
+    const std::string e = ApplyLocked(*this, /*force=*/true);
+    if (!e.empty()) return e;
+  }
   auto fail = [&](const std::string& msg) {
     im->last_error = "Compact: " + msg;
     return im->last_error;
@@ -971,25 +1161,19 @@ std::string Index::Compact() const {
   std::vector<uint8_t> bytes;
   bytes.reserve(total + 1024);
   std::vector<uint64_t> off(n2 + 1, 0);
-  std::vector<uint64_t> exists((n2 + 63) / 64, 0);
   std::vector<DocId> existing;
   {
     auto dit = m.delta_docs.begin();
     for (uint64_t i = 0; i < n2; ++i) {
       const DocId doc = first + static_cast<DocId>(i);
       while (dit != m.delta_docs.end() && dit->first < doc) ++dit;
-      bool here = false;
       if (dit != m.delta_docs.end() && dit->first == doc) {
         bytes.insert(bytes.end(), dit->second.begin(), dit->second.end());
-        here = true;
+        existing.push_back(doc);
       } else if (im->LiveInMain(doc)) {
         const uint64_t slot = doc - old_first;
         bytes.insert(bytes.end(), old_bytes.begin() + static_cast<std::ptrdiff_t>(old_off[slot]),
                      old_bytes.begin() + static_cast<std::ptrdiff_t>(old_off[slot + 1]));
-        here = true;
-      }
-      if (here) {
-        exists[i >> 6] |= 1ull << (i & 63);
         existing.push_back(doc);
       }
       off[i + 1] = bytes.size();
@@ -997,138 +1181,50 @@ std::string Index::Compact() const {
   }
   bytes.resize(bytes.size() + 16);
   std::vector<uint8_t>().swap(old_bytes);
-  // ---- the old generation's filter columns, by doc slot ----------------------------------------------------------------
-  struct OldColumn {
-    Impl::FilterColumn meta;
-    std::vector<uint64_t> values;
-    std::vector<uint8_t> nul;
-  };
-  std::vector<OldColumn> old_cols;
+  // ---- filter columns of the new generation: a document of the delta has the values recorded with it, a live document of
+  // the old main index keeps its value (the old generation's columns, by doc slot) ------------------------------------------
+  std::vector<Impl::FilterColumn> old_cols;
   {
     std::lock_guard<std::mutex> fl(im->filter_mu);
-    for (const auto& c : im->filter_columns) {
-      OldColumn oc;
-      oc.meta = c;
-      oc.values.resize(n_old);
-      oc.nul.resize(n_old);
-      if (mgx_index_filter_column_export(im->dev, c.device_id, oc.values.data(), oc.nul.data(), nullptr) != MGX_OK)
-        return fail(mgx_last_error());
-      old_cols.push_back(std::move(oc));
+    old_cols = im->filter_columns;
+  }
+  std::vector<std::string> names;
+  for (const auto& c : old_cols) names.push_back(c.name);
+  NamedValues columns = ValuesByName(m.delta_filters, std::move(names), n2, [&](DocId doc) { return static_cast<uint64_t>(doc - first); });
+  std::vector<uint64_t> old_values(n_old);
+  std::vector<uint8_t> old_nul(n_old);
+  for (size_t c = 0; c < old_cols.size(); ++c) {  // (columns[c] is old_cols[c]'s: the old names come first)
+    const Impl::FilterColumn& oc = old_cols[c];
+    if (oc.type == 0) continue;
+    if (mgx_index_filter_column_export(im->dev, oc.device_id, old_values.data(), old_nul.data(), nullptr) != MGX_OK)
+      return fail(mgx_last_error());
+    for (uint64_t slot = 0; slot < n_old; ++slot) {
+      if (!((m.main_live[slot >> 6] >> (slot & 63)) & 1) || old_nul[slot]) continue;
+      columns[c].second[static_cast<uint64_t>(old_first - first) + slot] = FilterValueFromBits(oc.type, old_values[slot], oc.dict);
     }
   }
   // ---- the new generation ----------------------------------------------------------------------------------------------
-  mgx_build_params bp{sizeof(mgx_build_params), MGX_ABI_VERSION, ngram_size_, kanji_ngram_size_, cross_boundary_ ? 1 : 0, 0};
-  mgx_columns* cols2 = nullptr;
-  if (mgx_columns_build(&bp, bytes.data(), off.data(), first, n2, &cols2) != MGX_OK) return fail(mgx_last_error());
-  mgx_columns_view view2{};
-  mgx_columns_view_get(cols2, &view2);
-  mgx_index_desc d{sizeof(mgx_index_desc), MGX_ABI_VERSION, im->device, 0, view2.first_doc_id, view2.n_docs, view2.n_grams,
-                   view2.offsets,            view2.docids,    view2.tf,   view2.doc_len, im->dense_threshold,
-                   view2.tf_overflow_pos,    view2.tf_overflow_val, view2.n_tf_overflow};
-  mgx_index* dev2 = nullptr;
-  if (mgx_index_create(&d, &dev2) != MGX_OK) {
-    mgx_columns_destroy(cols2);
-    return fail(mgx_last_error());
-  }
-  auto gen = std::make_shared<Impl::Handles>();
-  gen->cols = cols2;
-  gen->dev = dev2;
-  gen->owns = true;
-  if (mgx_index_attach_text(dev2, bytes.data(), off.data()) != MGX_OK) return fail(mgx_last_error());
-  const bool gaps = existing.size() != n2;
-  uint32_t exists_bitmap = 0;
-  if (gaps && (mgx_index_add_filter_bitmap(dev2, existing.data(), existing.size(), &exists_bitmap) != MGX_OK ||
-               mgx_index_set_live_bitmap(dev2, exists_bitmap, MGX_LIVE_BITMAPS_CLEAN) != MGX_OK))
-    return fail(mgx_last_error());
-  // what the re-added filter columns need of the old state
-  const std::vector<uint64_t> old_live = m.main_live;
-  const std::map<DocId, storage::FilterMap> delta_filters = m.delta_filters;
-  std::vector<DocId> delta_ids;
-  for (const auto& kv : m.delta_docs) delta_ids.push_back(kv.first);
+  GenerationSpec spec{im->device, im->dense_threshold, ngram_size_, kanji_ngram_size_, cross_boundary_, nullptr,
+                      bytes.data(), off.data(),    first,       n2};
+  if (existing.size() != n2) spec.existing = &existing;
+  spec.columns = &columns;
+  Impl::Generation gen;
+  const std::string err = BuildGeneration(spec, &gen);
+  if (!err.empty()) return fail(err);
   // ---- swap ----------------------------------------------------------------------------------------------------------------
   const std::shared_ptr<Impl::Handles> old_gen = im->handles;  // (let go at the end of this call, or by the last executor slot)
-  im->handles = gen;
-  im->cols = cols2;
-  im->dev = dev2;
-  im->view = view2;
-  im->owns_handles = true;
-  im->has_gaps = gaps;
-  im->exists_bitmap = exists_bitmap;
-  im->exists_bits = gaps ? exists : std::vector<uint64_t>();
+  im->Install(std::move(gen));
   im->global_sizes.clear();
   im->absent_grams.clear();
   im->global_docs = 0;
   im->global_avgdl = 0.0;
   const uint64_t epoch = m.epoch + 1;
   const auto staleness = m.staleness;
-  m = Impl::Mutable{};
+  m = Impl::Mutable{};  // (no build is in flight: the forced application above took it)
   m.epoch = epoch;
   m.staleness = staleness;
-  {
-    std::lock_guard<std::mutex> fl(im->filter_mu);
-    im->filter_columns.clear();
-    im->condition_cache.clear();
-    im->have_empty_bitmap = false;
-  }
-  lock.unlock();
-  // ---- filter columns of the new generation: a live document of the old main index keeps its value, a document of the delta
-  // has the values recorded with it ----------------------------------------------------------------------------------------------
-  std::vector<std::string> names;
-  for (const auto& oc : old_cols) names.push_back(oc.meta.name);
-  for (const auto& kv : delta_filters)
-    for (const auto& f : kv.second)
-      if (std::find(names.begin(), names.end(), f.first) == names.end()) names.push_back(f.first);
-  for (const auto& name : names) {
-    std::vector<storage::FilterValue> values(n2);
-    const OldColumn* oc = nullptr;
-    for (const auto& c : old_cols)
-      if (c.meta.name == name) oc = &c;
-    if (oc != nullptr && oc->meta.type != 0) {
-      for (uint64_t slot = 0; slot < n_old; ++slot) {
-        if (!((old_live[slot >> 6] >> (slot & 63)) & 1) || oc->nul[slot]) continue;
-        values[static_cast<uint64_t>(old_first - first) + slot] = FilterValueFromBits(oc->meta.type, oc->values[slot], oc->meta.dict);
-      }
-    }
-    for (DocId doc : delta_ids) {
-      storage::FilterValue v;
-      const auto fm = delta_filters.find(doc);
-      if (fm != delta_filters.end()) {
-        const auto fv = fm->second.find(name);
-        if (fv != fm->second.end()) v = fv->second;
-      }
-      values[doc - first] = std::move(v);
-    }
-    const std::string ferr = AddFilterColumn(name, values);
-    if (!ferr.empty()) return "Compact: " + ferr;
-  }
   return "";
 }
-
-namespace {
-// widened device value of a non-NULL FilterValue (strings: their dictionary rank, filled in by the caller)
-uint64_t WidenFilterValue(const storage::FilterValue& v) {
-  return std::visit(
-      [](const auto& val) -> uint64_t {
-        using T = std::decay_t<decltype(val)>;
-        if constexpr (std::is_same_v<T, std::monostate> || std::is_same_v<T, std::string>) return 0;
-        else if constexpr (std::is_same_v<T, storage::TimeValue>) return static_cast<uint64_t>(val.seconds);
-        else if constexpr (std::is_same_v<T, double>) {
-          uint64_t u;
-          std::memcpy(&u, &val, 8);
-          return u;
-        } else if constexpr (std::is_signed_v<T> || std::is_same_v<T, bool>) return static_cast<uint64_t>(static_cast<int64_t>(val));
-        else return static_cast<uint64_t>(val);
-      },
-      v);
-}
-uint32_t FilterClassOf(size_t type) {  // MGX_FC_* of a FilterValue alternative
-  switch (type) {
-    case 12: return MGX_FC_DOUBLE;
-    case 3: case 5: case 7: case 9: case 11: return MGX_FC_UNSIGNED;
-    default: return MGX_FC_SIGNED;  // bool, int8/16/32/64, TimeValue
-  }
-}
-}  // namespace
 
 uint64_t Index::DeviceMemoryBytes() const {
   uint64_t n = 0;
@@ -1139,38 +1235,12 @@ uint64_t Index::DeviceMemoryBytes() const {
 std::string Index::AddFilterColumn(const std::string& name, const std::vector<storage::FilterValue>& values) const {
   Finalize();
   Impl* im = impl_.get();
+  std::lock_guard<std::mutex> lock(im->mu);  // (then filter_mu: the order UpdateDocument and Compact use)
   if (!im->dev) return im->last_error.empty() ? "AddFilterColumn: no device index" : im->last_error;
-  if (values.size() != im->view.n_docs) return "AddFilterColumn: one value per doc slot of the index";
   Impl::FilterColumn col;
-  col.name = name;
-  for (const auto& v : values) {
-    if (v.index() == 0) continue;
-    if (col.type == 0) col.type = v.index();
-    if (v.index() != col.type) return "AddFilterColumn: the values of one column must hold one type";
-  }
-  std::vector<storage::FilterValue> nn;
-  for (const auto& v : values)
-    if (v.index() != 0) nn.push_back(v);
-  std::sort(nn.begin(), nn.end());
-  nn.erase(std::unique(nn.begin(), nn.end()), nn.end());
-  col.dict = std::move(nn);
-  const size_t n = values.size();
-  std::vector<uint64_t> wide(n, 0);
-  std::vector<uint8_t> nul(n, 0);
-  std::vector<uint32_t> ids(n, 0xFFFFFFFFu);
-  for (size_t i = 0; i < n; ++i) {
-    if (values[i].index() == 0) {
-      nul[i] = 1;
-      continue;
-    }
-    const auto it = std::lower_bound(col.dict.begin(), col.dict.end(), values[i]);
-    ids[i] = static_cast<uint32_t>(it - col.dict.begin());
-    wide[i] = col.type == 11 ? ids[i] : WidenFilterValue(values[i]);  // strings compare by their bytewise rank
-  }
-  mgx_filter_column_desc d{sizeof(mgx_filter_column_desc), MGX_ABI_VERSION, FilterClassOf(col.type),
-                           static_cast<uint32_t>(col.dict.size()), wide.data(), nul.data(), ids.data()};
-  if (mgx_index_add_filter_column(im->dev, &d, &col.device_id) != MGX_OK) return mgx_last_error();
-  std::lock_guard<std::mutex> lock(im->filter_mu);
+  const std::string err = BuildFilterColumn(im->dev, im->view.n_docs, name, values, &col);
+  if (!err.empty()) return err;
+  std::lock_guard<std::mutex> fl(im->filter_mu);
   for (auto& c : im->filter_columns)
     if (c.name == name) {
       c = std::move(col);  // (replaced: cached conditions of the old column are dropped)
@@ -1186,101 +1256,58 @@ void Index::AddDocumentBatch(const std::vector<DocumentItem>& documents) {
 }
 
 std::string Index::Finalize() const {
-  tl_last_index = this;  // (every search / scoring entry point passes through here)
+  if (!impl_->internal) tl_last_index = this;  // (every search / scoring entry point passes through here)
   std::lock_guard<std::mutex> lock(impl_->mu);
   if (impl_->finalized) return impl_->last_error;
   impl_->finalized = true;
-  g_last_finalized.store(this);
+  if (!impl_->internal) g_last_finalized.store(this);
   // dense id range [first, last]; ids never added are documents without text
   const DocId first = impl_->pending.empty() ? 1 : impl_->pending.begin()->first;
   const DocId last = impl_->pending.empty() ? 1 : impl_->pending.rbegin()->first;
   const uint64_t n = static_cast<uint64_t>(last) - first + 1;
   std::vector<uint8_t> bytes;
   std::vector<uint64_t> off(n + 1, 0);
+  std::vector<DocId> existing;
   {
     auto it = impl_->pending.begin();
     for (uint64_t i = 0; i < n; ++i) {
       if (it != impl_->pending.end() && it->first == first + i) {
         bytes.insert(bytes.end(), it->second.begin(), it->second.end());
+        existing.push_back(it->first);
         ++it;
       }
       off[i + 1] = bytes.size();
     }
   }
   bytes.resize(bytes.size() + 16);
-  std::vector<DocId> existing;
-  impl_->has_gaps = impl_->pending.size() != n && !impl_->pending.empty();
-  if (impl_->has_gaps) {
-    impl_->exists_bits.assign((n + 63) / 64, 0);
-    for (const auto& kv : impl_->pending) {
-      existing.push_back(kv.first);
-      const uint64_t slot = kv.first - first;
-      impl_->exists_bits[slot >> 6] |= 1ull << (slot & 63);
-    }
-  }
   impl_->pending.clear();
-  mgx_build_params bp{sizeof(mgx_build_params), MGX_ABI_VERSION, ngram_size_, kanji_ngram_size_, cross_boundary_ ? 1 : 0, 0};
-  static const bool kTraceBuild = std::getenv("MGX_TRACE_HOST") != nullptr;
-  const auto tb0 = std::chrono::steady_clock::now();
-  if (mgx_columns_build(&bp, bytes.data(), off.data(), first, n, &impl_->cols) != MGX_OK) {
-    impl_->last_error = mgx_last_error();
-    return impl_->last_error;
-  }
-  const auto tb1 = std::chrono::steady_clock::now();
-  mgx_columns_view_get(impl_->cols, &impl_->view);
-  const auto& v = impl_->view;
-  mgx_index_desc d{sizeof(mgx_index_desc), MGX_ABI_VERSION, impl_->device, 0, v.first_doc_id, v.n_docs, v.n_grams,
-                   v.offsets,               v.docids,        v.tf,          v.doc_len, impl_->dense_threshold,
-                   v.tf_overflow_pos,       v.tf_overflow_val, v.n_tf_overflow};
-  if (mgx_index_create(&d, &impl_->dev) != MGX_OK) {
-    impl_->last_error = mgx_last_error();
-    impl_->dev = nullptr;
-    return impl_->last_error;
-  }
-  impl_->Publish();
-  const auto tb2 = std::chrono::steady_clock::now();
-  // the shim's Index is also the DocumentStore of the texts it was given: BM25 terms longer than one n-gram are
-  // counted in the text on the device
-  if (mgx_index_attach_text(impl_->dev, bytes.data(), off.data()) != MGX_OK) impl_->last_error = mgx_last_error();
-  if (kTraceBuild)
-    fprintf(stderr, "[shim] Finalize of %llu docs: columns %.2f ms, device index %.2f ms, texts %.2f ms\n",
-            static_cast<unsigned long long>(n), std::chrono::duration<double, std::milli>(tb1 - tb0).count(),
-            std::chrono::duration<double, std::milli>(tb2 - tb1).count(),
-            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tb2).count());
-  // DocumentStore::GetAllDocIds (the NOT universe of boolean expressions) is the set of ids that were added
-  // As the index's live row it is ANDed into every query before the first funnel counter (a gap holds no posting, so the
-  // bitmap forms are clean by construction): a NOT node's complement, total_candidates, after_intersection and after_not
-  // count stored documents only, as ExecuteWithBooleanAst's all_docs does (search_pipeline.cpp:1469, :1477).
-  if (impl_->has_gaps &&
-      (mgx_index_add_filter_bitmap(impl_->dev, existing.data(), existing.size(), &impl_->exists_bitmap) != MGX_OK ||
-       mgx_index_set_live_bitmap(impl_->dev, impl_->exists_bitmap, MGX_LIVE_BITMAPS_CLEAN) != MGX_OK))
-    impl_->last_error = mgx_last_error();
+  GenerationSpec spec{impl_->device, impl_->dense_threshold, ngram_size_, kanji_ngram_size_, cross_boundary_, nullptr,
+                      bytes.data(),  off.data(),             first,       n};
+  if (existing.size() != n && !existing.empty()) spec.existing = &existing;
+  Impl::Generation gen;
+  impl_->last_error = BuildGeneration(spec, &gen);
+  if (!impl_->last_error.empty()) return impl_->last_error;
+  impl_->Install(std::move(gen));
   pending_columns_ready_ = !impl_->pending_filters.empty();
-  return impl_->last_error;
+  return "";
 }
 
 // The filter values recorded by AddDocument(doc, text, filters) become device columns (outside impl_->mu: AddFilterColumn
-// calls Finalize itself).
+// takes it).
 void Index::FlushPendingFilterColumns() const {
   std::map<DocId, storage::FilterMap> pending;
+  DocId first = 0;
+  uint64_t n = 0;
   {
     std::lock_guard<std::mutex> lock(impl_->mu);
     if (!pending_columns_ready_) return;
     pending_columns_ready_ = false;
     pending.swap(impl_->pending_filters);
+    first = impl_->view.first_doc_id;
+    n = impl_->view.n_docs;
   }
-  std::vector<std::string> names;
-  for (const auto& kv : pending)
-    for (const auto& f : kv.second)
-      if (std::find(names.begin(), names.end(), f.first) == names.end()) names.push_back(f.first);
-  const DocId first = impl_->view.first_doc_id;
-  for (const auto& name : names) {
-    std::vector<storage::FilterValue> values(impl_->view.n_docs);
-    for (const auto& kv : pending) {
-      const auto it = kv.second.find(name);
-      if (it != kv.second.end() && kv.first >= first && kv.first - first < values.size()) values[kv.first - first] = it->second;
-    }
-    const std::string err = AddFilterColumn(name, values);
+  for (const auto& c : ValuesByName(pending, {}, n, [&](DocId doc) { return doc >= first ? uint64_t{doc} - first : n; })) {
+    const std::string err = AddFilterColumn(c.first, c.second);
     if (!err.empty()) impl_->last_error = err;
   }
 }
@@ -1300,7 +1327,8 @@ uint64_t Index::PostingSize(std::string_view term) const {  // index.cpp:580-584
     std::lock_guard<std::mutex> lock(impl_->mu);
     mutable_table = impl_->mut.active;
   }
-  if (mutable_table) ApplyMutations();  // (the live postings of both indexes: what Count() is in the reference)
+  // (the live postings of both indexes: what Count() is in the reference; a failed application: 0, LastError() says why)
+  if (mutable_table && !ApplyMutations().empty()) return 0;
   uint32_t id = 0;
   uint64_t size = 0;
   return impl_->Resolve(term, &id, &size) ? size : 0;
@@ -3085,36 +3113,28 @@ BatchExecutor::~BatchExecutor() {
 Expected<uint64_t, Error> BatchExecutor::Submit(std::vector<BatchQuery>&& queries) {
   index::Index::Impl* im = impl_->index.impl();
   if (!im->dev) return MakeUnexpected(MakeError(ErrorCode::kInternalError, im->last_error));
-  // a mutable table: changes recorded since the last batch reach the device now — once nothing of this executor is
-  // being planned or compiled (batches already on the device finish first: ApplyMutations waits for it)
-  // install: something is about to change on the device (a finished background build, or — without a staleness bound, and
-  // the first time — everything recorded so far): nothing of this executor may be being planned or compiled meanwhile.
-  // kick: with a staleness bound that has passed, a background build of the recorded changes starts; nothing changes yet.
-  bool install = false, kick = false, mutable_table = false;
+  // a mutable table: what ApplyMutations would do now (NextMutationStep). An install changes the device, so nothing of
+  // this executor may be being planned or compiled meanwhile (batches already on the device finish first: the install
+  // waits for them); a kick only starts a background build.
+  index::MutationStep step;
+  bool mutable_table = false;
   {
     std::lock_guard<std::mutex> il(im->mu);
-    const auto& mm = im->mut;
-    const bool immediate = mm.staleness.count() == 0 || mm.epoch == 0;
-    install = mm.build_ready || (immediate && (mm.dirty || mm.build_running));
-    kick = !install && mm.dirty && !mm.build_running &&
-           std::chrono::steady_clock::now() - mm.last_apply >= mm.staleness;
-    mutable_table = mm.active;
+    step = index::NextMutationStep(im->mut, /*force=*/false);
+    mutable_table = im->mut.active;
   }
-  if (install) {
+  if (step == index::MutationStep::kInstall) {
     if (impl_->opt.comm)
       return MakeUnexpected(MakeError(ErrorCode::kNotImplemented, "a sharded table (Options::comm) is static"));
-    {
-      std::unique_lock<std::mutex> lock(impl_->mu);
-      impl_->cv_state.wait(lock, [&] {
-        for (auto& s : impl_->slots)
-          if (s.state == Impl::kPlanning || s.state == Impl::kPlanned || s.state == Impl::kCompiling || s.state == Impl::kCompiled)
-            return false;
-        return true;
-      });
-    }
-    const std::string merr = impl_->index.ApplyMutations();
-    if (!merr.empty()) return MakeUnexpected(MakeError(ErrorCode::kInternalError, merr));
-  } else if (kick) {
+    std::unique_lock<std::mutex> lock(impl_->mu);
+    impl_->cv_state.wait(lock, [&] {
+      for (auto& s : impl_->slots)
+        if (s.state == Impl::kPlanning || s.state == Impl::kPlanned || s.state == Impl::kCompiling || s.state == Impl::kCompiled)
+          return false;
+      return true;
+    });
+  }
+  if (step != index::MutationStep::kNothing) {
     const std::string merr = impl_->index.ApplyMutations();
     if (!merr.empty()) return MakeUnexpected(MakeError(ErrorCode::kInternalError, merr));
   }

@@ -167,9 +167,12 @@ class Index {
   //   AddDocument(doc, text[, filters]) after the first search: a NEW document (false + LastError() if the id is live);
   //   UpdateDocument: the document's text becomes new_text (index.cpp:199-233); its filter values stay, or become `filters`;
   //   RemoveDocument: the document leaves the table (index.cpp:148-197).
-  // Calls are cheap (host bookkeeping); they take effect at the next query entry point, which must not overlap another
-  // thread's query on the same Index while it applies them (one BatchExecutor / MicroBatcher per mutable table, or
-  // external exclusion — the reference holds its index write lock for the same span).
+  // Calls are cheap (host bookkeeping); they take effect at the next query entry point. Two exclusions:
+  //   enforced by the index lock: these calls, ApplyMutations and Compact are serialised against each other, from any
+  //   thread — a writer thread may run beside the thread that queries and compacts;
+  //   the caller's: while an entry point installs recorded changes, or Compact runs, no batch of this Index is planned,
+  //   compiled or run by another thread (one BatchExecutor / MicroBatcher per mutable table, or external exclusion — the
+  //   reference holds its index write lock for the same span).
   // Limits: BatchQuery::filters (raw bitmap ids) are per device index and are refused while a delta exists — use
   // filter_conditions; sharded tables (BatchExecutor::Options::comm) are static. Every page shape is merged on the device:
   // SORT _score and docid pages of any limit and offset, limit 0 included.
@@ -193,7 +196,10 @@ class Index {
   [[nodiscard]] uint64_t DeviceMemoryBytes() const;
   // Brings the device state up to date with the recorded changes (every query entry point calls it). "" or an error.
   // With a staleness bound set (below) the entry points' calls do nothing until the bound has passed since the last
-  // application; force = true applies now.
+  // application; force = true applies now. Recorded changes count as applied only once the device has taken all of them:
+  // after an error nothing is lost, the next entry point applies again in its own call (whatever the bound says), and
+  // every entry point returns the error until an application succeeds — no query runs on a half-applied state
+  // (PostingSize / EstimatePostingSize / Count have no error channel: they return 0 and LastError() holds the message).
   std::string ApplyMutations(bool force = false) const;
   // A table under a steady stream of changes would rebuild its delta index for every batch (0.07-0.2 s each). With a
   // staleness bound, recorded changes become visible to queries at most that long after they were made (they are applied
@@ -205,7 +211,8 @@ class Index {
   // Folds the delta back: the main index is rebuilt from the table's current documents (the texts of its live documents come
   // back from the device, where BM25 keeps them; filter values likewise) and the delta and the live row go. What the
   // reference's Optimize / a dump-and-reload do for a grown index. Same exclusion rule as the mutation-applying entry
-  // points; an executor's batch objects move to the new device index by themselves. "" or an error.
+  // points; an executor's batch objects move to the new device index by themselves. "" or an error: the new main index,
+  // filter columns included, is built off to the side and published in one step, so after an error the table is as it was.
   std::string Compact() const;
 
   [[nodiscard]] std::vector<DocId> SearchAnd(const std::vector<std::string>& terms, size_t limit = 0,
