@@ -126,6 +126,13 @@ struct LdsOffsets {
 
 __host__ __device__ inline uint32_t align8(uint32_t x) { return (x + 7u) & ~7u; }
 
+// Packed scan lanes of one wave in score mode: the result and every scored term, two 16-bit counts per u32. 16 hold the
+// result and 31 scored terms; a query may score up to kMaxScoreTerms.
+__host__ __device__ inline uint32_t scan_lanes(uint32_t max_score) {
+  const uint32_t n = (max_score + 2u) >> 1;
+  return n > 16u ? n : 16u;
+}
+
 __host__ __device__ inline LdsOffsets carve(const LdsPlan& p, bool score_mode) {
   LdsOffsets o;
   uint32_t at = 0;
@@ -135,7 +142,7 @@ __host__ __device__ inline LdsOffsets carve(const LdsPlan& p, bool score_mode) {
   o.seg_hi = at;    at += align8(p.max_leaves * 8);
   o.leaf = at;      at += align8(p.max_leaves * static_cast<uint32_t>(sizeof(DevLeaf)));
   o.prog = at;      at += align8(p.max_instr * 4);
-  o.scan_tot = at;  at += 4 * 16 * 4;  // 4 waves x up to 16 packed scan lanes
+  o.scan_tot = at;  at += 4 * scan_lanes(p.max_score) * 4;  // 4 waves x their packed scan lanes
   o.misc = at;      at += 128;  // page-pass masks (32 B), operand-presence mask (32 B), jump targets (8 B)
   o.pref = at;
   o.match = at;
@@ -783,6 +790,7 @@ __device__ __forceinline__ void tile_eval_body(const DevIndex& ix, const DevBatc
   DevLeaf* const leaf = reinterpret_cast<DevLeaf*>(smem + lo_.leaf);
   uint32_t* const prog = reinterpret_cast<uint32_t*>(smem + lo_.prog);
   uint32_t* const scan_tot = reinterpret_cast<uint32_t*>(smem + lo_.scan_tot);
+  const uint32_t scan_stride = scan_lanes(plan.max_score);
   uint32_t* const misc = reinterpret_cast<uint32_t*>(smem + lo_.misc);
   uint16_t* const pref = reinterpret_cast<uint16_t*>(smem + lo_.pref);
   uint16_t* const matchbuf = reinterpret_cast<uint16_t*>(smem + lo_.match);
@@ -1182,7 +1190,7 @@ __device__ __forceinline__ void tile_eval_body(const DevIndex& ix, const DevBatc
       const uint32_t vb = qb < n_q ? operand_pop(qb - 1) : 0u;
       const uint32_t v = va | (vb << 16);
       const uint32_t inc = wave_incl_scan(v);
-      if (lane_id() == 63) scan_tot[wave_id() * 16 + pk] = inc;
+      if (lane_id() == 63) scan_tot[wave_id() * scan_stride + pk] = inc;
       // stash the wave-local exclusive value; the cross-wave offset is added after the barrier
       const uint32_t ex = inc - v;
       pref[qa * kBlock + tid] = static_cast<uint16_t>(ex & 0xFFFFu);
@@ -1193,7 +1201,7 @@ __device__ __forceinline__ void tile_eval_body(const DevIndex& ix, const DevBatc
     for (uint32_t pk = 0; pk < n_packed; ++pk) {
       uint32_t off = 0, tot = 0;
       for (int w = 0; w < 4; ++w) {
-        const uint32_t t = scan_tot[w * 16 + pk];
+        const uint32_t t = scan_tot[w * scan_stride + pk];
         if (w < wave_id()) off += t;
         tot += t;
       }
