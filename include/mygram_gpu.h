@@ -303,7 +303,10 @@ typedef struct mgx_condition {
  * AND = intersection of its children, OR = union, NOT = universe minus child, where the universe is
  * DocumentStore::GetAllDocIds() (document_store_retrieval.cpp:242-258). */
 #define MGX_EXPR_TERM 0u  /* arg = index into mgx_query.terms */
-#define MGX_EXPR_EMPTY 1u /* a term the caller already knows to match nothing (unknown gram) */
+#define MGX_EXPR_EMPTY 1u /* a term the caller already knows to match nothing (unknown gram). Constant FALSE for the text
+                           * filter of an expression too (exact_text / fuzzy_verify_distance with n_expr > 0): with that
+                           * filter on, use it only for a term whose normalized text is empty, and send every other empty
+                           * leaf as a TERM whose only gram is MGX_GRAM_ABSENT and which carries its `text` */
 #define MGX_EXPR_AND 2u   /* arg = number of children (>= 1), already on the stack */
 #define MGX_EXPR_OR 3u    /* arg = number of children (>= 1) */
 #define MGX_EXPR_NOT 4u   /* one child */
@@ -339,7 +342,12 @@ typedef struct mgx_query {
    * the docs whose text contains EVERY positive term. The caller sets it when the reference would: memory.verify_text
    * says so (ShouldApplyVerifyText :42-66), or a mixed-script term has a code point no query n-gram covers
    * (RequiresExactTextForHybridFragments :138-150). Every positive term must then carry its normalized `text`;
-   * needs mgx_index_attach_text. after_filters still counts the docs before this filter, `total` those after it. */
+   * needs mgx_index_attach_text. after_filters still counts the docs before this filter, `total` those after it.
+   * With n_expr > 0 the rule is the TREE's (PostFilterByBooleanText, :404-416): a candidate stays when `expr` evaluates to
+   * true over its text, a TERM leaf being text.find(term), EMPTY false, AND / OR / NOT as written — the filter only
+   * narrows the set-algebra result. Every term a TERM token names must carry its `text` (1..4096 bytes); setting
+   * fuzzy_verify_distance as well is MGX_ERR_INVALID_ARGUMENT (one filter, d = 0 here). At most 64 operands may be
+   * pending in the postfix at once (MGX_ERR_OUT_OF_RANGE). Runs like a fuzzy_verify_distance query. */
   uint32_t exact_text;
   /* MGX_SORT_SCORE: which terms BM25 sums, as indices into `terms`, in summation order (bm25_scorer.cpp:77-86); a term
    * may be listed more than once (ScoreDocuments adds a repeated term's contribution each time). NULL => every positive
@@ -357,7 +365,9 @@ typedef struct mgx_query {
    * windows inside non-ASCII words). The caller sets it when ExecuteWithFuzzy would (:1722-1731:
    * ShouldApplyVerifyText(memory.verify_text, terms)). Every positive term must carry its normalized `text`; needs
    * mgx_index_attach_text. after_filters still counts the docs before this filter, `total` those after it. The query
-   * runs on the general kernel, in a launch of its own. */
+   * runs on the general kernel, in a launch of its own.
+   * With n_expr > 0 the rule is the TREE's with FUZZY leaves (ExecuteWithBooleanAst, :1538-1555): as exact_text above,
+   * a TERM leaf being "found exactly or within d edits". */
   uint32_t fuzzy_verify_distance;
   /* FILTER conditions the batch evaluates itself (mgx_condition), applied after `filters` in the same funnel step
    * (after_filters counts the docs that passed both). n_filters + n_conditions <= MGX_MAX_TERMS, else

@@ -1308,7 +1308,10 @@ struct QuerySpec {
   std::vector<double> deep_idfs;
   uint32_t pat_off = 0, pat_len = 0;  // kModeTextDf specs: the term in the batch's pattern pool
   uint32_t vt_begin = 0;              // first of the query's verify patterns in the batch-wide array
-  uint32_t fz_distance = 0;           // kOpVerifyFuzzy: d; the query then runs the FZ instantiation of the general kernel
+  uint32_t fz_distance = 0;           // kOpVerifyFuzzy / kOpVerifyTree: d
+  bool fz_op = false;                 // the program has one of those two ops: the query runs the FZ instantiation of the general kernel
+  std::vector<uint32_t> verify_prog;  // kOpVerifyTree: the tree as postfix VerifyTok tokens over the op's patterns
+  uint32_t vp_begin = 0;              // its first token in the batch-wide array
   // back to the freshly constructed state, keeping the vectors' storage (a re-prepared batch object compiles its new
   // queries into the specs of the old ones)
   void Clear() {
@@ -1331,7 +1334,9 @@ struct QuerySpec {
     wave_ok = flat = fast_score_ok = true;
     est_density = 0.0;
     total_docs = 0;
-    pat_off = pat_len = vt_begin = fz_distance = 0;
+    pat_off = pat_len = vt_begin = fz_distance = vp_begin = 0;
+    fz_op = false;
+    verify_prog.clear();
   }
 };
 
@@ -1636,7 +1641,52 @@ static int CompileQuery(const mgx_index* idx, const mgx_query& in, QuerySpec* ou
     c.Emit(in.conditions[i].negate ? kOpAndNot : kOpAnd, id);
   }
   c.Emit(kOpCount, 3);
-  if (in.fuzzy_verify_distance != 0) {
+  if (in.n_expr > 0 && (in.exact_text || in.fuzzy_verify_distance != 0)) {
+    // the text post-filter of ExecuteWithBooleanAst (search_pipeline.cpp:1505-1578): the TREE is re-evaluated over each
+    // candidate's text, a TERM leaf being text.find(term), or that or ContainsFuzzyMatch(text, term, d)
+    if (in.exact_text && in.fuzzy_verify_distance != 0)
+      return Fail(MGX_ERR_INVALID_ARGUMENT, "expression: exact_text and fuzzy_verify_distance are one filter, set one of them");
+    if (in.fuzzy_verify_distance > 2) return Fail(MGX_ERR_INVALID_ARGUMENT, "fuzzy_verify_distance must be 0, 1 or 2");
+    if (!idx->dev.text)
+      return Fail(MGX_ERR_INVALID_ARGUMENT, "expression with exact_text / fuzzy_verify_distance without mgx_index_attach_text");
+    const uint32_t first_pat = static_cast<uint32_t>(out->verify_patterns.size());
+    std::vector<uint32_t> pat_of(in.n_terms, kNoRow);  // term -> its pattern: a term is matched once however often it is named
+    uint32_t depth = 0;
+    for (uint32_t k = 0; k < in.n_expr; ++k) {  // (arity and term indices were checked when the set program was built)
+      const mgx_expr_token tk = in.expr[k];
+      switch (tk.op) {
+        case MGX_EXPR_TERM: {
+          const mgx_term& t = in.terms[tk.arg];
+          if (!t.text || t.text_len == 0 || t.text_len > 4096)
+            return Fail(MGX_ERR_INVALID_ARGUMENT,
+                        "expression with a text filter: every TERM token's term needs its normalized text (1..4096 bytes)");
+          if (pat_of[tk.arg] == kNoRow) {
+            pat_of[tk.arg] = static_cast<uint32_t>(out->verify_patterns.size()) - first_pat;
+            out->verify_patterns.emplace_back(reinterpret_cast<const char*>(t.text), t.text_len);
+          }
+          out->verify_prog.push_back((kVerifyTerm << 24) | pat_of[tk.arg]);
+          ++depth;
+          break;
+        }
+        case MGX_EXPR_EMPTY:
+          out->verify_prog.push_back(kVerifyFalse << 24);
+          ++depth;
+          break;
+        case MGX_EXPR_NOT: out->verify_prog.push_back(kVerifyNot << 24); break;
+        default:
+          out->verify_prog.push_back(((tk.op == MGX_EXPR_AND ? kVerifyAnd : kVerifyOr) << 24) | tk.arg);
+          depth -= tk.arg - 1;
+          break;
+      }
+      if (depth > kMaxVerifyDepth)
+        return Fail(MGX_ERR_OUT_OF_RANGE, "expression with a text filter: more than 64 pending operands");
+    }
+    static_assert(MGX_MAX_TERMS <= kMaxVerifyPatterns && kMaxVerifyTokens == 512, "patterns are bits of a u64; n_expr <= 512");
+    // (not a flat op: the query runs on the general kernel's FZ instantiation) argument: first pattern | tokens << 12
+    c.Emit(kOpVerifyTree, first_pat | (in.n_expr << 12));
+    out->fz_distance = in.fuzzy_verify_distance;
+    out->fz_op = true;
+  } else if (in.fuzzy_verify_distance != 0) {
     // PostFilterByFuzzyText (search_pipeline.cpp:1746-1755), before the exact-text rule of :1733-1741
     if (in.fuzzy_verify_distance > 2)
       return Fail(MGX_ERR_INVALID_ARGUMENT, "fuzzy_verify_distance must be 0, 1 or 2");
@@ -1652,8 +1702,9 @@ static int CompileQuery(const mgx_index* idx, const mgx_query& in, QuerySpec* ou
     // (not a flat op: the query runs on the general kernel's FZ instantiation) argument: first pattern | count << 12
     c.Emit(kOpVerifyFuzzy, first_fz | (in.n_terms << 12));
     out->fz_distance = in.fuzzy_verify_distance;
+    out->fz_op = true;
   }
-  if (in.exact_text) {
+  if (in.exact_text && in.n_expr == 0) {
     if (!idx->dev.text) return Fail(MGX_ERR_INVALID_ARGUMENT, "exact_text without mgx_index_attach_text");
     const uint32_t first_exact = static_cast<uint32_t>(out->verify_patterns.size());
     for (uint32_t i = 0; i < in.n_terms; ++i) {
@@ -1793,7 +1844,7 @@ struct mgx_batch {
     // The routes' launches run over disjoint item lists into the same outputs.
     RouteLaunch block;           // general kernel
     uint32_t n_items_plain = 0;  // block items [0, n_items_plain): queries of bitmap-form operands only (LaunchTileEval)
-    uint32_t n_items_fz = 0;     // the last n_items_fz block items: queries with kOpVerifyFuzzy (a launch of their own)
+    uint32_t n_items_fz = 0;     // the last n_items_fz block items: queries with kOpVerifyFuzzy / kOpVerifyTree (a launch of their own)
     // wave kernel: flat programs (score mode: dense or sparse scored operands, contribution tables in d_tables)
     RouteLaunch wave;
     DevBuf d_tables;
@@ -1825,7 +1876,7 @@ struct mgx_batch {
   // df pass of the text-level scored terms: one kModeTextDf query per term (the AND of its grams + a text scan)
   Group textdf;
   std::vector<mgx::QuerySpec> df_specs;
-  DevBuf d_patterns, d_text_terms, d_text_idf, d_text_df, d_verify_terms;
+  DevBuf d_patterns, d_text_terms, d_text_idf, d_text_df, d_verify_terms, d_verify_prog;
   // d_text_df is the array ranks all-reduce in place (table-wide df after the reduction); d_text_df_local keeps this
   // shard's own counts — the only thing the index's df cache ever holds, so what a rank contributes to the reduction is
   // the same whether a term's count came from the cache or from the df pass
@@ -2005,6 +2056,7 @@ static int LayOutQueries(mgx_batch* b, Group& g, const std::vector<QuerySpec>& s
     q.vt_begin = s.vt_begin;
     q.vt_count = static_cast<uint32_t>(s.verify_patterns.size());
     q.fz_distance = s.fz_distance;
+    q.vp_begin = s.vp_begin;
     q.k1 = s.k1;
     q.b = s.b;
     q.one_minus_b = 1.0 - s.b;
@@ -2293,7 +2345,7 @@ static int ChooseRoutes(mgx_batch* b, Group& g, const std::vector<QuerySpec>& sp
   if (g.plan.bytes > 160 * 1024)
     return Fail(MGX_ERR_NOT_IMPLEMENTED, "query shape exceeds the 160 KiB LDS of a CU");
   for (uint32_t i = 0; i < p.n; ++i)
-    if (specs[g.qids[i]].fz_distance != 0 && g.plan.bytes + kFzLdsBytes > 160 * 1024)
+    if (specs[g.qids[i]].fz_op && g.plan.bytes + kFzLdsBytes > 160 * 1024)
       return Fail(MGX_ERR_NOT_IMPLEMENTED, "query shape with the fuzzy text filter exceeds the 160 KiB LDS of a CU");
   return MGX_OK;
 }
@@ -2509,7 +2561,7 @@ static hipError_t MakeRoute(RouteLaunch& r, const DevBatch& base, const std::vec
 
 // (f, g) Block-kernel items: queries whose operands are all bitmap-form first (plain instantiation), then the queries
 // with a sorted list, an explicit id list or a slot range among their operands (the instantiation that skips / jumps
-// over tiles), and last the queries with kOpVerifyFuzzy (the FZ instantiation, launched apart). Then the group's
+// over tiles), and last the queries with kOpVerifyFuzzy or kOpVerifyTree (the FZ instantiation, launched apart). Then the group's
 // descriptor with the outputs sized by its candidate lists, and one launch per route over it.
 static int UploadItems(mgx_batch* b, Group& g, const std::vector<QuerySpec>& specs, GroupPlan& p) {
   const uint32_t n = p.n;
@@ -2517,7 +2569,7 @@ static int UploadItems(mgx_batch* b, Group& g, const std::vector<QuerySpec>& spe
   for (uint32_t i = 0; i < n; ++i) {
     for (const DevLeaf& lf : specs[g.qids[i]].leaves)
       if (lf.kind == kLeafList || lf.kind == kLeafExplicit || lf.kind == kLeafRange) listlike[i] = 1;
-    if (specs[g.qids[i]].fz_distance != 0) listlike[i] = 2;
+    if (specs[g.qids[i]].fz_op) listlike[i] = 2;
   }
   std::stable_partition(p.block.begin(), p.block.end(), [&](const DevItem& it) { return listlike[it.query] == 0; });
   if (std::find(listlike.begin(), listlike.end(), 2) != listlike.end())
@@ -2537,6 +2589,7 @@ static int UploadItems(mgx_batch* b, Group& g, const std::vector<QuerySpec>& spe
   d.text_terms = b->d_text_terms.as<DevTextTerm>();
   d.text_idf = b->d_text_idf.as<double>();
   d.verify_terms = b->d_verify_terms.as<DevTextTerm>();
+  d.verify_prog = b->d_verify_prog.as<uint32_t>();
   d.n_queries = n;
   d.counters = p.score_mode  ? b->sc_counters()
                : p.page_mode ? b->d_page_out.as<unsigned long long>()
@@ -2603,15 +2656,15 @@ static int UploadItems(mgx_batch* b, Group& g, const std::vector<QuerySpec>& spe
   MGX_HIP(MakeRoute(g.wave, d, p.wave));
   MGX_HIP(Upload(g.d_list_begin, p.list_begin.data(), p.list_begin.size()));
   if (p.page_mode) {
-    // the page pass: one item per query (cand_kernel writes its own pages); kOpVerifyFuzzy queries last in page_block,
+    // the page pass: one item per query (cand_kernel writes its own pages); kOpVerifyFuzzy / kOpVerifyTree queries last in page_block,
     // on the general kernel's FZ launch
     std::vector<DevItem> pw, pb;
     for (uint32_t i = 0; i < n; ++i)
-      if (p.route[i] != Route::kCand && specs[g.qids[i]].fz_distance == 0)
+      if (p.route[i] != Route::kCand && !specs[g.qids[i]].fz_op)
         (p.route[i] == Route::kWave ? pw : pb).push_back(DevItem{i, 0, 0, 0});
     g.n_page_fz = 0;
     for (uint32_t i = 0; i < n; ++i)
-      if (specs[g.qids[i]].fz_distance != 0) {
+      if (specs[g.qids[i]].fz_op) {
         pb.push_back(DevItem{i, 0, 0, 0});
         ++g.n_page_fz;
       }
@@ -2896,13 +2949,17 @@ static int PrepareInto(mgx_batch* b, mgx_index* idx, std::vector<QuerySpec>&& sp
     }
     // exact-text filters: their patterns share the pool
     std::vector<DevTextTerm> vts;
+    std::vector<uint32_t> vprog;  // ... and the verify programs of the expression queries among them
     for (QuerySpec& s : b->specs) {
       s.vt_begin = static_cast<uint32_t>(vts.size());
+      s.vp_begin = static_cast<uint32_t>(vprog.size());
+      vprog.insert(vprog.end(), s.verify_prog.begin(), s.verify_prog.end());
       for (const std::string& pat : s.verify_patterns) {
         vts.push_back(DevTextTerm{static_cast<uint32_t>(pool.size()), static_cast<uint32_t>(pat.size())});
         pool += pat;
       }
     }
+    if (!vprog.empty()) MGX_HIP(Upload(b->d_verify_prog, vprog.data(), vprog.size()));
     if (!vts.empty()) {
       MGX_HIP(Upload(b->d_verify_terms, vts.data(), vts.size()));
       if (tts.empty()) MGX_HIP(Upload(b->d_patterns, reinterpret_cast<const uint8_t*>(pool.data()), pool.size(), 16));

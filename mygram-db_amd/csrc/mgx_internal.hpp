@@ -73,8 +73,24 @@ enum Op : uint32_t {
   kOpVerifyFuzzy,   // acc &= docs whose text contains every pattern exactly or within DevQuery::fz_distance edits
                     // (PostFilterByFuzzyText, search_pipeline.cpp:1746-1755); argument like kOpVerifyText's. Only the
                     // FZ instantiation of the general kernel runs it, in a launch of its own
+  kOpVerifyTree,    // acc &= docs over whose text the query's boolean tree is true (the text post-filter of
+                    // ExecuteWithBooleanAst, search_pipeline.cpp:1505-1578). arg = first pattern | tokens << 12: the
+                    // verify program is DevBatch::verify_prog[vp_begin, + tokens) over the query's patterns from `first
+                    // pattern` on; DevQuery::fz_distance = d (0: exact only). FZ instantiation only, like kOpVerifyFuzzy
 };
 inline constexpr uint32_t MakeInstr(Op op, uint32_t arg) { return (static_cast<uint32_t>(op) << 24) | (arg & 0xFFFFFFu); }
+
+// The verify program of kOpVerifyTree: postfix tokens, op << 24 | arg, over one bit per pattern of the query.
+enum VerifyTok : uint32_t {
+  kVerifyTerm = 0,  // push "pattern arg matches the text"
+  kVerifyFalse,     // push false (MGX_EXPR_EMPTY)
+  kVerifyAnd,       // pop arg entries, push "all of them"
+  kVerifyOr,        // pop arg entries, push "any of them"
+  kVerifyNot,       // negate the top entry
+};
+constexpr uint32_t kMaxVerifyTokens = 512;   // tokens of one verify program (= the longest expression the ABI takes)
+constexpr uint32_t kMaxVerifyPatterns = 64;  // its distinct patterns: one bit each of a u64
+constexpr uint32_t kMaxVerifyDepth = 64;     // entries of its bit stack
 
 // A scored term takes its tf either from the tf column of ONE gram operand (term == that gram) or, for terms that span
 // several grams, from the doc text (CountTermOccurrences, bm25_scorer.cpp:27-45); the latter's idf comes from the
@@ -127,11 +143,12 @@ struct DevQuery {
   uint32_t out_slot;  // row of this query in the per-mode output arrays
   uint32_t pat_off, pat_len;  // kModeTextDf: the term searched in the candidates' text
   uint32_t vt_begin, vt_count;  // kOpVerifyText: the query's patterns in DevBatch::verify_terms
-  uint32_t fz_distance, fz_pad;  // kOpVerifyFuzzy: d (1 or 2); 0 = the query has no such op
+  uint32_t fz_distance;  // kOpVerifyFuzzy: d (1 or 2); kOpVerifyTree: d (0, 1 or 2)
+  uint32_t vp_begin;     // kOpVerifyTree: the query's first token in DevBatch::verify_prog (the count is in the op)
   double k1, b, one_minus_b, k1_plus_1, avgdl_clamped;  // BM25 constants, pre-evaluated on the host
 };
 
-// LDS the FZ instantiation of the general kernel takes beyond LdsPlan::bytes (kOpVerifyFuzzy): the tile's drop mask
+// LDS the FZ instantiation of the general kernel takes beyond LdsPlan::bytes (kOpVerifyFuzzy, kOpVerifyTree): the tile's drop mask
 // (one u64 per thread), the four waves' candidate counts, and kFzBuf candidate slots shared by the workgroup per round.
 constexpr uint32_t kFzBuf = 2048;
 constexpr uint32_t kFzLdsBytes = kWordsPerTile * 8 + 16 + kFzBuf * 2;
@@ -283,6 +300,8 @@ struct DevBatch {
   const uint64_t* totals;      // [n]
   uint32_t* page_docs;         // [n][page_stride]
   uint32_t page_stride;
+  // (last, so that no other member moves) kOpVerifyTree: the verify programs of the batch's queries, next to verify_terms
+  const uint32_t* verify_prog;
 };
 
 // ---- HIGHLIGHT (highlight_kernel, mgx_highlight.hip): one wave per (highlighted query, page entry) ------------------

@@ -716,17 +716,18 @@ __device__ __forceinline__ bool tile_may_match(const uint32_t* prog, uint32_t n_
   return acc;
 }
 
-// kOpVerifyFuzzy (PostFilterByFuzzyText, search_pipeline.cpp:1746-1755): a candidate stays when every pattern of the
-// instruction occurs in its text exactly (text.find) or within d edits (ContainsFuzzyMatch, mgx_fuzzy.hpp). A FUZZY
-// candidate set can cover much of a tile and the matcher's cost per doc varies with its text, so the tile's candidates
+// The text filters of the FZ launch (kOpVerifyFuzzy, kOpVerifyTree): `keep(t0, t1)` decides one candidate from its text
+// bytes [t0, t1). A FUZZY or an expression candidate set can cover much of a tile and the matcher's cost per doc varies
+// with its text, so the tile's candidates
 // are first compacted across the WORKGROUP (prefix sum of the per-thread counts into an LDS slot list, kFzBuf per
 // round) and shared out evenly, instead of each thread walking its own 64-bit word. The failing docs are collected in an
 // LDS drop mask and cleared from `acc` at the end. Workgroup scope is safe: tile_eval_body runs the program's instruction
 // loop with workgroup-uniform control flow (one query per workgroup, the program in LDS, every skip of a tile taken by
 // all threads), so all 256 threads arrive here together and reach every barrier below. Inlined: as a call it
 // made the FZ instantiation spill 74-94 VGPRs around it (12-21 inlined).
-__device__ __forceinline__ uint64_t verify_fuzzy(const DevIndex& ix, const DevBatch& bt, uint32_t vt_begin, uint32_t d,
-                                              uint32_t arg, uint32_t tile, uint64_t acc, unsigned char* lds) {
+template <class Keep>
+__device__ __forceinline__ uint64_t fz_filter_candidates(const DevIndex& ix, uint32_t tile, uint64_t acc, unsigned char* lds,
+                                                         Keep keep) {
   uint64_t* const drop = reinterpret_cast<uint64_t*>(lds);
   uint32_t* const wave_tot = reinterpret_cast<uint32_t*>(lds + kWordsPerTile * 8);
   uint16_t* const slots = reinterpret_cast<uint16_t*>(lds + kWordsPerTile * 8 + 16);
@@ -742,7 +743,6 @@ __device__ __forceinline__ uint64_t verify_fuzzy(const DevIndex& ix, const DevBa
     if (w < wave_id()) first += t;
     total += t;
   }
-  const uint32_t vfirst = arg & 0xFFFu, vcount = arg >> 12;
   for (uint32_t rb = 0; rb < total; rb += kFzBuf) {  // (total is workgroup-uniform)
     if (first < rb + kFzBuf && first + mine > rb) {
       uint64_t bits = acc;
@@ -759,26 +759,81 @@ __device__ __forceinline__ uint64_t verify_fuzzy(const DevIndex& ix, const DevBa
     for (uint32_t j = tid; j < n; j += kBlock) {
       const uint32_t ts = slots[j];
       const uint32_t slot = tile * kTileDocs + ts;
-      const uint64_t t0 = ix.text_off[slot], t1 = ix.text_off[slot + 1];
-      bool all = true;
-      for (uint32_t v = 0; all && v < vcount; ++v) {
-        const DevTextTerm vt = bt.verify_terms[vt_begin + vfirst + v];
-        const uint8_t* const pat = bt.patterns + vt.pat_off;
-        if (text_count_occurrences(ix.text, t0, t1, text_pattern(pat, vt.pat_len), true) != 0) continue;
-        all = d == 1 ? fuzzy::ContainsFuzzyMatch<1>(ix.text + t0, t1 - t0, pat, vt.pat_len)
-                     : fuzzy::ContainsFuzzyMatch<2>(ix.text + t0, t1 - t0, pat, vt.pat_len);
-      }
-      if (!all) atomicOr(reinterpret_cast<unsigned long long*>(&drop[ts >> 6]), 1ull << (ts & 63u));
+      if (!keep(ix.text_off[slot], ix.text_off[slot + 1]))
+        atomicOr(reinterpret_cast<unsigned long long*>(&drop[ts >> 6]), 1ull << (ts & 63u));
     }
     __syncthreads();  // (the slot list is refilled by the next round; the drop mask is complete after the last one)
   }
   return acc & ~drop[tid];
 }
 
+// one pattern against one text: found exactly (text.find), or, with d = 1 or 2, within d edits (ContainsFuzzyMatch)
+__device__ __forceinline__ bool fz_pattern_matches(const DevIndex& ix, const DevBatch& bt, const DevTextTerm vt, uint64_t t0,
+                                                   uint64_t t1, uint32_t d) {
+  const uint8_t* const pat = bt.patterns + vt.pat_off;
+  if (text_count_occurrences(ix.text, t0, t1, text_pattern(pat, vt.pat_len), true) != 0) return true;
+  if (d == 0) return false;
+  return d == 1 ? fuzzy::ContainsFuzzyMatch<1>(ix.text + t0, t1 - t0, pat, vt.pat_len)
+                : fuzzy::ContainsFuzzyMatch<2>(ix.text + t0, t1 - t0, pat, vt.pat_len);
+}
+
+// kOpVerifyFuzzy (PostFilterByFuzzyText, search_pipeline.cpp:1746-1755): a candidate stays when every pattern of the
+// instruction occurs in its text exactly or within d edits (d = 1 or 2).
+__device__ __forceinline__ uint64_t verify_fuzzy(const DevIndex& ix, const DevBatch& bt, uint32_t vt_begin, uint32_t d,
+                                              uint32_t arg, uint32_t tile, uint64_t acc, unsigned char* lds) {
+  const uint32_t vfirst = arg & 0xFFFu, vcount = arg >> 12;
+  return fz_filter_candidates(ix, tile, acc, lds, [&](uint64_t t0, uint64_t t1) -> bool {
+    bool all = true;
+    for (uint32_t v = 0; all && v < vcount; ++v)
+      all = fz_pattern_matches(ix, bt, bt.verify_terms[vt_begin + vfirst + v], t0, t1, d);
+    return all;
+  });
+}
+
+// kOpVerifyTree (the text post-filter of ExecuteWithBooleanAst, search_pipeline.cpp:1505-1578): a candidate stays when
+// the query's boolean tree is true over its text, a TERM leaf being "found exactly, or (d != 0) within d edits". The
+// tree arrives as the query's verify program: postfix tokens over the query's patterns [vfirst, q.vt_count) (the
+// validated output of CompileVerifyTree: no token pops more than the stack holds, depth <= 64). Every pattern is matched
+// once per candidate, however often the tree names it (bit p of `val`); the postfix then runs on a u64 bit stack.
+__device__ __forceinline__ uint64_t verify_tree(const DevIndex& ix, const DevBatch& bt, const DevQuery& q, uint32_t arg,
+                                                uint32_t tile, uint64_t acc, unsigned char* lds) {
+  const uint32_t vfirst = arg & 0xFFFu, n_tok = arg >> 12;
+  const uint32_t n_pat = q.vt_count - vfirst, d = q.fz_distance;
+  const DevTextTerm* const vts = bt.verify_terms + q.vt_begin + vfirst;
+  const uint32_t* const toks = bt.verify_prog + q.vp_begin;
+  return fz_filter_candidates(ix, tile, acc, lds, [&](uint64_t t0, uint64_t t1) -> bool {
+    uint64_t val = 0;
+    for (uint32_t p = 0; p < n_pat; ++p)
+      val |= static_cast<uint64_t>(fz_pattern_matches(ix, bt, vts[p], t0, t1, d) ? 1u : 0u) << p;
+    uint64_t stk = 0;
+    uint32_t sp = 0;
+    for (uint32_t k = 0; k < n_tok; ++k) {
+      const uint32_t tk = toks[k];
+      const uint32_t a = tk & 0xFFFFFFu;
+      uint64_t r;
+      switch (tk >> 24) {
+        case kVerifyTerm: r = (val >> a) & 1ull; break;
+        case kVerifyFalse: r = 0; break;
+        case kVerifyNot: --sp; r = ((stk >> sp) & 1ull) ^ 1ull; break;
+        default: {  // AND / OR of the top `a` entries
+          sp -= a;
+          const uint64_t m = (a >= 64 ? ~0ull : (1ull << a) - 1ull) << sp;
+          r = (tk >> 24) == kVerifyAnd ? ((stk & m) == m ? 1ull : 0ull) : ((stk & m) != 0 ? 1ull : 0ull);
+          break;
+        }
+      }
+      stk = (stk & ~(1ull << sp)) | (r << sp);
+      ++sp;
+    }
+    return (stk & 1ull) != 0;
+  });
+}
+
 // JUMP: the query has an operand that can be absent from a tile (a sorted list, an explicit id list, a slot range): tiles
 // are tested / jumped over as described above. Queries of bitmap-form operands only run the plain instantiation — the
 // same tile loop without that machinery (its registers cost the text-level scoring path 6 % when they shared one kernel).
-// FZ: the query may carry kOpVerifyFuzzy (launched apart from every other query; its LDS holds kFzLdsBytes more).
+// FZ: the query may carry kOpVerifyFuzzy or kOpVerifyTree (launched apart from every other query; its LDS holds
+// kFzLdsBytes more).
 template <int MODE, bool JUMP, bool FZ>
 __device__ __forceinline__ void tile_eval_body(const DevIndex& ix, const DevBatch& bt, const LdsPlan& plan) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -1067,6 +1122,10 @@ __device__ __forceinline__ void tile_eval_body(const DevIndex& ix, const DevBatc
             acc = verify_fuzzy(ix, bt, q.vt_begin, q.fz_distance, arg, tile, acc, smem + lo_.total);
             continue;
           }
+          if (op == kOpVerifyTree) {
+            acc = verify_tree(ix, bt, q, arg, tile, acc, smem + lo_.total);
+            continue;
+          }
         }
         switch (op) {
           case kOpLoad: acc = W(arg); break;
@@ -1348,7 +1407,7 @@ __device__ __forceinline__ void tile_eval_body(const DevIndex& ix, const DevBatc
 
 // One launch for both kinds of item (two launches meant two tails): the host puts the plain items first, the workgroup
 // picks its instantiation by its index. The two bodies share no registers in flight; the kernel's budget is the larger one's.
-// FZ: the launch of the queries that carry kOpVerifyFuzzy (every workgroup runs the jumping body, which takes any query).
+// FZ: the launch of the queries that carry kOpVerifyFuzzy or kOpVerifyTree (every workgroup runs the jumping body, which takes any query).
 template <int MODE, bool FZ>
 __global__ __launch_bounds__(kBlock, (MODE == kModeScore ? 3 : 4)) void tile_eval_kernel(DevIndex ix, DevBatch bt, LdsPlan plan,
                                                                                          uint32_t n_plain) {
@@ -3832,7 +3891,7 @@ int LaunchBuildBitmaps(const uint32_t* docids, const uint64_t* row_lo, const uin
 
 // Items [0, n_plain) belong to queries of bitmap-form operands only (plain instantiation), the rest to queries with an
 // operand that can be absent from a tile (jumping instantiation); n_plain >= n_items: everything plain.
-// The last n_fz items belong to queries with kOpVerifyFuzzy: they run the FZ instantiation in a launch of their own, so
+// The last n_fz items belong to queries with kOpVerifyFuzzy or kOpVerifyTree: they run the FZ instantiation in a launch of their own, so
 // that no other query pays for it.
 int LaunchTileEval(int mode, const DevIndex& ix, const DevBatch& bt, const LdsPlan& plan, hipStream_t s, uint32_t n_plain,
                    uint32_t n_fz) {

@@ -2267,6 +2267,57 @@ void PlanQuery(const index::Index& index, const BatchQuery& q, uint64_t total_do
     std::vector<std::string> leaves;
     std::vector<TermInfo> tis;
     bool bad = false;
+    // One distinct leaf as the tree's set algebra and its text filter see it.
+    struct Leaf {
+      bool substring = false;  // plain only: shorter than one n-gram — the documents whose text contains it
+      bool empty = false;      // the empty doc set
+      bool scored = false;     // may add to a score: every n-gram known (else it occurs in no text: tf = df = 0)
+      uint32_t threshold = 0;  // FUZZY: "at least theta of its known grams" (0: all of them)
+    };
+    std::vector<Leaf> lvs;
+    const uint32_t fz = q.fuzzy_max_distance;
+    // verify_text (search_pipeline.cpp:1505-1578): the tree is re-evaluated over each candidate's text, so every leaf
+    // carries its normalized text; an empty leaf still counts there (under a NOT), only "" is false on every text
+    const bool tree_verify = q.verify_text;
+    auto make_leaf = [&](TermInfo& ti) {
+      Leaf lf;
+      const bool known_all = ti.n_grams != 0 && ti.estimated_size != 0 && ti.estimated_size != UINT64_MAX;
+      lf.scored = known_all;
+      if (fz == 0) {
+        // a term with an unknown gram is an empty doc set inside the tree; a term shorter than one n-gram is the documents
+        // whose text contains it (regular_term_search -> SearchTermDocuments, search_pipeline.cpp:1446-1455, :438-446)
+        lf.substring = ti.n_grams == 0 && !ti.normalized.empty();
+        lf.empty = !lf.substring && !known_all;
+        return lf;
+      }
+      // FUZZY d: every leaf is fuzzy_term_search (:1424-1445) — no n-grams: the empty set (:1431-1433); else theta and the
+      // known grams exactly as ExecuteWithFuzzy's terms below (Index::SearchByThreshold skips unknown grams)
+      auto grams = GenerateQueryNgrams(ti.normalized, index.GetNgramSize(), im->query_kanji, index.GetCrossBoundaryNgrams());
+      DeduplicateSorted(grams);
+      if (grams.empty()) {
+        lf.empty = true;
+        return lf;
+      }
+      size_t n_eff = index.GetNgramSize() > 0 ? static_cast<size_t>(index.GetNgramSize()) : 2;
+      if (im->query_kanji > 0) {
+        size_t short_count = 0;
+        for (const auto& g : grams) short_count += g.size() <= 3 ? 1 : 0;
+        if (short_count > grams.size() / 2) n_eff = static_cast<size_t>(im->query_kanji);
+      }
+      const size_t drop = static_cast<size_t>(fz) * n_eff;
+      const size_t theta = grams.size() > drop ? grams.size() - drop : 1;
+      IdVec known;
+      for (const auto& g : grams) {
+        uint32_t id = 0;
+        uint64_t ps = 0;
+        if (im->Resolve(g, &id, &ps) && ps > 0) known.push_back(id);
+      }
+      lf.empty = known.empty() || (theta == grams.size() ? known.size() != grams.size() : known.size() < theta);
+      lf.scored = !lf.empty && known.size() == grams.size();
+      lf.threshold = (lf.empty || theta >= known.size()) ? 0u : static_cast<uint32_t>(theta);
+      ti.gram_ids = std::move(known);
+      return lf;
+    };
     // SORT _score: the TERM leaves that are not under a NOT, in tree order, repeats kept (CollectAstScoringTerms,
     // search_pipeline.cpp:232-254; search_handler.cpp:428-456 scores exactly those, whatever branch matched)
     p->has_score_list = q.sort_by_score;
@@ -2277,14 +2328,13 @@ void PlanQuery(const index::Index& index, const BatchQuery& q, uint64_t total_do
         if (k == leaves.size()) {
           leaves.push_back(nd.term);
           tis.push_back(MakeInfo(index, im, nd.term));
+          lvs.push_back(make_leaf(tis.back()));
         }
-        // a term with an unknown gram is an empty doc set inside the tree; a term shorter than one n-gram is the documents
-        // whose text contains it (regular_term_search -> SearchTermDocuments, search_pipeline.cpp:1446-1455, :438-446)
-        const bool substring = tis[k].n_grams == 0 && !tis[k].normalized.empty();
-        const bool empty = !substring && (tis[k].estimated_size == 0 || tis[k].estimated_size == UINT64_MAX);
-        p->expr.push_back(empty ? mgx_expr_token{MGX_EXPR_EMPTY, 0} : mgx_expr_token{MGX_EXPR_TERM, static_cast<uint32_t>(k)});
+        const bool as_term = !lvs[k].empty || (tree_verify && !tis[k].normalized.empty());
+        p->expr.push_back(as_term ? mgx_expr_token{MGX_EXPR_TERM, static_cast<uint32_t>(k)} : mgx_expr_token{MGX_EXPR_EMPTY, 0});
         // (a leaf with an unknown gram occurs in no text: tf = df = 0, it adds nothing to any score)
-        if (q.sort_by_score && !under_not && !empty) p->score_list.push_back(static_cast<uint32_t>(k));
+        if (q.sort_by_score && !under_not && !lvs[k].empty && (lvs[k].scored || lvs[k].substring))
+          p->score_list.push_back(static_cast<uint32_t>(k));
         return;
       }
       if (nd.children.empty() || (nd.type == query::NodeType::NOT && nd.children.size() != 1)) {
@@ -2301,26 +2351,31 @@ void PlanQuery(const index::Index& index, const BatchQuery& q, uint64_t total_do
     if (bad || leaves.empty() || leaves.size() > MGX_MAX_TERMS)
       return Fail(p, ErrorCode::kInvalidArgument, "malformed expression tree");
     p->ids.reserve(leaves.size() + q.not_terms.size());
-    for (auto& ti : tis) {
-      if (ti.n_grams == 0 && !ti.normalized.empty()) {  // substring leaf: a text scan on the device
+    for (size_t k = 0; k < tis.size(); ++k) {
+      TermInfo& ti = tis[k];
+      const Leaf& lf = lvs[k];
+      if (lf.substring) {  // a text scan on the device
         p->ids.emplace_back();
         p->texts.push_back(ti.normalized);
         p->terms.push_back(mgx_term{nullptr, 0, 0, 0.0, reinterpret_cast<const uint8_t*>(p->texts.back().data()),
                                     static_cast<uint32_t>(p->texts.back().size())});
         continue;
       }
-      const bool empty_leaf = ti.gram_ids.empty() || ti.estimated_size == 0 || ti.estimated_size == UINT64_MAX;
-      if (empty_leaf) ti.gram_ids.assign(1, 0u);  // placeholder of an EMPTY leaf
+      // an EMPTY leaf's placeholder; under tree_verify the leaf is a TERM of the absent gram (the empty set) with its text
+      if (lf.empty) ti.gram_ids.assign(1, tree_verify ? MGX_GRAM_ABSENT : 0u);
       p->ids.push_back(ti.gram_ids);
-      mgx_term mt{p->ids.back().data(), static_cast<uint32_t>(p->ids.back().size()), 0, 0.0, nullptr, 0};
-      if (q.sort_by_score && !empty_leaf) {
-        if (ti.is_gram) {
-          mt.idf = index::BM25Scorer::ComputeIDF(total_docs, ti.df);
-        } else {  // tf / df from the text on the device
-          p->texts.push_back(ti.normalized);
-          mt.text = reinterpret_cast<const uint8_t*>(p->texts.back().data());
-          mt.text_len = static_cast<uint32_t>(p->texts.back().size());
-        }
+      mgx_term mt{p->ids.back().data(), static_cast<uint32_t>(p->ids.back().size()), lf.threshold, 0.0, nullptr, 0};
+      bool with_text = tree_verify && !ti.normalized.empty();
+      if (q.sort_by_score && !lf.empty && lf.scored) {
+        // (with the text attached for the filter a single-gram term is scored from its text, like a FUZZY verify_text
+        // term: tf = CountTermOccurrences, which its gram's tf column holds, and df = its posting count, the same idf)
+        if (ti.is_gram) mt.idf = index::BM25Scorer::ComputeIDF(total_docs, ti.df);
+        else with_text = true;  // tf / df from the text on the device
+      }
+      if (with_text) {
+        p->texts.push_back(ti.normalized);
+        mt.text = reinterpret_cast<const uint8_t*>(p->texts.back().data());
+        mt.text_len = static_cast<uint32_t>(p->texts.back().size());
       }
       p->terms.push_back(mt);
     }
@@ -2331,6 +2386,7 @@ void PlanQuery(const index::Index& index, const BatchQuery& q, uint64_t total_do
     p->q.offset = q.sort_by_score ? q.offset : 0;
     p->q.expr = p->expr.data();
     p->q.n_expr = static_cast<uint32_t>(p->expr.size());
+    if (tree_verify) (fz != 0 ? p->q.fuzzy_verify_distance : p->q.exact_text) = fz != 0 ? fz : 1u;
     return;
   }
   if (q.terms.empty() || q.terms.size() > MGX_MAX_TERMS || q.not_terms.size() > MGX_MAX_TERMS)

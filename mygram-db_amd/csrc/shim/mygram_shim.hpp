@@ -413,6 +413,11 @@ struct BatchQuery {
   // tree (TERM = the term's doc set, NOT = every document of the index minus the child) and `terms` must be empty;
   // NOT terms and filters still apply to its result. With SORT _score the scored terms are the tree's TERM leaves that are
   // not under a NOT (CollectAstScoringTerms, search_pipeline.cpp:232-254), as SearchHandler scores them (:428-456).
+  // fuzzy_max_distance makes every leaf a FUZZY term (fuzzy_term_search :1424-1445). verify_text re-evaluates the tree
+  // over each candidate's stored text after NOT terms and filters (:1505-1578): a leaf is text.find(term), with FUZZY d
+  // that or ContainsFuzzyMatch(text, term, d); a leaf whose doc set is empty still counts there (under a NOT). On the
+  // device: mgx_query.exact_text / fuzzy_verify_distance beside expr. On a table with a delta each index filters its own
+  // candidates. `terms` beside a tree stays refused (query.and_terms is not served).
   std::shared_ptr<const query::QueryNode> ast;
   std::vector<std::string> not_terms;
   std::vector<std::pair<uint32_t, bool>> filters;  // (bitmap id from Index::AddFilterBitmap, negate = FilterOp::NE)

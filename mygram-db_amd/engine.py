@@ -979,6 +979,9 @@ class Index:
             shell.term_order = order
             orders.append(order)
             expr_tokens = None
+            # verify_text over an expression (search_pipeline.cpp:1505-1578): the tree is re-evaluated over each
+            # candidate's text, so every leaf carries its normalized text (exact_text / fuzzy_verify_distance + expr)
+            tree_verify = q.expr is not None and q.verify_text
             if q.expr is not None:
                 # ExecuteWithBooleanAst (search_pipeline.cpp:1408-1578): a term with an unknown gram is an empty
                 # doc set inside the tree, not the end of the query
@@ -996,7 +999,12 @@ class Index:
                 def emit(e):
                     if isinstance(e, str):
                         i = q.terms.index(e)
-                        toks.append((_capi.EXPR_EMPTY, 0) if leaf_empty(tis[i]) else (_capi.EXPR_TERM, i))
+                        # an empty leaf is still evaluated on the text under tree_verify (it matters under a NOT): it
+                        # goes as a TERM of the absent gram with its text; only "" is false there as well
+                        if leaf_empty(tis[i]) and not (tree_verify and tis[i].normalized):
+                            toks.append((_capi.EXPR_EMPTY, 0))
+                        else:
+                            toks.append((_capi.EXPR_TERM, i))
                         return
                     for c in e[1:]:
                         emit(c)
@@ -1022,7 +1030,7 @@ class Index:
                 # placeholder grams for EMPTY leaves so that every mgx_term stays well-formed
                 for t in tis:
                     if leaf_empty(t):
-                        t.gram_ids, t.threshold = [0], 0
+                        t.gram_ids, t.threshold = [_capi.GRAM_ABSENT if tree_verify else 0], 0
                     elif q.fuzzy:
                         t.gram_ids = t.fuzzy_ids
             elif any(t.estimated_size in (0, None) and (t.grams or not t.normalized) for t in tis):
@@ -1035,7 +1043,7 @@ class Index:
             exact = q.expr is None and (q.verify_text or any(
                 has_uncovered_hybrid_fragment(t.normalized, self.ngram_size, self.kanji_ngram_size, self.cross_boundary)
                 for t in tis))
-            if exact:
+            if exact or tree_verify:
                 self.ensure_text()
             cterms = (_capi.Term * len(tis))()
             for j, t in enumerate(tis):
@@ -1043,7 +1051,7 @@ class Index:
                 keep.append(ids)
                 thr = t.threshold if (q.fuzzy and t.threshold < len(ids)) else 0
                 idf, text_ptr, text_len = 0.0, None, 0
-                if exact or (not t.grams and q.expr is None):
+                if exact or (tree_verify and t.normalized) or (not t.grams and q.expr is None):
                     # (no grams at all: a term shorter than one n-gram — the device scans the texts for it,
                     # query::SearchNormalizedSubstring, src/query/substring_search.h:24-42)
                     self.ensure_text()
@@ -1087,7 +1095,9 @@ class Index:
                              C.cast(cf, C.c_void_p), len(q.filters),
                              _capi.SORT_SCORE if q.sort_score else _capi.SORT_DOCID, q.limit, q.offset,
                              int(q.descending), q.k1, q.b, self.total_docs, self.avg_doc_length)
-            cq.exact_text = int(exact)
+            cq.exact_text = int(exact or (tree_verify and not q.fuzzy))
+            if tree_verify and q.fuzzy:
+                cq.fuzzy_verify_distance = q.fuzzy
             _set_conditions(cq, q, keep)
             if expr_tokens is not None and q.sort_score:
                 sc = np.asarray(expr_scored, dtype=np.uint32)
