@@ -19,7 +19,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -29,6 +28,7 @@
 #include <vector>
 
 #include "../../include/mygram_gpu.h"
+#include "mgx_compile.hpp"
 #include "mgx_highlight.hpp"
 #include "mgx_host.hpp"
 #include "mgx_internal.hpp"
@@ -1271,556 +1271,6 @@ int mgx_index_synchronize(mgx_index* idx) {
 }  // extern "C"
 
 // =================================================================================================================
-// query compilation
-// =================================================================================================================
-
-namespace mgx {
-
-// One compiled query, before upload.
-struct QuerySpec {
-  std::vector<DevLeaf> leaves;
-  std::vector<uint32_t> prog;
-  std::vector<DevScoreTerm> score;
-  std::vector<uint32_t> explicit_ids;  // for kLeafExplicit leaves (offsets are relative to this vector)
-  std::vector<mgx_condition> conds;    // for kLeafCondBitmap leaves (a = index here until LayOutConditions gives them rows)
-  uint32_t mode = kModeBitmap;
-  uint32_t limit = 0, offset = 0, reverse = 0;
-  uint32_t stack_depth = 0;
-  double k1 = 1.2, b = 0.75, avgdl = 0.0;
-  uint64_t list_postings = 0;  // sum of |L| over gram operands (algorithmic bytes = 4x)
-  bool wave_ok = true;         // flat program + every scored term in its own register slot
-  bool flat = true;            // LOAD/AND/OR/ANDNOT/COUNT only
-  bool fast_score_ok = true;   // every scored term reads a dense gram's tf column (no text-level / absent terms)
-  double est_density = 0.0;    // estimated fraction of docs that match (work per tile grows with it)
-  // text-level scored terms (mgx_term.text): pattern bytes and the grams whose AND is the term's candidate set
-  struct TextTerm {
-    std::string pattern;
-    std::vector<uint32_t> grams;
-    uint32_t score_index = 0;  // position among the query's scored terms
-  };
-  std::vector<TextTerm> text_terms;
-  std::vector<std::string> verify_patterns;  // kOpVerifyText: every positive term's text
-  uint64_t total_docs = 0;       // N of ComputeIDF for the text-level terms
-  // SORT _score pages the fused top-k does not hold (offset + limit > kMaxNeeded, or limit 0 = all): every match is
-  // materialised, scored and fully sorted (ResultSorter::SortByScore's own shape, result_sorter.cpp:661-716)
-  bool deep_score = false;
-  std::vector<uint32_t> deep_grams;  // the scored terms' gram ids (kNoRow: a gram this shard lacks)
-  std::vector<double> deep_idfs;
-  uint32_t pat_off = 0, pat_len = 0;  // kModeTextDf specs: the term in the batch's pattern pool
-  uint32_t vt_begin = 0;              // first of the query's verify patterns in the batch-wide array
-  uint32_t fz_distance = 0;           // kOpVerifyFuzzy / kOpVerifyTree: d
-  bool fz_op = false;                 // the program has one of those two ops: the query runs the FZ instantiation of the general kernel
-  std::vector<uint32_t> verify_prog;  // kOpVerifyTree: the tree as postfix VerifyTok tokens over the op's patterns
-  uint32_t vp_begin = 0;              // its first token in the batch-wide array
-  // back to the freshly constructed state, keeping the vectors' storage (a re-prepared batch object compiles its new
-  // queries into the specs of the old ones)
-  void Clear() {
-    leaves.clear();
-    prog.clear();
-    score.clear();
-    explicit_ids.clear();
-    conds.clear();
-    text_terms.clear();
-    verify_patterns.clear();
-    deep_score = false;
-    deep_grams.clear();
-    deep_idfs.clear();
-    mode = kModeBitmap;
-    limit = offset = reverse = stack_depth = 0;
-    k1 = 1.2;
-    b = 0.75;
-    avgdl = 0.0;
-    list_postings = 0;
-    wave_ok = flat = fast_score_ok = true;
-    est_density = 0.0;
-    total_docs = 0;
-    pat_off = pat_len = vt_begin = fz_distance = vp_begin = 0;
-    fz_op = false;
-    verify_prog.clear();
-  }
-};
-
-struct Compiler {
-  const mgx_index* idx;
-  QuerySpec* q;
-  uint32_t sp = 0;
-
-  uint32_t GramLeaf(uint32_t g) {
-    // (a query has a handful of operands: a scan beats a hash map and allocates nothing)
-    for (uint32_t i = 0; i < q->leaves.size(); ++i) {
-      const DevLeaf& l = q->leaves[i];
-      if (g == MGX_GRAM_ABSENT ? (l.kind == kLeafRange && l.row == kNoRow && l.a == 0 && l.b == 0 && l.score_slot == kAbsentMark)
-                               : ((l.kind == kLeafList || l.kind == kLeafGramBitmap) && l.a == g))
-        return i;
-    }
-    DevLeaf lf{};
-    lf.score_slot = kNoSlot;
-    if (g == MGX_GRAM_ABSENT) {  // known to the table, no posting in this shard: the empty slot range
-      lf.kind = kLeafRange;
-      lf.row = kNoRow;
-      lf.score_slot = kAbsentMark;  // (tells this operand from the expression compiler's own empty ranges)
-      const uint32_t id = static_cast<uint32_t>(q->leaves.size());
-      q->leaves.push_back(lf);
-      return id;
-    }
-    lf.a = g;
-    lf.row = idx->h_skip_row[g];
-    if (idx->h_bm_row[g] != kNoRow) {
-      lf.kind = kLeafGramBitmap;
-      lf.b = idx->h_bm_row[g];
-    } else {
-      lf.kind = kLeafList;
-    }
-    const uint32_t id = static_cast<uint32_t>(q->leaves.size());
-    q->leaves.push_back(lf);
-    q->list_postings += idx->h_offsets[g + 1] - idx->h_offsets[g];
-    return id;
-  }
-  void Emit(Op op, uint32_t arg = 0) {
-    if (op == kOpCount) {
-      arg = 1u << arg;  // slot -> mask; consecutive counts of the same accumulator share one instruction
-      if (!q->prog.empty() && (q->prog.back() >> 24) == kOpCount) {
-        q->prog.back() |= arg;
-        return;
-      }
-    }
-    q->prog.push_back(MakeInstr(op, arg));
-    if (op != kOpLoad && op != kOpAnd && op != kOpOr && op != kOpAndNot && op != kOpCount) q->wave_ok = q->flat = false;
-    if (op == kOpPush) {
-      ++sp;
-      q->stack_depth = std::max(q->stack_depth, sp);
-    } else if (op == kOpPopAnd || op == kOpPopOr || op == kOpPopAndNot) {
-      --sp;
-    }
-  }
-  // acc = the term's doc set: AND of its grams, or "at least threshold of them"
-  // (SearchTermDocuments, search_pipeline.cpp:438-446; fuzzy terms :1697-1702)
-  uint32_t RangeLeaf(uint64_t lo, uint64_t hi) {  // doc slots [lo, hi) of this shard
-    DevLeaf lf{};
-    lf.score_slot = kNoSlot;
-    lf.row = kNoRow;
-    lf.kind = kLeafRange;
-    lf.a = static_cast<uint32_t>(lo);
-    lf.b = static_cast<uint32_t>(hi);
-    q->leaves.push_back(lf);
-    return static_cast<uint32_t>(q->leaves.size() - 1);
-  }
-  uint32_t FilterLeaf(uint32_t row) {
-    DevLeaf lf{};
-    lf.score_slot = kNoSlot;
-    lf.row = kNoRow;
-    lf.kind = kLeafFilterBitmap;
-    lf.b = row;
-    q->leaves.push_back(lf);
-    return static_cast<uint32_t>(q->leaves.size() - 1);
-  }
-  // kOpVerifyText argument for ONE more pattern of the query: its index among the query's patterns | count 1 << 12
-  uint32_t OnePattern(const mgx_term& t) {
-    q->verify_patterns.emplace_back(reinterpret_cast<const char*>(t.text), t.text_len);
-    return static_cast<uint32_t>(q->verify_patterns.size() - 1) | (1u << 12);
-  }
-  void LoadTerm(const mgx_term& t) {
-    if (t.n_grams == 0) {
-      // a term shorter than one n-gram: query::SearchNormalizedSubstring (src/query/substring_search.h:24-42) — every
-      // doc whose stored text contains it (SearchTermDocuments, search_pipeline.cpp:438-446)
-      Emit(kOpLoad, RangeLeaf(0, idx->dev.n_docs));
-      Emit(kOpVerifyText, OnePattern(t));
-      return;
-    }
-    if (t.threshold == 1 && t.n_grams > 1) {
-      // "at least one of its n-grams" is their union (FUZZY on a short term: theta = max(1, n - d * n_eff),
-      // search_pipeline.cpp:1700-1703): a flat program, which the wave kernels take
-      Emit(kOpLoad, GramLeaf(t.gram_ids[0]));
-      for (uint32_t i = 1; i < t.n_grams; ++i) Emit(kOpOr, GramLeaf(t.gram_ids[i]));
-    } else if (t.threshold != 0 && t.threshold < t.n_grams) {
-      Emit(kOpThreshBegin);
-      for (uint32_t i = 0; i < t.n_grams; ++i) Emit(kOpThreshAdd, GramLeaf(t.gram_ids[i]));
-      Emit(kOpThreshEnd, t.threshold);
-    } else {
-      Emit(kOpLoad, GramLeaf(t.gram_ids[0]));
-      for (uint32_t i = 1; i < t.n_grams; ++i) Emit(kOpAnd, GramLeaf(t.gram_ids[i]));
-    }
-  }
-};
-
-static int ValidateTerm(const mgx_index* idx, const mgx_term& t, const char* what) {
-  if (t.n_grams == 0) {  // substring term: needs its text and the docs' texts
-    if (!t.text || t.text_len == 0 || t.text_len > 4096)
-      return Fail(MGX_ERR_INVALID_ARGUMENT, std::string(what) + ": a term without grams needs its normalized text (1..4096 bytes)");
-    if (!idx->dev.text)
-      return Fail(MGX_ERR_INVALID_ARGUMENT, std::string(what) + ": a term without grams (substring search) needs mgx_index_attach_text");
-    return MGX_OK;
-  }
-  if (!t.gram_ids) return Fail(MGX_ERR_INVALID_ARGUMENT, std::string(what) + ": term without grams");
-  if (t.n_grams > 127) return Fail(MGX_ERR_OUT_OF_RANGE, std::string(what) + ": more than 127 grams in a term");
-  for (uint32_t i = 0; i < t.n_grams; ++i)
-    if (t.gram_ids[i] >= idx->n_grams && t.gram_ids[i] != MGX_GRAM_ABSENT)
-      return Fail(MGX_ERR_OUT_OF_RANGE, std::string(what) + ": unknown gram id");
-  return MGX_OK;
-}
-
-// search_pipeline::Execute (:812-853) as a tile program. Counter slots: 0 total_candidates, 1 after_intersection,
-// 2 after_not, 3 after_filters.
-static int CompileQuery(const mgx_index* idx, const mgx_query& in, QuerySpec* out) {
-  if (in.n_terms == 0 || !in.terms) return Fail(MGX_ERR_INVALID_ARGUMENT, "query without positive terms");
-  if (in.n_terms > MGX_MAX_TERMS || in.n_not_terms > MGX_MAX_TERMS || in.n_filters > MGX_MAX_TERMS)
-    return Fail(MGX_ERR_OUT_OF_RANGE, "more than 64 terms / NOT terms / filters (query_parser.h:270-272)");
-  if (static_cast<uint64_t>(in.n_filters) + in.n_conditions > MGX_MAX_TERMS)
-    return Fail(MGX_ERR_OUT_OF_RANGE, "more than 64 filters and conditions together (query_parser.h:270-272)");
-  if (in.n_conditions != 0) {
-    if (!in.conditions) return Fail(MGX_ERR_INVALID_ARGUMENT, "n_conditions without conditions");
-    const uint32_t n_columns = idx->n_filter_columns.load(std::memory_order_acquire);
-    for (uint32_t i = 0; i < in.n_conditions; ++i) {
-      if (in.conditions[i].op > MGX_CMP_GE) return Fail(MGX_ERR_INVALID_ARGUMENT, "condition: unknown operator");
-      if (in.conditions[i].column_id >= n_columns) return Fail(MGX_ERR_OUT_OF_RANGE, "condition: unknown filter column");
-    }
-  }
-  Compiler c{idx, out, 0};
-  for (uint32_t i = 0; i < in.n_terms; ++i) {
-    int rc = ValidateTerm(idx, in.terms[i], "term");
-    if (rc) return rc;
-  }
-  for (uint32_t i = 0; i < in.n_not_terms; ++i) {
-    int rc = ValidateTerm(idx, in.not_terms[i], "NOT term");
-    if (rc) return rc;
-  }
-  {
-    double dens = 1.0;
-    for (uint32_t i = 0; i < in.n_terms; ++i) {
-      uint64_t mn = in.terms[i].n_grams ? ~0ull : idx->dev.n_docs;  // (a substring term filters, it does not narrow the estimate)
-      for (uint32_t g = 0; g < in.terms[i].n_grams; ++g) {
-        const uint32_t id = in.terms[i].gram_ids[g];
-        mn = std::min<uint64_t>(mn, id == MGX_GRAM_ABSENT ? 0 : idx->h_offsets[id + 1] - idx->h_offsets[id]);
-      }
-      dens *= static_cast<double>(mn) / static_cast<double>(std::max<uint32_t>(idx->dev.n_docs, 1));
-    }
-    out->est_density = dens;
-  }
-  // a mutable table's main index: only its live documents exist (a removed document is in no posting list of the
-  // reference, index.cpp:148-197), so every funnel counter counts live documents only
-  const uint32_t live_row = idx->live_row.load(std::memory_order_relaxed);
-  const bool bitmaps_clean = idx->bitmaps_clean.load(std::memory_order_relaxed);
-  // (a term that is an AND of bitmap-form grams holds live documents only when the index keeps its bitmaps clean)
-  auto live_by_construction = [&](const mgx_term& t) {
-    if (!bitmaps_clean || t.n_grams == 0 || (t.threshold != 0 && t.threshold < t.n_grams)) return false;
-    for (uint32_t g = 0; g < t.n_grams; ++g)
-      if (t.gram_ids[g] != MGX_GRAM_ABSENT && idx->h_bm_row[t.gram_ids[g]] == kNoRow) return false;
-    return true;
-  };
-  auto and_live = [&](const mgx_term* first_term = nullptr) {
-    if (live_row == kNoRow) return;
-    if (first_term != nullptr && live_by_construction(*first_term)) return;
-    c.Emit(kOpAnd, c.FilterLeaf(live_row));
-  };
-  if (in.n_expr > 0) {
-    // ExecuteWithBooleanAst: the positive part is a boolean tree over the terms. Postfix -> tree -> accumulator code.
-    if (!in.expr) return Fail(MGX_ERR_INVALID_ARGUMENT, "n_expr without expr");
-    if (in.n_expr > 512) return Fail(MGX_ERR_OUT_OF_RANGE, "expression longer than 512 tokens");
-    struct Node {
-      uint32_t op, arg;
-      std::vector<int> kids;
-    };
-    std::vector<Node> nodes;
-    std::vector<int> st;
-    for (uint32_t k = 0; k < in.n_expr; ++k) {
-      const mgx_expr_token tk = in.expr[k];
-      Node n{tk.op, tk.arg, {}};
-      if (tk.op == MGX_EXPR_TERM) {
-        if (tk.arg >= in.n_terms) return Fail(MGX_ERR_OUT_OF_RANGE, "expression refers to a term that is not given");
-      } else if (tk.op == MGX_EXPR_AND || tk.op == MGX_EXPR_OR || tk.op == MGX_EXPR_NOT) {
-        const uint32_t nk = tk.op == MGX_EXPR_NOT ? 1u : tk.arg;
-        if (nk == 0 || nk > st.size()) return Fail(MGX_ERR_INVALID_ARGUMENT, "malformed postfix expression");
-        n.kids.assign(st.end() - nk, st.end());
-        st.resize(st.size() - nk);
-      } else if (tk.op != MGX_EXPR_EMPTY) {
-        return Fail(MGX_ERR_INVALID_ARGUMENT, "unknown expression token");
-      }
-      nodes.push_back(std::move(n));
-      st.push_back(static_cast<int>(nodes.size()) - 1);
-    }
-    if (st.size() != 1) return Fail(MGX_ERR_INVALID_ARGUMENT, "postfix expression does not reduce to one result");
-    // operand for the NOT universe / the empty set: a slot range of this shard
-    auto range_leaf = [&](uint64_t lo, uint64_t hi) {
-      DevLeaf lf{};
-      lf.score_slot = kNoSlot;
-      lf.row = kNoRow;
-      lf.kind = kLeafRange;
-      lf.a = static_cast<uint32_t>(lo);
-      lf.b = static_cast<uint32_t>(hi);
-      out->leaves.push_back(lf);
-      return static_cast<uint32_t>(out->leaves.size() - 1);
-    };
-    const uint64_t base = idx->dev.first_doc_id, span = idx->dev.n_docs;
-    uint64_t ulo = 0, uhi = span;
-    if (in.universe_count != 0) {
-      const uint64_t a = in.universe_first, b2 = a + in.universe_count;
-      ulo = a > base ? std::min(a - base, span) : 0;
-      uhi = b2 > base ? std::min(b2 - base, span) : 0;
-    }
-    uint32_t universe = kNoRow, empty = kNoRow;
-    std::function<void(int)> emit = [&](int ni) {
-      const Node& n = nodes[ni];
-      switch (n.op) {
-        case MGX_EXPR_TERM: c.LoadTerm(in.terms[n.arg]); break;
-        case MGX_EXPR_EMPTY:
-          if (empty == kNoRow) empty = range_leaf(0, 0);
-          c.Emit(kOpLoad, empty);
-          break;
-        case MGX_EXPR_AND:
-        case MGX_EXPR_OR:
-          emit(n.kids[0]);
-          for (size_t k = 1; k < n.kids.size(); ++k) {
-            c.Emit(kOpPush);
-            emit(n.kids[k]);
-            c.Emit(n.op == MGX_EXPR_AND ? kOpPopAnd : kOpPopOr);
-          }
-          break;
-        default:  // NOT: universe & ~child
-          if (universe == kNoRow) universe = range_leaf(ulo, uhi);
-          c.Emit(kOpLoad, universe);
-          c.Emit(kOpPush);
-          emit(n.kids[0]);
-          c.Emit(kOpPopAndNot);
-          break;
-      }
-    };
-    emit(st[0]);
-    if (out->stack_depth > 40) return Fail(MGX_ERR_OUT_OF_RANGE, "expression nests deeper than 40 levels");
-    and_live();
-    c.Emit(kOpCount, 0);
-    c.Emit(kOpCount, 1);
-  } else {
-    c.LoadTerm(in.terms[0]);
-    and_live(&in.terms[0]);
-    c.Emit(kOpCount, 0);
-    for (uint32_t i = 1; i < in.n_terms; ++i) {
-      const mgx_term& t = in.terms[i];
-      if (t.n_grams == 0) {  // substring term: the accumulator's docs whose text contains it (search_pipeline.cpp:817-826)
-        c.Emit(kOpVerifyText, c.OnePattern(t));
-      } else if (t.threshold != 0 && t.threshold < t.n_grams) {
-        c.Emit(kOpPush);
-        c.LoadTerm(t);
-        c.Emit(kOpPopAnd);
-      } else {
-        for (uint32_t g = 0; g < t.n_grams; ++g) c.Emit(kOpAnd, c.GramLeaf(t.gram_ids[g]));
-      }
-    }
-    c.Emit(kOpCount, 1);
-  }
-  for (uint32_t i = 0; i < in.n_not_terms; ++i) {
-    const mgx_term& t = in.not_terms[i];
-    if (t.n_grams == 1 && !(t.threshold != 0 && t.threshold < t.n_grams)) {
-      c.Emit(kOpAndNot, c.GramLeaf(t.gram_ids[0]));
-    } else {
-      c.Emit(kOpPush);
-      c.LoadTerm(t);
-      c.Emit(kOpPopAndNot);
-    }
-  }
-  c.Emit(kOpCount, 2);
-  for (uint32_t i = 0; i < in.n_filters; ++i) {
-    if (in.filters[i].bitmap_id >= idx->n_filter_rows) return Fail(MGX_ERR_OUT_OF_RANGE, "unknown filter bitmap id");
-    DevLeaf lf{};
-    lf.score_slot = kNoSlot;
-    lf.row = kNoRow;
-    lf.kind = kLeafFilterBitmap;
-    lf.b = in.filters[i].bitmap_id;
-    const uint32_t id = static_cast<uint32_t>(out->leaves.size());
-    out->leaves.push_back(lf);
-    c.Emit(in.filters[i].negate ? kOpAndNot : kOpAnd, id);
-  }
-  for (uint32_t i = 0; i < in.n_conditions; ++i) {  // a filter row in all but where it lives: the batch's own arena
-    DevLeaf lf{};
-    lf.score_slot = kNoSlot;
-    lf.row = kNoRow;
-    lf.kind = kLeafCondBitmap;
-    lf.a = static_cast<uint32_t>(out->conds.size());
-    out->conds.push_back(in.conditions[i]);
-    const uint32_t id = static_cast<uint32_t>(out->leaves.size());
-    out->leaves.push_back(lf);
-    c.Emit(in.conditions[i].negate ? kOpAndNot : kOpAnd, id);
-  }
-  c.Emit(kOpCount, 3);
-  if (in.n_expr > 0 && (in.exact_text || in.fuzzy_verify_distance != 0)) {
-    // the text post-filter of ExecuteWithBooleanAst (search_pipeline.cpp:1505-1578): the TREE is re-evaluated over each
-    // candidate's text, a TERM leaf being text.find(term), or that or ContainsFuzzyMatch(text, term, d)
-    if (in.exact_text && in.fuzzy_verify_distance != 0)
-      return Fail(MGX_ERR_INVALID_ARGUMENT, "expression: exact_text and fuzzy_verify_distance are one filter, set one of them");
-    if (in.fuzzy_verify_distance > 2) return Fail(MGX_ERR_INVALID_ARGUMENT, "fuzzy_verify_distance must be 0, 1 or 2");
-    if (!idx->dev.text)
-      return Fail(MGX_ERR_INVALID_ARGUMENT, "expression with exact_text / fuzzy_verify_distance without mgx_index_attach_text");
-    const uint32_t first_pat = static_cast<uint32_t>(out->verify_patterns.size());
-    std::vector<uint32_t> pat_of(in.n_terms, kNoRow);  // term -> its pattern: a term is matched once however often it is named
-    uint32_t depth = 0;
-    for (uint32_t k = 0; k < in.n_expr; ++k) {  // (arity and term indices were checked when the set program was built)
-      const mgx_expr_token tk = in.expr[k];
-      switch (tk.op) {
-        case MGX_EXPR_TERM: {
-          const mgx_term& t = in.terms[tk.arg];
-          if (!t.text || t.text_len == 0 || t.text_len > 4096)
-            return Fail(MGX_ERR_INVALID_ARGUMENT,
-                        "expression with a text filter: every TERM token's term needs its normalized text (1..4096 bytes)");
-          if (pat_of[tk.arg] == kNoRow) {
-            pat_of[tk.arg] = static_cast<uint32_t>(out->verify_patterns.size()) - first_pat;
-            out->verify_patterns.emplace_back(reinterpret_cast<const char*>(t.text), t.text_len);
-          }
-          out->verify_prog.push_back((kVerifyTerm << 24) | pat_of[tk.arg]);
-          ++depth;
-          break;
-        }
-        case MGX_EXPR_EMPTY:
-          out->verify_prog.push_back(kVerifyFalse << 24);
-          ++depth;
-          break;
-        case MGX_EXPR_NOT: out->verify_prog.push_back(kVerifyNot << 24); break;
-        default:
-          out->verify_prog.push_back(((tk.op == MGX_EXPR_AND ? kVerifyAnd : kVerifyOr) << 24) | tk.arg);
-          depth -= tk.arg - 1;
-          break;
-      }
-      if (depth > kMaxVerifyDepth)
-        return Fail(MGX_ERR_OUT_OF_RANGE, "expression with a text filter: more than 64 pending operands");
-    }
-    static_assert(MGX_MAX_TERMS <= kMaxVerifyPatterns && kMaxVerifyTokens == 512, "patterns are bits of a u64; n_expr <= 512");
-    // (not a flat op: the query runs on the general kernel's FZ instantiation) argument: first pattern | tokens << 12
-    c.Emit(kOpVerifyTree, first_pat | (in.n_expr << 12));
-    out->fz_distance = in.fuzzy_verify_distance;
-    out->fz_op = true;
-  } else if (in.fuzzy_verify_distance != 0) {
-    // PostFilterByFuzzyText (search_pipeline.cpp:1746-1755), before the exact-text rule of :1733-1741
-    if (in.fuzzy_verify_distance > 2)
-      return Fail(MGX_ERR_INVALID_ARGUMENT, "fuzzy_verify_distance must be 0, 1 or 2");
-    if (!idx->dev.text) return Fail(MGX_ERR_INVALID_ARGUMENT, "fuzzy_verify_distance without mgx_index_attach_text");
-    const uint32_t first_fz = static_cast<uint32_t>(out->verify_patterns.size());
-    for (uint32_t i = 0; i < in.n_terms; ++i) {
-      const mgx_term& t = in.terms[i];
-      if (!t.text || t.text_len == 0 || t.text_len > 4096)
-        return Fail(MGX_ERR_INVALID_ARGUMENT,
-                    "fuzzy_verify_distance: every positive term needs its normalized text (1..4096 bytes)");
-      out->verify_patterns.emplace_back(reinterpret_cast<const char*>(t.text), t.text_len);
-    }
-    // (not a flat op: the query runs on the general kernel's FZ instantiation) argument: first pattern | count << 12
-    c.Emit(kOpVerifyFuzzy, first_fz | (in.n_terms << 12));
-    out->fz_distance = in.fuzzy_verify_distance;
-    out->fz_op = true;
-  }
-  if (in.exact_text && in.n_expr == 0) {
-    if (!idx->dev.text) return Fail(MGX_ERR_INVALID_ARGUMENT, "exact_text without mgx_index_attach_text");
-    const uint32_t first_exact = static_cast<uint32_t>(out->verify_patterns.size());
-    for (uint32_t i = 0; i < in.n_terms; ++i) {
-      const mgx_term& t = in.terms[i];
-      if (!t.text || t.text_len == 0 || t.text_len > 4096)
-        return Fail(MGX_ERR_INVALID_ARGUMENT, "exact_text: every positive term needs its normalized text (1..4096 bytes)");
-      out->verify_patterns.emplace_back(reinterpret_cast<const char*>(t.text), t.text_len);
-    }
-    // (not a flat op: the query runs on the general workgroup kernel) argument: first pattern | count << 12
-    c.Emit(kOpVerifyText, first_exact | (in.n_terms << 12));
-  }
-
-  out->limit = in.limit;
-  out->offset = in.offset;
-  out->reverse = in.reverse;
-  out->k1 = in.k1;
-  out->b = in.b;
-  out->avgdl = in.avg_doc_length;
-  if (in.sort == MGX_SORT_SCORE) {
-    if (!idx->can_score) return Fail(MGX_ERR_NOT_IMPLEMENTED, "index was created without tf/doc_len columns");
-    // the scored terms: the caller's list (expression / FUZZY queries: search_handler.cpp:428-456 scores the positive
-    // terms of the tree or query, whatever branch produced the result set), or every positive term in order
-    const uint32_t n_scored = in.score_terms ? in.n_score_terms : in.n_terms;
-    auto scored_index = [&](uint32_t k) { return in.score_terms ? in.score_terms[k] : k; };
-    for (uint32_t k = 0; k < n_scored; ++k)
-      if (scored_index(k) >= in.n_terms) return Fail(MGX_ERR_OUT_OF_RANGE, "score_terms refers to a term that is not given");
-    const uint64_t needed = static_cast<uint64_t>(in.offset) + in.limit;
-    if (in.limit == 0 || needed > kMaxNeeded) {
-      // deep page (the reference is benchmarked with OFFSET 10000): the full-sort fallback. The matches are
-      // materialised like a docid-ordered result, then scored and sorted whole at fetch time.
-      for (uint32_t k = 0; k < n_scored; ++k) {
-        const mgx_term& t = in.terms[scored_index(k)];
-        if (t.text != nullptr) {
-          // a text-level term, as the fused path scores it: tf from the doc text, idf from the batch's df pass
-          // (PrepareInto numbers the term and puts kDeepText | its number in deep_grams[k])
-          if (!idx->dev.text)
-            return Fail(MGX_ERR_INVALID_ARGUMENT, "text-level scored term without mgx_index_attach_text");
-          if (t.text_len == 0 || t.text_len > 4096)
-            return Fail(MGX_ERR_OUT_OF_RANGE, "text-level scored term: length must be 1..4096 bytes");
-          QuerySpec::TextTerm tt;
-          tt.pattern.assign(reinterpret_cast<const char*>(t.text), t.text_len);
-          tt.grams.assign(t.gram_ids, t.gram_ids + t.n_grams);
-          tt.score_index = k;
-          out->text_terms.push_back(std::move(tt));
-          out->deep_grams.push_back(kDeepText);
-          out->deep_idfs.push_back(0.0);
-          continue;
-        }
-        if (t.n_grams != 1)
-          return Fail(MGX_ERR_INVALID_ARGUMENT,
-                      "a scored term of several n-grams needs its text (mgx_term.text) for tf and df");
-        out->deep_grams.push_back(t.gram_ids[0] == MGX_GRAM_ABSENT ? kNoRow : t.gram_ids[0]);
-        out->deep_idfs.push_back(t.idf);
-      }
-      out->deep_score = true;
-      out->total_docs = in.total_docs;
-      out->mode = kModeBitmap;
-      if (out->leaves.size() > kMaxLeaves)
-        return Fail(MGX_ERR_NOT_IMPLEMENTED, "more than 192 distinct operands in one query");
-      return MGX_OK;
-    }
-    if (n_scored > kMaxScoreTerms) return Fail(MGX_ERR_NOT_IMPLEMENTED, "more than 64 scored terms");
-    out->mode = kModeScore;
-    out->total_docs = in.total_docs;
-    if (in.score_terms) out->wave_ok = out->fast_score_ok = false;  // (a listed term need not be an AND operand of the result: the general kernel tests membership)
-    for (uint32_t i = 0; i < n_scored; ++i) {
-      const mgx_term& t = in.terms[scored_index(i)];
-      if (t.text != nullptr) {
-        // tf from the doc text, df from a scan of the term's candidates (N1: terms that are not one n-gram)
-        if (!idx->dev.text)
-          return Fail(MGX_ERR_INVALID_ARGUMENT, "text-level scored term without mgx_index_attach_text");
-        if (t.text_len == 0 || t.text_len > 4096)
-          return Fail(MGX_ERR_OUT_OF_RANGE, "text-level scored term: length must be 1..4096 bytes");
-        // (a FUZZY term is scored as the exact term: tf = its occurrences in the text, df = the candidates of the AND of
-        // ALL its n-grams whose text contains it — PopulateTermDocumentFrequency does not know about the threshold)
-        QuerySpec::TextTerm tt;
-        tt.pattern.assign(reinterpret_cast<const char*>(t.text), t.text_len);
-        tt.grams.assign(t.gram_ids, t.gram_ids + t.n_grams);
-        tt.score_index = i;
-        out->text_terms.push_back(std::move(tt));
-        DevScoreTerm st{};
-        st.leaf = kNoLeaf;
-        out->wave_ok = out->fast_score_ok = false;  // the wave kernels score from tf columns only
-        out->score.push_back(st);
-        continue;
-      }
-      if (t.n_grams != 1)
-        return Fail(MGX_ERR_INVALID_ARGUMENT,
-                    "a scored term of several n-grams needs its text (mgx_term.text) for tf and df");
-      DevScoreTerm st{};
-      st.leaf = c.GramLeaf(t.gram_ids[0]);
-      st.idf = t.idf;
-      // the same gram scored twice (a repeated term) keeps the first slot; the block kernel handles that shape
-      if (t.gram_ids[0] == MGX_GRAM_ABSENT)
-        out->wave_ok = out->fast_score_ok = false;  // an empty operand: never a member, contributes nothing
-      else if (out->leaves[st.leaf].score_slot == kNoSlot && i < static_cast<uint32_t>(kWaveScoreSlots))
-        out->leaves[st.leaf].score_slot = i;
-      else
-        out->wave_ok = false;
-      out->score.push_back(st);
-    }
-  } else if (in.sort == MGX_SORT_DOCID) {
-    // a bounded page in docid order needs no materialised result bitmap: count pass + page pass
-    out->mode = (in.limit != 0 && in.limit <= kMaxDocPage) ? kModeDocPage : kModeBitmap;
-    out->offset = 0;  // (pagination offset belongs to SORT _score, search_handler.cpp:469-470)
-  } else {
-    return Fail(MGX_ERR_INVALID_ARGUMENT, "unknown sort");
-  }
-  if (out->leaves.size() > kMaxLeaves)
-    return Fail(MGX_ERR_NOT_IMPLEMENTED, "more than 192 distinct operands in one query");
-  return MGX_OK;
-}
-
-}  // namespace mgx
-
-// =================================================================================================================
 // batch
 // =================================================================================================================
 
@@ -2708,6 +2158,33 @@ static int UploadGroup(mgx_batch* b, Group& g, uint32_t mode, const std::vector<
   return MGX_OK;
 }
 
+// The host facts the query compiler reads (mgx_compile.hpp): one per CompileAll, single-operator call and df pass.
+static CompileView ViewOf(const mgx_index* idx) {
+  CompileView v;
+  v.offsets = idx->h_offsets.data();
+  v.skip_row = idx->h_skip_row.data();
+  v.bm_row = idx->h_bm_row.data();
+  v.n_grams = idx->n_grams;
+  v.n_docs = idx->dev.n_docs;
+  v.first_doc_id = idx->dev.first_doc_id;
+  v.has_text = idx->dev.text != nullptr;
+  v.can_score = idx->can_score;
+  v.n_filter_rows = idx->n_filter_rows;
+  v.n_filter_columns = idx->n_filter_columns.load(std::memory_order_acquire);
+  v.live_row = idx->live_row.load(std::memory_order_relaxed);
+  v.bitmaps_clean = idx->bitmaps_clean.load(std::memory_order_relaxed);
+  return v;
+}
+
+// queries [a, b) into their specs, up to the first that fails: its code, and "query i: <its message>" as the last error
+static int CompileRange(const CompileView& view, const mgx_query* queries, std::vector<QuerySpec>* specs, uint32_t a, uint32_t b) {
+  for (uint32_t i = a; i < b; ++i) {
+    (*specs)[i].Clear();
+    if (const int rc = CompileQuery(view, queries[i], &(*specs)[i])) return Fail(rc, "query " + std::to_string(i) + ": " + g_last_error);
+  }
+  return MGX_OK;
+}
+
 // CompileQuery over a whole batch. Queries are independent, so batches of a few hundred and more are cut into chunks for
 // a small process-wide helper pool (MGX_COMPILE_THREADS helpers, default 3, beside the calling thread): on a doc-range
 // shard the device finishes a batch in a fraction of a millisecond and the host's per-batch compile is what a rank's
@@ -2716,7 +2193,7 @@ struct CompilePool {
   std::mutex mu, gate;
   std::condition_variable cv_work, cv_done;
   std::vector<std::thread> helpers;
-  const mgx_index* idx = nullptr;
+  const CompileView* view = nullptr;
   const mgx_query* queries = nullptr;
   std::vector<QuerySpec>* specs = nullptr;
   uint32_t next = 0, end = 0, pending = 0;
@@ -2730,17 +2207,11 @@ struct CompilePool {
       const uint32_t a = next, b = std::min(end, a + kChunk);
       next = b;
       lock.unlock();
-      int local = MGX_OK;
-      std::string msg;
-      for (uint32_t i = a; i < b && local == MGX_OK; ++i) {
-        (*specs)[i].Clear();
-        local = CompileQuery(idx, queries[i], &(*specs)[i]);
-        if (local) msg = "query " + std::to_string(i) + ": " + g_last_error;
-      }
+      const int local = CompileRange(*view, queries, specs, a, b);
       lock.lock();
       if (local && rc == MGX_OK) {
         rc = local;
-        error = msg;
+        error = g_last_error;
       }
       pending -= b - a;
     }
@@ -2776,20 +2247,11 @@ static int CompileAll(const mgx_index* idx, const mgx_query* queries, uint32_t n
   // one pool per calling thread: an executor's dispatcher threads compile different batches at the same time, and a
   // shared pool handed its helpers to one of them while the other compiled its 1024 queries alone (4x the time)
   static thread_local CompilePool pool;
+  const CompileView view = ViewOf(idx);
   std::unique_lock<std::mutex> gate(pool.gate, std::try_to_lock);
-  if (n < 4 * CompilePool::kChunk || pool.helpers.empty() || !gate.owns_lock()) {
-    for (uint32_t i = 0; i < n; ++i) {
-      (*specs)[i].Clear();
-      const int rc = CompileQuery(idx, queries[i], &(*specs)[i]);
-      if (rc) {
-        SetError("query " + std::to_string(i) + ": " + g_last_error);
-        return rc;
-      }
-    }
-    return MGX_OK;
-  }
+  if (n < 4 * CompilePool::kChunk || pool.helpers.empty() || !gate.owns_lock()) return CompileRange(view, queries, specs, 0, n);
   std::unique_lock<std::mutex> lock(pool.mu);
-  pool.idx = idx;
+  pool.view = &view;
   pool.queries = queries;
   pool.specs = specs;
   pool.next = 0;
@@ -2869,6 +2331,53 @@ static int LayOutConditions(mgx_batch* b) {
   return MGX_OK;
 }
 
+// Text-level scored terms: numbered across the batch and deduplicated — the df of a term depends on the term (and on
+// N), not on the query around it — their bytes pooled, and one df query compiled per distinct term (b->df_specs).
+static int NumberTextTerms(mgx_batch* b, std::string* pool, std::vector<DevTextTerm>* tts) {
+  mgx_index* idx = b->idx;
+  const CompileView view = ViewOf(idx);
+  std::map<std::pair<std::string, uint64_t>, uint32_t> seen;
+  for (QuerySpec& s : b->specs) {
+    for (const QuerySpec::TextTerm& tt : s.text_terms) {
+      const auto ins = seen.emplace(std::make_pair(tt.pattern, s.total_docs), static_cast<uint32_t>(tts->size()));
+      const uint32_t id = ins.first->second;
+      if (s.deep_score) s.deep_grams[tt.score_index] = kDeepText | id;
+      else s.score[tt.score_index].text_term = id;
+      if (!ins.second) continue;
+      const DevTextTerm d{static_cast<uint32_t>(pool->size()), static_cast<uint32_t>(tt.pattern.size())};
+      *pool += tt.pattern;
+      tts->push_back(d);
+      b->text_total_docs.push_back(s.total_docs);
+      std::string ckey = tt.pattern + '\0' + std::to_string(s.total_docs);
+      uint64_t known = ~0ull;
+      {
+        std::lock_guard<std::mutex> lock(idx->table_mu);
+        const auto hit = idx->df_cache.find(ckey);
+        if (hit != idx->df_cache.end()) known = hit->second;
+      }
+      b->text_df_known.push_back(tt.grams.empty() ? 0ull : known);
+      b->text_df_key.push_back(std::move(ckey));
+      QuerySpec ds;
+      if (const int rc = CompileTextDf(view, tt.grams, tt.grams.empty() || known != ~0ull, d.pat_off, d.pat_len, &ds)) return rc;
+      b->df_specs.push_back(std::move(ds));
+    }
+  }
+  return MGX_OK;
+}
+
+// The patterns of the exact-text / FUZZY / tree filters share the pool; the tree filters' verify programs one array.
+static void PoolVerifyPatterns(mgx_batch* b, std::string* pool, std::vector<DevTextTerm>* vts, std::vector<uint32_t>* vprog) {
+  for (QuerySpec& s : b->specs) {
+    s.vt_begin = static_cast<uint32_t>(vts->size());
+    s.vp_begin = static_cast<uint32_t>(vprog->size());
+    vprog->insert(vprog->end(), s.verify_prog.begin(), s.verify_prog.end());
+    for (const std::string& pat : s.verify_patterns) {
+      vts->push_back(DevTextTerm{static_cast<uint32_t>(pool->size()), static_cast<uint32_t>(pat.size())});
+      *pool += pat;
+    }
+  }
+}
+
 // Compiles `specs` into batch object `b` (fresh, or just emptied by ResetBatch): every device array comes from the
 // batch's arenas, nothing is copied to the device here — the first execute ships the upload arena.
 static int PrepareInto(mgx_batch* b, mgx_index* idx, std::vector<QuerySpec>&& specs) {
@@ -2882,101 +2391,25 @@ static int PrepareInto(mgx_batch* b, mgx_index* idx, std::vector<QuerySpec>&& sp
   }
   MGX_HIP(hipSetDevice(idx->device));
   if (const int rc = LayOutConditions(b)) return rc;
-  // text-level scored terms: number them across the batch, pool their bytes, and give each one a df query
-  {
-    std::string pool;
-    std::vector<DevTextTerm> tts;
-    // the df of a term depends on the term (and on N), not on the query around it: one df query per distinct term
-    std::map<std::pair<std::string, uint64_t>, uint32_t> seen;
-    for (QuerySpec& s : b->specs) {
-      for (const QuerySpec::TextTerm& tt : s.text_terms) {
-        const auto key = std::make_pair(tt.pattern, s.total_docs);
-        const auto hit = seen.find(key);
-        if (hit != seen.end()) {
-          if (s.deep_score) s.deep_grams[tt.score_index] = kDeepText | hit->second;
-          else s.score[tt.score_index].text_term = hit->second;
-          continue;
-        }
-        const uint32_t id = static_cast<uint32_t>(tts.size());
-        seen.emplace(key, id);
-        DevTextTerm d{static_cast<uint32_t>(pool.size()), static_cast<uint32_t>(tt.pattern.size())};
-        pool += tt.pattern;
-        tts.push_back(d);
-        if (s.deep_score) s.deep_grams[tt.score_index] = kDeepText | id;
-        else s.score[tt.score_index].text_term = id;
-        b->text_total_docs.push_back(s.total_docs);
-        QuerySpec ds;
-        ds.mode = kModeTextDf;
-        ds.pat_off = d.pat_off;
-        ds.pat_len = d.pat_len;
-        Compiler c{idx, &ds, 0};
-        double dens = 1.0;
-        uint64_t mn = ~0ull;
-        std::string ckey = tt.pattern;
-        ckey.push_back('\0');
-        ckey += std::to_string(s.total_docs);
-        uint64_t known = ~0ull;
-        {
-          std::lock_guard<std::mutex> lock(idx->table_mu);
-          const auto hit = idx->df_cache.find(ckey);
-          if (hit != idx->df_cache.end()) known = hit->second;
-        }
-        b->text_df_known.push_back(tt.grams.empty() ? 0ull : known);
-        b->text_df_key.push_back(std::move(ckey));
-        if (tt.grams.empty() || known != ~0ull) {
-          // nothing to count: a term shorter than one n-gram has df 0 (PopulateTermDocumentFrequency returns before
-          // counting, search_pipeline.cpp:546-549), a term seen before has this shard's count in the index's cache — the
-          // df query runs over the empty doc range and the known LOCAL value takes its place on the device
-          // (gather_df_kernel), before any rank sums the counts
-          c.Emit(kOpLoad, c.RangeLeaf(0, 0));
-          mn = 0;
-        } else {
-          c.Emit(kOpLoad, c.GramLeaf(tt.grams[0]));
-          for (size_t k = 1; k < tt.grams.size(); ++k) c.Emit(kOpAnd, c.GramLeaf(tt.grams[k]));
-          const uint32_t live_row = idx->live_row.load(std::memory_order_relaxed);
-          bool all_bitmaps = idx->bitmaps_clean.load(std::memory_order_relaxed);
-          for (uint32_t gid : tt.grams) all_bitmaps = all_bitmaps && (gid == MGX_GRAM_ABSENT || idx->h_bm_row[gid] != kNoRow);
-          if (live_row != kNoRow && !all_bitmaps) c.Emit(kOpAnd, c.FilterLeaf(live_row));  // (df counts live documents only)
-        }
-        for (uint32_t gid : tt.grams)
-          mn = std::min<uint64_t>(mn, gid == MGX_GRAM_ABSENT ? 0 : idx->h_offsets[gid + 1] - idx->h_offsets[gid]);
-        dens = static_cast<double>(mn) / static_cast<double>(std::max<uint32_t>(idx->dev.n_docs, 1));
-        ds.est_density = dens;
-        if (ds.leaves.size() > kMaxLeaves)
-          return Fail(MGX_ERR_NOT_IMPLEMENTED, "more than 192 distinct n-grams in one text-level term");
-        b->df_specs.push_back(std::move(ds));
-      }
-    }
-    // exact-text filters: their patterns share the pool
-    std::vector<DevTextTerm> vts;
-    std::vector<uint32_t> vprog;  // ... and the verify programs of the expression queries among them
-    for (QuerySpec& s : b->specs) {
-      s.vt_begin = static_cast<uint32_t>(vts.size());
-      s.vp_begin = static_cast<uint32_t>(vprog.size());
-      vprog.insert(vprog.end(), s.verify_prog.begin(), s.verify_prog.end());
-      for (const std::string& pat : s.verify_patterns) {
-        vts.push_back(DevTextTerm{static_cast<uint32_t>(pool.size()), static_cast<uint32_t>(pat.size())});
-        pool += pat;
-      }
-    }
-    if (!vprog.empty()) MGX_HIP(Upload(b->d_verify_prog, vprog.data(), vprog.size()));
-    if (!vts.empty()) {
-      MGX_HIP(Upload(b->d_verify_terms, vts.data(), vts.size()));
-      if (tts.empty()) MGX_HIP(Upload(b->d_patterns, reinterpret_cast<const uint8_t*>(pool.data()), pool.size(), 16));
-    }
-    const uint32_t n_tt = static_cast<uint32_t>(tts.size());
-    if (n_tt != 0) {
-      MGX_HIP(Upload(b->d_patterns, reinterpret_cast<const uint8_t*>(pool.data()), pool.size(), 16));
-      MGX_HIP(Upload(b->d_text_terms, tts.data(), tts.size()));
-      MGX_HIP(b->d_text_idf.Alloc(static_cast<size_t>(n_tt) * sizeof(double)));
-      MGX_HIP(b->d_text_df.Alloc(static_cast<size_t>(n_tt) * sizeof(uint64_t)));
-      MGX_HIP(b->d_text_df_local.Alloc(static_cast<size_t>(n_tt) * sizeof(uint64_t)));
-      MGX_HIP(Upload(b->d_text_df_known, b->text_df_known.data(), b->text_df_known.size()));
-      b->h_text_df.assign(n_tt, 0);
-      b->h_text_df_local.assign(n_tt, 0);
-      b->h_text_idf.assign(n_tt, 0.0);
-      for (uint32_t i = 0; i < n_tt; ++i) b->textdf.qids.push_back(i);
-    }
+  std::string pool;  // the bytes of every pattern of the batch: text-level scored terms, then verify patterns
+  std::vector<DevTextTerm> tts, vts;
+  std::vector<uint32_t> vprog;
+  if (const int rc = NumberTextTerms(b, &pool, &tts)) return rc;
+  PoolVerifyPatterns(b, &pool, &vts, &vprog);
+  if (!vprog.empty()) MGX_HIP(Upload(b->d_verify_prog, vprog.data(), vprog.size()));
+  if (!vts.empty()) MGX_HIP(Upload(b->d_verify_terms, vts.data(), vts.size()));
+  if (!pool.empty()) MGX_HIP(Upload(b->d_patterns, reinterpret_cast<const uint8_t*>(pool.data()), pool.size(), 16));
+  const uint32_t n_tt = static_cast<uint32_t>(tts.size());
+  if (n_tt != 0) {
+    MGX_HIP(Upload(b->d_text_terms, tts.data(), tts.size()));
+    MGX_HIP(b->d_text_idf.Alloc(static_cast<size_t>(n_tt) * sizeof(double)));
+    MGX_HIP(b->d_text_df.Alloc(static_cast<size_t>(n_tt) * sizeof(uint64_t)));
+    MGX_HIP(b->d_text_df_local.Alloc(static_cast<size_t>(n_tt) * sizeof(uint64_t)));
+    MGX_HIP(Upload(b->d_text_df_known, b->text_df_known.data(), b->text_df_known.size()));
+    b->h_text_df.assign(n_tt, 0);
+    b->h_text_df_local.assign(n_tt, 0);
+    b->h_text_idf.assign(n_tt, 0.0);
+    for (uint32_t i = 0; i < n_tt; ++i) b->textdf.qids.push_back(i);
   }
   int rc = UploadGroup(b, b->score, kModeScore, b->specs);
   if (rc) return rc;
@@ -4535,7 +3968,8 @@ template <class Emit>
 int RunSingle(mgx_index* idx, const char* name, uint32_t** out_docs, uint64_t* out_n, Emit&& emit) {
   return Guarded(name, [&] {
     mgx::QuerySpec q;
-    mgx::Compiler c{idx, &q, 0};
+    const mgx::CompileView view = mgx::ViewOf(idx);
+    mgx::Compiler c{&view, &q, 0};
     const int rc = emit(c, q);
     if (rc) return rc;
     if (q.leaves.size() > mgx::kMaxLeaves)
@@ -4588,7 +4022,7 @@ int mgx_facet_counts(mgx_index* idx, const mgx_query* query, uint32_t column_id,
     q.score_terms = nullptr;
     q.n_score_terms = 0;
     mgx::QuerySpec spec;
-    int rc = mgx::CompileQuery(idx, q, &spec);
+    int rc = mgx::CompileQuery(mgx::ViewOf(idx), q, &spec);
     if (rc) return rc;
     const mgx_index::FilterColumn* colp = nullptr;
     {
@@ -4661,14 +4095,7 @@ int mgx_not(mgx_index* idx, const uint32_t* all_docs, uint64_t n_all, const uint
       else if (all_docs[i] >= hi) above.push_back(all_docs[i]);
       else q.explicit_ids.push_back(all_docs[i]);
     }
-    mgx::DevLeaf lf{};
-    lf.score_slot = mgx::kNoSlot;
-    lf.row = mgx::kNoRow;
-    lf.kind = mgx::kLeafExplicit;
-    lf.a = 0;
-    lf.b = static_cast<uint32_t>(q.explicit_ids.size());
-    q.leaves.push_back(lf);
-    c.Emit(mgx::kOpLoad, 0);
+    c.Emit(mgx::kOpLoad, c.Leaf(mgx::kLeafExplicit, 0, static_cast<uint32_t>(q.explicit_ids.size())));
     for (uint32_t i = 0; i < n; ++i) c.Emit(mgx::kOpAndNot, c.GramLeaf(gram_ids[i]));
     return MGX_OK;
   });
