@@ -7,7 +7,7 @@ LIB := mygram-db_amd/libmygram_gpu.so
 CXXFLAGS := -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wextra -Wno-unused-parameter -Iinclude
 HIPFLAGS := --offload-arch=$(ARCH) $(CXXFLAGS)
 
-OBJS := $(CSRC)/mgx_kernels.o $(CSRC)/mgx_highlight.o $(CSRC)/mgx_api.o $(CSRC)/mgx_compile.o $(CSRC)/mgx_columns.o $(CSRC)/mgx_tools.o
+OBJS := $(CSRC)/mgx_kernels.o $(CSRC)/mgx_highlight.o $(CSRC)/mgx_colsort.o $(CSRC)/mgx_api.o $(CSRC)/mgx_compile.o $(CSRC)/mgx_columns.o $(CSRC)/mgx_tools.o
 
 SHIM := mygram-db_amd/libmygram_shim.so
 
@@ -18,7 +18,10 @@ $(CSRC)/mgx_kernels.o: $(CSRC)/mgx_kernels.hip $(CSRC)/mgx_internal.hpp $(CSRC)/
 # the HIGHLIGHT kernel is a translation unit of its own: the code of every other kernel is compiled from unchanged input
 $(CSRC)/mgx_highlight.o: $(CSRC)/mgx_highlight.hip $(CSRC)/mgx_highlight.hpp $(CSRC)/mgx_internal.hpp $(CSRC)/mgx_launch.hpp
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(CSRC)/mgx_api.o: $(CSRC)/mgx_api.cpp $(CSRC)/mgx_compile.hpp $(CSRC)/mgx_internal.hpp $(CSRC)/mgx_launch.hpp $(CSRC)/mgx_host.hpp $(CSRC)/mgx_highlight.hpp include/mygram_gpu.h
+# SORT <filter column>: its kernels too are a unit of their own (it restates the comparator it shares with the others)
+$(CSRC)/mgx_colsort.o: $(CSRC)/mgx_colsort.hip $(CSRC)/mgx_colsort.hpp
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+$(CSRC)/mgx_api.o: $(CSRC)/mgx_api.cpp $(CSRC)/mgx_colsort.hpp $(CSRC)/mgx_compile.hpp $(CSRC)/mgx_internal.hpp $(CSRC)/mgx_launch.hpp $(CSRC)/mgx_host.hpp $(CSRC)/mgx_highlight.hpp include/mygram_gpu.h
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
 $(CSRC)/mgx_compile.o: $(CSRC)/mgx_compile.cpp $(CSRC)/mgx_compile.hpp $(CSRC)/mgx_internal.hpp $(CSRC)/mgx_host.hpp include/mygram_gpu.h
 	g++ $(CXXFLAGS) -c $< -o $@
@@ -47,9 +50,15 @@ oracle:
 ablation:
 	$(HIPCC) $(HIPFLAGS) -DMGX_ABLATION -c $(CSRC)/mgx_kernels.hip -o /tmp/mgx_kernels_abl.o
 	$(HIPCC) $(HIPFLAGS) -DMGX_ABLATION -x hip -c $(CSRC)/mgx_api.cpp -o /tmp/mgx_api_abl.o
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o mygram-db_amd/libmygram_gpu_ablation.so /tmp/mgx_kernels_abl.o $(CSRC)/mgx_highlight.o /tmp/mgx_api_abl.o $(CSRC)/mgx_compile.o $(CSRC)/mgx_columns.o $(CSRC)/mgx_tools.o -pthread
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o mygram-db_amd/libmygram_gpu_ablation.so /tmp/mgx_kernels_abl.o $(CSRC)/mgx_highlight.o $(CSRC)/mgx_colsort.o /tmp/mgx_api_abl.o $(CSRC)/mgx_compile.o $(CSRC)/mgx_columns.o $(CSRC)/mgx_tools.o -pthread
+
+# the host pieces of mgx_colsort.hpp (key transform, collision scan) under the sanitizers: a stand-alone program, no GPU
+colsort-host-asan:
+	g++ -O1 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -o colsort_host_check_asan tests/cpp/colsort_host_check.cpp
+	python3 tests/test_column_sort_cpu.py > colsort_host_check_lines.txt
+	./colsort_host_check_asan colsort_host_check_lines.txt
 
 clean:
-	rm -f $(OBJS) $(LIB) $(SHIM)
+	rm -f $(OBJS) $(LIB) $(SHIM) colsort_host_check_asan colsort_host_check_lines.txt
 	$(MAKE) -C oracle clean
-.PHONY: all oracle clean ablation
+.PHONY: all oracle clean ablation colsort-host-asan

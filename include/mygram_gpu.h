@@ -243,6 +243,26 @@ int mgx_index_attach_text(mgx_index* idx, const uint8_t* text_bytes, const uint6
 
 #define MGX_SORT_DOCID 0u /* no SORT _score: docid order; `reverse` selects descending (SearchAnd limit/reverse) */
 #define MGX_SORT_SCORE 1u /* SORT _score: BM25 + ResultSorter::SortByScore */
+/* SORT <filter column> ASC|DESC (ResultSorter::SortAndPaginate, result_sorter.cpp:489-650): the result set ordered by
+ * the column mgx_query.sort_column (an id from mgx_index_add_filter_column) before offset / limit. `reverse` = 1: DESC.
+ * The order is that of the reference's string keys (FilterValueToSortKey, :187-217) restated in 64 bits: signed values
+ * (bool, int8..int64, TimeValue) by value; doubles by their bits in IEEE total order (-0.0 before +0.0, NaNs by their
+ * bits); unsigned values v as v + 2^63 up to INT64_MAX and as v above it (the reference's own rule, :205-212, kept);
+ * NULL first in ASC and last in DESC; ties by doc id in the sort's own direction (:43-54). Any limit (0 = all) and any
+ * offset; scores come back 0.0; totals and funnel counters as without SORT.
+ * MGX_SORT_COLUMN_RANK: the same on an MGX_FC_UNSIGNED column that holds ranks in the caller's bytewise-sorted string
+ * dictionary: the key is rank + sort_key_bias, bias 0 when the dictionary holds the empty string (which then ties with
+ * NULL as in the reference, both keys being ""), otherwise 1. The ranks of two dictionaries do not compare: a table with
+ * a delta index sorts by such a column only after it is compacted.
+ * Refused: an unknown column MGX_ERR_OUT_OF_RANGE; sort_key_bias above 1, or non-zero with MGX_SORT_COLUMN,
+ * MGX_ERR_INVALID_ARGUMENT; MGX_SORT_COLUMN_RANK on a column of another class MGX_ERR_INVALID_ARGUMENT. With
+ * MGX_ERR_NOT_IMPLEMENTED and a message: a column that holds NULLs beside a value whose key is also 0 (INT64_MIN; the
+ * double whose bits are all ones), which 64 bits cannot tell apart (mgx_index_add_filter_column marks it; without NULLs
+ * such a column sorts exactly; mgx_batch_merge_local refuses the same way when the main index's and the delta's column
+ * hold the two between them); the sharded entry points (mgx_batch_export_topk / _export_buffer, _merge_shards,
+ * _exchange, _execute_gather, _execute_sharded); a highlighted batch that holds such a query. */
+#define MGX_SORT_COLUMN 2u
+#define MGX_SORT_COLUMN_RANK 3u
 
 #define MGX_MAX_TERMS 64u /* query_parser.h:270-272 */
 /* Gram id of an n-gram the TABLE knows but this doc-range shard holds no posting for: an empty doc set. (A gram the
@@ -325,8 +345,11 @@ typedef struct mgx_query {
   uint32_t n_filters;
   uint32_t sort;    /* MGX_SORT_* */
   uint32_t limit;   /* 0 => all */
-  uint32_t offset;  /* MGX_SORT_SCORE only */
-  uint32_t reverse; /* MGX_SORT_DOCID: descending docids; MGX_SORT_SCORE: 1 => SortOrder::DESC */
+  uint32_t offset;  /* MGX_SORT_SCORE and MGX_SORT_COLUMN / _RANK */
+  uint32_t reverse; /* MGX_SORT_DOCID: descending docids; MGX_SORT_SCORE / MGX_SORT_COLUMN: 1 => SortOrder::DESC */
+  uint32_t sort_column; /* MGX_SORT_COLUMN / _RANK: the column's id. (It and sort_key_bias fill what was padding: no other
+                         * field moves and the struct keeps its size, so MGX_ABI_VERSION stays; a zero-initialised
+                         * struct means what it meant.) */
   double k1, b;     /* BM25Params (bm25_scorer.h:20-23) */
   uint64_t total_docs;    /* BM25Stats::doc_count; only documents the caller's idf values already encode */
   double avg_doc_length;  /* BM25Stats::avg_doc_length() */
@@ -349,6 +372,7 @@ typedef struct mgx_query {
    * fuzzy_verify_distance as well is MGX_ERR_INVALID_ARGUMENT (one filter, d = 0 here). At most 64 operands may be
    * pending in the postfix at once (MGX_ERR_OUT_OF_RANGE). Runs like a fuzzy_verify_distance query. */
   uint32_t exact_text;
+  uint32_t sort_key_bias; /* MGX_SORT_COLUMN_RANK: 0 or 1, see there */
   /* MGX_SORT_SCORE: which terms BM25 sums, as indices into `terms`, in summation order (bm25_scorer.cpp:77-86); a term
    * may be listed more than once (ScoreDocuments adds a repeated term's contribution each time). NULL => every positive
    * term in order (the plain conjunctive query). An expression query lists the TERM leaves that are not under a NOT, in

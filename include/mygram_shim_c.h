@@ -109,6 +109,15 @@ int mgxs_search(mgxs_table* table, uint32_t n_terms, const char* const* terms, u
                 uint32_t n_cond, const char* const* cond_columns, const uint32_t* cond_ops, const char* const* cond_values,
                 int sort_by_score, int descending, uint32_t limit, uint32_t offset, uint64_t* total, uint32_t* n_docs,
                 uint32_t* docs, double* scores /* may be NULL */);
+/* mgxs_search with SORT <filter column> ASC|DESC (BatchQuery::sort_column; `descending` its direction, offset / limit the
+ * page): sort_column names a column of mgxs_table_add_filter_column, exactly or by its one case-insensitive match; NULL or
+ * "" is mgxs_search. An unknown column: 3007 (kQueryInvalidSort); together with sort_by_score: MGX_ERR_INVALID_ARGUMENT; a
+ * string column on a table with a delta index: MGX_ERR_NOT_IMPLEMENTED until mgxs_table_compact. Scores come back 0. */
+int mgxs_search_sorted(mgxs_table* table, uint32_t n_terms, const char* const* terms, uint32_t n_not,
+                       const char* const* not_terms, uint32_t n_cond, const char* const* cond_columns, const uint32_t* cond_ops,
+                       const char* const* cond_values, int sort_by_score, int descending, uint32_t limit, uint32_t offset,
+                       const char* sort_column, uint64_t* total, uint32_t* n_docs, uint32_t* docs,
+                       double* scores /* may be NULL */);
 /* mgxs_search with HIGHLIGHT (BatchQuery::highlight: GenerateHighlightSnippets on the page, search_handler.cpp:473-482, on the
  * device): the page's snippets, packed into `snippets`; doc k's snippet is snippets[snippet_off[k] .. snippet_off[k+1]).
  * snippet_off has room for limit + 1 entries. Tags NUL-terminated, at most 256 bytes; snippet_length 1..10000,

@@ -12,7 +12,7 @@ LIB_PATH = os.environ.get("MGX_LIBRARY") or os.path.join(_HERE, "libmygram_gpu.s
 
 ABI_VERSION = 5
 GRAM_ABSENT = 0xFFFFFFFF
-SORT_DOCID, SORT_SCORE = 0, 1
+SORT_DOCID, SORT_SCORE, SORT_COLUMN, SORT_COLUMN_RANK = 0, 1, 2, 3
 
 # every symbol include/mygram_gpu.h and include/mygram_tools.h declare
 # int (*mgx_gather_fn)(void* user, const void* mine, void* all, uint64_t bytes, void* hip_stream)
@@ -84,9 +84,10 @@ class Query(C.Structure):
     _fields_ = [("terms", C.c_void_p), ("n_terms", C.c_uint32), ("not_terms", C.c_void_p),
                 ("n_not_terms", C.c_uint32), ("filters", C.c_void_p), ("n_filters", C.c_uint32),
                 ("sort", C.c_uint32), ("limit", C.c_uint32), ("offset", C.c_uint32), ("reverse", C.c_uint32),
+                ("sort_column", C.c_uint32),  # (fills what was padding: every other field keeps its offset)
                 ("k1", C.c_double), ("b", C.c_double), ("total_docs", C.c_uint64), ("avg_doc_length", C.c_double),
                 ("expr", C.c_void_p), ("n_expr", C.c_uint32), ("universe_first", C.c_uint32),
-                ("universe_count", C.c_uint64), ("exact_text", C.c_uint32), ("score_terms", C.c_void_p),
+                ("universe_count", C.c_uint64), ("exact_text", C.c_uint32), ("sort_key_bias", C.c_uint32), ("score_terms", C.c_void_p),
                 ("n_score_terms", C.c_uint32), ("fuzzy_verify_distance", C.c_uint32),
                 ("conditions", C.c_void_p), ("n_conditions", C.c_uint32)]
 

@@ -30,6 +30,7 @@
 #include "../../include/mygram_gpu.h"
 #include "mgx_compile.hpp"
 #include "mgx_highlight.hpp"
+#include "mgx_colsort.hpp"
 #include "mgx_host.hpp"
 #include "mgx_internal.hpp"
 #include "mgx_launch.hpp"
@@ -315,6 +316,8 @@ struct mgx_index {
   uint32_t n_filter_rows = 0, filter_cap_rows = 0;
   struct FilterColumn {  // mgx_index_add_filter_column
     uint32_t value_class = 0, n_values = 0;
+    mgx::colsort::KeyScan sort_keys;  // has a NULL / has a non-NULL value whose sort key is 0 too (mgx_colsort.hpp): a
+                                      // column, or the two columns of a table with a delta, with both is not sortable
     DevBuf d_values, d_null, d_value_ids;
   };
   std::vector<std::unique_ptr<FilterColumn>> filter_columns;
@@ -1006,6 +1009,7 @@ int mgx_index_add_filter_column(mgx_index* idx, const mgx_filter_column_desc* d,
     auto col = std::make_unique<mgx_index::FilterColumn>();
     col->value_class = d->value_class;
     col->n_values = d->value_ids ? d->n_values : 0;
+    col->sort_keys = mgx::colsort::ScanKeys(d->value_class, static_cast<const uint64_t*>(d->values), d->is_null, n);
     MGX_HIP(mgx::Upload(col->d_values, static_cast<const uint64_t*>(d->values), n));
     if (d->is_null) MGX_HIP(mgx::Upload(col->d_null, d->is_null, n));
     if (d->value_ids) MGX_HIP(mgx::Upload(col->d_value_ids, d->value_ids, n));
@@ -2080,7 +2084,7 @@ static int UploadItems(mgx_batch* b, Group& g, const std::vector<QuerySpec>& spe
     MGX_HIP(b->d_take.Alloc(static_cast<size_t>(n) * 8));
     MGX_HIP(b->d_out_off.Alloc(static_cast<size_t>(n) * 8));
     std::vector<uint32_t> rev(n);
-    for (uint32_t i = 0; i < n; ++i) rev[i] = specs[g.qids[i]].deep_score ? 0u : specs[g.qids[i]].reverse;
+    for (uint32_t i = 0; i < n; ++i) rev[i] = (specs[g.qids[i]].deep_score || specs[g.qids[i]].col_sort) ? 0u : specs[g.qids[i]].reverse;
     MGX_HIP(Upload(b->d_reverse, rev.data(), n));
     d.rbits = b->d_rbits.as<uint64_t>();
     d.tile_cnt = b->d_tile_cnt.as<uint32_t>();
@@ -2243,7 +2247,43 @@ struct CompilePool {
   }
 };
 
+// SORT <filter column>: what the compiler cannot see of the column (its class, the mark of mgx_index_add_filter_column)
+static int CheckSortColumns(const mgx_index* idx, const std::vector<QuerySpec>& specs) {
+  bool any = false;
+  for (const QuerySpec& sp : specs) any = any || sp.col_sort;
+  if (!any) return MGX_OK;
+  std::lock_guard<std::mutex> lock(const_cast<mgx_index*>(idx)->mu);
+  for (size_t i = 0; i < specs.size(); ++i) {
+    const QuerySpec& sp = specs[i];
+    if (!sp.col_sort) continue;
+    const std::string who = "query " + std::to_string(i) + ": ";
+    if (sp.sort_column >= idx->filter_columns.size()) return Fail(MGX_ERR_OUT_OF_RANGE, who + "sort_column: unknown filter column");
+    const mgx_index::FilterColumn& col = *idx->filter_columns[sp.sort_column];
+    if (sp.sort_ranks && col.value_class != MGX_FC_UNSIGNED)
+      return Fail(MGX_ERR_INVALID_ARGUMENT, who + "MGX_SORT_COLUMN_RANK needs an MGX_FC_UNSIGNED column of dictionary ranks");
+    if (colsort::KeysCollide(col.sort_keys, col.sort_keys))
+      return Fail(MGX_ERR_NOT_IMPLEMENTED,
+                  who + "SORT by this column is not implemented: it holds NULLs beside a value whose 64-bit sort key is "
+                        "NULL's (INT64_MIN, or the double whose bits are all ones)");
+  }
+  return MGX_OK;
+}
+
+// The key scan of a filter column (false: no such column), read under the index's lock
+static bool SortKeysOf(const mgx_index* idx, uint32_t column, colsort::KeyScan* out) {
+  std::lock_guard<std::mutex> lock(const_cast<mgx_index*>(idx)->mu);
+  if (column >= idx->filter_columns.size()) return false;
+  *out = idx->filter_columns[column]->sort_keys;
+  return true;
+}
+
+static int CompileQueries(const mgx_index* idx, const mgx_query* queries, uint32_t n, std::vector<QuerySpec>* specs);
 static int CompileAll(const mgx_index* idx, const mgx_query* queries, uint32_t n, std::vector<QuerySpec>* specs) {
+  if (const int rc = CompileQueries(idx, queries, n, specs)) return rc;
+  return CheckSortColumns(idx, *specs);
+}
+
+static int CompileQueries(const mgx_index* idx, const mgx_query* queries, uint32_t n, std::vector<QuerySpec>* specs) {
   // one pool per calling thread: an executor's dispatcher threads compile different batches at the same time, and a
   // shared pool handed its helpers to one of them while the other compiled its 1024 queries alone (4x the time)
   static thread_local CompilePool pool;
@@ -2766,6 +2806,10 @@ static std::vector<double> DeepIdfs(const mgx_batch* b, const QuerySpec& sp) {
 //     can need (min(total, limit) in page order for docid pages, every match for limit 0 and for deep SORT _score);
 //   - deep SORT _score: each side scores its matches with its own index's columns on local slots; when two sides merge,
 //     the delta's slots then become table ids; each side's (key, docid') run is sorted by the bitonic network;
+//   - SORT <filter column>: each side's run is its best min(total, offset + limit) (key, docid') pairs under the column's
+//     key (mgx_colsort.hpp), docid' already a table id: from column_topk_kernel, which reads the side's result bitmap,
+//     when offset + limit <= 1024; otherwise (and under MGX_COLSORT_FULL=1) every match is expanded, keyed by
+//     column_keys_kernel and sorted by the bitonic network;
 //   - rank_merge_kernel cuts every query's page from its sorted, disjoint runs (one per side), in one launch.
 // Everything lives in the batch's d_merge scratch. On the delta's batch of a merge (merged_away) every page is empty:
 // the primary's fetch returned them.
@@ -2808,8 +2852,16 @@ static int FetchBitmapPages(mgx_batch* a, BitmapPages* m) {
   m->total.resize(n);
   m->page_off.resize(n);
   m->page_n.resize(n);
-  std::vector<uint64_t> take[2], off[2], soff[2], koff[2], n2[2], toff[2];
+  std::vector<uint64_t> take[2], off[2], soff[2], koff[2], n2[2], toff[2], run_n[2];
+  std::vector<int> job_side;
+  std::vector<uint32_t> job_column;
+  std::vector<colsort::TopkJob> jobs;  // SORT <filter column> pages the fused selection serves, one per (query, side)
+  const char* const full_env = std::getenv("MGX_COLSORT_FULL");
+  const bool colsort_full = full_env != nullptr && full_env[0] != '\0' && full_env[0] != '0';
+  uint64_t n_lists = 0;
+  uint32_t n_groups_total = 0, max_cap = 0, max_job_elems = 0;
   for (int k = 0; k < 2; ++k) {
+    run_n[k].assign(n, 0);
     take[k].assign(n, 0);
     off[k].assign(n, 0);
     soff[k].assign(n, 0);
@@ -2826,7 +2878,7 @@ static int FetchBitmapPages(mgx_batch* a, BitmapPages* m) {
     const QuerySpec& sp = a->specs[g.qids[i]];
     const uint64_t t = a->merged_away ? 0 : tot[0][i] + tot[1][i];  // (merged_away: sizes the empty page only)
     uint64_t lo = 0, hi = 0;
-    if (sp.deep_score) {
+    if (sp.deep_score || sp.col_sort) {
       lo = std::min<uint64_t>(sp.offset, t);
       hi = sp.limit == 0 ? t : std::min<uint64_t>(lo + sp.limit, t);
     } else {
@@ -2838,16 +2890,60 @@ static int FetchBitmapPages(mgx_batch* a, BitmapPages* m) {
     m->page_n[i] = hi - lo;
     pages += hi - lo;
     DevMergeRun& r = runs[i];
-    r.kind = sp.deep_score ? kMergeScore : sp.reverse ? kMergeDocDesc : kMergeDocAsc;
+    r.kind = (sp.deep_score || sp.col_sort) ? kMergeScore : sp.reverse ? kMergeDocDesc : kMergeDocAsc;
+    // the fused selection holds offset + limit <= 1024 pairs per side; past that every match is sorted
+    const bool col_topk = sp.col_sort && !colsort_full && hi <= colsort::kMaxNeeded;
     r.descending = sp.reverse ? 1u : 0u;
     r.lo = static_cast<uint32_t>(lo);
     r.hi = static_cast<uint32_t>(hi);
     r.out_off = m->page_off[i];
     for (int k = 0; k < n_side; ++k) {
       // a docid page needs each side's first hi ids in page order; a score page needs every match
-      take[k][i] = hi == lo ? 0 : sp.deep_score ? tot[k][i] : std::min<uint64_t>(tot[k][i], hi);
+      take[k][i] = hi == lo ? 0 : (sp.deep_score || sp.col_sort) ? tot[k][i] : std::min<uint64_t>(tot[k][i], hi);
+      run_n[k][i] = take[k][i];
+      if (col_topk && take[k][i] != 0) {  // nothing is expanded: the run comes from the side's result bitmap
+        const QuerySpec& ks = side[k]->specs[g.qids[i]];
+        const mgx_index* ix = side[k]->idx;
+        run_n[k][i] = std::min<uint64_t>(tot[k][i], hi);
+        take[k][i] = 0;
+        koff[k][i] = n_keys;
+        n_keys += run_n[k][i];
+        colsort::TopkJob j{};
+        j.rbits = side[k]->bitmap.dev.rbits;
+        j.doc_map = n_side == 2 ? ix->d_doc_map.as<uint32_t>() : nullptr;
+        j.n_words = ix->dev.n_tiles * kWordsPerTile;
+        j.word_begin = static_cast<uint64_t>(i) * j.n_words;
+        j.out_off = koff[k][i];
+        j.list_off = n_lists;
+        j.n_docs = ix->dev.n_docs;
+        j.first_doc_id = ix->dev.first_doc_id;
+        j.needed = static_cast<uint32_t>(run_n[k][i]);
+        j.cap = 64;
+        while (j.cap < j.needed) j.cap <<= 1;
+        // workgroups per job: about 8192 in the launch (32 per CU), so that a query with ten times the matches of the
+        // others is spread over several and the launch has no long tail; a workgroup covers at least two tiles
+        const uint32_t want = static_cast<uint32_t>((8192 + n - 1) / n);
+        j.n_groups = std::max<uint32_t>(1, std::min<uint32_t>({want, colsort::kTopkMaxGroups, (ix->dev.n_tiles + 1) / 2}));
+        j.group_begin = n_groups_total;
+        j.ranks = ks.sort_ranks;
+        j.bias = ks.sort_bias;
+        j.descending = sp.reverse ? 1u : 0u;
+        n_groups_total += j.n_groups;
+        n_lists += static_cast<uint64_t>(j.n_groups) * j.needed;
+        max_cap = std::max(max_cap, j.cap);
+        max_job_elems = std::max(max_job_elems, j.n_groups * j.needed);
+        jobs.push_back(j);
+        job_side.push_back(k);
+        job_column.push_back(ks.sort_column);  // (resolved to its class and arrays below, under the index's lock)
+      }
       off[k][i] = at[k];
       at[k] += take[k][i];
+      if (sp.col_sort && take[k][i] != 0) {  // every match, keyed and sorted whole
+        n2[k][i] = 2048;  // (LaunchSortPairs: a power of two, at least one LDS run)
+        while (n2[k][i] < take[k][i]) n2[k][i] <<= 1;
+        koff[k][i] = n_keys;
+        n_keys += n2[k][i];
+      }
       if (sp.deep_score && take[k][i] != 0) {
         const QuerySpec& ks = side[k]->specs[g.qids[i]];
         soff[k][i] = n_scores;
@@ -2862,15 +2958,46 @@ static int FetchBitmapPages(mgx_batch* a, BitmapPages* m) {
         idfs.insert(idfs.end(), ki.begin(), ki.end());
       }
     }
-    r.a_n = static_cast<uint32_t>(take[0][i]);
-    r.b_n = static_cast<uint32_t>(take[1][i]);  // (one index: 0, so an element's rank is its index in its own run)
+    r.a_n = static_cast<uint32_t>(run_n[0][i]);
+    r.b_n = static_cast<uint32_t>(run_n[1][i]);  // (one index: 0, so an element's rank is its index in its own run)
     run_start[i] = elems;
-    elems += take[0][i] + take[1][i];
+    elems += run_n[0][i] + run_n[1][i];
   }
   run_start[n] = elems;
   if (elems == 0) return MGX_OK;  // every page is empty
-  if (elems > 0xFFFFFFFFull || pages > 0xFFFFFFFFull || n_keys > 0xFFFFFFFFull)
+  if (elems > 0xFFFFFFFFull || pages > 0xFFFFFFFFull || n_keys > 0xFFFFFFFFull || n_lists > 0xFFFFFFFFull)
     return Fail(MGX_ERR_OUT_OF_RANGE, "batch result exceeds 2^32 doc ids");
+  // SORT <filter column>: every column a side's queries name, read under that index's lock (a column is immutable once
+  // added; the vector that holds them may grow)
+  struct SortCol {
+    const uint64_t* values;
+    const uint8_t* is_null;
+    uint32_t value_class;
+  };
+  std::map<uint32_t, SortCol> resolved[2];  // per side: each column is looked up once, whatever the number of queries
+  for (int k = 0; k < n_side; ++k) {
+    const mgx_index* ix = side[k]->idx;
+    std::lock_guard<std::mutex> lock(const_cast<mgx_index*>(ix)->mu);
+    for (size_t i = 0; i < n; ++i) {
+      const QuerySpec& ks = side[k]->specs[g.qids[i]];
+      if (!ks.col_sort || resolved[k].count(ks.sort_column) || ks.sort_column >= ix->filter_columns.size()) continue;
+      const mgx_index::FilterColumn& c = *ix->filter_columns[ks.sort_column];
+      resolved[k][ks.sort_column] = SortCol{c.d_values.as<uint64_t>(), c.d_null.as<uint8_t>(), c.value_class};
+    }
+  }
+  auto sort_col = [&](int k, uint32_t id, SortCol* out) {
+    const auto it = resolved[k].find(id);
+    if (it == resolved[k].end()) return false;
+    *out = it->second;
+    return true;
+  };
+  for (size_t j = 0; j < jobs.size(); ++j) {
+    SortCol c{};
+    if (!sort_col(job_side[j], job_column[j], &c)) return Fail(MGX_ERR_INTERNAL, "sort column vanished");
+    jobs[j].values = c.values;
+    jobs[j].is_null = c.is_null;
+    jobs[j].value_class = c.value_class;
+  }
   for (size_t i = 0; i < n; ++i) {
     DevMergeRun& r = runs[i];
     r.a_off = r.kind == kMergeScore ? koff[0][i] : off[0][i];
@@ -2880,14 +3007,18 @@ static int FetchBitmapPages(mgx_batch* a, BitmapPages* m) {
   const uint64_t o_start = Align8(n * sizeof(DevMergeRun));
   const uint64_t o_terms = o_start + (n + 1) * 8;
   const uint64_t o_idfs = Align8(o_terms + terms.size() * 4);
-  const uint64_t up_bytes = o_idfs + idfs.size() * 8;
+  const uint64_t o_jobs = o_idfs + idfs.size() * 8;
+  const uint64_t up_bytes = o_jobs + jobs.size() * sizeof(colsort::TopkJob);
   const uint64_t o_docs = Align8(up_bytes);
   const uint64_t o_scores = Align8(o_docs + (at[0] + at[1]) * 4);
   const uint64_t o_keys = o_scores + n_scores * 8;
   const uint64_t o_dprime = o_keys + n_keys * 8;
   const uint64_t o_pdocs = Align8(o_dprime + n_keys * 4);
   const uint64_t o_pscores = Align8(o_pdocs + pages * 4);
-  const uint64_t bytes = o_pscores + pages * 8;
+  const uint64_t o_lkeys = o_pscores + pages * 8;
+  const uint64_t o_ldocs = o_lkeys + n_lists * 8;
+  const uint64_t o_ln = Align8(o_ldocs + n_lists * 4);
+  const uint64_t bytes = o_ln + static_cast<uint64_t>(n_groups_total) * 4;
   if (a->d_merge.bytes < bytes) MGX_HIP(a->d_merge.Alloc(bytes));
   char* base = static_cast<char*>(a->d_merge.p);
   std::vector<char> up(up_bytes);
@@ -2895,6 +3026,7 @@ static int FetchBitmapPages(mgx_batch* a, BitmapPages* m) {
   std::memcpy(up.data() + o_start, run_start.data(), (n + 1) * 8);
   if (!terms.empty()) std::memcpy(up.data() + o_terms, terms.data(), terms.size() * 4);
   if (!idfs.empty()) std::memcpy(up.data() + o_idfs, idfs.data(), idfs.size() * 8);
+  if (!jobs.empty()) std::memcpy(up.data() + o_jobs, jobs.data(), jobs.size() * sizeof(colsort::TopkJob));
   MGX_HIP(hipMemcpyAsync(base, up.data(), up_bytes, hipMemcpyHostToDevice, s));
   uint32_t* docs = reinterpret_cast<uint32_t*>(base + o_docs);
   double* scores = reinterpret_cast<double*>(base + o_scores);
@@ -2921,13 +3053,45 @@ static int FetchBitmapPages(mgx_batch* a, BitmapPages* m) {
   const double* d_idfs = reinterpret_cast<const double*>(base + o_idfs);
   for (size_t i = 0; i < n; ++i)
     for (int k = 0; k < n_side; ++k) {
-      if (n2[k][i] == 0) continue;
+      if (n2[k][i] == 0 || !a->specs[g.qids[i]].deep_score) continue;
       mgx_batch* x = side[k];
       const QuerySpec& ks = x->specs[g.qids[i]];
       MGX_LAUNCH(LaunchScoreCandidatesMixed(x->idx->dev, docs + out_off[k][i], take[k][i], d_terms + toff[k][i],
                                             d_idfs + toff[k][i], static_cast<uint32_t>(ks.deep_grams.size()),
                                             x->d_patterns.as<uint8_t>(), x->d_text_terms.as<DevTextTerm>(), ks.k1,
                                             ks.b, ks.avgdl, scores + soff[k][i], s));
+    }
+  if (std::getenv("MGX_VERBOSE")) {
+    size_t full_runs = 0;
+    for (size_t i = 0; i < n; ++i)
+      for (int k = 0; k < n_side; ++k) full_runs += (a->specs[g.qids[i]].col_sort && n2[k][i] != 0) ? 1 : 0;
+    if (!jobs.empty() || full_runs)
+      fprintf(stderr, "[mgx] column sort: %zu fused runs in %u workgroups, %zu full-sort runs\n", jobs.size(), n_groups_total, full_runs);
+  }
+  // ---- SORT <filter column>: the fused selection from the result bitmaps; the expanded runs' pairs from local slots,
+  // their docid' a table id already (the doc map is read here: the slots are gone once the docs below are remapped)
+  if (!jobs.empty())
+    MGX_LAUNCH(LaunchColumnTopk(reinterpret_cast<const colsort::TopkJob*>(base + o_jobs), static_cast<uint32_t>(jobs.size()),
+                                n_groups_total, max_cap, max_job_elems, reinterpret_cast<uint64_t*>(base + o_lkeys),
+                                reinterpret_cast<uint32_t*>(base + o_ldocs), reinterpret_cast<uint32_t*>(base + o_ln), keys,
+                                dprime, s));
+  for (size_t i = 0; i < n; ++i)
+    for (int k = 0; k < n_side; ++k) {
+      mgx_batch* x = side[k];
+      const QuerySpec& ks = x->specs[g.qids[i]];
+      if (!ks.col_sort || n2[k][i] == 0) continue;
+      SortCol c{};
+      if (!sort_col(k, ks.sort_column, &c)) return Fail(MGX_ERR_INTERNAL, "sort column vanished");
+      const uint64_t cnt = take[k][i];
+      if (n2[k][i] > cnt) {
+        MGX_HIP(hipMemsetAsync(keys + koff[k][i] + cnt, 0, (n2[k][i] - cnt) * 8, s));
+        MGX_HIP(hipMemsetAsync(dprime + koff[k][i] + cnt, 0, (n2[k][i] - cnt) * 4, s));
+      }
+      MGX_LAUNCH(LaunchColumnKeys(docs + out_off[k][i], cnt, c.values, c.is_null,
+                                  n_side == 2 ? x->idx->d_doc_map.as<uint32_t>() : nullptr, x->idx->dev.first_doc_id,
+                                  x->idx->dev.n_docs, c.value_class, ks.sort_ranks, ks.sort_bias, runs[i].descending,
+                                  keys + koff[k][i], dprime + koff[k][i], s));
+      MGX_LAUNCH(LaunchSortPairs(keys + koff[k][i], dprime + koff[k][i], n2[k][i], s));
     }
   // ---- a merge: local slots -> table ids (a delta index numbers its documents in ascending table-id order; one index's
   // fetch returns its own ids) ----
@@ -2941,7 +3105,7 @@ static int FetchBitmapPages(mgx_batch* a, BitmapPages* m) {
   // ---- deep SORT _score: (key, docid') runs, each sorted best first ----
   for (size_t i = 0; i < n; ++i)
     for (int k = 0; k < n_side; ++k) {
-      if (n2[k][i] == 0) continue;
+      if (n2[k][i] == 0 || !a->specs[g.qids[i]].deep_score) continue;
       const int rc = SortRun(docs + out_off[k][i], scores + soff[k][i], take[k][i], n2[k][i], runs[i].descending,
                              keys + koff[k][i], dprime + koff[k][i], s);
       if (rc) return rc;
@@ -3171,6 +3335,14 @@ int mgx_batch_set_highlight(mgx_batch* batch, const mgx_highlight_request* reque
     return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_batch_set_highlight: one request per query of the batch");
   if (batch->res->uploaded || batch->executed || batch->hl.on())
     return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_batch_set_highlight: call it once, after prepare / reset and before the first execute");
+  {
+    bool any_hl = false;
+    for (uint32_t qi = 0; qi < n_queries; ++qi) any_hl = any_hl || requests[qi].enabled;
+    if (any_hl)
+      for (const mgx::QuerySpec& sp : batch->specs)
+        if (sp.col_sort)
+          return mgx::Fail(MGX_ERR_NOT_IMPLEMENTED, "mgx_batch_set_highlight: a highlighted batch that holds a query sorted by a filter column is not implemented");
+  }
   try {
     mgx_index* idx = batch->idx;
     std::vector<mgx::DevHlQuery> queries;
@@ -3370,6 +3542,17 @@ int mgx_batch_df_buffer(mgx_batch* batch, uint64_t** device_counts, uint32_t* n)
 // One group of a batch (its SORT _score queries, or its docid-ordered pages) in the exchange layout. The public entry
 // points below take uniform batches (one all-gather moves one blob); the local merge of a mutable table takes each group
 // of a mixed batch in turn.
+// SORT <filter column> on a sharded table: the ranks of a page need every shard's column values
+static bool HasColumnSort(const mgx_batch* batch) {
+  for (const mgx::QuerySpec& sp : batch->specs)
+    if (sp.col_sort) return true;
+  return false;
+}
+static int RefuseColumnSort(const mgx_batch* batch, const char* entry) {
+  if (!HasColumnSort(batch)) return MGX_OK;
+  return mgx::Fail(MGX_ERR_NOT_IMPLEMENTED, std::string(entry) + ": SORT by a filter column on a sharded table is not implemented: a page's order needs every shard's column values");
+}
+
 static int ExportGroup(mgx_batch* batch, bool pages, uint64_t* blob64, uint32_t* blob32, uint32_t* stride, void* hip_stream);
 static int MergeGroup(mgx_batch* batch, bool pages, uint32_t n_shards, const uint64_t* blob64, uint64_t pitch64,
                       const uint32_t* blob32, uint64_t pitch32, void* hip_stream);
@@ -3378,6 +3561,7 @@ int mgx_batch_export_topk(mgx_batch* batch, uint64_t* blob64, uint32_t* blob32, 
                           void* hip_stream) {
   if (!batch || !stride) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_batch_export_topk: null argument");
   if (batch->hl.on()) return mgx::Fail(MGX_ERR_NOT_IMPLEMENTED, "mgx_batch_export_topk: highlight on a sharded table is not implemented: the page's texts live on other ranks");
+  if (const int rc_cs = RefuseColumnSort(batch, "mgx_batch_export_topk")) return rc_cs;
   const bool pages = batch->score.qids.empty() && batch->bitmap.qids.empty() && !batch->page.qids.empty();
   if (!pages && (!batch->bitmap.qids.empty() || !batch->page.qids.empty() || batch->score.qids.empty()))
     return mgx::Fail(MGX_ERR_INVALID_ARGUMENT,
@@ -3419,6 +3603,7 @@ int mgx_batch_export_buffer(mgx_batch* batch, void** device_blob, uint64_t* byte
     return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_batch_export_buffer: null argument");
   if (batch->hl.on())
     return mgx::Fail(MGX_ERR_NOT_IMPLEMENTED, "mgx_batch_export_buffer: highlight on a sharded table is not implemented: the page's texts live on other ranks");
+  if (const int rc_cs = RefuseColumnSort(batch, "mgx_batch_export_buffer")) return rc_cs;
   if (!batch->bitmap.qids.empty() || !batch->page.qids.empty() || batch->score.qids.empty()) return MGX_OK;  // none
   *device_blob = batch->d_export.p;
   *bytes = batch->ex_bytes;
@@ -3431,6 +3616,7 @@ int mgx_batch_merge_shards(mgx_batch* batch, uint32_t n_shards, const uint64_t* 
   if (!batch || !blob64 || !blob32 || n_shards == 0)
     return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_batch_merge_shards: null argument");
   if (batch->hl.on()) return mgx::Fail(MGX_ERR_NOT_IMPLEMENTED, "mgx_batch_merge_shards: highlight on a sharded table is not implemented: the page's texts live on other ranks");
+  if (const int rc_cs = RefuseColumnSort(batch, "mgx_batch_merge_shards")) return rc_cs;
   const bool pages = batch->score.qids.empty() && batch->bitmap.qids.empty() && !batch->page.qids.empty();
   if (!pages && (!batch->bitmap.qids.empty() || !batch->page.qids.empty() || batch->score.qids.empty()))
     return mgx::Fail(MGX_ERR_INVALID_ARGUMENT,
@@ -3527,6 +3713,23 @@ int mgx_batch_merge_local(mgx_batch* primary, mgx_batch* const* others, uint32_t
           others[j]->page.qids.size() != primary->page.qids.size() ||
           others[j]->bitmap.qids != primary->bitmap.qids || !others[j]->executed)
         return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_batch_merge_local: the batches do not hold the same queries");
+    if (n_others == 1) {
+      // SORT <filter column> across two indexes: their runs are merged by key, so a NULL on one side ties with a value
+      // whose key is 0 (INT64_MIN, the all-ones double) on the other, which neither column's own mark can see
+      for (uint32_t qi = 0; qi < primary->n_queries; ++qi) {
+        const mgx::QuerySpec& sa = primary->specs[qi];
+        const mgx::QuerySpec& sb = others[0]->specs[qi];
+        if (!sa.col_sort) continue;
+        mgx::colsort::KeyScan ka, kb;
+        if (!sb.col_sort || !mgx::SortKeysOf(primary->idx, sa.sort_column, &ka) || !mgx::SortKeysOf(others[0]->idx, sb.sort_column, &kb))
+          return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_batch_merge_local: the batches do not hold the same queries");
+        if (mgx::colsort::KeysCollide(ka, kb))
+          return mgx::Fail(MGX_ERR_NOT_IMPLEMENTED,
+                           "mgx_batch_merge_local: query " + std::to_string(qi) + ": SORT by this column is not implemented "
+                           "on a table with a delta index: between them the two indexes hold NULLs beside a value whose "
+                           "64-bit sort key is NULL's (INT64_MIN, or the double whose bits are all ones)");
+      }
+    }
     MGX_HIP(hipSetDevice(primary->idx->device));
     if (!primary->bitmap.qids.empty() && n_others == 1) {
       // the bitmap group's page sizes need the totals on the host: its merge runs inside mgx_batch_fetch(primary)
@@ -3727,6 +3930,7 @@ int mgx_batch_exchange_df(mgx_batch* batch, mgx_comm* comm, void* hip_stream) {
 int mgx_batch_exchange(mgx_batch* batch, mgx_comm* comm, void* hip_stream) {
   if (!batch || !comm) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_batch_exchange: null argument");
   if (batch->hl.on()) return mgx::Fail(MGX_ERR_NOT_IMPLEMENTED, "mgx_batch_exchange: highlight on a sharded table is not implemented: the page's texts live on other ranks");
+  if (const int rc_cs = RefuseColumnSort(batch, "mgx_batch_exchange")) return rc_cs;
   if (!comm->comm) return mgx::Fail(MGX_ERR_INTERNAL, "mgx_batch_exchange: the communicator was aborted");
   if (batch->n_queries == 0) return MGX_OK;
   if (!batch->executed) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_batch_exchange: not executed");
@@ -3789,6 +3993,7 @@ static int RcclGather(void* user, const void* mine, void* all, uint64_t bytes, v
 int mgx_batch_execute_gather(mgx_batch* batch, int world, mgx_gather_fn gather, void* user, void* hip_stream) {
   if (!batch || !gather || world < 1) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_batch_execute_gather: bad argument");
   if (batch->hl.on()) return mgx::Fail(MGX_ERR_NOT_IMPLEMENTED, "mgx_batch_execute_gather: highlight on a sharded table is not implemented: the page's texts live on other ranks");
+  if (const int rc_cs = RefuseColumnSort(batch, "mgx_batch_execute_gather")) return rc_cs;
   try {
     hipStream_t s = nullptr;
     int rc = mgx::BatchStream(batch, hip_stream, &s);

@@ -422,6 +422,18 @@ int CompileQuery(const CompileView& v, const mgx_query& in, QuerySpec* out) {
   } else if (in.sort == MGX_SORT_DOCID) {  // a bounded page needs no materialised result bitmap: count pass + page pass
     out->mode = (in.limit != 0 && in.limit <= kMaxDocPage) ? kModeDocPage : kModeBitmap;
     out->offset = 0;  // (pagination offset belongs to SORT _score, search_handler.cpp:469-470)
+  } else if (in.sort == MGX_SORT_COLUMN || in.sort == MGX_SORT_COLUMN_RANK) {
+    // SORT <filter column>: always the bitmap group (totals and funnel counters as an unbounded docid query has them);
+    // the fetch ranks the matches by the column's key (mgx_colsort.hpp)
+    if (in.sort_column >= v.n_filter_columns) return Fail(MGX_ERR_OUT_OF_RANGE, "sort_column: unknown filter column");
+    if (in.sort_key_bias > 1) return Fail(MGX_ERR_INVALID_ARGUMENT, "sort_key_bias must be 0 or 1");
+    if (in.sort == MGX_SORT_COLUMN && in.sort_key_bias != 0)
+      return Fail(MGX_ERR_INVALID_ARGUMENT, "sort_key_bias belongs to a column of string ranks (MGX_SORT_COLUMN_RANK)");
+    out->mode = kModeBitmap;
+    out->col_sort = true;
+    out->sort_column = in.sort_column;
+    out->sort_ranks = in.sort == MGX_SORT_COLUMN_RANK ? 1u : 0u;
+    out->sort_bias = in.sort_key_bias;
   } else {
     return Fail(MGX_ERR_INVALID_ARGUMENT, "unknown sort");
   }

@@ -56,6 +56,9 @@ struct QuerySpec {
   bool deep_score = false;
   std::vector<uint32_t> deep_grams;  // the scored terms' gram ids (kNoRow: a gram this shard lacks)
   std::vector<double> deep_idfs;
+  // SORT <filter column> (MGX_SORT_COLUMN / _RANK): the bitmap group's fetch ranks the matches by the column's key
+  bool col_sort = false;
+  uint32_t sort_column = 0, sort_ranks = 0, sort_bias = 0;
   uint32_t pat_off = 0, pat_len = 0;  // kModeTextDf specs: the term in the batch's pattern pool
   uint32_t vt_begin = 0;              // first of the query's verify patterns in the batch-wide array
   uint32_t fz_distance = 0;           // kOpVerifyFuzzy / kOpVerifyTree: d
@@ -72,7 +75,8 @@ struct QuerySpec {
     conds.clear();
     text_terms.clear();
     verify_patterns.clear();
-    deep_score = false;
+    deep_score = col_sort = false;
+    sort_column = sort_ranks = sort_bias = 0;
     deep_grams.clear();
     deep_idfs.clear();
     mode = kModeBitmap;

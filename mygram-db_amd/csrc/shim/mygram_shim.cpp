@@ -1917,6 +1917,7 @@ struct TermInfo {  // search_pipeline.h:44-55
 // boolean branch (:1842-1913) plans it: everything the C ABI's mgx_query points at lives in this object.
 struct PlannedQuery {
   mgx_query q{};
+  bool sort_string = false;        // BatchQuery::sort_column names a string column (dictionary ranks)
   bool on_device = false;          // false: resolved on the host (empty_term_detected) or failed
   bool empty_term_detected = false;
   ErrorCode error = ErrorCode::kSuccess;
@@ -2192,7 +2193,42 @@ std::string ResolveCondition(const index::Index& index, const query::FilterCondi
   return "";
 }
 
+void PlanQueryBody(const index::Index& index, const BatchQuery& q, uint64_t total_docs, double avgdl, PlannedQuery* p);
+
+// PlanQueryBody, and BatchQuery::sort_column resolved against the index's columns: the device query then asks for
+// MGX_SORT_COLUMN / _RANK with the pagination offset.
 void PlanQuery(const index::Index& index, const BatchQuery& q, uint64_t total_docs, double avgdl, PlannedQuery* p) {
+  p->sort_string = false;
+  if (q.sort_column.empty()) return PlanQueryBody(index, q, total_docs, avgdl, p);
+  if (q.sort_by_score) return Fail(p, ErrorCode::kInvalidArgument, "sort_column and sort_by_score are two orders: set one of them");
+  index.FlushPendingFilterColumns();
+  const index::Index::Impl* im = index.impl();
+  uint32_t device_column = 0, bias = 0;
+  bool is_string = false;
+  {
+    std::lock_guard<std::mutex> lock(im->filter_mu);
+    const index::Index::Impl::FilterColumn* col = im->ResolveColumn(q.sort_column);
+    if (col == nullptr) {  // result_sorter.cpp:549-552
+      p->error = ErrorCode::kQueryInvalidSort;
+      p->error_message = "Sort column '" + q.sort_column +
+                         "' not found. Column does not exist as filter column or primary key. Check column name spelling.";
+      return;
+    }
+    device_column = col->device_id;
+    is_string = col->type == 11;
+    // the key of a string is the string: the empty one ties with NULL (both keys are ""), so its rank 0 stays 0
+    if (is_string) bias = (!col->dict.empty() && std::get<std::string>(col->dict.front()).empty()) ? 0u : 1u;
+  }
+  PlanQueryBody(index, q, total_docs, avgdl, p);
+  p->sort_string = is_string;
+  if (p->error != ErrorCode::kSuccess || !p->on_device) return;
+  p->q.sort = is_string ? MGX_SORT_COLUMN_RANK : MGX_SORT_COLUMN;
+  p->q.sort_column = device_column;
+  p->q.sort_key_bias = bias;
+  p->q.offset = q.offset;
+}
+
+void PlanQueryBody(const index::Index& index, const BatchQuery& q, uint64_t total_docs, double avgdl, PlannedQuery* p) {
   const index::Index::Impl* im = index.impl();
   // FILTER clauses: caller-resolved bitmaps, then the parsed conditions (resolved here, cached by the Index)
   auto add_filters = [&]() -> bool {
@@ -2675,6 +2711,12 @@ bool PlanForDelta(const index::Index& delta, const BatchQuery& q, uint64_t total
   }
   PlanQuery(delta, q, total_docs, avgdl, p);
   if (p->error != ErrorCode::kSuccess) return false;
+  if (main_plan.sort_string || p->sort_string) {
+    Fail(p, ErrorCode::kNotImplemented,
+         "SORT by a string column on a table with a delta index is not implemented: the ranks of the two indexes' "
+         "dictionaries do not compare (Compact() the table)");
+    return false;
+  }
   if (p->on_device != main_plan.on_device) {
     Fail(p, ErrorCode::kInternalError, "the main and the delta index plan a query differently");
     return false;
@@ -2784,6 +2826,7 @@ Error FacetOne(const index::Index& index, const BatchQuery& query, const std::st
   // its NOT terms and filters: the expression NOT(<empty>) is the universe
   BatchQuery q = query;
   q.sort_by_score = false;
+  q.sort_column.clear();
   q.limit = 0;
   q.offset = 0;
   if (q.terms.empty() && !q.ast) {

@@ -434,6 +434,18 @@ struct BatchQuery {
                                        // text holds every term exactly or within d edits (PostFilterByFuzzyText
                                        // :1746-1755, on the device: mgx_query.fuzzy_verify_distance)
   bool sort_by_score = false;          // SORT _score
+  // SORT <filter column> ASC|DESC (ResultSorter::SortAndPaginate, src/query/result_sorter.cpp:489-650): the result set
+  // ordered by this column of Index::AddFilterColumn before offset / limit, `order` its direction; empty: as before.
+  // The name resolves like the reference's (:516-520): exact, else the one case-insensitive match; an unknown name is
+  // kQueryInvalidSort with the reference's message (:549-552); together with sort_by_score: kInvalidArgument. NULL sorts
+  // first in ASC, ties go to the doc id in the sort's direction; scores are 0. On the device: MGX_SORT_COLUMN (strings:
+  // MGX_SORT_COLUMN_RANK over the column's dictionary ranks). A table with a delta index serves numeric, bool, time and
+  // double columns; a string column is refused there (kNotImplemented: the ranks of two dictionaries do not compare)
+  // until Compact(). Refused as well (kNotImplemented): on a sharded executor, beside `highlight`, and a column that
+  // holds NULLs beside INT64_MIN or the double whose bits are all ones (on a table with a delta: the main index's and
+  // the delta's column between them). The primary key is no column of this layer:
+  // SORT by it stays the doc-id page (`order`).
+  std::string sort_column;
   bool verify_text = false;            // the caller's ShouldApplyVerifyText(memory.verify_text, terms) decision
                                        // (search_pipeline.cpp:42-66); mixed-script fragments force it (:858-866)
   query::SortOrder order = query::SortOrder::DESC;

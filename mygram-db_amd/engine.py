@@ -339,7 +339,8 @@ class Query:
     """The parts of query::Query (src/query/query_parser.h:207-243) the hot path consumes."""
 
     def __init__(self, terms=(), not_terms=(), filters=(), sort_score=False, limit=100, offset=0, descending=True,
-                 k1=1.2, b=0.75, fuzzy=0, expr=None, universe=None, verify_text=False, highlight=None, conditions=()):
+                 k1=1.2, b=0.75, fuzzy=0, expr=None, universe=None, verify_text=False, highlight=None, conditions=(),
+                 sort_column=None, sort_key_bias=0, sort_ranks=False):
         """`expr`: boolean tree over term strings instead of the plain AND of `terms` (query::QueryNode):
         "term" | ("and", e, ...) | ("or", e, ...) | ("not", e). `universe` = (first_doc_id, count) of the NOT universe
         (DocumentStore::GetAllDocIds); None = every slot of the index."""
@@ -348,6 +349,12 @@ class Query:
         # eq_epsilon=0.0, null_matches=False, never_matches=False, negate=False) with op and literal as in
         # DeviceIndex.filter_compare — no filter row is registered for them
         self.conditions = list(conditions)
+        # sort_column: SORT <filter column> (the id DeviceIndex.add_filter_column returned), `descending` its direction,
+        # any limit / offset. sort_ranks: the column holds ranks in a sorted string dictionary; sort_key_bias is then 0
+        # when the dictionary holds "" and 1 otherwise (MGX_SORT_COLUMN_RANK)
+        if sort_column is not None and sort_score:
+            raise ValueError("sort_score and sort_column are two orders: set one of them")
+        self.sort_column, self.sort_key_bias, self.sort_ranks = sort_column, sort_key_bias, sort_ranks
         self.sort_score, self.limit, self.offset, self.descending = sort_score, limit, offset, descending
         self.k1, self.b, self.fuzzy = k1, b, fuzzy
         # verify_text: the caller's memory.verify_text decision (ShouldApplyVerifyText, search_pipeline.cpp:42-66);
@@ -369,6 +376,15 @@ class Query:
                         walk(c)
             walk(expr)
             self.terms = seen
+
+
+def _set_sort_column(cq, q):
+    """q.sort_column -> cq.sort / sort_column / sort_key_bias (offset and reverse are set as for SORT _score)."""
+    if q.sort_column is None:
+        return
+    cq.sort = _capi.SORT_COLUMN_RANK if q.sort_ranks else _capi.SORT_COLUMN
+    cq.sort_column = int(q.sort_column)
+    cq.sort_key_bias = int(q.sort_key_bias)
 
 
 def _set_conditions(cq, q, keep):
@@ -956,8 +972,9 @@ class Index:
                 cq = _capi.Query(C.cast(cterms, C.c_void_p), len(tis), C.cast(cnots, C.c_void_p), len(nts),
                                  C.cast(cf, C.c_void_p), len(q.filters),
                                  _capi.SORT_SCORE if q.sort_score else _capi.SORT_DOCID, q.limit, q.offset,
-                                 int(q.descending), q.k1, q.b, self.total_docs, self.avg_doc_length)
+                                 int(q.descending), 0, q.k1, q.b, self.total_docs, self.avg_doc_length)
                 _set_conditions(cq, q, keep)
+                _set_sort_column(cq, q)
                 if q.verify_text:
                     cq.fuzzy_verify_distance = q.fuzzy
                 if q.sort_score:
@@ -1094,7 +1111,8 @@ class Index:
             cq = _capi.Query(C.cast(cterms, C.c_void_p), len(tis), C.cast(cnots, C.c_void_p), len(nts),
                              C.cast(cf, C.c_void_p), len(q.filters),
                              _capi.SORT_SCORE if q.sort_score else _capi.SORT_DOCID, q.limit, q.offset,
-                             int(q.descending), q.k1, q.b, self.total_docs, self.avg_doc_length)
+                             int(q.descending), 0, q.k1, q.b, self.total_docs, self.avg_doc_length)
+            _set_sort_column(cq, q)
             cq.exact_text = int(exact or (tree_verify and not q.fuzzy))
             if tree_verify and q.fuzzy:
                 cq.fuzzy_verify_distance = q.fuzzy

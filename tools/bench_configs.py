@@ -202,9 +202,58 @@ def range_filter(mg, args):
                           "distinct_literals": int(lits.size), "mean_total": float(np.mean([r.total for r in res]))}}))
 
 
+def sortcol(mg, args):
+    """The bench.py batch (1024 x 3-term AND by df) as SORT <int64 column> DESC LIMIT 100, three ways on one table: the
+    default route (the fused selection from the result bitmaps), the same under MGX_COLSORT_FULL=1 (every match
+    expanded, keyed and sorted), and the same queries as plain doc-id pages (DESC LIMIT 100): what the set algebra alone
+    costs. Prints ms per batch (execute + fetch) of each; the library reads MGX_COLSORT_FULL at every fetch."""
+    import torch
+    corpus = mg.Corpus.synthetic(args.docs, seed=42)
+    idx = mg.Index(corpus=corpus, ngram_size=2)
+    c = idx.columns
+    sizes = np.diff(c.offsets.astype(np.int64))
+    cand = [g for g in range(c.n_grams) if b" " not in c.gram(g)]
+    w = sizes[cand].astype(np.float64)
+    w /= w.sum()
+    rng = np.random.default_rng(42)
+    col = idx.device_index.add_filter_column(rng.integers(0, 1 << 40, size=c.n_docs, dtype=np.int64))
+    terms = [[c.gram(cand[i]).decode() for i in rng.choice(len(cand), size=3, replace=False, p=w)] for _ in range(args.batch)]
+    sorted_qs = [mg.engine.Query(t, sort_column=col, descending=True, limit=100) for t in terms]
+    docid_qs = [mg.engine.Query(t, descending=True, limit=100) for t in terms]
+
+    def run(qs, full):
+        os.environ.pop("MGX_COLSORT_FULL", None)
+        if full:
+            os.environ["MGX_COLSORT_FULL"] = "1"
+        batch = idx.prepare(qs)
+        for _ in range(args.warmup):
+            batch.execute()
+            batch.fetch_raw()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            batch.execute()
+            batch.fetch_raw()
+        torch.cuda.synchronize()
+        ms = 1e3 * (time.perf_counter() - t0) / args.steps
+        res = batch.fetch()
+        os.environ.pop("MGX_COLSORT_FULL", None)
+        return ms, res
+
+    ms_default, res = run(sorted_qs, False)
+    ms_full, res_full = run(sorted_qs, True)
+    ms_docid, _ = run(docid_qs, False)
+    same = all(a.docs.tolist() == b.docs.tolist() and a.total == b.total for a, b in zip(res, res_full))
+    print(json.dumps({"metric": "ms per batch", "value": ms_default, "unit": "ms", "ms_per_batch_default": ms_default,
+                      "ms_per_batch_colsort_full": ms_full, "ms_per_batch_docid_pages": ms_docid, "steps": args.steps,
+                      "config": {"workload": "sortcol: %d docs, bigram, batch %d x 3-term AND, SORT int64 column DESC LIMIT 100"
+                                             % (args.docs, args.batch),
+                                 "default_equals_full": bool(same), "mean_total": float(np.mean([r.total for r in res]))}}))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("config", choices=["cfg3", "cfg4", "cfg5", "cfg2doc", "text2", "score5", "range"])
+    ap.add_argument("config", choices=["cfg3", "cfg4", "cfg5", "cfg2doc", "text2", "score5", "range", "sortcol"])
     ap.add_argument("--via", choices=["conditions", "rows"], default="conditions", help="range: how the conditions are served")
     ap.add_argument("--docs", type=int, default=0)
     ap.add_argument("--batch", type=int, default=0)
@@ -212,14 +261,16 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--check", type=int, default=0, help="sample this many queries of the batch against the CPU oracle")
     args = ap.parse_args()
-    args.docs = args.docs or {"cfg3": 1_000_000, "cfg5": 12_500_000, "cfg2doc": 10_000_000, "text2": 2_000_000, "cfg4": 12_500_000, "score5": 10_000_000, "range": 10_000_000}[args.config]
-    args.batch = args.batch or {"cfg3": 4096, "cfg5": 8192, "cfg2doc": 1024, "text2": 1024, "cfg4": 1024, "score5": 1024, "range": 1024}[args.config]
+    args.docs = args.docs or {"cfg3": 1_000_000, "cfg5": 12_500_000, "cfg2doc": 10_000_000, "text2": 2_000_000, "cfg4": 12_500_000, "score5": 10_000_000, "range": 10_000_000, "sortcol": 10_000_000}[args.config]
+    args.batch = args.batch or {"cfg3": 4096, "cfg5": 8192, "cfg2doc": 1024, "text2": 1024, "cfg4": 1024, "score5": 1024, "range": 1024, "sortcol": 1024}[args.config]
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("needs an MI355X")
     mg = entry.load_package()
     if args.config == "range":
         return range_filter(mg, args)
+    if args.config == "sortcol":
+        return sortcol(mg, args)
     t0 = time.perf_counter()
     idx, qs, cfg = {"cfg3": cfg3, "cfg5": cfg5, "cfg2doc": cfg2doc, "text2": text2, "cfg4": cfg4, "score5": score5}[args.config](mg, args)
     batch = idx.prepare(qs)
