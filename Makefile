@@ -7,7 +7,7 @@ LIB := mygram-db_amd/libmygram_gpu.so
 CXXFLAGS := -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wextra -Wno-unused-parameter -Iinclude
 HIPFLAGS := --offload-arch=$(ARCH) $(CXXFLAGS)
 
-OBJS := $(CSRC)/mgx_kernels.o $(CSRC)/mgx_highlight.o $(CSRC)/mgx_colsort.o $(CSRC)/mgx_api.o $(CSRC)/mgx_compile.o $(CSRC)/mgx_columns.o $(CSRC)/mgx_tools.o
+OBJS := $(CSRC)/mgx_kernels.o $(CSRC)/mgx_highlight.o $(CSRC)/mgx_colsort.o $(CSRC)/mgx_facet.o $(CSRC)/mgx_api.o $(CSRC)/mgx_compile.o $(CSRC)/mgx_columns.o $(CSRC)/mgx_tools.o
 
 SHIM := mygram-db_amd/libmygram_shim.so
 
@@ -21,7 +21,10 @@ $(CSRC)/mgx_highlight.o: $(CSRC)/mgx_highlight.hip $(CSRC)/mgx_highlight.hpp $(C
 # SORT <filter column>: its kernels too are a unit of their own (it restates the comparator it shares with the others)
 $(CSRC)/mgx_colsort.o: $(CSRC)/mgx_colsort.hip $(CSRC)/mgx_colsort.hpp
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(CSRC)/mgx_api.o: $(CSRC)/mgx_api.cpp $(CSRC)/mgx_colsort.hpp $(CSRC)/mgx_compile.hpp $(CSRC)/mgx_internal.hpp $(CSRC)/mgx_launch.hpp $(CSRC)/mgx_host.hpp $(CSRC)/mgx_highlight.hpp include/mygram_gpu.h
+# FACET in a batch: one more unit of its own (mgx_facet.hpp also holds the host-side plan, which compiles without HIP)
+$(CSRC)/mgx_facet.o: $(CSRC)/mgx_facet.hip $(CSRC)/mgx_facet.hpp
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+$(CSRC)/mgx_api.o: $(CSRC)/mgx_api.cpp $(CSRC)/mgx_colsort.hpp $(CSRC)/mgx_facet.hpp $(CSRC)/mgx_compile.hpp $(CSRC)/mgx_internal.hpp $(CSRC)/mgx_launch.hpp $(CSRC)/mgx_host.hpp $(CSRC)/mgx_highlight.hpp include/mygram_gpu.h
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
 $(CSRC)/mgx_compile.o: $(CSRC)/mgx_compile.cpp $(CSRC)/mgx_compile.hpp $(CSRC)/mgx_internal.hpp $(CSRC)/mgx_host.hpp include/mygram_gpu.h
 	g++ $(CXXFLAGS) -c $< -o $@
@@ -50,7 +53,7 @@ oracle:
 ablation:
 	$(HIPCC) $(HIPFLAGS) -DMGX_ABLATION -c $(CSRC)/mgx_kernels.hip -o /tmp/mgx_kernels_abl.o
 	$(HIPCC) $(HIPFLAGS) -DMGX_ABLATION -x hip -c $(CSRC)/mgx_api.cpp -o /tmp/mgx_api_abl.o
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o mygram-db_amd/libmygram_gpu_ablation.so /tmp/mgx_kernels_abl.o $(CSRC)/mgx_highlight.o $(CSRC)/mgx_colsort.o /tmp/mgx_api_abl.o $(CSRC)/mgx_compile.o $(CSRC)/mgx_columns.o $(CSRC)/mgx_tools.o -pthread
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o mygram-db_amd/libmygram_gpu_ablation.so /tmp/mgx_kernels_abl.o $(CSRC)/mgx_highlight.o $(CSRC)/mgx_colsort.o $(CSRC)/mgx_facet.o /tmp/mgx_api_abl.o $(CSRC)/mgx_compile.o $(CSRC)/mgx_columns.o $(CSRC)/mgx_tools.o -pthread
 
 # the host pieces of mgx_colsort.hpp (key transform, collision scan) under the sanitizers: a stand-alone program, no GPU
 colsort-host-asan:

@@ -512,6 +512,46 @@ int mgx_highlight_render(const mgx_highlight_entry* entry, const uint8_t* open_t
 /* Length in bytes of the longest text attached to the index (0 without mgx_index_attach_text). */
 int mgx_index_max_text_bytes(const mgx_index* idx, uint32_t* out);
 
+/* ---- FACET in a batch (FACET <column> of many queries and columns per execute; mgx_facet_counts serves one query and
+ * one column per call and waits for the device each time).
+ * mgx_batch_set_facets attaches the requests to a prepared or reset batch, BEFORE its first execute and once;
+ * requests[i] belongs to query i (n_queries = the batch's); mgx_batch_reset drops them. A faceted query (n_columns != 0)
+ * must be MGX_SORT_DOCID with limit 0, the shape mgx_facet_counts forces. It returns NO page (n_docs = 0); its total and
+ * its funnel counters are what the same query reports without the request. counts[v] of an entry is the number of
+ * documents of the query's whole result set (terms or expression, NOT terms, filters, conditions, text post-filters, the
+ * live row) whose value id in the column is v; NULLs are not counted. One more kernel (facet_batch_kernel) runs behind
+ * the batch's others on the batch's stream: it reads each faceted query's result bitmap once, whatever the number of its
+ * columns, after a memset of the counts; the counts ride the batch's result copy and its event. A batch without a
+ * faceted query allocates, launches and copies nothing. The counts' device memory and pinned block are kept across
+ * mgx_batch_reset and only grow. mgx_batch_merge_local leaves the counts per index, like the funnel counters: the caller
+ * fetches the facets of both batches and adds them by value.
+ * Refused: null arguments, a wrong n_queries, a second call, a call after the first execute, a faceted query of another
+ * sort or with a limit, a column added without value_ids: MGX_ERR_INVALID_ARGUMENT; an unknown column, more than
+ * MGX_FACET_MAX_COLUMNS columns in one request, counts above MGX_FACET_ARENA_CAP bytes in the batch: MGX_ERR_OUT_OF_RANGE
+ * (the message names the query). A faceted batch handed to a sharded entry point (mgx_batch_export_topk /
+ * _export_buffer, mgx_batch_merge_shards, mgx_batch_exchange, mgx_batch_execute_gather, mgx_batch_execute_sharded):
+ * MGX_ERR_NOT_IMPLEMENTED, before anything is touched. */
+#define MGX_FACET_MAX_COLUMNS 8u
+#define MGX_FACET_ARENA_CAP (256ull << 20)
+#define MGX_FACET_LDS_BINS 8192u /* 32-bit bins of the kernel's LDS histogram; columns past them count in global memory */
+typedef struct mgx_facet_request {
+  uint32_t n_columns;          /* 0: the query is not faceted */
+  uint32_t reserved;           /* 0 */
+  const uint32_t* column_ids;  /* ids from mgx_index_add_filter_column; the same id may appear twice */
+} mgx_facet_request;
+int mgx_batch_set_facets(mgx_batch* batch, const mgx_facet_request* requests, uint32_t n_queries);
+typedef struct mgx_facet_entry {
+  uint32_t query, column_id, n_values, reserved;
+  const uint64_t* counts;      /* n_values */
+} mgx_facet_entry;
+typedef struct mgx_facet_view {
+  uint32_t n_entries;          /* in query order, then in request order */
+  const mgx_facet_entry* entries;
+} mgx_facet_view;
+/* After mgx_batch_fetch of the same execute: no further wait, no further copy. The view stays valid until the batch's
+ * next execute, reset or destroy. */
+int mgx_batch_fetch_facets(mgx_batch* batch, mgx_facet_view* out);
+
 /* Multi-GPU exchange (one rank per doc-range shard). The batch must be all MGX_SORT_SCORE, or all docid-ordered
  * pages (MGX_SORT_DOCID with 0 < limit <= 16384): a page is a best-first list under the key "doc id" (or its
  * complement for ascending order), so the same two calls serve both.

@@ -141,6 +141,18 @@ int mgxs_facet(mgxs_table* table, uint32_t n_terms, const char* const* terms, ui
                const char* column, uint32_t limit, uint32_t offset, uint64_t* matched, uint64_t* total_values,
                uint32_t* n_out, uint64_t* counts, char* display, size_t display_cap, uint32_t* display_off);
 
+/* FACET of several columns over ONE search part, run as one device batch (BatchQuery::facet_columns through ExecuteBatch:
+ * the result is read once on the device for all of them). Per column c what mgxs_facet returns for it: total_values[c],
+ * n_out[c], the counts at counts[c * limit ..], and value k's printable form at
+ * display[display_off[c * (limit + 1) + k] .. display_off[c * (limit + 1) + k + 1]). total_values and n_out have room for
+ * n_columns entries, counts for n_columns * limit, display_off for n_columns * (limit + 1). *matched: the documents the
+ * search part matched. An unknown column fails the call with the host layer's kIndexNotFound (4000), as mgxs_facet does. */
+int mgxs_facet_columns(mgxs_table* table, uint32_t n_terms, const char* const* terms, uint32_t n_not,
+                       const char* const* not_terms, uint32_t n_cond, const char* const* cond_columns, const uint32_t* cond_ops,
+                       const char* const* cond_values, uint32_t n_columns, const char* const* columns, uint32_t limit,
+                       uint32_t offset, uint64_t* matched, uint64_t* total_values, uint32_t* n_out, uint64_t* counts,
+                       char* display, size_t display_cap, uint32_t* display_off);
+
 /* search_pipeline::MicroBatcher: the thread-safe front end. mgxs_batcher_search may be called from any number of threads at
  * once and blocks until the query's batch has run; queries are gathered into batches of at most `max_batch`, a batch
  * closing when full or when its first query has waited `max_delay_us`. docs / scores have room for

@@ -35,6 +35,7 @@ EXPORTS = [
     "mgxt_contains_fuzzy_match",
     "mgx_batch_set_highlight", "mgx_batch_fetch_highlight", "mgx_highlight_render", "mgx_index_max_text_bytes", "mgx_batch_defer_highlight",
     "mgxt_highlight_generate", "mgxt_highlight_match_positions",
+    "mgx_batch_set_facets", "mgx_batch_fetch_facets",
 ]
 
 
@@ -140,6 +141,22 @@ class HighlightView(C.Structure):
     _fields_ = [("n_entries", C.c_uint32), ("entries", C.POINTER(HighlightEntry))]
 
 
+class FacetRequest(C.Structure):
+    _fields_ = [("n_columns", C.c_uint32), ("reserved", C.c_uint32), ("column_ids", C.POINTER(C.c_uint32))]
+
+
+class FacetEntry(C.Structure):
+    _fields_ = [("query", C.c_uint32), ("column_id", C.c_uint32), ("n_values", C.c_uint32), ("reserved", C.c_uint32),
+                ("counts", C.POINTER(C.c_uint64))]
+
+
+class FacetView(C.Structure):
+    _fields_ = [("n_entries", C.c_uint32), ("entries", C.POINTER(FacetEntry))]
+
+
+FACET_MAX_COLUMNS = 8
+FACET_ARENA_CAP = 256 << 20
+FACET_LDS_BINS = 8192
 HIGHLIGHT_ARENA_CAP = 256 << 20
 CONDITION_ARENA_MAX_BYTES = 1 << 30
 HIGHLIGHT_MAX_TERMS = 256
@@ -237,6 +254,8 @@ def load():
                                           sz, C.c_char_p, sz, vp, sz, C.POINTER(sz)]
     L.mgxt_highlight_match_positions.argtypes = [C.c_char_p, sz, C.POINTER(C.c_char_p), C.POINTER(sz), u32, vp, sz,
                                                  C.POINTER(sz)]
+    L.mgx_batch_set_facets.argtypes = [vp, C.POINTER(FacetRequest), u32]
+    L.mgx_batch_fetch_facets.argtypes = [vp, C.POINTER(FacetView)]
     _lib = L
     return L
 

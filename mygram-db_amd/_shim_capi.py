@@ -11,7 +11,7 @@ LIB_PATH = os.path.join(_HERE, "libmygram_shim.so")
 EXPORTS = ["mgxs_last_error", "mgxs_table_adopt", "mgxs_table_set_global_stats", "mgxs_table_destroy",
            "mgxs_table_set_normalization", "mgxs_table_set_absent_grams", "mgxs_normalize_uses_icu", "mgxs_normalize_text",
            "mgxs_executor_create", "mgxs_executor_create_sharded", "mgxs_executor_destroy", "mgxs_executor_warm",
-           "mgxs_submit", "mgxs_wait", "mgxs_table_from_dump", "mgxs_table_add_filter_column", "mgxs_search", "mgxs_search_sorted", "mgxs_facet", "mgxs_search_highlight", "mgxs_highlight_generate",
+           "mgxs_submit", "mgxs_wait", "mgxs_table_from_dump", "mgxs_table_add_filter_column", "mgxs_search", "mgxs_search_sorted", "mgxs_facet", "mgxs_facet_columns", "mgxs_search_highlight", "mgxs_highlight_generate",
            "mgxs_table_add_document", "mgxs_table_update_document", "mgxs_table_remove_document", "mgxs_table_mutation_stats", "mgxs_table_compact", "mgxs_table_set_mutation_staleness", "mgxs_table_update_filters",
            "mgxs_batcher_create", "mgxs_batcher_destroy", "mgxs_batcher_search", "mgxs_batcher_stats"]
 _lib = None
@@ -58,6 +58,8 @@ def load():
                                           C.c_size_t, C.POINTER(C.c_size_t)]
     L.mgxs_facet.argtypes = [vp, u32, vp, u32, vp, u32, vp, vp, vp, C.c_char_p, u32, u32, C.POINTER(u64), C.POINTER(u64),
                              C.POINTER(u32), vp, vp, C.c_size_t, vp]
+    L.mgxs_facet_columns.argtypes = [vp, u32, vp, u32, vp, u32, vp, vp, vp, u32, vp, u32, u32, C.POINTER(u64), vp, vp, vp, vp,
+                                     C.c_size_t, vp]
     L.mgxs_table_add_document.argtypes = [vp, u32, C.c_char_p, C.c_size_t, u32, vp, vp, vp, vp]
     L.mgxs_table_update_document.argtypes = [vp, u32, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, i32, u32, vp, vp, vp, vp]
     L.mgxs_table_remove_document.argtypes = [vp, u32, C.c_char_p, C.c_size_t]
@@ -297,6 +299,33 @@ class Table:
                                  off.ctypes.data))
         out = [(buf.raw[off[k]: off[k + 1]], int(counts[k])) for k in range(n.value)]
         return int(matched.value), int(total_values.value), out
+
+
+    def facet_columns(self, columns, terms=(), not_terms=(), conditions=(), limit=100, offset=0):
+        """mgxs_facet_columns: one search part, several columns, one device batch -> (matched documents,
+        [(total values, [(display value, count)]) per column])."""
+        t, nt = self._strs(terms)
+        x, nx = self._strs(not_terms)
+        cols, ops, vals, nc = self._conds(list(conditions))
+        names, n_names = self._strs(columns)
+        matched = C.c_uint64()
+        total_values = np.zeros(n_names, np.uint64)
+        n_out = np.zeros(n_names, np.uint32)
+        counts = np.zeros(n_names * max(limit, 1), np.uint64)
+        cap = 1 << 20
+        buf = C.create_string_buffer(cap)
+        off = np.zeros(n_names * (max(limit, 1) + 1), np.uint32)
+        _check(load().mgxs_facet_columns(self._h, nt, C.cast(t, C.c_void_p), nx, C.cast(x, C.c_void_p), nc,
+                                         C.cast(cols, C.c_void_p), ops.ctypes.data, C.cast(vals, C.c_void_p), n_names,
+                                         C.cast(names, C.c_void_p), limit, offset, C.byref(matched),
+                                         total_values.ctypes.data, n_out.ctypes.data, counts.ctypes.data, buf, cap,
+                                         off.ctypes.data))
+        out = []
+        for c in range(n_names):
+            o = off[c * (limit + 1):]
+            out.append((int(total_values[c]),
+                        [(buf.raw[o[k]: o[k + 1]], int(counts[c * limit + k])) for k in range(int(n_out[c]))]))
+        return int(matched.value), out
 
 
 class Executor:

@@ -31,6 +31,7 @@
 #include "mgx_compile.hpp"
 #include "mgx_highlight.hpp"
 #include "mgx_colsort.hpp"
+#include "mgx_facet.hpp"
 #include "mgx_host.hpp"
 #include "mgx_internal.hpp"
 #include "mgx_launch.hpp"
@@ -140,8 +141,8 @@ struct Arena {
 struct BatchResources {
   Arena upload{true}, out{false};
   bool uploaded = false;
-  void* h_down[3] = {nullptr, nullptr, nullptr};  // pinned result blocks (score group, docid-page group, highlight records)
-  size_t h_down_cap[3] = {0, 0, 0};
+  void* h_down[4] = {nullptr, nullptr, nullptr, nullptr};  // pinned result blocks (score group, docid-page group, highlight records, facet counts)
+  size_t h_down_cap[4] = {0, 0, 0, 0};
   hipEvent_t fork_ev = nullptr, join_ev = nullptr;  // fork/join of the side-stream launch
   // A batch object is one pipeline slot: with a NULL stream argument it runs on its own non-blocking stream, and the
   // copy of its (small) result block to pinned memory is part of the execute, fenced by done_ev — so fetching batch i
@@ -1397,6 +1398,18 @@ struct mgx_batch {
     bool on() const { return !queries.empty(); }
   };
   Highlight hl;
+  // FACET in a batch (mgx_batch_set_facets): the plan of mgx_facet.hpp, its descriptors on the device, and the counts
+  // facet_batch_kernel fills behind the bitmap group, copied to pinned memory with the batch's results
+  struct Facets {
+    mgx::facet::Plan plan;
+    std::vector<int32_t> of_query;  // batch query -> index into plan.queries, or -1
+    DevBuf d_queries, d_columns, d_items, d_counts;
+    void* h_counts = nullptr;  // pinned (BatchResources)
+    std::vector<mgx_facet_entry> entries;  // of the last fetch
+    bool on() const { return !plan.queries.empty(); }
+    bool faceted(uint32_t qi) const { return on() && of_query[qi] >= 0; }
+  };
+  Facets fc;
   bool fetched = false;  // mgx_batch_fetch assembled h_results for the last execute
   // host results
   std::vector<mgx_query_result> h_results;
@@ -2593,6 +2606,24 @@ static int RunHighlight(mgx_batch* b, hipStream_t s, bool merged, const mgx_inde
   return MGX_OK;
 }
 
+// FACET in a batch: the counts of every (faceted query, column) from the bitmap group's result bitmaps, behind the
+// group's kernels, and their copy to pinned memory (the caller records the batch's done event after it).
+static int RunFacets(mgx_batch* b, hipStream_t s) {
+  mgx_batch::Facets& f = b->fc;
+  if (f.plan.arena_bytes == 0) return MGX_OK;  // (every requested column is empty: there is nothing to count)
+  MGX_HIP(hipMemsetAsync(f.d_counts.p, 0, f.plan.arena_bytes, s));
+  facet::DevBatch fb{};
+  fb.rbits = b->bitmap.dev.rbits;
+  fb.queries = f.d_queries.as<facet::DevQuery>();
+  fb.columns = f.d_columns.as<facet::DevColumn>();
+  fb.items = f.d_items.as<facet::Item>();
+  fb.n_items = static_cast<uint32_t>(f.plan.items.size());
+  fb.n_docs = b->idx->dev.n_docs;
+  MGX_LAUNCH(LaunchFacetBatch(fb, s));
+  MGX_HIP(hipMemcpyAsync(f.h_counts, f.d_counts.p, f.plan.arena_bytes, hipMemcpyDeviceToHost, s));
+  return MGX_OK;
+}
+
 static int ExecuteImpl(mgx_batch* b, hipStream_t s, const SeedGather* sg = nullptr) {
   mgx_index* idx = b->idx;
   MGX_HIP(hipSetDevice(idx->device));
@@ -2780,6 +2811,10 @@ static int ExecuteImpl(mgx_batch* b, hipStream_t s, const SeedGather* sg = nullp
     const int rc = RunHighlight(b, s, /*merged=*/false, nullptr, idx);  // (a page of one index holds that index's own ids)
     if (rc) return rc;
   }
+  if (b->fc.on()) {
+    const int rc = RunFacets(b, s);
+    if (rc) return rc;
+  }
   {
     int rc = IssueResultCopy(b, s);
     if (rc) return rc;
@@ -2878,7 +2913,9 @@ static int FetchBitmapPages(mgx_batch* a, BitmapPages* m) {
     const QuerySpec& sp = a->specs[g.qids[i]];
     const uint64_t t = a->merged_away ? 0 : tot[0][i] + tot[1][i];  // (merged_away: sizes the empty page only)
     uint64_t lo = 0, hi = 0;
-    if (sp.deep_score || sp.col_sort) {
+    if (a->fc.faceted(g.qids[i])) {
+      // a faceted query returns its counts, no page: nothing is expanded for it
+    } else if (sp.deep_score || sp.col_sort) {
       lo = std::min<uint64_t>(sp.offset, t);
       hi = sp.limit == 0 ? t : std::min<uint64_t>(lo + sp.limit, t);
     } else {
@@ -3493,6 +3530,117 @@ static_assert(sizeof(mgx_highlight_window) == sizeof(mgx::highlight::Window) &&
                   offsetof(mgx_highlight_span, end) == offsetof(mgx::highlight::Span, end),
               "the ABI's record structs are the shared header's, field by field");
 
+int mgx_batch_set_facets(mgx_batch* batch, const mgx_facet_request* requests, uint32_t n_queries) {
+  namespace fc = mgx::facet;
+  if (!batch || (n_queries && !requests)) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_batch_set_facets: null argument");
+  if (!batch->res_owned) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_batch_set_facets: not a prepared batch object");
+  if (n_queries != batch->n_queries)
+    return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_batch_set_facets: one request per query of the batch");
+  if (batch->res->uploaded || batch->executed || batch->fc.on())
+    return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_batch_set_facets: call it once, after prepare / reset and before the first execute");
+  try {
+    mgx_index* idx = batch->idx;
+    std::vector<uint32_t> pos_in_group(n_queries, 0);
+    for (size_t i = 0; i < batch->bitmap.qids.size(); ++i) pos_in_group[batch->bitmap.qids[i]] = static_cast<uint32_t>(i);
+    std::vector<fc::Request> reqs;
+    std::vector<const uint32_t*> value_ids;  // of every requested column, in plan order
+    for (uint32_t qi = 0; qi < n_queries; ++qi) {
+      const mgx_facet_request& r = requests[qi];
+      if (r.n_columns == 0) continue;
+      const std::string who = "mgx_batch_set_facets: query " + std::to_string(qi) + ": ";
+      if (!r.column_ids) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, who + "null column list");
+      if (r.n_columns > MGX_FACET_MAX_COLUMNS)
+        return mgx::Fail(MGX_ERR_OUT_OF_RANGE, who + "more than MGX_FACET_MAX_COLUMNS (8) facet columns");
+      const mgx::QuerySpec& sp = batch->specs[qi];
+      if (sp.mode != mgx::kModeBitmap || sp.limit != 0 || sp.deep_score || sp.col_sort)
+        return mgx::Fail(MGX_ERR_INVALID_ARGUMENT,
+                         who + "a faceted query must be MGX_SORT_DOCID with limit 0 (it returns counts, not a page)");
+      fc::Request rq;
+      rq.query = qi;
+      rq.row = pos_in_group[qi];
+      std::lock_guard<std::mutex> lock(idx->mu);  // (columns are added under mu; the objects themselves never move)
+      for (uint32_t c = 0; c < r.n_columns; ++c) {
+        const uint32_t id = r.column_ids[c];
+        if (id >= idx->filter_columns.size())
+          return mgx::Fail(MGX_ERR_OUT_OF_RANGE, who + "unknown filter column " + std::to_string(id));
+        const mgx_index::FilterColumn& col = *idx->filter_columns[id];
+        if (!col.d_value_ids.p)
+          return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, who + "filter column " + std::to_string(id) + " was added without value ids");
+        rq.column_ids.push_back(id);
+        rq.n_values.push_back(col.n_values);
+        value_ids.push_back(col.d_value_ids.as<uint32_t>());
+      }
+      reqs.push_back(std::move(rq));
+    }
+    if (reqs.empty()) return MGX_OK;  // nothing is faceted: the batch allocates, launches and copies nothing new
+    // MGX_FACET_BALLOT_MAX: the largest column the ballot path takes (tools/bench_facet.py times the paths against each other)
+    static const char* const ballot_env = std::getenv("MGX_FACET_BALLOT_MAX");
+    const uint32_t ballot_max =
+        ballot_env ? std::min<uint32_t>(static_cast<uint32_t>(std::max(0, atoi(ballot_env))), 63u) : fc::kBallotMaxValues;
+    fc::Plan plan;
+    size_t bad = 0;
+    const fc::Status st = fc::Build(reqs, idx->dev.n_tiles, ballot_max, &plan, &bad);
+    if (st == fc::kTooManyColumns)
+      return mgx::Fail(MGX_ERR_OUT_OF_RANGE, "mgx_batch_set_facets: query " + std::to_string(reqs[bad].query) +
+                                                 ": more than MGX_FACET_MAX_COLUMNS (8) facet columns");
+    if (st == fc::kArenaTooLarge)
+      return mgx::Fail(MGX_ERR_OUT_OF_RANGE,
+                       "mgx_batch_set_facets: the batch's counts exceed MGX_FACET_ARENA_CAP (256 MiB) at query " +
+                           std::to_string(reqs[bad].query) + "; facet fewer queries or columns per batch");
+    mgx::ResourceScope scope(batch->res);
+    MGX_HIP(hipSetDevice(idx->device));
+    mgx_batch::Facets& f = batch->fc;
+    MGX_HIP(f.d_counts.Alloc(plan.arena_bytes));
+    MGX_HIP(batch->res->Pinned(3, plan.arena_bytes, &f.h_counts));
+    const uint64_t row_words = static_cast<uint64_t>(idx->dev.n_tiles) * mgx::kWordsPerTile;
+    std::vector<fc::DevQuery> dq(plan.queries.size());
+    std::vector<fc::DevColumn> dc(plan.columns.size());
+    std::vector<int32_t> of_query(n_queries, -1);
+    for (size_t i = 0; i < plan.queries.size(); ++i) {
+      const fc::QueryPlan& q = plan.queries[i];
+      of_query[q.query] = static_cast<int32_t>(i);
+      dq[i] = fc::DevQuery{q.row * row_words, q.col_begin, q.n_cols, q.lds_bins, 0};
+    }
+    for (size_t i = 0; i < plan.columns.size(); ++i) {
+      const fc::ColumnPlan& c = plan.columns[i];
+      dc[i] = fc::DevColumn{value_ids[i], f.d_counts.as<unsigned long long>() + c.count_off, c.n_values, c.lds_begin,
+                            c.ballot, 0};
+    }
+    MGX_HIP(mgx::Upload(f.d_queries, dq.data(), dq.size()));
+    MGX_HIP(mgx::Upload(f.d_columns, dc.data(), dc.size()));
+    MGX_HIP(mgx::Upload(f.d_items, plan.items.data(), plan.items.size()));
+    f.of_query = std::move(of_query);
+    f.plan = std::move(plan);
+    return MGX_OK;
+  } catch (const std::exception& e) {
+    return mgx::Fail(MGX_ERR_INTERNAL, std::string("mgx_batch_set_facets: ") + e.what());
+  }
+}
+
+int mgx_batch_fetch_facets(mgx_batch* batch, mgx_facet_view* out) {
+  if (out) std::memset(out, 0, sizeof(*out));
+  if (!batch || !out) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_batch_fetch_facets: null argument");
+  if (!batch->executed || !batch->fetched)
+    return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_batch_fetch_facets: call mgx_batch_fetch for this execute first");
+  try {
+    mgx_batch::Facets& f = batch->fc;
+    f.entries.clear();
+    for (const mgx::facet::ColumnPlan& c : f.plan.columns) {
+      mgx_facet_entry e{};
+      e.query = c.query;
+      e.column_id = c.column_id;
+      e.n_values = c.n_values;
+      e.counts = c.n_values ? static_cast<const uint64_t*>(f.h_counts) + c.count_off : nullptr;
+      f.entries.push_back(e);
+    }
+    out->n_entries = static_cast<uint32_t>(f.entries.size());
+    out->entries = f.entries.data();
+    return MGX_OK;
+  } catch (const std::exception& e) {
+    return mgx::Fail(MGX_ERR_INTERNAL, std::string("mgx_batch_fetch_facets: ") + e.what());
+  }
+}
+
 int mgx_highlight_render(const mgx_highlight_entry* entry, const uint8_t* open_tag, size_t open_len,
                          const uint8_t* close_tag, size_t close_len, uint8_t* out, size_t cap, size_t* out_len) {
   namespace hl = mgx::highlight;
@@ -3553,6 +3701,11 @@ static int RefuseColumnSort(const mgx_batch* batch, const char* entry) {
   return mgx::Fail(MGX_ERR_NOT_IMPLEMENTED, std::string(entry) + ": SORT by a filter column on a sharded table is not implemented: a page's order needs every shard's column values");
 }
 
+// (the counts of a sharded table's facets would need an all-reduce across the ranks: out of scope)
+static int RefuseFacets(const char* entry) {
+  return mgx::Fail(MGX_ERR_NOT_IMPLEMENTED, std::string(entry) + ": facets (mgx_batch_set_facets) on a sharded table are not implemented: the counts of the shards are not reduced");
+}
+
 static int ExportGroup(mgx_batch* batch, bool pages, uint64_t* blob64, uint32_t* blob32, uint32_t* stride, void* hip_stream);
 static int MergeGroup(mgx_batch* batch, bool pages, uint32_t n_shards, const uint64_t* blob64, uint64_t pitch64,
                       const uint32_t* blob32, uint64_t pitch32, void* hip_stream);
@@ -3560,6 +3713,7 @@ static int MergeGroup(mgx_batch* batch, bool pages, uint32_t n_shards, const uin
 int mgx_batch_export_topk(mgx_batch* batch, uint64_t* blob64, uint32_t* blob32, uint32_t* stride,
                           void* hip_stream) {
   if (!batch || !stride) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_batch_export_topk: null argument");
+  if (batch->fc.on()) return RefuseFacets("mgx_batch_export_topk");
   if (batch->hl.on()) return mgx::Fail(MGX_ERR_NOT_IMPLEMENTED, "mgx_batch_export_topk: highlight on a sharded table is not implemented: the page's texts live on other ranks");
   if (const int rc_cs = RefuseColumnSort(batch, "mgx_batch_export_topk")) return rc_cs;
   const bool pages = batch->score.qids.empty() && batch->bitmap.qids.empty() && !batch->page.qids.empty();
@@ -3601,6 +3755,7 @@ int mgx_batch_export_buffer(mgx_batch* batch, void** device_blob, uint64_t* byte
   if (offset32) *offset32 = 0;
   if (!batch || !device_blob || !bytes || !offset32)
     return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_batch_export_buffer: null argument");
+  if (batch->fc.on()) return RefuseFacets("mgx_batch_export_buffer");
   if (batch->hl.on())
     return mgx::Fail(MGX_ERR_NOT_IMPLEMENTED, "mgx_batch_export_buffer: highlight on a sharded table is not implemented: the page's texts live on other ranks");
   if (const int rc_cs = RefuseColumnSort(batch, "mgx_batch_export_buffer")) return rc_cs;
@@ -3615,6 +3770,7 @@ int mgx_batch_merge_shards(mgx_batch* batch, uint32_t n_shards, const uint64_t* 
                            const uint32_t* blob32, uint64_t pitch32, void* hip_stream) {
   if (!batch || !blob64 || !blob32 || n_shards == 0)
     return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_batch_merge_shards: null argument");
+  if (batch->fc.on()) return RefuseFacets("mgx_batch_merge_shards");
   if (batch->hl.on()) return mgx::Fail(MGX_ERR_NOT_IMPLEMENTED, "mgx_batch_merge_shards: highlight on a sharded table is not implemented: the page's texts live on other ranks");
   if (const int rc_cs = RefuseColumnSort(batch, "mgx_batch_merge_shards")) return rc_cs;
   const bool pages = batch->score.qids.empty() && batch->bitmap.qids.empty() && !batch->page.qids.empty();
@@ -3928,6 +4084,7 @@ int mgx_batch_exchange_df(mgx_batch* batch, mgx_comm* comm, void* hip_stream) {
 }
 
 int mgx_batch_exchange(mgx_batch* batch, mgx_comm* comm, void* hip_stream) {
+  if (batch && batch->fc.on()) return RefuseFacets("mgx_batch_exchange");  // (before anything else is looked at)
   if (!batch || !comm) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_batch_exchange: null argument");
   if (batch->hl.on()) return mgx::Fail(MGX_ERR_NOT_IMPLEMENTED, "mgx_batch_exchange: highlight on a sharded table is not implemented: the page's texts live on other ranks");
   if (const int rc_cs = RefuseColumnSort(batch, "mgx_batch_exchange")) return rc_cs;
@@ -3992,6 +4149,7 @@ static int RcclGather(void* user, const void* mine, void* all, uint64_t bytes, v
 
 int mgx_batch_execute_gather(mgx_batch* batch, int world, mgx_gather_fn gather, void* user, void* hip_stream) {
   if (!batch || !gather || world < 1) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_batch_execute_gather: bad argument");
+  if (batch->fc.on()) return RefuseFacets("mgx_batch_execute_gather");
   if (batch->hl.on()) return mgx::Fail(MGX_ERR_NOT_IMPLEMENTED, "mgx_batch_execute_gather: highlight on a sharded table is not implemented: the page's texts live on other ranks");
   if (const int rc_cs = RefuseColumnSort(batch, "mgx_batch_execute_gather")) return rc_cs;
   try {
@@ -4019,6 +4177,7 @@ int mgx_batch_execute_gather(mgx_batch* batch, int world, mgx_gather_fn gather, 
 }
 
 int mgx_batch_execute_sharded(mgx_batch* batch, mgx_comm* comm, void* hip_stream) {
+  if (batch && batch->fc.on()) return RefuseFacets("mgx_batch_execute_sharded");
   if (!batch || !comm) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_batch_execute_sharded: null argument");
   if (!comm->comm) return mgx::Fail(MGX_ERR_INTERNAL, "mgx_batch_execute_sharded: the communicator was aborted");
   return mgx_batch_execute_gather(batch, comm->world, &mgx::RcclGather, comm->comm, hip_stream);

@@ -1931,6 +1931,14 @@ struct PlannedQuery {
   std::vector<uint32_t> score_list;  // mgx_query::score_terms of expression / FUZZY queries
   bool has_score_list = false;
   std::deque<std::string> texts;  // normalized text-level terms (addresses stay valid as the deque grows)
+  // BatchQuery::facet_columns resolved against this index, one per name: its device column and its values (ascending)
+  struct FacetColumn {
+    bool found = false;
+    uint32_t device_id = 0;
+    std::vector<storage::FilterValue> dict;
+  };
+  bool faceted = false;
+  std::vector<FacetColumn> facets;
   // Back to the freshly constructed state WITHOUT giving memory back: an executor slot re-plans a thousand of these
   // per batch, and constructing one allocates (the deque's map and first node alone are two mallocs).
   void Reset() {
@@ -1948,6 +1956,8 @@ struct PlannedQuery {
     score_list.clear();
     has_score_list = false;
     texts.clear();
+    faceted = false;
+    facets.clear();
   }
 };
 
@@ -2197,8 +2207,51 @@ void PlanQueryBody(const index::Index& index, const BatchQuery& q, uint64_t tota
 
 // PlanQueryBody, and BatchQuery::sort_column resolved against the index's columns: the device query then asks for
 // MGX_SORT_COLUMN / _RANK with the pagination offset.
+// The search part of a FACET (ExecuteFacetPipeline): the query's own, or — FACET without search terms — every document
+// (GetAllDocIds, :2118) narrowed by its NOT terms and filters: the expression NOT(<empty>) is the universe. No order, no
+// page: limit and offset page the values.
+BatchQuery FacetSearchPart(const BatchQuery& query) {
+  BatchQuery q = query;
+  q.sort_by_score = false;
+  q.sort_column.clear();
+  q.facet_columns.clear();
+  q.limit = 0;
+  q.offset = 0;
+  if (q.terms.empty() && !q.ast) {
+    auto all = std::make_shared<query::QueryNode>(query::NodeType::NOT);
+    all->children.push_back(std::make_unique<query::QueryNode>(std::string()));
+    q.ast = std::move(all);
+  }
+  return q;
+}
+
+// BatchQuery::facet_columns: the names resolved against this index (a name it does not know is left to the caller: on a
+// table with a delta the other index may hold it), and the search part planned as a limit-0 doc-id query.
+void PlanFacetQuery(const index::Index& index, const BatchQuery& q, uint64_t total_docs, double avgdl, PlannedQuery* p) {
+  if (q.highlight) return Fail(p, ErrorCode::kInvalidArgument, "facet_columns and highlight: a faceted query returns counts, not a page");
+  if (q.facet_columns.size() > MGX_FACET_MAX_COLUMNS)
+    return Fail(p, ErrorCode::kOutOfRange, "more than MGX_FACET_MAX_COLUMNS (8) facet columns in one query");
+  index.FlushPendingFilterColumns();
+  const index::Index::Impl* im = index.impl();
+  std::vector<PlannedQuery::FacetColumn> cols(q.facet_columns.size());
+  {
+    std::lock_guard<std::mutex> lock(im->filter_mu);
+    for (size_t c = 0; c < cols.size(); ++c) {
+      const index::Index::Impl::FilterColumn* col = im->ResolveColumn(q.facet_columns[c]);
+      if (col == nullptr) continue;
+      cols[c].found = true;
+      cols[c].device_id = col->device_id;
+      cols[c].dict = col->dict;
+    }
+  }
+  PlanQueryBody(index, FacetSearchPart(q), total_docs, avgdl, p);
+  p->faceted = true;
+  p->facets = std::move(cols);
+}
+
 void PlanQuery(const index::Index& index, const BatchQuery& q, uint64_t total_docs, double avgdl, PlannedQuery* p) {
   p->sort_string = false;
+  if (!q.facet_columns.empty()) return PlanFacetQuery(index, q, total_docs, avgdl, p);
   if (q.sort_column.empty()) return PlanQueryBody(index, q, total_docs, avgdl, p);
   if (q.sort_by_score) return Fail(p, ErrorCode::kInvalidArgument, "sort_column and sort_by_score are two orders: set one of them");
   index.FlushPendingFilterColumns();
@@ -2542,6 +2595,7 @@ void Collect(const std::vector<PlannedQuery>& plans, const mgx_result_view& v, s
     o.total_candidates = o.after_intersection = o.after_not = o.after_filters = 0;
     o.empty_term_detected = false;
     o.snippets.clear();
+    o.facets.clear();
     if (!plans[qi].on_device) {
       o.empty_term_detected = plans[qi].empty_term_detected;
       continue;
@@ -2670,6 +2724,159 @@ int CollectSnippets(const std::vector<BatchQuery>& queries, const std::vector<Pl
   }
   return MGX_OK;
 }
+
+// The counts of a mutable table's two indexes meet by value, not by per-index id: (dict, counts) of the main index (found:
+// it has the column) and of the delta -> the merged pair, values ascending.
+void MergeFacetValues(bool* found, std::vector<storage::FilterValue>* dict, std::vector<uint64_t>* counts,
+                      const std::vector<storage::FilterValue>& ddict, const std::vector<uint64_t>& dcounts) {
+  std::vector<storage::FilterValue> merged;
+  std::vector<uint64_t> mcounts;
+  size_t i = 0, j = 0;
+  const size_t ni = *found ? dict->size() : 0;
+  while (i < ni || j < ddict.size()) {
+    if (j == ddict.size() || (i < ni && (*dict)[i] < ddict[j])) {
+      merged.push_back((*dict)[i]);
+      mcounts.push_back((*counts)[i]);
+      ++i;
+    } else if (i == ni || ddict[j] < (*dict)[i]) {
+      merged.push_back(ddict[j]);
+      mcounts.push_back(dcounts[j]);
+      ++j;
+    } else {
+      merged.push_back((*dict)[i]);
+      mcounts.push_back((*counts)[i] + dcounts[j]);
+      ++i;
+      ++j;
+    }
+  }
+  dict->swap(merged);
+  counts->swap(mcounts);
+  *found = true;
+}
+
+Error FacetColumnNotFound(const std::string& column) {  // search_pipeline.cpp:2089-2092
+  return MakeError(ErrorCode::kIndexNotFound, "Facet column \"" + column + "\" not found");
+}
+
+// The values with a non-zero count, count descending (:307), then offset and limit (:2141-2148).
+void PageFacetValues(const std::vector<storage::FilterValue>& dict, const std::vector<uint64_t>& counts, uint32_t limit,
+                     uint32_t offset, FacetOutput* out) {
+  std::vector<size_t> order;
+  for (size_t v = 0; v < dict.size(); ++v)
+    if (counts[v] > 0) order.push_back(v);
+  std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return counts[a] > counts[b]; });
+  out->total_values = order.size();
+  const size_t first = std::min<size_t>(offset, order.size());
+  const size_t last = std::min<size_t>(order.size(), first + static_cast<size_t>(limit));
+  for (size_t k = first; k < last; ++k) {
+    out->value_counts.emplace_back(storage::SerializeFilterValue(dict[order[k]]), counts[order[k]]);
+    out->display.push_back(storage::FilterValueToDisplayString(dict[order[k]]));
+  }
+}
+
+// ---- FACET in a batch -------------------------------------------------------------------------------------------------
+// The requests of one batch's device queries (mgx_batch_set_facets) and the ids they point at.
+struct FacetRequests {
+  std::vector<mgx_facet_request> reqs;
+  std::vector<std::vector<uint32_t>> ids;
+};
+
+bool AnyFacets(const std::vector<BatchQuery>& queries) {
+  for (const auto& q : queries)
+    if (!q.facet_columns.empty()) return true;
+  return false;
+}
+
+// A facet column must exist in the table: in the main index or, on a table with a delta, in the delta (ExecuteFacet's rule).
+Error CheckFacetColumns(const std::vector<BatchQuery>& queries, const std::vector<PlannedQuery>& plans,
+                        const std::vector<PlannedQuery>* dplans) {
+  for (size_t qi = 0; qi < plans.size(); ++qi) {
+    if (!plans[qi].faceted) continue;
+    for (size_t c = 0; c < plans[qi].facets.size(); ++c) {
+      const bool in_delta = dplans != nullptr && c < (*dplans)[qi].facets.size() && (*dplans)[qi].facets[c].found;
+      if (!plans[qi].facets[c].found && !in_delta) return FacetColumnNotFound(queries[qi].facet_columns[c]);
+    }
+  }
+  return Error{ErrorCode::kSuccess, ""};
+}
+
+// After prepare / reset and before the execute, next to the highlight requests; `plans` are those the batch was compiled
+// from (the main index's, or the delta's for the delta's batch). A column this index does not hold is left out.
+Error AttachFacets(const std::vector<PlannedQuery>& plans, mgx_batch* batch, FacetRequests* f) {
+  f->reqs.clear();
+  size_t n_dev = 0;
+  bool any = false;
+  for (const auto& p : plans) {
+    n_dev += p.on_device ? 1 : 0;
+    any = any || (p.on_device && p.faceted);
+  }
+  if (!any) return Error{ErrorCode::kSuccess, ""};
+  f->reqs.assign(n_dev, mgx_facet_request{});
+  f->ids.resize(n_dev);
+  size_t k = 0;
+  for (const auto& p : plans) {
+    if (!p.on_device) continue;
+    const size_t at = k++;
+    f->ids[at].clear();
+    if (!p.faceted) continue;
+    for (const auto& c : p.facets)
+      if (c.found) f->ids[at].push_back(c.device_id);
+    f->reqs[at].n_columns = static_cast<uint32_t>(f->ids[at].size());
+    f->reqs[at].column_ids = f->ids[at].data();
+  }
+  const int rc = mgx_batch_set_facets(batch, f->reqs.data(), static_cast<uint32_t>(f->reqs.size()));
+  return rc == MGX_OK ? Error{ErrorCode::kSuccess, ""} : MakeError(static_cast<ErrorCode>(rc), mgx_last_error());
+}
+
+// After mgx_batch_fetch (of both batches on a table with a delta) and Collect: BatchResult::facets of the faceted queries,
+// what ExecuteFacet returns per column. batch / dbatch: nullptr when no query reached the device.
+Error CollectFacets(const std::vector<BatchQuery>& queries, const std::vector<PlannedQuery>& plans,
+                  const std::vector<PlannedQuery>* dplans, mgx_batch* batch, mgx_batch* dbatch,
+                  std::vector<BatchResult>* out) {
+  if (!AnyFacets(queries)) return Error{ErrorCode::kSuccess, ""};
+  mgx_facet_view fv{}, dfv{};
+  int rc = batch != nullptr ? mgx_batch_fetch_facets(batch, &fv) : MGX_OK;
+  if (rc == MGX_OK && dbatch != nullptr) rc = mgx_batch_fetch_facets(dbatch, &dfv);
+  if (rc != MGX_OK) return MakeError(static_cast<ErrorCode>(rc), mgx_last_error());
+  uint32_t e = 0, de = 0, k = 0;  // the next entry of each view; the device query's position in its batch
+  // the counts of column c of one index's plan, by that index's value ids
+  auto take = [](const PlannedQuery& p, size_t c, const mgx_facet_view& view, uint32_t* next, uint32_t dev_query,
+                 std::vector<uint64_t>* counts) {
+    const PlannedQuery::FacetColumn& col = p.facets[c];
+    counts->assign(std::max<size_t>(col.dict.size(), 1), 0);
+    if (!p.on_device || !col.found) return true;
+    if (*next >= view.n_entries) return false;
+    const mgx_facet_entry& en = view.entries[(*next)++];
+    if (en.query != dev_query || en.column_id != col.device_id) return false;
+    for (uint32_t v = 0; v < en.n_values && v < counts->size(); ++v) (*counts)[v] = en.counts[v];
+    return true;
+  };
+  for (size_t qi = 0; qi < plans.size(); ++qi) {
+    const PlannedQuery& p = plans[qi];
+    if (p.faceted) {
+      const PlannedQuery* d = dplans != nullptr ? &(*dplans)[qi] : nullptr;
+      BatchResult& o = (*out)[qi];
+      o.results.clear();  // (counts, not a page)
+      o.scores.clear();
+      o.facets.resize(p.facets.size());
+      for (size_t c = 0; c < p.facets.size(); ++c) {
+        std::vector<uint64_t> counts, dcounts;
+        if (!take(p, c, fv, &e, k, &counts) || (d != nullptr && !take(*d, c, dfv, &de, k, &dcounts))) {
+          return MakeError(ErrorCode::kInternalError, "the batch's facet entries do not match its requests");
+        }
+        bool found = p.facets[c].found;
+        std::vector<storage::FilterValue> dict = p.facets[c].dict;
+        if (d != nullptr && d->facets[c].found) MergeFacetValues(&found, &dict, &counts, d->facets[c].dict, dcounts);
+        FacetOutput& fo = o.facets[c];
+        fo = FacetOutput{};
+        fo.matched_documents = o.total;
+        PageFacetValues(dict, counts, queries[qi].limit, queries[qi].offset, &fo);
+      }
+    }
+    if (p.on_device) ++k;
+  }
+  return Error{ErrorCode::kSuccess, ""};
+}
 }  // namespace
 
 std::vector<std::string> BuildHighlightTerms(const std::vector<std::string>& search_terms, const index::Index* index) {
@@ -2760,10 +2967,16 @@ Expected<std::vector<BatchResult>, Error> ExecuteBatch(const index::Index& index
       if (dplans[qi].on_device) dq.push_back(dplans[qi].q);
     }
   }
+  {
+    const Error fe = CheckFacetColumns(queries, plans, delta ? &dplans : nullptr);
+    if (fe.code() != ErrorCode::kSuccess) return MakeUnexpected(fe);
+  }
   std::vector<BatchResult> out;
   mgx_result_view v{};
   if (mq.empty()) {
     Collect(plans, v, &out);
+    const Error fe = CollectFacets(queries, plans, delta ? &dplans : nullptr, nullptr, nullptr, &out);
+    if (fe.code() != ErrorCode::kSuccess) return MakeUnexpected(fe);
     return out;
   }
   mgx_batch* batch = nullptr;
@@ -2771,15 +2984,22 @@ Expected<std::vector<BatchResult>, Error> ExecuteBatch(const index::Index& index
   if (rc != MGX_OK) return MakeUnexpected(MakeError(static_cast<ErrorCode>(rc), mgx_last_error()));
   std::unique_ptr<mgx_batch, void (*)(mgx_batch*)> guard(batch, mgx_batch_destroy);
   HighlightRequests hreq;
+  FacetRequests freq, dfreq;
   {
     const Error he = AttachHighlight(index, delta.get(), queries, plans, batch, &hreq);
     if (he.code() != ErrorCode::kSuccess) return MakeUnexpected(he);
+    const Error fe = AttachFacets(plans, batch, &freq);
+    if (fe.code() != ErrorCode::kSuccess) return MakeUnexpected(fe);
   }
   if (delta) {
     mgx_batch* dbatch = nullptr;
     rc = mgx_batch_prepare(delta->impl()->dev, dq.data(), static_cast<uint32_t>(dq.size()), &dbatch);
     if (rc != MGX_OK) return MakeUnexpected(MakeError(static_cast<ErrorCode>(rc), mgx_last_error()));
     std::unique_ptr<mgx_batch, void (*)(mgx_batch*)> dguard(dbatch, mgx_batch_destroy);
+    {
+      const Error fe = AttachFacets(dplans, dbatch, &dfreq);  // both batches carry the requests
+      if (fe.code() != ErrorCode::kSuccess) return MakeUnexpected(fe);
+    }
     void* stream = nullptr;
     rc = mgx_batch_stream(batch, &stream);
     if (rc == MGX_OK) rc = RunWithDelta(batch, dbatch, stream);
@@ -2791,6 +3011,8 @@ Expected<std::vector<BatchResult>, Error> ExecuteBatch(const index::Index& index
     Collect(plans, v, &out, &dv);
     rc = CollectSnippets(queries, plans, batch, v, &out);
     if (rc != MGX_OK) return MakeUnexpected(MakeError(static_cast<ErrorCode>(rc), mgx_last_error()));
+    const Error fe = CollectFacets(queries, plans, &dplans, batch, dbatch, &out);
+    if (fe.code() != ErrorCode::kSuccess) return MakeUnexpected(fe);
     return out;
   }
   rc = mgx_batch_execute(batch, nullptr);
@@ -2800,6 +3022,8 @@ Expected<std::vector<BatchResult>, Error> ExecuteBatch(const index::Index& index
   Collect(plans, v, &out);
   rc = CollectSnippets(queries, plans, batch, v, &out);
   if (rc != MGX_OK) return MakeUnexpected(MakeError(static_cast<ErrorCode>(rc), mgx_last_error()));
+  const Error fe = CollectFacets(queries, plans, nullptr, batch, nullptr, &out);
+  if (fe.code() != ErrorCode::kSuccess) return MakeUnexpected(fe);
   return out;
 }
 
@@ -2824,16 +3048,7 @@ Error FacetOne(const index::Index& index, const BatchQuery& query, const std::st
   }
   // the search part: the query's own, or — FACET without search terms — every document (GetAllDocIds, :2118) narrowed by
   // its NOT terms and filters: the expression NOT(<empty>) is the universe
-  BatchQuery q = query;
-  q.sort_by_score = false;
-  q.sort_column.clear();
-  q.limit = 0;
-  q.offset = 0;
-  if (q.terms.empty() && !q.ast) {
-    auto all = std::make_shared<query::QueryNode>(query::NodeType::NOT);
-    all->children.push_back(std::make_unique<query::QueryNode>(std::string()));
-    q.ast = std::move(all);
-  }
+  const BatchQuery q = FacetSearchPart(query);
   PlannedQuery plan;
   PlanQuery(index, q, index.Bm25DocCount(), index.Bm25AvgDocLength(), &plan);
   if (plan.error != ErrorCode::kSuccess) return MakeError(plan.error, plan.error_message);
@@ -2869,45 +3084,10 @@ Expected<FacetOutput, Error> ExecuteFacet(const index::Index& index, const Batch
     e = FacetOne(*delta, query, column, &dfound, &ddict, &dcounts, &dmatched);
     if (e.code() != ErrorCode::kSuccess) return MakeUnexpected(e);
     out.matched_documents += dmatched;
-    if (dfound) {
-      std::vector<storage::FilterValue> merged;
-      std::vector<uint64_t> mcounts;
-      size_t i = 0, j = 0;
-      const size_t ni = found ? dict.size() : 0;
-      while (i < ni || j < ddict.size()) {
-        if (j == ddict.size() || (i < ni && dict[i] < ddict[j])) {
-          merged.push_back(dict[i]);
-          mcounts.push_back(counts[i]);
-          ++i;
-        } else if (i == ni || ddict[j] < dict[i]) {
-          merged.push_back(ddict[j]);
-          mcounts.push_back(dcounts[j]);
-          ++j;
-        } else {
-          merged.push_back(dict[i]);
-          mcounts.push_back(counts[i] + dcounts[j]);
-          ++i;
-          ++j;
-        }
-      }
-      dict.swap(merged);
-      counts.swap(mcounts);
-      found = true;
-    }
+    if (dfound) MergeFacetValues(&found, &dict, &counts, ddict, dcounts);
   }
-  if (!found)  // search_pipeline.cpp:2089-2092
-    return MakeUnexpected(MakeError(ErrorCode::kIndexNotFound, "Facet column \"" + column + "\" not found"));
-  std::vector<size_t> order;
-  for (size_t v = 0; v < dict.size(); ++v)
-    if (counts[v] > 0) order.push_back(v);
-  std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return counts[a] > counts[b]; });  // :307
-  out.total_values = order.size();
-  const size_t first = std::min<size_t>(query.offset, order.size());                         // :2141-2148
-  const size_t last = std::min<size_t>(order.size(), first + static_cast<size_t>(query.limit));
-  for (size_t k = first; k < last; ++k) {
-    out.value_counts.emplace_back(storage::SerializeFilterValue(dict[order[k]]), counts[order[k]]);
-    out.display.push_back(storage::FilterValueToDisplayString(dict[order[k]]));
-  }
+  if (!found) return MakeUnexpected(FacetColumnNotFound(column));
+  PageFacetValues(dict, counts, query.limit, query.offset, &out);
   return out;
 }
 
@@ -2937,6 +3117,7 @@ struct BatchExecutor::Impl {
     std::vector<PlannedQuery> dplans;
     std::vector<mgx_query> dq;
     HighlightRequests hreq;  // mgx_batch_set_highlight of this batch (storage re-used from batch to batch)
+    FacetRequests freq, dfreq;  // mgx_batch_set_facets of the batch and of the delta's batch
     mgx_batch* dbatch = nullptr;
     uint64_t total_docs = 0;  // BM25Stats the batch is planned with (a mutable table's change between batches)
     double avgdl = 0.0;
@@ -3001,6 +3182,8 @@ struct BatchExecutor::Impl {
         if (p.on_device) slot->dq.push_back(p.q);
       }
     }
+    slot->error = CheckFacetColumns(slot->queries, slot->plans, slot->delta ? &slot->dplans : nullptr);
+    if (slot->error.code() != ErrorCode::kSuccess) return;
     if (slot->mq.empty()) return;
     if (kTrace) {
       static std::atomic<uint64_t> n{0}, us{0};
@@ -3030,6 +3213,8 @@ struct BatchExecutor::Impl {
     }
     slot->error = AttachHighlight(index, slot->delta.get(), slot->queries, slot->plans, slot->batch, &slot->hreq);
     if (slot->error.code() != ErrorCode::kSuccess) return;
+    slot->error = AttachFacets(slot->plans, slot->batch, &slot->freq);
+    if (slot->error.code() != ErrorCode::kSuccess) return;
     if (slot->dbatch && slot->dbatch_index != slot->delta) {  // the delta index was rebuilt (or went away)
       mgx_batch_destroy(slot->dbatch);
       slot->dbatch = nullptr;
@@ -3042,7 +3227,11 @@ struct BatchExecutor::Impl {
     } else {
       rc = mgx_batch_reset(slot->dbatch, slot->dq.data(), static_cast<uint32_t>(slot->dq.size()));
     }
-    if (rc != MGX_OK) slot->error = MakeError(static_cast<ErrorCode>(rc), mgx_last_error());
+    if (rc != MGX_OK) {
+      slot->error = MakeError(static_cast<ErrorCode>(rc), mgx_last_error());
+      return;
+    }
+    slot->error = AttachFacets(slot->dplans, slot->dbatch, &slot->dfreq);
   }
 
   // device side, in ticket order. Called with mu held; the HIP calls themselves (they only enqueue, but a batch is a
@@ -3241,6 +3430,10 @@ Expected<uint64_t, Error> BatchExecutor::Submit(std::vector<BatchQuery>&& querie
     impl_->total_docs = impl_->index.Bm25DocCount();
     impl_->avgdl = impl_->index.Bm25AvgDocLength();
   }
+  if (impl_->opt.comm && AnyFacets(queries))
+    return MakeUnexpected(MakeError(ErrorCode::kNotImplemented,
+                                    "facet_columns on a sharded table (Options::comm) is not implemented: the counts of "
+                                    "the shards are not reduced"));
   if (impl_->opt.comm && AnyHighlight(queries))
     return MakeUnexpected(MakeError(ErrorCode::kNotImplemented,
                                     "highlight on a sharded table (Options::comm) is not implemented: the page's texts "
@@ -3342,6 +3535,16 @@ Error BatchExecutor::WaitInto(uint64_t ticket, std::vector<BatchResult>* results
       lock.lock();
       s->state = Impl::kFree;
       return e;
+    }
+  }
+  {
+    const bool dev = !s->mq.empty();
+    const Error fe = CollectFacets(s->queries, s->plans, s->delta ? &s->dplans : nullptr, dev ? s->batch : nullptr,
+                                   dev && s->delta ? s->dbatch : nullptr, &out);
+    if (fe.code() != ErrorCode::kSuccess) {
+      lock.lock();
+      s->state = Impl::kFree;
+      return fe;
     }
   }
   s->timing.wait_ms = std::chrono::duration<double, std::milli>(Impl::clock::now() - t0).count();

@@ -458,27 +458,20 @@ struct BatchQuery {
   // BuildHighlightTerms. Needs limit > 0 and offset + limit <= 1024 (docid pages: limit <= 1024, the offset is the
   // caller's cut); refused (kNotImplemented) on a sharded executor (Options::comm): the page's texts live on other ranks.
   std::optional<query::HighlightOptions> highlight;
+  // FACET in a batch: the value counts of these columns of Index::AddFilterColumn over the query's whole result set, all
+  // from ONE pass over the result on the device (mgx_batch_set_facets), beside whatever else the batch holds. Each name
+  // resolves as ExecuteFacet resolves its column; BatchResult::facets holds what ExecuteFacet returns for that column.
+  // The search part is ExecuteFacet's: no terms and no tree select every document; sort_by_score, sort_column and order
+  // are ignored; limit / offset page the VALUES. `results` stays empty and `total` is the matched count. At most 8
+  // names (kOutOfRange); `highlight` beside it: kInvalidArgument; a name no index of the table knows fails the batch
+  // with kIndexNotFound; refused (kNotImplemented) on a sharded executor (Options::comm).
+  std::vector<std::string> facet_columns;
 };
 
 // search_pipeline::BuildHighlightTerms (src/server/search_pipeline.cpp:712-745) without the synonym branch: normalize
 // (index == nullptr: the terms are normalized already), skip empty terms, add the whitespace-separated pieces, sort and
 // dedupe.
 std::vector<std::string> BuildHighlightTerms(const std::vector<std::string>& search_terms, const index::Index* index);
-
-// SearchPipelineResult (src/server/search_pipeline.h:58-65) plus the page the handler would format.
-struct BatchResult {
-  std::vector<DocId> results;          // the page, in rank order
-  std::vector<double> scores;          // parallel to results for SORT _score
-  uint64_t total = 0;                  // results.size() before pagination
-  size_t total_candidates = 0, after_intersection = 0, after_not = 0, after_filters = 0;
-  bool empty_term_detected = false;
-  std::vector<std::string> snippets;   // parallel to results when the query asked for highlight, else empty
-};
-
-// N queries planned like ExecuteFullPipeline's regular branch (GenerateTermInfos with df, sort by estimated size,
-// Execute, BM25 + SortByScore) and run as ONE device batch.
-mygram::utils::Expected<std::vector<BatchResult>, mygram::utils::Error> ExecuteBatch(
-    const index::Index& index, const std::vector<BatchQuery>& queries);
 
 // FACET (ExecuteFacetPipeline, src/server/search_pipeline.cpp:2061-2153): how many documents of the query's result set
 // hold each value of `column`. query.terms / ast / not_terms / filters / filter_conditions select the documents (none of
@@ -491,6 +484,23 @@ struct FacetOutput {
   std::vector<std::pair<std::string, uint64_t>> value_counts;
   std::vector<std::string> display;  // DeserializeToDisplayString of each key, parallel to value_counts
 };
+
+// SearchPipelineResult (src/server/search_pipeline.h:58-65) plus the page the handler would format.
+struct BatchResult {
+  std::vector<DocId> results;          // the page, in rank order
+  std::vector<double> scores;          // parallel to results for SORT _score
+  uint64_t total = 0;                  // results.size() before pagination
+  size_t total_candidates = 0, after_intersection = 0, after_not = 0, after_filters = 0;
+  bool empty_term_detected = false;
+  std::vector<std::string> snippets;   // parallel to results when the query asked for highlight, else empty
+  std::vector<FacetOutput> facets;     // one per BatchQuery::facet_columns name, else empty
+};
+
+// N queries planned like ExecuteFullPipeline's regular branch (GenerateTermInfos with df, sort by estimated size,
+// Execute, BM25 + SortByScore) and run as ONE device batch.
+mygram::utils::Expected<std::vector<BatchResult>, mygram::utils::Error> ExecuteBatch(
+    const index::Index& index, const std::vector<BatchQuery>& queries);
+
 mygram::utils::Expected<FacetOutput, mygram::utils::Error> ExecuteFacet(const index::Index& index, const BatchQuery& query,
                                                                         const std::string& column);
 

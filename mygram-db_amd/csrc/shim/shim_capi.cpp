@@ -552,6 +552,44 @@ int mgxs_facet(mgxs_table* table, uint32_t n_terms, const char* const* terms, ui
   }
 }
 
+int mgxs_facet_columns(mgxs_table* table, uint32_t n_terms, const char* const* terms, uint32_t n_not,
+                       const char* const* not_terms, uint32_t n_cond, const char* const* cond_columns, const uint32_t* cond_ops,
+                       const char* const* cond_values, uint32_t n_columns, const char* const* columns, uint32_t limit,
+                       uint32_t offset, uint64_t* matched, uint64_t* total_values, uint32_t* n_out, uint64_t* counts,
+                       char* display, size_t display_cap, uint32_t* display_off) {
+  if (!table || !n_columns || !columns || !matched || !total_values || !n_out || (limit && (!counts || !display || !display_off)))
+    return Fail(MGX_ERR_INVALID_ARGUMENT, "mgxs_facet_columns: null argument");
+  try {
+    BatchQuery q = MakeQuery(n_terms, terms, n_not, not_terms, n_cond, cond_columns, cond_ops, cond_values, 0, 1, limit, offset);
+    for (uint32_t c = 0; c < n_columns; ++c) {
+      if (!columns[c]) return Fail(MGX_ERR_INVALID_ARGUMENT, "mgxs_facet_columns: null column name");
+      q.facet_columns.emplace_back(columns[c]);
+    }
+    auto r = mygramdb::search_pipeline::ExecuteBatch(*table->index, {q});  // one search part, one device batch
+    if (!r) return Fail(static_cast<int>(r.error().code()), r.error().message());
+    const std::vector<mygramdb::search_pipeline::FacetOutput>& f = (*r)[0].facets;
+    if (f.size() != n_columns) return Fail(MGX_ERR_INTERNAL, "mgxs_facet_columns: the batch returned no facets");
+    *matched = (*r)[0].total;
+    size_t at = 0;
+    for (uint32_t c = 0; c < n_columns; ++c) {
+      total_values[c] = f[c].total_values;
+      n_out[c] = static_cast<uint32_t>(f[c].value_counts.size());
+      for (size_t k = 0; k < f[c].value_counts.size(); ++k) {
+        counts[static_cast<size_t>(c) * limit + k] = f[c].value_counts[k].second;
+        display_off[static_cast<size_t>(c) * (limit + 1) + k] = static_cast<uint32_t>(at);
+        if (at + f[c].display[k].size() > display_cap)
+          return Fail(MGX_ERR_OUT_OF_RANGE, "mgxs_facet_columns: display buffer too small");
+        std::memcpy(display + at, f[c].display[k].data(), f[c].display[k].size());
+        at += f[c].display[k].size();
+      }
+      if (limit) display_off[static_cast<size_t>(c) * (limit + 1) + f[c].value_counts.size()] = static_cast<uint32_t>(at);
+    }
+    return MGX_OK;
+  } catch (const std::exception& e) {
+    return Fail(MGX_ERR_INTERNAL, e.what());
+  }
+}
+
 int mgxs_batcher_create(mgxs_table* table, uint32_t max_batch, uint32_t max_delay_us, int depth, int planner_threads,
                         mgxs_batcher** out) {
   if (out) *out = nullptr;

@@ -245,6 +245,7 @@ class DeviceIndex:
         check(L.mgx_index_create(C.byref(d), C.byref(h)))
         self._h = h
         self.device = device
+        self.facet_values = {}  # column id -> n_values of the columns added with value ids (the lengths of their counts)
 
     def __del__(self):
         if getattr(self, "_h", None):
@@ -289,6 +290,8 @@ class DeviceIndex:
                                    nul.ctypes.data if nul is not None else None, ids.ctypes.data if ids is not None else None)
         out = C.c_uint32()
         check(load().mgx_index_add_filter_column(self._h, C.byref(d), C.byref(out)))
+        if ids is not None:
+            self.facet_values[int(out.value)] = int(n_values)
         return int(out.value)
 
     @staticmethod
@@ -340,7 +343,7 @@ class Query:
 
     def __init__(self, terms=(), not_terms=(), filters=(), sort_score=False, limit=100, offset=0, descending=True,
                  k1=1.2, b=0.75, fuzzy=0, expr=None, universe=None, verify_text=False, highlight=None, conditions=(),
-                 sort_column=None, sort_key_bias=0, sort_ranks=False):
+                 sort_column=None, sort_key_bias=0, sort_ranks=False, facet_columns=None):
         """`expr`: boolean tree over term strings instead of the plain AND of `terms` (query::QueryNode):
         "term" | ("and", e, ...) | ("or", e, ...) | ("not", e). `universe` = (first_doc_id, count) of the NOT universe
         (DocumentStore::GetAllDocIds); None = every slot of the index."""
@@ -364,6 +367,14 @@ class Query:
         # highlight: None / False = off; True = default options; or a Highlight. SearchResult.snippets then holds one
         # snippet per returned doc (GenerateHighlightSnippets on the page, search_handler.cpp:473-482)
         self.highlight = Highlight() if highlight is True else (highlight or None)
+        # facet_columns: FACET in a batch (mgx_batch_set_facets): ids DeviceIndex.add_filter_column returned for columns
+        # with value ids, at most 8, repeats allowed. SearchResult.facets then holds one count array per column over the
+        # query's whole result set; the query returns no page: it runs in doc-id order with limit 0, whatever was given
+        self.facet_columns = [int(c) for c in facet_columns] if facet_columns else None
+        if self.facet_columns:
+            if sort_score or sort_column is not None or self.highlight is not None:
+                raise ValueError("a faceted query returns counts, not a page: no sort order and no highlight")
+            self.limit, self.offset = 0, 0
         if expr is not None and not self.terms:
             seen = []
 
@@ -410,7 +421,7 @@ class TermInfo:
 
 class SearchResult:
     __slots__ = ("total", "docs", "scores", "total_candidates", "after_intersection", "after_not", "after_filters",
-                 "empty_term_detected", "term_order", "snippets")
+                 "empty_term_detected", "term_order", "snippets", "facets")
 
     def __init__(self):
         self.total = 0
@@ -420,6 +431,7 @@ class SearchResult:
         self.empty_term_detected = False
         self.term_order = []
         self.snippets = []  # bytes per returned doc, when the query asked for highlight
+        self.facets = []  # np.uint64 counts per value id, one array per requested facet column
 
 
 def _take_u32(ptr, n):
@@ -444,7 +456,7 @@ def _render_snippet(entry, opts):
 class PreparedBatch:
     """mgx_batch: a compiled, device-resident batch of queries that can be executed repeatedly."""
 
-    def __init__(self, index, cqueries, keep, shells, orders, highlights=None):
+    def __init__(self, index, cqueries, keep, shells, orders, highlights=None, facets=None):
         self.index, self._keep, self._shells, self._orders = index, keep, shells, orders
         self.n = len(cqueries)
         self._h = None
@@ -454,6 +466,21 @@ class PreparedBatch:
             check(load().mgx_batch_prepare(index.device_index._h, arr, self.n, C.byref(h)))
             self._h = h
         self._set_highlight(highlights)
+        self._set_facets(facets)
+
+    def _set_facets(self, facets):
+        """mgx_batch_set_facets: facets[i] = None or the column ids of device query i."""
+        self._facets = facets if facets and any(f for f in facets) else None
+        if not self._facets or not self._h:
+            return
+        reqs = (_capi.FacetRequest * self.n)()
+        for i, f in enumerate(self._facets):
+            if not f:
+                continue
+            ids = (C.c_uint32 * len(f))(*f)
+            self._keep.append(ids)
+            reqs[i] = _capi.FacetRequest(len(f), 0, ids)
+        check(load().mgx_batch_set_facets(self._h, reqs, self.n))
 
     def _set_highlight(self, highlights):
         """mgx_batch_set_highlight: highlights[i] = None or (Highlight, term list as bytes) of device query i."""
@@ -476,7 +503,7 @@ class PreparedBatch:
             load().mgx_batch_destroy(self._h)
             self._h = None
 
-    def reset(self, cqueries, keep, shells, orders, highlights=None):
+    def reset(self, cqueries, keep, shells, orders, highlights=None, facets=None):
         """mgx_batch_reset: the same batch object (device arenas, pinned result block) for a new set of queries."""
         self._keep, self._shells, self._orders = keep, shells, orders
         self.n = len(cqueries)
@@ -489,6 +516,7 @@ class PreparedBatch:
         else:
             check(load().mgx_batch_reset(self._h, arr, self.n))
         self._set_highlight(highlights)
+        self._set_facets(facets)
 
     def execute(self, stream=None):
         if self._h:
@@ -528,6 +556,14 @@ class PreparedBatch:
             check(load().mgx_batch_fetch(self._h, C.byref(v)))
             if self._highlights:
                 check(load().mgx_batch_fetch_highlight(self._h, C.byref(hv)))
+        counts_of = {}  # device query -> its count arrays, in request order
+        if self._h and self._facets:
+            fv = _capi.FacetView()
+            check(load().mgx_batch_fetch_facets(self._h, C.byref(fv)))
+            for j in range(fv.n_entries):
+                e = fv.entries[j]
+                counts_of.setdefault(e.query, []).append(
+                    np.ctypeslib.as_array(e.counts, shape=(e.n_values,)).copy() if e.n_values else np.zeros(0, np.uint64))
         out = []
         k = 0
         for qi, shell in enumerate(self._shells):
@@ -547,6 +583,7 @@ class PreparedBatch:
             if self._highlights and self._highlights[k - 1] is not None:
                 opts = self._highlights[k - 1][0]
                 s.snippets = [_render_snippet(hv.entries[r.docs_begin + j], opts) for j in range(r.n_docs)]
+            s.facets = counts_of.get(k - 1, [])
             out.append(s)
         return out
 
@@ -1132,10 +1169,17 @@ class Index:
             shells.append(None)
         if into == "raw":  # (facet: the compiled C queries themselves)
             return cqueries, keep, shells
+        # FACET in a batch: the requests of the device queries; a query resolved on the host counts nothing
+        wanted = [getattr(q, "facet_columns", None) for q in queries]
+        facets = [w for w, shell in zip(wanted, shells) if shell is None]
+        for w, shell in zip(wanted, shells):
+            if shell is not None and w:
+                known = self.device_index.facet_values
+                shell.facets = [np.zeros(known.get(c, 0), np.uint64) for c in w]
         if into is not None:
-            into.reset(cqueries, keep, shells, orders, highlights)
+            into.reset(cqueries, keep, shells, orders, highlights, facets)
             return into
-        return PreparedBatch(self, cqueries, keep, shells, orders, highlights)
+        return PreparedBatch(self, cqueries, keep, shells, orders, highlights, facets)
 
     def facet_counts(self, query, column_id, n_values):
         """mgx_facet_counts: (matched documents, counts per value id) of the query's whole result set."""
