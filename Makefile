@@ -19,12 +19,12 @@ $(CSRC)/mgx_kernels.o: $(CSRC)/mgx_kernels.hip $(CSRC)/mgx_internal.hpp $(CSRC)/
 $(CSRC)/mgx_highlight.o: $(CSRC)/mgx_highlight.hip $(CSRC)/mgx_highlight.hpp $(CSRC)/mgx_internal.hpp $(CSRC)/mgx_launch.hpp
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 # SORT <filter column>: its kernels too are a unit of their own (it restates the comparator it shares with the others)
-$(CSRC)/mgx_colsort.o: $(CSRC)/mgx_colsort.hip $(CSRC)/mgx_colsort.hpp
+$(CSRC)/mgx_colsort.o: $(CSRC)/mgx_colsort.hip $(CSRC)/mgx_colsort.hpp $(CSRC)/mgx_pkey.hpp
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 # FACET in a batch: one more unit of its own (mgx_facet.hpp also holds the host-side plan, which compiles without HIP)
 $(CSRC)/mgx_facet.o: $(CSRC)/mgx_facet.hip $(CSRC)/mgx_facet.hpp
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(CSRC)/mgx_api.o: $(CSRC)/mgx_api.cpp $(CSRC)/mgx_colsort.hpp $(CSRC)/mgx_facet.hpp $(CSRC)/mgx_compile.hpp $(CSRC)/mgx_internal.hpp $(CSRC)/mgx_launch.hpp $(CSRC)/mgx_host.hpp $(CSRC)/mgx_highlight.hpp include/mygram_gpu.h
+$(CSRC)/mgx_api.o: $(CSRC)/mgx_api.cpp $(CSRC)/mgx_colsort.hpp $(CSRC)/mgx_pkey.hpp $(CSRC)/mgx_facet.hpp $(CSRC)/mgx_compile.hpp $(CSRC)/mgx_internal.hpp $(CSRC)/mgx_launch.hpp $(CSRC)/mgx_host.hpp $(CSRC)/mgx_highlight.hpp include/mygram_gpu.h
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
 $(CSRC)/mgx_compile.o: $(CSRC)/mgx_compile.cpp $(CSRC)/mgx_compile.hpp $(CSRC)/mgx_internal.hpp $(CSRC)/mgx_host.hpp include/mygram_gpu.h
 	g++ $(CXXFLAGS) -c $< -o $@
@@ -61,7 +61,13 @@ colsort-host-asan:
 	python3 tests/test_column_sort_cpu.py > colsort_host_check_lines.txt
 	./colsort_host_check_asan colsort_host_check_lines.txt
 
+# the host side of mgx_pkey.hpp (key derivation, the key column, the comparator key_merge_kernel runs) likewise
+pksort-host-asan:
+	g++ -O1 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -o pksort_host_check_asan tests/cpp/pksort_host_check.cpp
+	python3 tests/test_primary_key_sort_cpu.py > pksort_host_check_lines.txt
+	./pksort_host_check_asan pksort_host_check_lines.txt > /dev/null
+
 clean:
-	rm -f $(OBJS) $(LIB) $(SHIM) colsort_host_check_asan colsort_host_check_lines.txt
+	rm -f $(OBJS) $(LIB) $(SHIM) colsort_host_check_asan colsort_host_check_lines.txt pksort_host_check_asan pksort_host_check_lines.txt
 	$(MAKE) -C oracle clean
-.PHONY: all oracle clean ablation colsort-host-asan
+.PHONY: all oracle clean ablation colsort-host-asan pksort-host-asan

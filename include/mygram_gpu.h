@@ -140,6 +140,10 @@ typedef struct mgx_dump_filter_column {
 int mgx_dump_open(const uint8_t* data, uint64_t len, const char* table, mgx_dump** out);
 int mgx_dump_view_get(const mgx_dump* dump, mgx_dump_view* out);
 int mgx_dump_filter_column_get(const mgx_dump* dump, uint32_t i, mgx_dump_filter_column* out);
+/* The documents' primary keys by doc slot of the dump's range (mgx_dump_view.first_doc_id, n_docs): key i is
+ * bytes[off[i] .. off[i + 1]); a slot mgx_dump_view.exists marks 0 holds no document and no bytes. The arrays are the
+ * dump's: they live until mgx_dump_destroy. What mgx_index_set_primary_keys takes, with `exists` as has_key. */
+int mgx_dump_primary_keys_get(const mgx_dump* dump, const uint8_t** bytes, const uint64_t** off);
 /* Hands the table's columns to the caller (release with mgx_columns_destroy); a second call returns NULL. */
 int mgx_dump_take_columns(mgx_dump* dump, mgx_columns** out);
 void mgx_dump_destroy(mgx_dump* dump);
@@ -263,6 +267,20 @@ int mgx_index_attach_text(mgx_index* idx, const uint8_t* text_bytes, const uint6
  * _exchange, _execute_gather, _execute_sharded); a highlighted batch that holds such a query. */
 #define MGX_SORT_COLUMN 2u
 #define MGX_SORT_COLUMN_RANK 3u
+/* SORT by primary key: the reference's order for every query without a SORT clause (primary key DESC,
+ * result_sorter.cpp:502-510), for SORT id and for SORT <primary key column> (:239-262). `reverse` = 1: DESC. The sort
+ * key of a document is its primary key as mgx_index_set_primary_keys took it: a non-empty string of ASCII digits that
+ * fits a uint64_t counts as that number zero-padded to 20 characters, any other key as its bytes, a document without a
+ * key as its doc id zero-padded to 20 characters; keys compare as std::string::compare (unsigned bytes, a proper prefix
+ * first), ties go to the doc id in the sort's own direction. On an index without keys the page is therefore the docid
+ * page in that direction. Any limit (0 = all) and any offset; scores come back 0.0; totals and funnel counters as
+ * without SORT. sort_column and sort_key_bias must be 0 (MGX_ERR_INVALID_ARGUMENT). mgx_batch_merge_local merges the
+ * runs of a main index and its delta by the key strings (by the numbers when both indexes hold numeric keys only).
+ * Where the keys of an index never decrease with the doc slot, a query with offset 0 runs as the docid page it equals
+ * (see mgx_index_set_primary_key_shortcut; the environment variable MGX_PK_SORT_GENERAL=1 turns that off).
+ * Refused with MGX_ERR_NOT_IMPLEMENTED and a message, like MGX_SORT_COLUMN: the sharded entry points; a highlighted
+ * batch that holds such a query. */
+#define MGX_SORT_PRIMARY_KEY 4u
 
 #define MGX_MAX_TERMS 64u /* query_parser.h:270-272 */
 /* Gram id of an n-gram the TABLE knows but this doc-range shard holds no posting for: an empty doc set. (A gram the
@@ -345,8 +363,8 @@ typedef struct mgx_query {
   uint32_t n_filters;
   uint32_t sort;    /* MGX_SORT_* */
   uint32_t limit;   /* 0 => all */
-  uint32_t offset;  /* MGX_SORT_SCORE and MGX_SORT_COLUMN / _RANK */
-  uint32_t reverse; /* MGX_SORT_DOCID: descending docids; MGX_SORT_SCORE / MGX_SORT_COLUMN: 1 => SortOrder::DESC */
+  uint32_t offset;  /* MGX_SORT_SCORE, MGX_SORT_COLUMN / _RANK and MGX_SORT_PRIMARY_KEY */
+  uint32_t reverse; /* MGX_SORT_DOCID: descending docids; MGX_SORT_SCORE / _COLUMN / _PRIMARY_KEY: 1 => SortOrder::DESC */
   uint32_t sort_column; /* MGX_SORT_COLUMN / _RANK: the column's id. (It and sort_key_bias fill what was padding: no other
                          * field moves and the struct keeps its size, so MGX_ABI_VERSION stays; a zero-initialised
                          * struct means what it meant.) */
@@ -623,6 +641,7 @@ int mgx_batch_algorithmic_bytes(mgx_batch* batch, uint64_t* list_bytes, uint64_t
 /* Average duration (ms) of the dominant kernel over the executes since the last call, measured with HIP events on
  * the stream the kernel ran on; *n receives how many launches were averaged. Enables event recording from now on. */
 int mgx_batch_kernel_time_ms(mgx_batch* batch, double* avg_ms, uint32_t* n);
+/* Reads the batch's index: destroy every batch of an index before mgx_index_destroy. */
 void mgx_batch_destroy(mgx_batch* batch);
 
 /* =====================================================================================================
@@ -709,6 +728,18 @@ int mgx_index_update_filter_bitmap(mgx_index* idx, uint32_t bitmap_id, const uin
 int mgx_index_set_doc_map(mgx_index* idx, const uint32_t* table_ids, uint64_t n);
 int mgx_index_invalidate_statistics(mgx_index* idx);
 int mgx_index_synchronize(mgx_index* idx);
+/* The primary keys of an index by local doc slot, for MGX_SORT_PRIMARY_KEY: key i is bytes[off[i] .. off[i + 1]), off has
+ * n_docs + 1 entries; has_key (NULL: every document has a key) marks the documents that have one, the others sort by
+ * their table doc id. The library derives the sort keys, stores 8 bytes per slot (the number when every key of the index
+ * is numeric, else the key's rank among the index's distinct keys plus that dictionary) and copies what it needs: the
+ * arrays may be freed after the call. Calling it again replaces the keys; no batch of this index may be between execute
+ * and fetch then (the call waits for the device and frees the old column). On a delta index call it after
+ * mgx_index_set_doc_map, which names the table ids the documents without a key fall back to.
+ * mgx_index_set_primary_key_shortcut: enable = 0 keeps MGX_SORT_PRIMARY_KEY queries of this index from running as docid
+ * pages; the owner of a table does that on the main index while a delta index exists, since the two sides' runs are
+ * then merged by key. An index with a doc map never takes the shortcut. Default: enabled. */
+int mgx_index_set_primary_keys(mgx_index* idx, const uint8_t* bytes, const uint64_t* off, const uint8_t* has_key);
+int mgx_index_set_primary_key_shortcut(mgx_index* idx, int enable);
 int mgx_batch_df_merge_local(mgx_batch* primary, mgx_batch* const* others, uint32_t n_others, void* hip_stream);
 int mgx_batch_merge_local(mgx_batch* primary, mgx_batch* const* others, uint32_t n_others, void* hip_stream);
 

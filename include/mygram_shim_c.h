@@ -118,6 +118,14 @@ int mgxs_search_sorted(mgxs_table* table, uint32_t n_terms, const char* const* t
                        const char* const* cond_values, int sort_by_score, int descending, uint32_t limit, uint32_t offset,
                        const char* sort_column, uint64_t* total, uint32_t* n_docs, uint32_t* docs,
                        double* scores /* may be NULL */);
+/* mgxs_search in primary-key order (BatchQuery::sort_primary_key: the reference's order for a query without a SORT
+ * clause, result_sorter.cpp:502-510; `descending` its direction, offset / limit the page). The keys are those of the
+ * table's documents: a dump's (mgxs_table_from_dump), or what mgx_index_set_primary_keys gave an adopted device index; a
+ * document without a key sorts by its doc id. docs has room for `limit` entries. */
+int mgxs_search_by_primary_key(mgxs_table* table, uint32_t n_terms, const char* const* terms, uint32_t n_not,
+                               const char* const* not_terms, uint32_t n_cond, const char* const* cond_columns,
+                               const uint32_t* cond_ops, const char* const* cond_values, int descending, uint32_t limit,
+                               uint32_t offset, uint64_t* total, uint32_t* n_docs, uint32_t* docs);
 /* mgxs_search with HIGHLIGHT (BatchQuery::highlight: GenerateHighlightSnippets on the page, search_handler.cpp:473-482, on the
  * device): the page's snippets, packed into `snippets`; doc k's snippet is snippets[snippet_off[k] .. snippet_off[k+1]).
  * snippet_off has room for limit + 1 entries. Tags NUL-terminated, at most 256 bytes; snippet_length 1..10000,

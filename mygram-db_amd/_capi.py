@@ -12,7 +12,7 @@ LIB_PATH = os.environ.get("MGX_LIBRARY") or os.path.join(_HERE, "libmygram_gpu.s
 
 ABI_VERSION = 5
 GRAM_ABSENT = 0xFFFFFFFF
-SORT_DOCID, SORT_SCORE, SORT_COLUMN, SORT_COLUMN_RANK = 0, 1, 2, 3
+SORT_DOCID, SORT_SCORE, SORT_COLUMN, SORT_COLUMN_RANK, SORT_PRIMARY_KEY = 0, 1, 2, 3, 4
 
 # every symbol include/mygram_gpu.h and include/mygram_tools.h declare
 # int (*mgx_gather_fn)(void* user, const void* mine, void* all, uint64_t bytes, void* hip_stream)
@@ -36,6 +36,7 @@ EXPORTS = [
     "mgx_batch_set_highlight", "mgx_batch_fetch_highlight", "mgx_highlight_render", "mgx_index_max_text_bytes", "mgx_batch_defer_highlight",
     "mgxt_highlight_generate", "mgxt_highlight_match_positions",
     "mgx_batch_set_facets", "mgx_batch_fetch_facets",
+    "mgx_index_set_primary_keys", "mgx_index_set_primary_key_shortcut", "mgx_dump_primary_keys_get",
 ]
 
 
@@ -256,6 +257,11 @@ def load():
                                                  C.POINTER(sz)]
     L.mgx_batch_set_facets.argtypes = [vp, C.POINTER(FacetRequest), u32]
     L.mgx_batch_fetch_facets.argtypes = [vp, C.POINTER(FacetView)]
+    L.mgx_index_set_primary_keys.argtypes = [vp, vp, vp, vp]
+    L.mgx_index_set_primary_key_shortcut.argtypes = [vp, i32]
+    L.mgx_dump_primary_keys_get.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+    L.mgx_index_set_doc_map.argtypes = [vp, vp, u64]
+    L.mgx_batch_merge_local.argtypes = [vp, C.POINTER(vp), u32, vp]
     _lib = L
     return L
 

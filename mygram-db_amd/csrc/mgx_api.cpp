@@ -31,6 +31,7 @@
 #include "mgx_compile.hpp"
 #include "mgx_highlight.hpp"
 #include "mgx_colsort.hpp"
+#include "mgx_pkey.hpp"
 #include "mgx_facet.hpp"
 #include "mgx_host.hpp"
 #include "mgx_internal.hpp"
@@ -393,6 +394,17 @@ struct mgx_index {
   // them): a term whose grams are all bitmap-form is live by construction and takes no live-row operand
   std::atomic<bool> bitmaps_clean{false};
   DevBuf d_doc_map;  // mgx_index_set_doc_map: local slot -> table doc id (a delta index), or empty
+  std::vector<uint32_t> h_doc_map;  // the same on the host: the key of a document without a primary key is its table id
+  // mgx_index_set_primary_keys (MGX_SORT_PRIMARY_KEY, mgx_pkey.hpp): one value per doc slot and, for kKeyRanks, the
+  // dictionary of the index's distinct keys. Without it (has_pkeys false) every document's key is its table doc id:
+  // kind numeric, no column. Guarded by mu; the atomics are what ViewOf reads without it.
+  bool has_pkeys = false;
+  uint32_t pk_kind = mgx::pkey::kKeyNumeric;
+  bool pk_any_missing = false;
+  DevBuf d_pk_values, d_pk_off, d_pk_bytes;
+  std::atomic<bool> pk_monotone{true};  // the keys never decrease with the slot (true without keys: doc ids ascend)
+  std::atomic<bool> pk_shortcut{true};  // mgx_index_set_primary_key_shortcut
+  std::atomic<bool> has_doc_map{false};  // d_doc_map is set (a delta index: its keys are never in doc-id order of a table)
   DevBuf d_fine_rows;                 // fine row -> bitmap row
   std::vector<uint32_t> h_fine_map;   // bitmap row -> fine row (kNoRow: none)
 };
@@ -642,6 +654,11 @@ int mgx_dump_filter_column_get(const mgx_dump* dump, uint32_t i, mgx_dump_filter
   if (!dump || !out) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dump_filter_column_get: null argument");
   if (!mgx::DumpFilterColumn(reinterpret_cast<const mgx::DumpData*>(dump), i, out))
     return mgx::Fail(MGX_ERR_OUT_OF_RANGE, "mgx_dump_filter_column_get: no such column");
+  return MGX_OK;
+}
+int mgx_dump_primary_keys_get(const mgx_dump* dump, const uint8_t** bytes, const uint64_t** off) {
+  if (!dump || !bytes || !off) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dump_primary_keys_get: null argument");
+  mgx::DumpPrimaryKeys(reinterpret_cast<const mgx::DumpData*>(dump), bytes, off);
   return MGX_OK;
 }
 int mgx_dump_take_columns(mgx_dump* dump, mgx_columns** out) {
@@ -1245,11 +1262,53 @@ int mgx_index_set_doc_map(mgx_index* idx, const uint32_t* table_ids, uint64_t n)
   try {
     std::lock_guard<std::mutex> lock(idx->mu);
     MGX_HIP(hipSetDevice(idx->device));
+    if (idx->has_pkeys && idx->pk_any_missing)
+      return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_index_set_doc_map: the index holds primary keys that fell back to "
+                                                 "doc ids: set the doc map before mgx_index_set_primary_keys");
     MGX_HIP(mgx::Upload(idx->d_doc_map, table_ids, n));
+    idx->h_doc_map.assign(table_ids, table_ids + n);
+    idx->has_doc_map.store(true, std::memory_order_release);
     return MGX_OK;
   } catch (const std::exception& e) {
     return mgx::Fail(MGX_ERR_INTERNAL, std::string("mgx_index_set_doc_map: ") + e.what());
   }
+}
+
+int mgx_index_set_primary_keys(mgx_index* idx, const uint8_t* bytes, const uint64_t* off, const uint8_t* has_key) {
+  if (!idx || !off) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_index_set_primary_keys: null argument");
+  const uint64_t n = idx->dev.n_docs;
+  for (uint64_t i = 0; i < n; ++i)
+    if (off[i + 1] < off[i]) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_index_set_primary_keys: offsets must ascend");
+  if (off[n] != off[0] && !bytes) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_index_set_primary_keys: null key bytes");
+  try {
+    std::lock_guard<std::mutex> lock(idx->mu);
+    MGX_HIP(hipSetDevice(idx->device));
+    const mgx::pkey::KeyColumn col = mgx::pkey::BuildKeyColumn(
+        bytes, off, has_key, n, idx->h_doc_map.empty() ? nullptr : idx->h_doc_map.data(), idx->dev.first_doc_id);
+    if (idx->has_pkeys) MGX_HIP(hipDeviceSynchronize());  // (a replaced column may still be read by a fetch's kernels)
+    MGX_HIP(mgx::Upload(idx->d_pk_values, col.values.data(), n));
+    idx->d_pk_off.Free();
+    idx->d_pk_bytes.Free();
+    if (col.kind == mgx::pkey::kKeyRanks) {
+      MGX_HIP(mgx::Upload(idx->d_pk_off, col.off.data(), col.off.size()));
+      // (one byte of padding: an index whose only key is "" has an empty dictionary and still needs an address)
+      const std::vector<uint8_t> pad(1, 0);
+      MGX_HIP(mgx::Upload(idx->d_pk_bytes, col.bytes.empty() ? pad.data() : col.bytes.data(), std::max<size_t>(1, col.bytes.size())));
+    }
+    idx->pk_kind = col.kind;
+    idx->pk_any_missing = col.any_missing;
+    idx->has_pkeys = true;
+    idx->pk_monotone.store(col.monotone, std::memory_order_release);
+    return MGX_OK;
+  } catch (const std::exception& e) {
+    return mgx::Fail(MGX_ERR_INTERNAL, std::string("mgx_index_set_primary_keys: ") + e.what());
+  }
+}
+
+int mgx_index_set_primary_key_shortcut(mgx_index* idx, int enable) {
+  if (!idx) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_index_set_primary_key_shortcut: null index");
+  idx->pk_shortcut.store(enable != 0, std::memory_order_relaxed);
+  return MGX_OK;
 }
 
 int mgx_index_invalidate_statistics(mgx_index* idx) {
@@ -2190,6 +2249,12 @@ static CompileView ViewOf(const mgx_index* idx) {
   v.n_filter_columns = idx->n_filter_columns.load(std::memory_order_acquire);
   v.live_row = idx->live_row.load(std::memory_order_relaxed);
   v.bitmaps_clean = idx->bitmaps_clean.load(std::memory_order_relaxed);
+  static const bool pk_general = [] {
+    const char* e = std::getenv("MGX_PK_SORT_GENERAL");
+    return e != nullptr && e[0] != '\0' && e[0] != '0';
+  }();
+  v.pk_docid_order = !pk_general && !idx->has_doc_map.load(std::memory_order_acquire) && idx->pk_monotone.load(std::memory_order_acquire) &&
+                     idx->pk_shortcut.load(std::memory_order_relaxed);
   return v;
 }
 
@@ -2263,12 +2328,12 @@ struct CompilePool {
 // SORT <filter column>: what the compiler cannot see of the column (its class, the mark of mgx_index_add_filter_column)
 static int CheckSortColumns(const mgx_index* idx, const std::vector<QuerySpec>& specs) {
   bool any = false;
-  for (const QuerySpec& sp : specs) any = any || sp.col_sort;
+  for (const QuerySpec& sp : specs) any = any || (sp.col_sort && !sp.pk_sort);
   if (!any) return MGX_OK;
   std::lock_guard<std::mutex> lock(const_cast<mgx_index*>(idx)->mu);
   for (size_t i = 0; i < specs.size(); ++i) {
     const QuerySpec& sp = specs[i];
-    if (!sp.col_sort) continue;
+    if (!sp.col_sort || sp.pk_sort) continue;  // (the primary keys are no filter column and hold no NULL)
     const std::string who = "query " + std::to_string(i) + ": ";
     if (sp.sort_column >= idx->filter_columns.size()) return Fail(MGX_ERR_OUT_OF_RANGE, who + "sort_column: unknown filter column");
     const mgx_index::FilterColumn& col = *idx->filter_columns[sp.sort_column];
@@ -2845,7 +2910,11 @@ static std::vector<double> DeepIdfs(const mgx_batch* b, const QuerySpec& sp) {
 //     key (mgx_colsort.hpp), docid' already a table id: from column_topk_kernel, which reads the side's result bitmap,
 //     when offset + limit <= 1024; otherwise (and under MGX_COLSORT_FULL=1) every match is expanded, keyed by
 //     column_keys_kernel and sorted by the bitonic network;
-//   - rank_merge_kernel cuts every query's page from its sorted, disjoint runs (one per side), in one launch.
+//   - SORT by primary key: the same two paths over the index's key column (mgx_pkey.hpp; an index without keys has no
+//     column and the kernels take the table doc id as the value);
+//   - rank_merge_kernel cuts every query's page from its sorted, disjoint runs (one per side), in one launch; the pages
+//     sorted by primary key come from key_merge_kernel instead when two sides merge and not both hold numeric keys
+//     only: their values are ranks in two dictionaries, or a rank and a number, and compare as key strings.
 // Everything lives in the batch's d_merge scratch. On the delta's batch of a merge (merged_away) every page is empty:
 // the primary's fetch returned them.
 struct BitmapPages {
@@ -2895,6 +2964,29 @@ static int FetchBitmapPages(mgx_batch* a, BitmapPages* m) {
   const bool colsort_full = full_env != nullptr && full_env[0] != '\0' && full_env[0] != '0';
   uint64_t n_lists = 0;
   uint32_t n_groups_total = 0, max_cap = 0, max_job_elems = 0;
+  // SORT by primary key: each side's key column, read under that index's lock
+  constexpr uint32_t kKeyColumn = 0xFFFFFFFFu;  // its place among a side's resolved sort columns
+  struct SideKeys {
+    pkey::KeySide side{pkey::kKeyNumeric, nullptr, nullptr};
+    const uint64_t* values = nullptr;  // nullptr: no keys set, the value is the table doc id
+  };
+  SideKeys pk[2];
+  bool any_pk = false;
+  for (size_t i = 0; i < n && !any_pk; ++i) any_pk = a->specs[g.qids[i]].pk_sort && a->specs[g.qids[i]].col_sort;
+  if (any_pk)
+    for (int k = 0; k < n_side; ++k) {
+      const mgx_index* ix = side[k]->idx;
+      std::lock_guard<std::mutex> lock(const_cast<mgx_index*>(ix)->mu);
+      if (!ix->has_pkeys) continue;
+      pk[k].side = pkey::KeySide{ix->pk_kind, ix->d_pk_off.as<uint64_t>(), ix->d_pk_bytes.as<uint8_t>()};
+      pk[k].values = ix->d_pk_values.as<uint64_t>();
+    }
+  // two sides whose values do not compare as numbers: those pages are merged by key string
+  const bool merge_by_string = n_side == 2 && !(pk[0].side.kind == pkey::kKeyNumeric && pk[1].side.kind == pkey::kKeyNumeric);
+  std::vector<pkey::KeyMergeRun> kruns;
+  std::vector<uint64_t> krun_start;
+  std::vector<size_t> krun_query;
+  uint64_t kelems = 0;
   for (int k = 0; k < 2; ++k) {
     run_n[k].assign(n, 0);
     take[k].assign(n, 0);
@@ -2971,7 +3063,7 @@ static int FetchBitmapPages(mgx_batch* a, BitmapPages* m) {
         max_job_elems = std::max(max_job_elems, j.n_groups * j.needed);
         jobs.push_back(j);
         job_side.push_back(k);
-        job_column.push_back(ks.sort_column);  // (resolved to its class and arrays below, under the index's lock)
+        job_column.push_back(ks.pk_sort ? kKeyColumn : ks.sort_column);  // (resolved to its class and arrays below, under the index's lock)
       }
       off[k][i] = at[k];
       at[k] += take[k][i];
@@ -2997,12 +3089,20 @@ static int FetchBitmapPages(mgx_batch* a, BitmapPages* m) {
     }
     r.a_n = static_cast<uint32_t>(run_n[0][i]);
     r.b_n = static_cast<uint32_t>(run_n[1][i]);  // (one index: 0, so an element's rank is its index in its own run)
+    if (sp.pk_sort && sp.col_sort && merge_by_string) {  // key_merge_kernel's query: the rank merge sees two empty runs
+      krun_start.push_back(kelems);
+      kelems += run_n[0][i] + run_n[1][i];
+      kruns.push_back(pkey::KeyMergeRun{0, 0, r.out_off, r.a_n, r.b_n, r.lo, r.hi, r.descending, 0});
+      krun_query.push_back(i);
+      r.a_n = r.b_n = 0;
+    }
     run_start[i] = elems;
-    elems += run_n[0][i] + run_n[1][i];
+    elems += r.a_n + r.b_n;
   }
   run_start[n] = elems;
-  if (elems == 0) return MGX_OK;  // every page is empty
-  if (elems > 0xFFFFFFFFull || pages > 0xFFFFFFFFull || n_keys > 0xFFFFFFFFull || n_lists > 0xFFFFFFFFull)
+  krun_start.push_back(kelems);
+  if (elems + kelems == 0) return MGX_OK;  // every page is empty
+  if (elems > 0xFFFFFFFFull || kelems > 0xFFFFFFFFull || pages > 0xFFFFFFFFull || n_keys > 0xFFFFFFFFull || n_lists > 0xFFFFFFFFull)
     return Fail(MGX_ERR_OUT_OF_RANGE, "batch result exceeds 2^32 doc ids");
   // SORT <filter column>: every column a side's queries name, read under that index's lock (a column is immutable once
   // added; the vector that holds them may grow)
@@ -3017,6 +3117,10 @@ static int FetchBitmapPages(mgx_batch* a, BitmapPages* m) {
     std::lock_guard<std::mutex> lock(const_cast<mgx_index*>(ix)->mu);
     for (size_t i = 0; i < n; ++i) {
       const QuerySpec& ks = side[k]->specs[g.qids[i]];
+      if (ks.col_sort && ks.pk_sort) {
+        resolved[k][kKeyColumn] = SortCol{pk[k].values, nullptr, colsort::kUnsigned};
+        continue;
+      }
       if (!ks.col_sort || resolved[k].count(ks.sort_column) || ks.sort_column >= ix->filter_columns.size()) continue;
       const mgx_index::FilterColumn& c = *ix->filter_columns[ks.sort_column];
       resolved[k][ks.sort_column] = SortCol{c.d_values.as<uint64_t>(), c.d_null.as<uint8_t>(), c.value_class};
@@ -3040,12 +3144,18 @@ static int FetchBitmapPages(mgx_batch* a, BitmapPages* m) {
     r.a_off = r.kind == kMergeScore ? koff[0][i] : off[0][i];
     r.b_off = r.kind == kMergeScore ? koff[1][i] : at[0] + off[1][i];
   }
+  for (size_t j = 0; j < kruns.size(); ++j) {
+    kruns[j].a_off = koff[0][krun_query[j]];
+    kruns[j].b_off = koff[1][krun_query[j]];
+  }
   // [runs | run_start | terms | idfs] uploaded as one block, then device-only arrays
   const uint64_t o_start = Align8(n * sizeof(DevMergeRun));
   const uint64_t o_terms = o_start + (n + 1) * 8;
   const uint64_t o_idfs = Align8(o_terms + terms.size() * 4);
   const uint64_t o_jobs = o_idfs + idfs.size() * 8;
-  const uint64_t up_bytes = o_jobs + jobs.size() * sizeof(colsort::TopkJob);
+  const uint64_t o_kruns = Align8(o_jobs + jobs.size() * sizeof(colsort::TopkJob));
+  const uint64_t o_kstart = o_kruns + kruns.size() * sizeof(pkey::KeyMergeRun);
+  const uint64_t up_bytes = o_kstart + krun_start.size() * 8;
   const uint64_t o_docs = Align8(up_bytes);
   const uint64_t o_scores = Align8(o_docs + (at[0] + at[1]) * 4);
   const uint64_t o_keys = o_scores + n_scores * 8;
@@ -3064,6 +3174,8 @@ static int FetchBitmapPages(mgx_batch* a, BitmapPages* m) {
   if (!terms.empty()) std::memcpy(up.data() + o_terms, terms.data(), terms.size() * 4);
   if (!idfs.empty()) std::memcpy(up.data() + o_idfs, idfs.data(), idfs.size() * 8);
   if (!jobs.empty()) std::memcpy(up.data() + o_jobs, jobs.data(), jobs.size() * sizeof(colsort::TopkJob));
+  if (!kruns.empty()) std::memcpy(up.data() + o_kruns, kruns.data(), kruns.size() * sizeof(pkey::KeyMergeRun));
+  std::memcpy(up.data() + o_kstart, krun_start.data(), krun_start.size() * 8);
   MGX_HIP(hipMemcpyAsync(base, up.data(), up_bytes, hipMemcpyHostToDevice, s));
   uint32_t* docs = reinterpret_cast<uint32_t*>(base + o_docs);
   double* scores = reinterpret_cast<double*>(base + o_scores);
@@ -3104,6 +3216,8 @@ static int FetchBitmapPages(mgx_batch* a, BitmapPages* m) {
       for (int k = 0; k < n_side; ++k) full_runs += (a->specs[g.qids[i]].col_sort && n2[k][i] != 0) ? 1 : 0;
     if (!jobs.empty() || full_runs)
       fprintf(stderr, "[mgx] column sort: %zu fused runs in %u workgroups, %zu full-sort runs\n", jobs.size(), n_groups_total, full_runs);
+    if (!kruns.empty())
+      fprintf(stderr, "[mgx] key merge: %zu queries, %llu elements\n", kruns.size(), static_cast<unsigned long long>(kelems));
   }
   // ---- SORT <filter column>: the fused selection from the result bitmaps; the expanded runs' pairs from local slots,
   // their docid' a table id already (the doc map is read here: the slots are gone once the docs below are remapped)
@@ -3118,7 +3232,7 @@ static int FetchBitmapPages(mgx_batch* a, BitmapPages* m) {
       const QuerySpec& ks = x->specs[g.qids[i]];
       if (!ks.col_sort || n2[k][i] == 0) continue;
       SortCol c{};
-      if (!sort_col(k, ks.sort_column, &c)) return Fail(MGX_ERR_INTERNAL, "sort column vanished");
+      if (!sort_col(k, ks.pk_sort ? kKeyColumn : ks.sort_column, &c)) return Fail(MGX_ERR_INTERNAL, "sort column vanished");
       const uint64_t cnt = take[k][i];
       if (n2[k][i] > cnt) {
         MGX_HIP(hipMemsetAsync(keys + koff[k][i] + cnt, 0, (n2[k][i] - cnt) * 8, s));
@@ -3150,6 +3264,9 @@ static int FetchBitmapPages(mgx_batch* a, BitmapPages* m) {
   // ---- every query's page from its runs ----
   MGX_LAUNCH(LaunchRankMerge(reinterpret_cast<const DevMergeRun*>(base), reinterpret_cast<const uint64_t*>(base + o_start),
                              static_cast<uint32_t>(n), elems, docs, keys, dprime, pdocs, pscores, s));
+  MGX_LAUNCH(LaunchKeyMerge(reinterpret_cast<const pkey::KeyMergeRun*>(base + o_kruns),
+                            reinterpret_cast<const uint64_t*>(base + o_kstart), static_cast<uint32_t>(kruns.size()), kelems,
+                            pk[0].side, pk[1].side, keys, dprime, pdocs, pscores, s));
   m->docs.resize(pages);
   if (pages) MGX_HIP(hipMemcpyAsync(m->docs.data(), pdocs, pages * 4, hipMemcpyDeviceToHost, s));
   if (pages && n_keys) {  // (scores: a deep SORT _score page is in the batch)
@@ -3377,8 +3494,8 @@ int mgx_batch_set_highlight(mgx_batch* batch, const mgx_highlight_request* reque
     for (uint32_t qi = 0; qi < n_queries; ++qi) any_hl = any_hl || requests[qi].enabled;
     if (any_hl)
       for (const mgx::QuerySpec& sp : batch->specs)
-        if (sp.col_sort)
-          return mgx::Fail(MGX_ERR_NOT_IMPLEMENTED, "mgx_batch_set_highlight: a highlighted batch that holds a query sorted by a filter column is not implemented");
+        if (sp.col_sort || sp.pk_sort)
+          return mgx::Fail(MGX_ERR_NOT_IMPLEMENTED, "mgx_batch_set_highlight: a highlighted batch that holds a query sorted by a filter column or by the primary key is not implemented");
   }
   try {
     mgx_index* idx = batch->idx;
@@ -3693,12 +3810,12 @@ int mgx_batch_df_buffer(mgx_batch* batch, uint64_t** device_counts, uint32_t* n)
 // SORT <filter column> on a sharded table: the ranks of a page need every shard's column values
 static bool HasColumnSort(const mgx_batch* batch) {
   for (const mgx::QuerySpec& sp : batch->specs)
-    if (sp.col_sort) return true;
+    if (sp.col_sort || sp.pk_sort) return true;
   return false;
 }
 static int RefuseColumnSort(const mgx_batch* batch, const char* entry) {
   if (!HasColumnSort(batch)) return MGX_OK;
-  return mgx::Fail(MGX_ERR_NOT_IMPLEMENTED, std::string(entry) + ": SORT by a filter column on a sharded table is not implemented: a page's order needs every shard's column values");
+  return mgx::Fail(MGX_ERR_NOT_IMPLEMENTED, std::string(entry) + ": SORT by a filter column or by the primary key on a sharded table is not implemented: a page's order needs every shard's column values");
 }
 
 // (the counts of a sharded table's facets would need an all-reduce across the ranks: out of scope)
@@ -3862,6 +3979,16 @@ int mgx_batch_merge_local(mgx_batch* primary, mgx_batch* const* others, uint32_t
                      "two batches, not more");
   try {
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    // SORT by primary key: a side that ran such a query as a docid page (the shortcut of monotone keys) cannot be merged
+    // by key with one that did not
+    for (uint32_t j = 0; j < n_others; ++j)
+      for (uint32_t qi = 0; others[j] && others[j]->n_queries == primary->n_queries && qi < primary->n_queries; ++qi)
+        if (primary->specs[qi].pk_sort && others[j]->specs[qi].pk_sort &&
+            !(primary->specs[qi].col_sort && others[j]->specs[qi].col_sort))
+          return mgx::Fail(MGX_ERR_INVALID_ARGUMENT,
+                           "mgx_batch_merge_local: query " + std::to_string(qi) + " is sorted by primary key and ran as a "
+                           "docid page on one index: call mgx_index_set_primary_key_shortcut(index, 0) on a main index "
+                           "that has a delta, before its batches are prepared");
     for (uint32_t j = 0; j < n_others; ++j)
       if (!others[j] || others[j] == primary || others[j]->n_queries != primary->n_queries ||
           others[j]->idx->device != primary->idx->device ||
@@ -3875,7 +4002,7 @@ int mgx_batch_merge_local(mgx_batch* primary, mgx_batch* const* others, uint32_t
       for (uint32_t qi = 0; qi < primary->n_queries; ++qi) {
         const mgx::QuerySpec& sa = primary->specs[qi];
         const mgx::QuerySpec& sb = others[0]->specs[qi];
-        if (!sa.col_sort) continue;
+        if (!sa.col_sort || sa.pk_sort) continue;  // (the primary keys hold no NULL)
         mgx::colsort::KeyScan ka, kb;
         if (!sb.col_sort || !mgx::SortKeysOf(primary->idx, sa.sort_column, &ka) || !mgx::SortKeysOf(others[0]->idx, sb.sort_column, &kb))
           return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_batch_merge_local: the batches do not hold the same queries");

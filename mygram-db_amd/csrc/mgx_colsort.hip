@@ -5,6 +5,8 @@
 //   column_topk_kernel   the bounded page: reads a query's result bitmap, gathers the column under every set bit and keeps
 //                        the best `needed` pairs; no expansion, no full sort
 //   column_merge_kernel  the per-workgroup lists of a (query, side) -> one sorted run of `needed` pairs
+//   key_merge_kernel     SORT by primary key on a table with a delta index: the page of two runs whose values are ranks
+//                        in two different key dictionaries, merged by the key strings (mgx_pkey.hpp)
 //
 // The pair and its order are those of make_sort_keys_kernel / better() (mgx_colsort.hpp restates them: this unit shares no
 // code object with the others). Every store is a vector store of one lane.
@@ -23,6 +25,7 @@
 
 #define MGX_COLSORT_LAUNCHERS
 #include "mgx_colsort.hpp"
+#include "mgx_pkey.hpp"
 
 namespace mgx {
 
@@ -156,9 +159,10 @@ __global__ __launch_bounds__(cs::kTopkBlock) void column_topk_kernel(const cs::T
       uint32_t doc = 0;
       if (valid) {
         const bool nul = job.is_null != nullptr && job.is_null[slot] != 0;
-        const uint64_t v = job.values[slot];
+        const uint32_t table_doc = job.doc_map ? job.doc_map[slot] : job.first_doc_id + slot;
+        const uint64_t v = job.values ? job.values[slot] : table_doc;  // (no column: an index without primary keys)
         key = cs::PairKey(cs::KeyOf(job.value_class, job.ranks != 0, job.bias, v, nul), desc);
-        doc = cs::PairDoc(job.doc_map ? job.doc_map[slot] : job.first_doc_id + slot, desc);
+        doc = cs::PairDoc(table_doc, desc);
       }
       cs_offer(t, lane, valid, key, doc);
     };
@@ -250,8 +254,55 @@ __global__ __launch_bounds__(256) void column_keys_kernel(const uint32_t* __rest
     return;
   }
   const bool nul = is_null != nullptr && is_null[slot] != 0;
-  keys[i] = cs::PairKey(cs::KeyOf(value_class, ranks != 0, bias, values[slot], nul), descending != 0);
-  dprime[i] = cs::PairDoc(doc_map ? doc_map[slot] : doc, descending != 0);
+  const uint32_t table_doc = doc_map ? doc_map[slot] : doc;
+  const uint64_t v = values ? values[slot] : table_doc;  // (no column: an index without primary keys)
+  keys[i] = cs::PairKey(cs::KeyOf(value_class, ranks != 0, bias, v, nul), descending != 0);
+  dprime[i] = cs::PairDoc(table_doc, descending != 0);
+}
+
+// SORT by primary key across a main index and its delta: rank_merge_kernel's shape (one thread per element, flat over
+// the batch via run_start; a binary search in the other side's run; merged rank = own index + lo; only ranks in
+// [lo, hi) are written), with pkey::PairBefore as the order: the values of run A are side a's, those of run B side b's.
+// The two runs hold different documents, so no two elements compare equal and the ranks are 0..a_n+b_n-1, each once.
+// A wave's lanes mostly share a query, hence the side kinds; the byte loop's trip count differs per lane (common
+// prefixes), its loads are single bytes at unrelated addresses: the kernel is latency-bound on 2 * (offset + limit)
+// elements per query.
+__global__ __launch_bounds__(256) void key_merge_kernel(const pkey::KeyMergeRun* __restrict__ runs,
+                                                        const uint64_t* __restrict__ run_start, uint32_t n_runs,
+                                                        pkey::KeySide side_a, pkey::KeySide side_b,
+                                                        const uint64_t* __restrict__ keys,
+                                                        const uint32_t* __restrict__ dprime,
+                                                        uint32_t* __restrict__ out_docs, double* __restrict__ out_scores) {
+  const uint64_t e = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (e >= run_start[n_runs]) return;
+  uint32_t qlo = 0, qhi = n_runs;  // the run q with run_start[q] <= e < run_start[q + 1]
+  while (qhi - qlo > 1) {
+    const uint32_t mid = (qlo + qhi) >> 1;
+    if (run_start[mid] <= e) qlo = mid;
+    else qhi = mid;
+  }
+  const pkey::KeyMergeRun r = runs[qlo];
+  const uint32_t j = static_cast<uint32_t>(e - run_start[qlo]);
+  const bool from_a = j < r.a_n;
+  const uint32_t k = from_a ? j : j - r.a_n;
+  const uint64_t own = from_a ? r.a_off : r.b_off, other = from_a ? r.b_off : r.a_off;
+  const uint32_t other_n = from_a ? r.b_n : r.a_n;
+  const pkey::KeySide& s_own = from_a ? side_a : side_b;
+  const pkey::KeySide& s_other = from_a ? side_b : side_a;
+  const bool desc = r.descending != 0;
+  const uint64_t kx = keys[own + k];
+  const uint32_t x = dprime[own + k];
+  uint32_t lo = 0, hi = other_n;
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (pkey::PairBefore(s_other, keys[other + mid], dprime[other + mid], s_own, kx, x, desc)) lo = mid + 1;
+    else hi = mid;
+  }
+  const uint32_t rank = k + lo;
+  if (rank < r.lo || rank >= r.hi) return;
+  const uint64_t o = r.out_off + (rank - r.lo);
+  out_docs[o] = desc ? x : ~x;
+  out_scores[o] = 0.0;
 }
 
 int LaunchColumnKeys(const uint32_t* docs, uint64_t n, const uint64_t* values, const uint8_t* is_null,
@@ -260,6 +311,15 @@ int LaunchColumnKeys(const uint32_t* docs, uint64_t n, const uint64_t* values, c
   if (n == 0) return 0;
   hipLaunchKernelGGL(column_keys_kernel, dim3(static_cast<uint32_t>((n + 255) / 256)), dim3(256), 0, s, docs, n, values,
                      is_null, doc_map, first_doc_id, n_docs, value_class, ranks, bias, descending, keys, dprime);
+  return static_cast<int>(hipGetLastError());
+}
+
+int LaunchKeyMerge(const pkey::KeyMergeRun* runs, const uint64_t* run_start, uint32_t n_runs, uint64_t n_elems,
+                   pkey::KeySide a, pkey::KeySide b, const uint64_t* keys, const uint32_t* dprime, uint32_t* out_docs,
+                   double* out_scores, hipStream_t s) {
+  if (n_runs == 0 || n_elems == 0) return 0;
+  hipLaunchKernelGGL(key_merge_kernel, dim3(static_cast<uint32_t>((n_elems + 255) / 256)), dim3(256), 0, s, runs,
+                     run_start, n_runs, a, b, keys, dprime, out_docs, out_scores);
   return static_cast<int>(hipGetLastError());
 }
 

@@ -872,6 +872,8 @@ struct DumpData {
     std::vector<uint64_t> str_off;
   };
   std::vector<Col> filter_cols;
+  std::vector<uint8_t> pk_bytes;  // the documents' primary keys by slot (a slot without a document: no bytes)
+  std::vector<uint64_t> pk_off;
   bool has_scores = false;  // the texts were stored: tf / doc_len columns exist
   ~DumpData() { DestroyColumns(cols); }
 };
@@ -978,6 +980,7 @@ int DumpOpen(const uint8_t* data, uint64_t len, const char* table, DumpData** ou
   struct Doc {
     uint32_t id;
     uint64_t text_at, text_len;
+    std::string pk;
     std::vector<std::pair<uint32_t, std::pair<uint8_t, std::pair<uint64_t, uint64_t>>>> filters;  // column -> (type, (value | str at, str len))
   };
   std::vector<Doc> docs;
@@ -987,8 +990,7 @@ int DumpOpen(const uint8_t* data, uint64_t len, const char* table, DumpData** ou
   for (uint64_t d = 0; d < doc_count; ++d) {
     Doc doc{};
     doc.id = dr.U32();
-    std::string pk;
-    if (!ReadStr(dr, 1u << 20, &pk)) return fail(MGX_ERR_INVALID_ARGUMENT, "truncated document");
+    if (!ReadStr(dr, 1u << 20, &doc.pk)) return fail(MGX_ERR_INVALID_ARGUMENT, "truncated document");
     const uint32_t nf = dr.U32();
     if (!dr.ok || nf > 4096) return fail(MGX_ERR_INVALID_ARGUMENT, "implausible filter count");
     for (uint32_t f = 0; f < nf; ++f) {
@@ -1066,6 +1068,12 @@ int DumpOpen(const uint8_t* data, uint64_t len, const char* table, DumpData** ou
   for (uint64_t sl = 0; sl < dump->n_docs; ++sl)
     if (by_slot[sl] && by_slot[sl]->text_len)
       std::memcpy(dump->text_bytes.data() + dump->text_off[sl], dr.p + by_slot[sl]->text_at, by_slot[sl]->text_len);
+  dump->pk_off.assign(dump->n_docs + 1, 0);
+  for (uint64_t sl = 0; sl < dump->n_docs; ++sl) {
+    if (by_slot[sl]) dump->pk_bytes.insert(dump->pk_bytes.end(), by_slot[sl]->pk.begin(), by_slot[sl]->pk.end());
+    dump->pk_off[sl + 1] = dump->pk_bytes.size();
+  }
+  dump->pk_bytes.push_back(0);  // (an address even when every key is empty)
   // filter columns by slot
   dump->filter_cols.resize(col_names.size());
   for (size_t c = 0; c < col_names.size(); ++c) {
@@ -1151,6 +1159,10 @@ bool DumpFilterColumn(const DumpData* d, uint32_t i, mgx_dump_filter_column* o) 
   o->string_bytes = c.str_bytes.empty() ? nullptr : c.str_bytes.data();
   o->string_off = c.str_off.empty() ? nullptr : c.str_off.data();
   return true;
+}
+void DumpPrimaryKeys(const DumpData* d, const uint8_t** bytes, const uint64_t** off) {
+  *bytes = d->pk_bytes.data();
+  *off = d->pk_off.data();
 }
 Columns* DumpTakeColumns(DumpData* d) {
   Columns* c = d->cols;

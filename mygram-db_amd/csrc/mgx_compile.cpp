@@ -434,6 +434,20 @@ int CompileQuery(const CompileView& v, const mgx_query& in, QuerySpec* out) {
     out->sort_column = in.sort_column;
     out->sort_ranks = in.sort == MGX_SORT_COLUMN_RANK ? 1u : 0u;
     out->sort_bias = in.sort_key_bias;
+  } else if (in.sort == MGX_SORT_PRIMARY_KEY) {
+    if (in.sort_column != 0 || in.sort_key_bias != 0)
+      return Fail(MGX_ERR_INVALID_ARGUMENT, "MGX_SORT_PRIMARY_KEY takes no sort_column and no sort_key_bias: both must be 0");
+    out->pk_sort = true;
+    if (v.pk_docid_order && in.offset == 0) {
+      // the keys never decrease with the doc slot: the page is the docid page in the same direction, the cheapest path
+      out->mode = (in.limit != 0 && in.limit <= kMaxDocPage) ? kModeDocPage : kModeBitmap;
+    } else {
+      // the key column is a column of values (numeric keys) or of dictionary ranks, both ordered as they are: KeyOf's
+      // rank branch with bias 0 is the identity
+      out->mode = kModeBitmap;
+      out->col_sort = true;
+      out->sort_ranks = 1;
+    }
   } else {
     return Fail(MGX_ERR_INVALID_ARGUMENT, "unknown sort");
   }

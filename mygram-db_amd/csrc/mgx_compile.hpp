@@ -24,6 +24,7 @@ struct CompileView {
   uint32_t n_filter_rows = 0, n_filter_columns = 0;
   uint32_t live_row = kNoRow;  // mgx_index_set_live_bitmap: the filter row of the live documents, or kNoRow
   bool bitmaps_clean = false;  // ... and the bitmap-form grams hold live documents only
+  bool pk_docid_order = false;  // primary-key order is doc-id order on this index, and the shortcut is allowed
 };
 
 // One compiled query, before upload.
@@ -59,6 +60,9 @@ struct QuerySpec {
   // SORT <filter column> (MGX_SORT_COLUMN / _RANK): the bitmap group's fetch ranks the matches by the column's key
   bool col_sort = false;
   uint32_t sort_column = 0, sort_ranks = 0, sort_bias = 0;
+  // MGX_SORT_PRIMARY_KEY: with col_sort, the "column" is the index's key column (mgx_index_set_primary_keys); without,
+  // the query took the doc-id shortcut and is an ordinary docid page
+  bool pk_sort = false;
   uint32_t pat_off = 0, pat_len = 0;  // kModeTextDf specs: the term in the batch's pattern pool
   uint32_t vt_begin = 0;              // first of the query's verify patterns in the batch-wide array
   uint32_t fz_distance = 0;           // kOpVerifyFuzzy / kOpVerifyTree: d
@@ -75,7 +79,7 @@ struct QuerySpec {
     conds.clear();
     text_terms.clear();
     verify_patterns.clear();
-    deep_score = col_sort = false;
+    deep_score = col_sort = pk_sort = false;
     sort_column = sort_ranks = sort_bias = 0;
     deep_grams.clear();
     deep_idfs.clear();

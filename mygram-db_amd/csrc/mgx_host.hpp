@@ -21,6 +21,7 @@ int DumpOpen(const uint8_t* data, uint64_t len, const char* table, DumpData** ou
 void DumpDestroy(DumpData* d);
 void DumpView(const DumpData* d, mgx_dump_view* v);
 bool DumpFilterColumn(const DumpData* d, uint32_t i, mgx_dump_filter_column* o);
+void DumpPrimaryKeys(const DumpData* d, const uint8_t** bytes, const uint64_t** off);
 Columns* DumpTakeColumns(DumpData* d);
 
 // thread-local last-error message

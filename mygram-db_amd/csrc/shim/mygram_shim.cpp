@@ -203,6 +203,11 @@ struct Index::Impl {
   int query_kanji = 0;  // table-config kanji size used for QUERY n-grams (the Index itself keeps kanji = ngram if 0)
   mutable std::mutex mu;
   mutable std::map<DocId, std::string> pending;  // documents recorded before the first search
+  // The primary key of every document of the table that has one (AddDocument(..., primary_key), a dump's keys): what
+  // SORT by primary key orders by. Kept here for the table's lifetime, as the reference's DocumentStore keeps them: every
+  // index built from the table's documents (main, delta, a compacted main) takes its slots' keys from it. Under mu.
+  mutable std::map<DocId, std::string> primary_keys;
+  std::string primary_key_column;  // SetPrimaryKeyColumn
   mutable mgx_columns* cols = nullptr;
   mutable mgx_index* dev = nullptr;
   mutable mgx_columns_view view{};
@@ -521,7 +526,33 @@ struct GenerationSpec {
   uint64_t n = 0;
   const std::vector<DocId>* existing = nullptr;  // the ids that exist, when some of [first, first + n) do not
   const NamedValues* columns = nullptr;          // filter values by doc slot
+  const std::map<DocId, std::string>* primary_keys = nullptr;  // the table's (those of [first, first + n) are taken)
 };
+
+// The primary keys of an index's doc slots to the device (mgx_index_set_primary_keys). doc_of(slot): the slot's table id,
+// ascending with the slot (one walk over the table's keys).
+// An index none of whose documents has a key gets none: its documents then sort by doc id, which is what each would do.
+template <class DocOf>
+std::string UploadPrimaryKeys(mgx_index* dev, const std::map<DocId, std::string>& keys, uint64_t n, DocOf doc_of) {
+  if (keys.empty()) return "";
+  std::vector<uint8_t> bytes, has(n, 0);
+  std::vector<uint64_t> off(n + 1, 0);
+  bool any = false;
+  auto it = n ? keys.lower_bound(doc_of(0)) : keys.end();
+  for (uint64_t slot = 0; slot < n; ++slot) {
+    const DocId doc = doc_of(slot);
+    while (it != keys.end() && it->first < doc) ++it;
+    if (it != keys.end() && it->first == doc) {
+      bytes.insert(bytes.end(), it->second.begin(), it->second.end());
+      has[slot] = 1;
+      any = true;
+    }
+    off[slot + 1] = bytes.size();
+  }
+  if (!any) return "";
+  bytes.push_back(0);  // (an address even when every key is empty)
+  return mgx_index_set_primary_keys(dev, bytes.data(), off.data(), has.data()) == MGX_OK ? "" : mgx_last_error();
+}
 
 // One generation of the main index: column arrays, device index, texts, the exists row, every filter column. It touches
 // no Impl (Impl::Install publishes the result); when it fails, what it made is freed and `out` is as it was.
@@ -573,6 +604,10 @@ std::string BuildGeneration(const GenerationSpec& in, Index::Impl::Generation* o
     if (mgx_index_add_filter_bitmap(dev, in.existing->data(), in.existing->size(), &g.exists_bitmap) != MGX_OK ||
         mgx_index_set_live_bitmap(dev, g.exists_bitmap, MGX_LIVE_BITMAPS_CLEAN) != MGX_OK)
       return mgx_last_error();
+  }
+  if (in.primary_keys) {
+    const std::string err = UploadPrimaryKeys(dev, *in.primary_keys, v.n_docs, [&](uint64_t slot) { return v.first_doc_id + static_cast<DocId>(slot); });
+    if (!err.empty()) return err;
   }
   if (in.columns)
     for (const auto& c : *in.columns) {
@@ -662,12 +697,28 @@ std::unique_ptr<Index> Index::FromDump(const void* data, size_t len, const std::
     columns.emplace_back(fc.name, std::move(vals));
   }
   spec.columns = &columns;
+  // DocumentStore::LoadFromStream restores every document's primary key (document_store_persistence.cpp)
+  std::map<DocId, std::string> keys;
+  {
+    const uint8_t* pk_bytes = nullptr;
+    const uint64_t* pk_off = nullptr;
+    if (mgx_dump_primary_keys_get(dump, &pk_bytes, &pk_off) != MGX_OK) {
+      mgx_columns_destroy(spec.cols);
+      return fail(mgx_last_error());
+    }
+    for (uint64_t i = 0; i < v.n_docs; ++i)
+      if (v.exists[i])
+        keys.emplace_hint(keys.end(), v.first_doc_id + static_cast<DocId>(i),
+                          std::string(reinterpret_cast<const char*>(pk_bytes + pk_off[i]), static_cast<size_t>(pk_off[i + 1] - pk_off[i])));
+  }
+  spec.primary_keys = &keys;
   Impl::Generation gen;
   const std::string err = BuildGeneration(spec, &gen);
   if (!err.empty()) return fail(err);
   {
     std::lock_guard<std::mutex> lock(im->mu);
     im->Install(std::move(gen));
+    im->primary_keys = std::move(keys);
   }
   g_last_finalized.store(idx.get());
   return idx;
@@ -696,6 +747,9 @@ std::string EnsureMutable(Index::Impl* im) {
   for (uint64_t g = 0; g < im->view.n_grams; ++g) im->global_sizes[g] = im->view.offsets[g + 1] - im->view.offsets[g];
   im->global_docs = m.main_docs;
   im->global_avgdl = m.main_docs ? static_cast<double>(m.main_len) / static_cast<double>(m.main_docs) : 0.0;
+  // SORT by primary key: from now on a delta index may stand beside this one, and the two sides' runs are merged by key —
+  // the main index must not answer such a query with a docid page (a compacted main index starts with the shortcut again)
+  if (mgx_index_set_primary_key_shortcut(im->dev, 0) != MGX_OK) return mgx_last_error();
   m.active = true;
   return "";
 }
@@ -703,7 +757,8 @@ std::string EnsureMutable(Index::Impl* im) {
 
 namespace {
 // Both forms of AddDocument, in one critical section: the text and its filter values are recorded together or not at all.
-bool AddDocumentLocked(const Index& index, DocId doc_id, std::string_view text, const storage::FilterMap* filters) {
+bool AddDocumentLocked(const Index& index, DocId doc_id, std::string_view text, const storage::FilterMap* filters,
+                       const std::string_view* primary_key = nullptr) {
   Index::Impl* im = index.impl();
   std::lock_guard<std::mutex> lock(im->mu);
   if (im->finalized) {  // index.cpp:39-74 on a built index: the document joins the delta
@@ -723,6 +778,8 @@ bool AddDocumentLocked(const Index& index, DocId doc_id, std::string_view text, 
     im->pending[doc_id] = std::string(text);
     if (filters) im->pending_filters[doc_id] = *filters;
   }
+  if (primary_key) im->primary_keys[doc_id] = std::string(*primary_key);
+  else im->primary_keys.erase(doc_id);  // (an id added again without a key has none)
   return !GenerateHybridNgrams(text, index.GetNgramSize(), index.GetKanjiNgramSize(), index.GetCrossBoundaryNgrams()).empty();
 }
 }  // namespace
@@ -730,6 +787,13 @@ bool AddDocumentLocked(const Index& index, DocId doc_id, std::string_view text, 
 bool Index::AddDocument(DocId doc_id, std::string_view text) { return AddDocumentLocked(*this, doc_id, text, nullptr); }
 bool Index::AddDocument(DocId doc_id, std::string_view text, const storage::FilterMap& filters) {
   return AddDocumentLocked(*this, doc_id, text, &filters);
+}
+bool Index::AddDocument(DocId doc_id, std::string_view text, const storage::FilterMap& filters, std::string_view primary_key) {
+  return AddDocumentLocked(*this, doc_id, text, &filters, &primary_key);
+}
+void Index::SetPrimaryKeyColumn(const std::string& name) {
+  std::lock_guard<std::mutex> lock(impl_->mu);
+  impl_->primary_key_column = name;
 }
 
 namespace {
@@ -775,6 +839,7 @@ void Index::RemoveDocument(DocId doc_id, std::string_view text) {
     return;
   }
   RemoveLocked(*this, impl_.get(), doc_id, text);
+  impl_->primary_keys.erase(doc_id);  // (UpdateDocument and UpdateFilters go through RemoveLocked and keep the key)
 }
 
 void Index::UpdateDocument(DocId doc_id, std::string_view old_text, std::string_view new_text) {
@@ -899,8 +964,20 @@ std::vector<std::string> ColumnNames(const Index::Impl* im) {
 
 // The delta index over `docs`: column build, device index, doc map, filter columns. Touches nothing of `self` that changes
 // (its configuration only), so it runs with or without the index lock — in a builder thread when changes may wait.
+// The primary keys of the delta's documents: a copy, for a build that runs without the index lock. im->mu held.
+std::map<DocId, std::string> DeltaKeys(const Index::Impl* im) {
+  std::map<DocId, std::string> keys;
+  if (im->primary_keys.empty()) return keys;
+  for (const auto& kv : im->mut.delta_docs) {
+    const auto it = im->primary_keys.find(kv.first);
+    if (it != im->primary_keys.end()) keys.emplace_hint(keys.end(), *it);
+  }
+  return keys;
+}
+
 BuiltDelta BuildDelta(const Index& self, const std::map<DocId, std::string>& docs,
-                      const std::map<DocId, storage::FilterMap>& filters, std::vector<std::string> column_names) {
+                      const std::map<DocId, storage::FilterMap>& filters, std::vector<std::string> column_names,
+                      const std::map<DocId, std::string>& primary_keys) {
   BuiltDelta out;
   out.rebuilt = true;
   if (docs.empty()) return out;
@@ -924,6 +1001,8 @@ BuiltDelta BuildDelta(const Index& self, const std::map<DocId, std::string>& doc
     out.error = mgx_last_error();
     return out;
   }
+  out.error = UploadPrimaryKeys(nd->impl()->dev, primary_keys, ids.size(), [&](uint64_t slot) { return ids[slot]; });  // (after the doc map)
+  if (!out.error.empty()) return out;
   const NamedValues columns = ValuesByName(filters, std::move(column_names), ids.size(), [&](DocId doc) {
     return static_cast<uint64_t>(std::lower_bound(ids.begin(), ids.end(), doc) - ids.begin());  // (every key is a delta document)
   });
@@ -1085,9 +1164,10 @@ std::string ApplyLocked(const Index& self, bool force) {
         const bool changed = m.build_snapshot.delta_changed;  // (false: removals only, nothing to copy or build)
         m.build = std::async(std::launch::async, [&self, changed, docs = changed ? m.delta_docs : decltype(m.delta_docs)(),
                                                   filters = changed ? m.delta_filters : decltype(m.delta_filters)(),
-                                                  names = ColumnNames(im)] {
+                                                  names = ColumnNames(im),
+                                                  keys = changed ? DeltaKeys(im) : std::map<DocId, std::string>()] {
           pthread_setname_np(pthread_self(), "mgx-delta");
-          return changed ? BuildDelta(self, docs, filters, names) : BuiltDelta{};
+          return changed ? BuildDelta(self, docs, filters, names, keys) : BuiltDelta{};
         });
         return "";
       }
@@ -1099,7 +1179,7 @@ std::string ApplyLocked(const Index& self, bool force) {
           built = m.build.get();
         } else {
           snap = TakeSnapshot(m);
-          if (snap.delta_changed) built = BuildDelta(self, m.delta_docs, m.delta_filters, ColumnNames(im));
+          if (snap.delta_changed) built = BuildDelta(self, m.delta_docs, m.delta_filters, ColumnNames(im), DeltaKeys(im));
         }
         Laps lap;
         const std::string err = InstallMutations(im, snap, built, lap);
@@ -1208,6 +1288,7 @@ std::string Index::Compact() const {
                       bytes.data(), off.data(),    first,       n2};
   if (existing.size() != n2) spec.existing = &existing;
   spec.columns = &columns;
+  spec.primary_keys = &im->primary_keys;  // (removed documents' keys are gone from it: a gap of the new range has none)
   Impl::Generation gen;
   const std::string err = BuildGeneration(spec, &gen);
   if (!err.empty()) return fail(err);
@@ -1252,7 +1333,10 @@ std::string Index::AddFilterColumn(const std::string& name, const std::vector<st
 }
 
 void Index::AddDocumentBatch(const std::vector<DocumentItem>& documents) {
-  for (const auto& d : documents) AddDocument(d.doc_id, d.text);
+  for (const auto& d : documents) {
+    if (d.primary_key) AddDocument(d.doc_id, d.text, {}, *d.primary_key);
+    else AddDocument(d.doc_id, d.text);
+  }
 }
 
 std::string Index::Finalize() const {
@@ -1284,6 +1368,7 @@ std::string Index::Finalize() const {
   GenerationSpec spec{impl_->device, impl_->dense_threshold, ngram_size_, kanji_ngram_size_, cross_boundary_, nullptr,
                       bytes.data(),  off.data(),             first,       n};
   if (existing.size() != n && !existing.empty()) spec.existing = &existing;
+  spec.primary_keys = &impl_->primary_keys;
   Impl::Generation gen;
   impl_->last_error = BuildGeneration(spec, &gen);
   if (!impl_->last_error.empty()) return impl_->last_error;
@@ -2249,13 +2334,35 @@ void PlanFacetQuery(const index::Index& index, const BatchQuery& q, uint64_t tot
   p->facets = std::move(cols);
 }
 
+// BatchQuery::sort_column names the table's primary-key column (EqualsIgnoreCase, result_sorter.cpp:239). A delta index
+// asks the main index it stands beside: the name is the table's.
+bool IsPrimaryKeyColumn(const index::Index::Impl* im, const std::string& name) {
+  const std::string& pk = im->fallback ? im->fallback->primary_key_column : im->primary_key_column;
+  if (name.empty() || pk.size() != name.size()) return false;
+  for (size_t i = 0; i < name.size(); ++i)
+    if (std::tolower(static_cast<unsigned char>(pk[i])) != std::tolower(static_cast<unsigned char>(name[i]))) return false;
+  return true;
+}
+
 void PlanQuery(const index::Index& index, const BatchQuery& q, uint64_t total_docs, double avgdl, PlannedQuery* p) {
   p->sort_string = false;
   if (!q.facet_columns.empty()) return PlanFacetQuery(index, q, total_docs, avgdl, p);
+  const index::Index::Impl* im = index.impl();
+  if (q.sort_primary_key || IsPrimaryKeyColumn(im, q.sort_column)) {
+    // GetSortKey's first branch (result_sorter.cpp:239): the empty ORDER BY column, or the primary-key column's name —
+    // before any filter column of that name is looked for
+    if (q.sort_by_score) return Fail(p, ErrorCode::kInvalidArgument, "sort_primary_key and sort_by_score are two orders: set one of them");
+    PlanQueryBody(index, q, total_docs, avgdl, p);
+    if (p->error != ErrorCode::kSuccess || !p->on_device) return;
+    p->q.sort = MGX_SORT_PRIMARY_KEY;
+    p->q.sort_column = 0;
+    p->q.sort_key_bias = 0;
+    p->q.offset = q.offset;
+    return;
+  }
   if (q.sort_column.empty()) return PlanQueryBody(index, q, total_docs, avgdl, p);
   if (q.sort_by_score) return Fail(p, ErrorCode::kInvalidArgument, "sort_column and sort_by_score are two orders: set one of them");
   index.FlushPendingFilterColumns();
-  const index::Index::Impl* im = index.impl();
   uint32_t device_column = 0, bias = 0;
   bool is_string = false;
   {

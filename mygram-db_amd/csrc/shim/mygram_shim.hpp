@@ -148,6 +148,7 @@ class Index {
   struct DocumentItem {
     DocId doc_id;
     std::string text;  // normalized
+    std::optional<std::string> primary_key = std::nullopt;  // DocumentStore's primary key of the document, if it has one
   };
 
   // Recorded on the host until the first search. Returns whether the text yields any n-gram.
@@ -250,6 +251,17 @@ class Index {
   std::string AddFilterColumn(const std::string& name, const std::vector<storage::FilterValue>& values) const;
   // AddDocument with the document's filter values (recorded until the first search, like the text)
   bool AddDocument(DocId doc_id, std::string_view text, const storage::FilterMap& filters);
+  // ... and with its primary key (DocumentStore::AddDocument(primary_key, filters), document_store.h), before or after
+  // the first search. The keys are what BatchQuery::sort_primary_key orders by; a document added without one sorts by
+  // its doc id (GetSortKey's fallback, result_sorter.cpp:258-261). The table's keys stay on the host beside the index
+  // (as the reference's DocumentStore holds them) and go to the device with every index built from the table's
+  // documents: the main index, a delta, a compacted main index. A document keeps its key through UpdateDocument and
+  // UpdateFilters (it moves to the delta with it); RemoveDocument drops it; FromDump takes the dump's keys.
+  bool AddDocument(DocId doc_id, std::string_view text, const storage::FilterMap& filters, std::string_view primary_key);
+  // The name of the table's primary-key column (TableConfig::primary_key): BatchQuery::sort_column equal to it, ASCII
+  // case-insensitively, sorts by the primary key, before any filter column of that name (result_sorter.cpp:239, :516).
+  // Table configuration: set it before the first query (the planner reads it without the index lock).
+  void SetPrimaryKeyColumn(const std::string& name);
 
   // An Index over column arrays and a device index that already exist (built through the C ABI by the caller, e.g. a
   // loader that read them from a dump): nothing is copied, the handles stay the caller's and must outlive the Index.
@@ -443,8 +455,8 @@ struct BatchQuery {
   // double columns; a string column is refused there (kNotImplemented: the ranks of two dictionaries do not compare)
   // until Compact(). Refused as well (kNotImplemented): on a sharded executor, beside `highlight`, and a column that
   // holds NULLs beside INT64_MIN or the double whose bits are all ones (on a table with a delta: the main index's and
-  // the delta's column between them). The primary key is no column of this layer:
-  // SORT by it stays the doc-id page (`order`).
+  // the delta's column between them). A name equal (ASCII case-insensitively) to Index::SetPrimaryKeyColumn's is the
+  // primary key and means sort_primary_key, before any filter column of that name.
   std::string sort_column;
   bool verify_text = false;            // the caller's ShouldApplyVerifyText(memory.verify_text, terms) decision
                                        // (search_pipeline.cpp:42-66); mixed-script fragments force it (:858-866)
@@ -466,6 +478,14 @@ struct BatchQuery {
   // names (kOutOfRange); `highlight` beside it: kInvalidArgument; a name no index of the table knows fails the batch
   // with kIndexNotFound; refused (kNotImplemented) on a sharded executor (Options::comm).
   std::vector<std::string> facet_columns;
+  // SORT by primary key: the reference's empty order_by.column, its order for every query without a SORT clause
+  // (primary key DESC, result_sorter.cpp:502-510), in direction `order`, before offset / limit. Keys as
+  // Index::AddDocument(..., primary_key) recorded them, compared as GetSortKey's strings (:239-262): numeric keys by
+  // value, any other key bytewise, a document without a key by its doc id; ties go to the doc id in the sort's
+  // direction; scores are 0. On the device: MGX_SORT_PRIMARY_KEY; a table with a delta index merges the two indexes'
+  // runs by key string (key_merge_kernel) and is served like any other. Together with sort_by_score: kInvalidArgument.
+  // Refused (kNotImplemented) on a sharded executor and beside `highlight`.
+  bool sort_primary_key = false;
 };
 
 // search_pipeline::BuildHighlightTerms (src/server/search_pipeline.cpp:712-745) without the synonym branch: normalize

@@ -469,6 +469,28 @@ int mgxs_search_sorted(mgxs_table* table, uint32_t n_terms, const char* const* t
   }
 }
 
+int mgxs_search_by_primary_key(mgxs_table* table, uint32_t n_terms, const char* const* terms, uint32_t n_not,
+                               const char* const* not_terms, uint32_t n_cond, const char* const* cond_columns,
+                               const uint32_t* cond_ops, const char* const* cond_values, int descending, uint32_t limit,
+                               uint32_t offset, uint64_t* total, uint32_t* n_docs, uint32_t* docs) {
+  if (!table || !total || !n_docs || (limit && !docs)) return Fail(MGX_ERR_INVALID_ARGUMENT, "mgxs_search_by_primary_key: null argument");
+  try {
+    BatchQuery q = MakeQuery(n_terms, terms, n_not, not_terms, n_cond, cond_columns, cond_ops, cond_values, 0, descending,
+                             limit, offset);
+    q.sort_primary_key = true;
+    auto r = mygramdb::search_pipeline::ExecuteBatch(*table->index, {q});
+    if (!r) return Fail(static_cast<int>(r.error().code()), r.error().message());
+    const auto& res = (*r)[0];
+    *total = res.total;
+    const size_t n = limit ? std::min<size_t>(res.results.size(), limit) : 0;
+    *n_docs = static_cast<uint32_t>(n);
+    for (size_t k = 0; k < n; ++k) docs[k] = res.results[k];
+    return MGX_OK;
+  } catch (const std::exception& e) {
+    return Fail(MGX_ERR_INTERNAL, e.what());
+  }
+}
+
 int mgxs_search_highlight(mgxs_table* table, uint32_t n_terms, const char* const* terms, uint32_t n_not,
                           const char* const* not_terms, int sort_by_score, int descending, uint32_t limit, uint32_t offset,
                           const char* open_tag, const char* close_tag, uint32_t snippet_length, uint32_t max_fragments,

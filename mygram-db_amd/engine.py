@@ -246,10 +246,20 @@ class DeviceIndex:
         self._h = h
         self.device = device
         self.facet_values = {}  # column id -> n_values of the columns added with value ids (the lengths of their counts)
+        # handles of the batches prepared on this index and not yet destroyed. A batch keeps its index alive, but when
+        # both end up in one unreachable reference cycle (a caught exception's traceback holds the frame that holds the
+        # batch) the collector runs their __del__ in no particular order, and mgx_batch_destroy reads its index: the one
+        # that goes first takes the batches with it. A plain dict, shared with every PreparedBatch.
+        self._live_batches = {}
 
     def __del__(self):
         if getattr(self, "_h", None):
-            load().mgx_index_destroy(self._h)
+            L = load()
+            live = getattr(self, "_live_batches", {})
+            for h in list(live):
+                L.mgx_batch_destroy(C.c_void_p(h))
+            live.clear()
+            L.mgx_index_destroy(self._h)
             self._h = None
 
     def memory_bytes(self):
@@ -293,6 +303,21 @@ class DeviceIndex:
         if ids is not None:
             self.facet_values[int(out.value)] = int(n_values)
         return int(out.value)
+
+    def set_primary_keys(self, keys):
+        """mgx_index_set_primary_keys: the documents' primary keys by doc slot (bytes or str; None: the document has no
+        key and sorts by its doc id). Query(sort_primary_key=True) then pages by them. Calling it again replaces them."""
+        enc = [None if k is None else (k if isinstance(k, bytes) else str(k).encode("utf-8")) for k in keys]
+        blob = np.frombuffer(b"".join(k or b"" for k in enc) or b"\0", dtype=np.uint8)
+        off = np.zeros(len(enc) + 1, dtype=np.uint64)
+        np.cumsum([len(k or b"") for k in enc], out=off[1:])
+        has = np.asarray([k is not None for k in enc], dtype=np.uint8)
+        check(load().mgx_index_set_primary_keys(self._h, blob.ctypes.data, off.ctypes.data,
+                                                None if has.all() else has.ctypes.data))
+
+    def set_primary_key_shortcut(self, enable=True):
+        """mgx_index_set_primary_key_shortcut: off on a main index while a delta index merges with it."""
+        check(load().mgx_index_set_primary_key_shortcut(self._h, int(bool(enable))))
 
     @staticmethod
     def literal_bits(literal):
@@ -343,7 +368,7 @@ class Query:
 
     def __init__(self, terms=(), not_terms=(), filters=(), sort_score=False, limit=100, offset=0, descending=True,
                  k1=1.2, b=0.75, fuzzy=0, expr=None, universe=None, verify_text=False, highlight=None, conditions=(),
-                 sort_column=None, sort_key_bias=0, sort_ranks=False, facet_columns=None):
+                 sort_column=None, sort_key_bias=0, sort_ranks=False, facet_columns=None, sort_primary_key=False):
         """`expr`: boolean tree over term strings instead of the plain AND of `terms` (query::QueryNode):
         "term" | ("and", e, ...) | ("or", e, ...) | ("not", e). `universe` = (first_doc_id, count) of the NOT universe
         (DocumentStore::GetAllDocIds); None = every slot of the index."""
@@ -358,6 +383,11 @@ class Query:
         if sort_column is not None and sort_score:
             raise ValueError("sort_score and sort_column are two orders: set one of them")
         self.sort_column, self.sort_key_bias, self.sort_ranks = sort_column, sort_key_bias, sort_ranks
+        # sort_primary_key: the reference's order without a SORT clause (MGX_SORT_PRIMARY_KEY) over the keys given to
+        # DeviceIndex.set_primary_keys, `descending` its direction, any limit / offset
+        if sort_primary_key and (sort_score or sort_column is not None):
+            raise ValueError("sort_primary_key, sort_score and sort_column are three orders: set one of them")
+        self.sort_primary_key = bool(sort_primary_key)
         self.sort_score, self.limit, self.offset, self.descending = sort_score, limit, offset, descending
         self.k1, self.b, self.fuzzy = k1, b, fuzzy
         # verify_text: the caller's memory.verify_text decision (ShouldApplyVerifyText, search_pipeline.cpp:42-66);
@@ -372,7 +402,7 @@ class Query:
         # query's whole result set; the query returns no page: it runs in doc-id order with limit 0, whatever was given
         self.facet_columns = [int(c) for c in facet_columns] if facet_columns else None
         if self.facet_columns:
-            if sort_score or sort_column is not None or self.highlight is not None:
+            if sort_score or sort_column is not None or sort_primary_key or self.highlight is not None:
                 raise ValueError("a faceted query returns counts, not a page: no sort order and no highlight")
             self.limit, self.offset = 0, 0
         if expr is not None and not self.terms:
@@ -391,6 +421,11 @@ class Query:
 
 def _set_sort_column(cq, q):
     """q.sort_column -> cq.sort / sort_column / sort_key_bias (offset and reverse are set as for SORT _score)."""
+    if q.sort_primary_key:
+        cq.sort = _capi.SORT_PRIMARY_KEY
+        cq.sort_column = int(q.sort_column or 0)  # (0 unless a test sets them: the library refuses anything else)
+        cq.sort_key_bias = int(q.sort_key_bias)
+        return
     if q.sort_column is None:
         return
     cq.sort = _capi.SORT_COLUMN_RANK if q.sort_ranks else _capi.SORT_COLUMN
@@ -464,7 +499,7 @@ class PreparedBatch:
             h = C.c_void_p()
             arr = (_capi.Query * self.n)(*cqueries)
             check(load().mgx_batch_prepare(index.device_index._h, arr, self.n, C.byref(h)))
-            self._h = h
+            self._adopt(h)
         self._set_highlight(highlights)
         self._set_facets(facets)
 
@@ -498,9 +533,16 @@ class PreparedBatch:
             reqs[i] = _capi.HighlightRequest(1, opts.snippet_length, opts.max_fragments, len(terms), arr, lens)
         check(load().mgx_batch_set_highlight(self._h, reqs, self.n, 0))
 
+    def _adopt(self, h):
+        """Takes the handle of a batch just prepared and enters it in its index's list of live batches."""
+        self._h = h
+        self._live = self.index.device_index._live_batches
+        self._live[h.value] = True
+
     def __del__(self):
         if getattr(self, "_h", None):
-            load().mgx_batch_destroy(self._h)
+            if self._live.pop(self._h.value, None):  # (else the index went first and took the batch with it)
+                load().mgx_batch_destroy(self._h)
             self._h = None
 
     def reset(self, cqueries, keep, shells, orders, highlights=None, facets=None):
@@ -512,7 +554,7 @@ class PreparedBatch:
         if self._h is None:
             h = C.c_void_p()
             check(load().mgx_batch_prepare(self.index.device_index._h, arr, self.n, C.byref(h)))
-            self._h = h
+            self._adopt(h)
         else:
             check(load().mgx_batch_reset(self._h, arr, self.n))
         self._set_highlight(highlights)
@@ -691,7 +733,7 @@ class Index:
         """A table of a reference dump (DUMP SAVE, "MGDB" v2: src/storage/dump_format_v2.cpp) as a ranking index: columns
         built from the dump's stored texts (and checked against its own MGIX index), texts attached, filter columns kept in
         `dump_filter_columns` [(name, value type 1..12, values, is_null, strings)]; `exists` marks the doc ids the store
-        holds."""
+        holds; `dump_primary_keys` [bytes | None by slot] are the documents' primary keys, given to the device index."""
         L = load()
         raw = bytes(data)
         h = C.c_void_p()
@@ -723,6 +765,11 @@ class Index:
                     sb = np.ctypeslib.as_array(C.cast(fc.string_bytes, C.POINTER(C.c_uint8)), shape=(int(so[-1]) + 1,)).tobytes()
                     strings = [sb[int(so[k]): int(so[k + 1])] for k in range(n)]
                 self.dump_filter_columns.append((fc.name.decode(), int(fc.value_type), vals, nul.astype(bool), strings))
+            pkb, pko = C.c_void_p(), C.c_void_p()
+            check(L.mgx_dump_primary_keys_get(h, C.byref(pkb), C.byref(pko)))
+            po = np.ctypeslib.as_array(C.cast(pko, C.POINTER(C.c_uint64)), shape=(n + 1,)).copy()
+            pb = np.ctypeslib.as_array(C.cast(pkb, C.POINTER(C.c_uint8)), shape=(int(po[-1]) + 1,)).tobytes()
+            self.dump_primary_keys = [pb[int(po[k]): int(po[k + 1])] if self.exists[k] else None for k in range(n)]
             ch = C.c_void_p()
             check(L.mgx_dump_take_columns(h, C.byref(ch)))
             cols = Columns.__new__(Columns)
@@ -733,6 +780,8 @@ class Index:
             L.mgx_dump_destroy(h)
         self.columns = cols
         self.device_index = DeviceIndex(cols, device, dense_threshold, with_scoring=has_texts)
+        if n:
+            self.device_index.set_primary_keys(self.dump_primary_keys)  # Query(sort_primary_key=True) pages by them
         self._text_attached = False
         self.total_docs = cols.bm25_doc_count if has_texts else 0
         self.avg_doc_length = cols.avg_doc_length() if has_texts else 0.0
