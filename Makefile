@@ -24,7 +24,7 @@ $(CSRC)/mgx_colsort.o: $(CSRC)/mgx_colsort.hip $(CSRC)/mgx_colsort.hpp $(CSRC)/m
 # FACET in a batch: one more unit of its own (mgx_facet.hpp also holds the host-side plan, which compiles without HIP)
 $(CSRC)/mgx_facet.o: $(CSRC)/mgx_facet.hip $(CSRC)/mgx_facet.hpp
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(CSRC)/mgx_api.o: $(CSRC)/mgx_api.cpp $(CSRC)/mgx_colsort.hpp $(CSRC)/mgx_pkey.hpp $(CSRC)/mgx_facet.hpp $(CSRC)/mgx_compile.hpp $(CSRC)/mgx_internal.hpp $(CSRC)/mgx_launch.hpp $(CSRC)/mgx_host.hpp $(CSRC)/mgx_highlight.hpp include/mygram_gpu.h
+$(CSRC)/mgx_api.o: $(CSRC)/mgx_api.cpp $(CSRC)/mgx_colsort.hpp $(CSRC)/mgx_pkey.hpp $(CSRC)/mgx_facet.hpp $(CSRC)/mgx_compile.hpp $(CSRC)/mgx_internal.hpp $(CSRC)/mgx_launch.hpp $(CSRC)/mgx_host.hpp $(CSRC)/mgx_highlight.hpp $(CSRC)/mgx_text.hpp include/mygram_gpu.h
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
 $(CSRC)/mgx_compile.o: $(CSRC)/mgx_compile.cpp $(CSRC)/mgx_compile.hpp $(CSRC)/mgx_internal.hpp $(CSRC)/mgx_host.hpp include/mygram_gpu.h
 	g++ $(CXXFLAGS) -c $< -o $@
@@ -67,7 +67,13 @@ pksort-host-asan:
 	python3 tests/test_primary_key_sort_cpu.py > pksort_host_check_lines.txt
 	./pksort_host_check_asan pksort_host_check_lines.txt > /dev/null
 
+# the original-text path of mgx_highlight.hpp (translation, pending-range filter, code point -> byte walk) likewise
+highlight-original-host-asan:
+	g++ -O1 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -o highlight_original_host_check_asan tests/cpp/highlight_original_host_check.cpp
+	python3 tests/test_highlight_original_cpu.py > highlight_original_host_check_lines.txt
+	./highlight_original_host_check_asan highlight_original_host_check_lines.txt
+
 clean:
-	rm -f $(OBJS) $(LIB) $(SHIM) colsort_host_check_asan colsort_host_check_lines.txt pksort_host_check_asan pksort_host_check_lines.txt
+	rm -f $(OBJS) $(LIB) $(SHIM) colsort_host_check_asan colsort_host_check_lines.txt pksort_host_check_asan pksort_host_check_lines.txt highlight_original_host_check_asan highlight_original_host_check_lines.txt
 	$(MAKE) -C oracle clean
-.PHONY: all oracle clean ablation colsort-host-asan pksort-host-asan
+.PHONY: all oracle clean ablation colsort-host-asan pksort-host-asan highlight-original-host-asan

@@ -144,6 +144,11 @@ int mgx_dump_filter_column_get(const mgx_dump* dump, uint32_t i, mgx_dump_filter
  * bytes[off[i] .. off[i + 1]); a slot mgx_dump_view.exists marks 0 holds no document and no bytes. The arrays are the
  * dump's: they live until mgx_dump_destroy. What mgx_index_set_primary_keys takes, with `exists` as has_key. */
 int mgx_dump_primary_keys_get(const mgx_dump* dump, const uint8_t** bytes, const uint64_t** off);
+/* The documents' original texts, likewise by doc slot (the store section's "MGDS" v3 writes one per document,
+ * src/storage/document_store_persistence.cpp:159-167; length 0: the store holds none for that document, as in a v2
+ * stream). What HIGHLIGHT answers with where there is one (mgx_index_attach_original_text, after the caller built the
+ * documents' maps). */
+int mgx_dump_original_texts_get(const mgx_dump* dump, const uint8_t** bytes, const uint64_t** off);
 /* Hands the table's columns to the caller (release with mgx_columns_destroy); a second call returns NULL. */
 int mgx_dump_take_columns(mgx_dump* dump, mgx_columns** out);
 void mgx_dump_destroy(mgx_dump* dump);
@@ -529,6 +534,35 @@ int mgx_highlight_render(const mgx_highlight_entry* entry, const uint8_t* open_t
                          const uint8_t* close_tag, size_t close_len, uint8_t* out, size_t cap, size_t* out_len);
 /* Length in bytes of the longest text attached to the index (0 without mgx_index_attach_text). */
 int mgx_index_max_text_bytes(const mgx_index* idx, uint32_t* out);
+
+/* ---- HIGHLIGHT from original texts (query::Highlighter::GenerateOriginal, src/query/highlighter.cpp:311-356; the
+ * normal path of SearchHandler::GenerateHighlightSnippets, search_handler.cpp:277-307, for a document whose store holds
+ * the text as the user wrote it). Matches are found in the NORMALIZED text, as always; each is translated to code points
+ * of the original through a map the host builds once per document (one (cp_start, cp_end) pair per normalized code
+ * point: the original segment it came from, :328-336), and the windows, spans and bytes of such an entry's record are
+ * ranges and bytes of the ORIGINAL. Its `flags` carries MGX_HL_ORIGINAL. No Unicode work happens on the device.
+ *
+ * mgx_index_attach_original_text, after mgx_index_attach_text: arrays by doc slot; off has n_docs + 1 entries (bytes),
+ * map_off n_docs + 1 entries counted in PAIRS of map_pairs (two uint32_t each); only MGX_ORIG_MAPPED documents have
+ * pairs, so an index whose normalizer only folds case stores none. Everything is checked on the host, in one pass,
+ * MGX_ERR_INVALID_ARGUMENT naming the slot: a kind above 3; pairs on a document that is not MAPPED; an original of kind
+ * 1-3 that is not valid UTF-8 (render such a document on the host and attach it as MGX_ORIG_NONE); an IDENTITY document
+ * whose code points differ in number from its normalized text's; a MAPPED document whose pairs differ in number from its
+ * normalized text's code points, or hold a pair that is not start < end <= the original's code points, or whose starts
+ * or ends decrease. Calling it again replaces the originals; mgx_index_attach_text called again drops them (they were
+ * checked against the texts it replaces): attach them again after it.
+ * mgx_batch_set_highlight(max_text_bytes = 0) sizes the records from the longer of the two texts; a table with a delta
+ * passes the largest of mgx_index_max_text_bytes and mgx_index_max_original_text_bytes over both indexes. A batch on
+ * indexes without originals launches the kernel it always launched. */
+#define MGX_ORIG_NONE 0u       /* the document has no original: Generate over the normalized text */
+#define MGX_ORIG_IDENTITY 1u   /* normalized code point i <-> original code points [i, i + 1): no map stored */
+#define MGX_ORIG_MAPPED 2u     /* an explicit (cp_start, cp_end) pair per normalized code point */
+#define MGX_ORIG_UNMAPPABLE 3u /* :342-344: the no-match window over the original, whatever the terms */
+#define MGX_HL_ORIGINAL 8u     /* mgx_highlight_entry.flags: the entry was built from the document's original */
+int mgx_index_attach_original_text(mgx_index* idx, const uint8_t* bytes, const uint64_t* off, const uint8_t* kind,
+                                   const uint32_t* map_pairs, const uint64_t* map_off);
+/* Length in bytes of the longest original attached to the index (0 without mgx_index_attach_original_text). */
+int mgx_index_max_original_text_bytes(const mgx_index* idx, uint32_t* out);
 
 /* ---- FACET in a batch (FACET <column> of many queries and columns per execute; mgx_facet_counts serves one query and
  * one column per call and waits for the device each time).

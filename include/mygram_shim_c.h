@@ -129,7 +129,9 @@ int mgxs_search_by_primary_key(mgxs_table* table, uint32_t n_terms, const char* 
 /* mgxs_search with HIGHLIGHT (BatchQuery::highlight: GenerateHighlightSnippets on the page, search_handler.cpp:473-482, on the
  * device): the page's snippets, packed into `snippets`; doc k's snippet is snippets[snippet_off[k] .. snippet_off[k+1]).
  * snippet_off has room for limit + 1 entries. Tags NUL-terminated, at most 256 bytes; snippet_length 1..10000,
- * max_fragments 1..100. MGX_ERR_OUT_OF_RANGE when the snippets exceed snippets_cap. */
+ * max_fragments 1..100. MGX_ERR_OUT_OF_RANGE when the snippets exceed snippets_cap. A document whose original text is
+ * on the adopted index (mgx_index_attach_original_text) gets the snippet of what the user wrote
+ * (Highlighter::GenerateOriginal), every other document the snippet of its normalized text. */
 int mgxs_search_highlight(mgxs_table* table, uint32_t n_terms, const char* const* terms, uint32_t n_not,
                           const char* const* not_terms, int sort_by_score, int descending, uint32_t limit, uint32_t offset,
                           const char* open_tag, const char* close_tag, uint32_t snippet_length, uint32_t max_fragments,

@@ -53,6 +53,22 @@ int mgxt_highlight_generate(const uint8_t* text, size_t text_len, const uint8_t*
 int mgxt_highlight_match_positions(const uint8_t* text, size_t text_len, const uint8_t* const* terms,
                                    const size_t* term_lens, uint32_t n_terms, uint32_t* out_pairs, size_t cap_pairs,
                                    size_t* n_pairs);
+/* query::Highlighter::GenerateOriginal (src/query/highlighter.cpp:311-356) with the normalized-to-original map given
+ * instead of a normalizer: the scalar path of the source highlight_original_kernel runs. `kind` is a MGX_ORIG_* value
+ * of mygram_gpu.h and map_pairs holds n_pairs (cp_start, cp_end) pairs (MGX_ORIG_MAPPED only), as
+ * mgx_index_attach_original_text takes them for one document; MGX_ORIG_NONE is mgxt_highlight_generate over the
+ * normalized text. The arguments are trusted as the device trusts an attached document; on input that breaks the
+ * contract the call stays inside the buffers and the output is unspecified. */
+int mgxt_highlight_generate_original(const uint8_t* original, size_t original_len, const uint8_t* normalized,
+                                     size_t normalized_len, uint32_t kind, const uint32_t* map_pairs, size_t n_pairs,
+                                     const uint8_t* const* terms, const size_t* term_lens, uint32_t n_terms,
+                                     uint32_t snippet_length, uint32_t max_fragments, const uint8_t* open_tag,
+                                     size_t open_len, const uint8_t* close_tag, size_t close_len, uint8_t* out,
+                                     size_t cap, size_t* out_len);
+/* RemoveOverlappingMatchPositions (:227-248) as the stream GenerateOriginal's translated ranges pass on the device and in
+ * mgxt_highlight_generate_original: n_pairs (start, end) pairs with non-decreasing starts and non-decreasing ends in,
+ * the kept ones out (out_pairs holds up to n_pairs pairs), their number in *n_out. */
+int mgxt_highlight_filter_ranges(const uint32_t* pairs, size_t n_pairs, uint32_t* out_pairs, size_t* n_out);
 
 #ifdef __cplusplus
 }

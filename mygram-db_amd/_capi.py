@@ -35,8 +35,10 @@ EXPORTS = [
     "mgxt_contains_fuzzy_match",
     "mgx_batch_set_highlight", "mgx_batch_fetch_highlight", "mgx_highlight_render", "mgx_index_max_text_bytes", "mgx_batch_defer_highlight",
     "mgxt_highlight_generate", "mgxt_highlight_match_positions",
+    "mgx_index_attach_original_text", "mgx_index_max_original_text_bytes", "mgxt_highlight_generate_original",
+    "mgxt_highlight_filter_ranges",
     "mgx_batch_set_facets", "mgx_batch_fetch_facets",
-    "mgx_index_set_primary_keys", "mgx_index_set_primary_key_shortcut", "mgx_dump_primary_keys_get",
+    "mgx_index_set_primary_keys", "mgx_index_set_primary_key_shortcut", "mgx_dump_primary_keys_get", "mgx_dump_original_texts_get",
 ]
 
 
@@ -161,6 +163,8 @@ FACET_LDS_BINS = 8192
 HIGHLIGHT_ARENA_CAP = 256 << 20
 CONDITION_ARENA_MAX_BYTES = 1 << 30
 HIGHLIGHT_MAX_TERMS = 256
+ORIG_NONE, ORIG_IDENTITY, ORIG_MAPPED, ORIG_UNMAPPABLE = 0, 1, 2, 3
+HL_ORIGINAL = 8
 
 _lib = None
 
@@ -251,6 +255,12 @@ def load():
     L.mgx_highlight_render.argtypes = [C.POINTER(HighlightEntry), C.c_char_p, sz, C.c_char_p, sz, vp, sz, C.POINTER(sz)]
     L.mgx_batch_defer_highlight.argtypes = [vp, i32]
     L.mgx_index_max_text_bytes.argtypes = [vp, C.POINTER(u32)]
+    L.mgx_index_attach_original_text.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.mgx_index_max_original_text_bytes.argtypes = [vp, C.POINTER(u32)]
+    L.mgxt_highlight_generate_original.argtypes = [C.c_char_p, sz, C.c_char_p, sz, u32, vp, sz, C.POINTER(C.c_char_p),
+                                                   C.POINTER(sz), u32, u32, u32, C.c_char_p, sz, C.c_char_p, sz, vp, sz,
+                                                   C.POINTER(sz)]
+    L.mgxt_highlight_filter_ranges.argtypes = [vp, sz, vp, C.POINTER(sz)]
     L.mgxt_highlight_generate.argtypes = [C.c_char_p, sz, C.POINTER(C.c_char_p), C.POINTER(sz), u32, u32, u32, C.c_char_p,
                                           sz, C.c_char_p, sz, vp, sz, C.POINTER(sz)]
     L.mgxt_highlight_match_positions.argtypes = [C.c_char_p, sz, C.POINTER(C.c_char_p), C.POINTER(sz), u32, vp, sz,
@@ -260,6 +270,7 @@ def load():
     L.mgx_index_set_primary_keys.argtypes = [vp, vp, vp, vp]
     L.mgx_index_set_primary_key_shortcut.argtypes = [vp, i32]
     L.mgx_dump_primary_keys_get.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+    L.mgx_dump_original_texts_get.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
     L.mgx_index_set_doc_map.argtypes = [vp, vp, u64]
     L.mgx_batch_merge_local.argtypes = [vp, C.POINTER(vp), u32, vp]
     _lib = L

@@ -36,6 +36,7 @@
 #include "mgx_host.hpp"
 #include "mgx_internal.hpp"
 #include "mgx_launch.hpp"
+#include "mgx_text.hpp"
 #include "mygram_tools.h"
 
 namespace mgx {
@@ -310,6 +311,10 @@ struct mgx_index {
   DevBuf d_offsets, d_docids, d_tf, d_doc_len, d_skip_row, d_tile_off, d_gram_bitmaps, d_filter_bitmaps;
   DevBuf d_text, d_text_off;  // mgx_index_attach_text
   uint32_t max_text_bytes = 0;  // the longest attached text (sizes the highlight records)
+  // mgx_index_attach_original_text: the texts as the user wrote them, their kinds and the mapped documents' maps
+  DevBuf d_orig, d_orig_off, d_orig_kind, d_orig_map, d_orig_map_off;
+  mgx::highlight::DevOriginals originals{};  // all null without them
+  uint32_t max_original_bytes = 0;
   DevBuf d_dl8, d_tfnib, d_tf_ovf_pos, d_tf_ovf_val;
   DevBuf d_dev_index;  // `dev` in device memory: what out-of-line device functions take a pointer to (SyncDevIndex)
   std::vector<uint64_t> h_offsets;
@@ -661,6 +666,11 @@ int mgx_dump_primary_keys_get(const mgx_dump* dump, const uint8_t** bytes, const
   mgx::DumpPrimaryKeys(reinterpret_cast<const mgx::DumpData*>(dump), bytes, off);
   return MGX_OK;
 }
+int mgx_dump_original_texts_get(const mgx_dump* dump, const uint8_t** bytes, const uint64_t** off) {
+  if (!dump || !bytes || !off) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dump_original_texts_get: null argument");
+  mgx::DumpOriginalTexts(reinterpret_cast<const mgx::DumpData*>(dump), bytes, off);
+  return MGX_OK;
+}
 int mgx_dump_take_columns(mgx_dump* dump, mgx_columns** out) {
   if (out) *out = nullptr;
   if (!dump || !out) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_dump_take_columns: null argument");
@@ -937,7 +947,8 @@ int mgx_index_memory_bytes(const mgx_index* idx, uint64_t* out) {
   *out = idx->d_offsets.bytes + idx->d_docids.bytes + idx->d_tf.bytes + idx->d_doc_len.bytes +
          idx->d_skip_row.bytes + idx->d_tile_off.bytes + idx->d_gram_bitmaps.bytes + idx->d_filter_bitmaps.bytes +
          idx->d_text.bytes + idx->d_text_off.bytes + idx->d_dl8.bytes + idx->d_tfnib.bytes + idx->d_table_pool.bytes +
-         idx->d_tf_ovf_pos.bytes + idx->d_tf_ovf_val.bytes;
+         idx->d_tf_ovf_pos.bytes + idx->d_tf_ovf_val.bytes + idx->d_orig.bytes + idx->d_orig_off.bytes +
+         idx->d_orig_kind.bytes + idx->d_orig_map.bytes + idx->d_orig_map_off.bytes;
   {  // the per-(k1, b, avgdl) pruning arrays built so far
     std::lock_guard<std::mutex> lock(const_cast<mgx_index*>(idx)->table_mu);
     for (const auto& t : idx->block_max) *out += t->d.bytes + t->d_fine.bytes;
@@ -972,6 +983,14 @@ int mgx_index_attach_text(mgx_index* idx, const uint8_t* text_bytes, const uint6
   uint64_t longest = 0;
   for (uint64_t i = 0; i < n; ++i) longest = std::max<uint64_t>(longest, text_off[i + 1] - text_off[i]);
   idx->max_text_bytes = static_cast<uint32_t>(longest);
+  // originals and maps were checked against the texts they replace: attach them again after new texts
+  idx->d_orig.Free();
+  idx->d_orig_off.Free();
+  idx->d_orig_kind.Free();
+  idx->d_orig_map.Free();
+  idx->d_orig_map_off.Free();
+  idx->originals = mgx::highlight::DevOriginals{};
+  idx->max_original_bytes = 0;
   MGX_HIP(mgx::SyncDevIndex(idx));
   return MGX_OK;
 }
@@ -980,6 +999,101 @@ int mgx_index_max_text_bytes(const mgx_index* idx, uint32_t* out) {
   if (out) *out = 0;
   if (!idx || !out) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_index_max_text_bytes: null argument");
   *out = idx->dev.text ? idx->max_text_bytes : 0;
+  return MGX_OK;
+}
+
+int mgx_index_attach_original_text(mgx_index* idx, const uint8_t* bytes, const uint64_t* off, const uint8_t* kind,
+                                   const uint32_t* map_pairs, const uint64_t* map_off) {
+  namespace hl = mgx::highlight;
+  if (!idx || !off || !kind || !map_off)
+    return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_index_attach_original_text: null argument");
+  if (!idx->dev.text)
+    return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_index_attach_original_text: call mgx_index_attach_text first");
+  const uint64_t n = idx->dev.n_docs;
+  for (uint64_t i = 0; i < n; ++i) {
+    if (off[i + 1] < off[i] || off[i + 1] - off[i] > 0x7FFFFF00ull)
+      return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_index_attach_original_text: offsets must ascend (slot " + std::to_string(i) + ")");
+    if (map_off[i + 1] < map_off[i])
+      return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_index_attach_original_text: map offsets must ascend (slot " + std::to_string(i) + ")");
+  }
+  const uint64_t total = off[n] - off[0], total_pairs = map_off[n] - map_off[0];
+  if ((total && !bytes) || (total_pairs && !map_pairs))
+    return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_index_attach_original_text: null text or map");
+  try {
+    std::lock_guard<std::mutex> lock(idx->mu);
+    MGX_HIP(hipSetDevice(idx->device));
+    // the normalized texts' code points, from the resident copy (attach time only: no query reads anything back), in
+    // pieces of whole documents of about 64 MiB so that the host never holds the corpus twice
+    std::vector<uint64_t> t_off(n + 1);
+    MGX_HIP(hipMemcpy(t_off.data(), idx->d_text_off.p, (n + 1) * 8, hipMemcpyDeviceToHost));
+    constexpr uint64_t kPiece = 64ull << 20;
+    std::vector<uint8_t> norm;
+    uint64_t piece_begin = 0, piece_end = 0;  // the documents [piece_begin, piece_end) are in `norm`
+    uint64_t longest = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+      if (i >= piece_end) {
+        piece_begin = i;
+        piece_end = i + 1;
+        while (piece_end < n && t_off[piece_end + 1] - t_off[piece_begin] <= kPiece) ++piece_end;
+        const uint64_t bytes = t_off[piece_end] - t_off[piece_begin];
+        norm.resize(bytes);
+        if (bytes) MGX_HIP(hipMemcpy(norm.data(), idx->d_text.as<uint8_t>() + t_off[piece_begin], bytes, hipMemcpyDeviceToHost));
+      }
+      const std::string who = "mgx_index_attach_original_text: slot " + std::to_string(i) + ": ";
+      const uint64_t pairs = map_off[i + 1] - map_off[i];
+      if (kind[i] > MGX_ORIG_UNMAPPABLE) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, who + "unknown kind " + std::to_string(kind[i]));
+      if (kind[i] != MGX_ORIG_MAPPED && pairs) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, who + "only a MGX_ORIG_MAPPED document has map pairs");
+      if (kind[i] == MGX_ORIG_NONE) continue;
+      const uint8_t* o = bytes + off[i];
+      const uint64_t len = off[i + 1] - off[i];
+      uint64_t cps = 0;
+      for (uint64_t p = 0; p < len; ++cps) {
+        uint32_t cp = 0;
+        const int k = mgx::text::ParseUtf8(o + p, len - p, &cp);
+        if (k <= 0) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, who + "the original is not valid UTF-8");
+        p += static_cast<uint64_t>(k);
+      }
+      longest = std::max(longest, len);
+      if (kind[i] == MGX_ORIG_UNMAPPABLE) continue;
+      const uint64_t norm_cps = hl::CountCps(norm.data() + (t_off[i] - t_off[piece_begin]), t_off[i + 1] - t_off[i]);
+      if (kind[i] == MGX_ORIG_IDENTITY) {
+        if (cps != norm_cps)
+          return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, who + "an identity original has " + std::to_string(cps) + " code points, its normalized text " + std::to_string(norm_cps));
+        continue;
+      }
+      if (pairs != norm_cps)
+        return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, who + "the map has " + std::to_string(pairs) + " pairs, the normalized text " + std::to_string(norm_cps) + " code points");
+      const uint32_t* m = map_pairs + 2 * map_off[i];
+      for (uint64_t p = 0; p < pairs; ++p) {
+        if (!(m[2 * p] < m[2 * p + 1] && m[2 * p + 1] <= cps))
+          return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, who + "map pair " + std::to_string(p) + " is not start < end <= the original's code points");
+        if (p && (m[2 * p] < m[2 * p - 2] || m[2 * p + 1] < m[2 * p - 1]))
+          return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, who + "map pair " + std::to_string(p) + ": starts and ends must not decrease");
+      }
+    }
+    std::vector<uint64_t> rel(n + 1), mrel(n + 1);
+    for (uint64_t i = 0; i <= n; ++i) {
+      rel[i] = off[i] - off[0];
+      mrel[i] = map_off[i] - map_off[0];
+    }
+    MGX_HIP(mgx::Upload(idx->d_orig, bytes ? bytes + off[0] : nullptr, total, 128));
+    MGX_HIP(mgx::Upload(idx->d_orig_off, rel.data(), rel.size()));
+    MGX_HIP(mgx::Upload(idx->d_orig_kind, kind, n, 16));
+    MGX_HIP(mgx::Upload(idx->d_orig_map, map_pairs ? map_pairs + 2 * map_off[0] : nullptr, 2 * total_pairs, 16));
+    MGX_HIP(mgx::Upload(idx->d_orig_map_off, mrel.data(), mrel.size()));
+    idx->originals = hl::DevOriginals{idx->d_orig.as<uint8_t>(), idx->d_orig_off.as<uint64_t>(), idx->d_orig_kind.as<uint8_t>(),
+                                      idx->d_orig_map.as<hl::MapPair>(), idx->d_orig_map_off.as<uint64_t>()};
+    idx->max_original_bytes = static_cast<uint32_t>(longest);
+    return MGX_OK;
+  } catch (const std::exception& e) {
+    return mgx::Fail(MGX_ERR_INTERNAL, std::string("mgx_index_attach_original_text: ") + e.what());
+  }
+}
+
+int mgx_index_max_original_text_bytes(const mgx_index* idx, uint32_t* out) {
+  if (out) *out = 0;
+  if (!idx || !out) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_index_max_original_text_bytes: null argument");
+  *out = idx->originals.kind ? idx->max_original_bytes : 0;
   return MGX_OK;
 }
 
@@ -2666,7 +2780,12 @@ static int RunHighlight(mgx_batch* b, hipStream_t s, bool merged, const mgx_inde
   hb.mapped = source(mapped, true);
   hb.plain = source(plain, false);
   hb.merged = merged ? 1u : 0u;
-  MGX_LAUNCH(LaunchHighlight(hb, s));
+  // an index with originals: the kernel that reads them; else what a batch has always launched
+  const highlight::DevOriginals none{};
+  const highlight::DevOriginals& om = mapped ? mapped->originals : none;
+  const highlight::DevOriginals& op = plain ? plain->originals : none;
+  if (om.kind || op.kind) MGX_LAUNCH(LaunchHighlightOriginal(hb, om, op, s));
+  else MGX_LAUNCH(LaunchHighlight(hb, s));
   MGX_HIP(hipMemcpyAsync(h.h_arena, h.d_arena.p, h.bytes, hipMemcpyDeviceToHost, s));
   return MGX_OK;
 }
@@ -3506,7 +3625,8 @@ int mgx_batch_set_highlight(mgx_batch* batch, const mgx_highlight_request* reque
     std::vector<uint32_t> pos_in_group(n_queries, 0);
     for (size_t i = 0; i < batch->score.qids.size(); ++i) pos_in_group[batch->score.qids[i]] = static_cast<uint32_t>(i);
     for (size_t i = 0; i < batch->page.qids.size(); ++i) pos_in_group[batch->page.qids[i]] = static_cast<uint32_t>(i);
-    const uint32_t longest = max_text_bytes ? max_text_bytes : idx->max_text_bytes;
+    const uint32_t longest =
+        max_text_bytes ? max_text_bytes : std::max(idx->max_text_bytes, idx->originals.kind ? idx->max_original_bytes : 0u);
     uint64_t arena = 0;
     uint32_t n_entries = 0;
     for (uint32_t qi = 0; qi < n_queries; ++qi) {

@@ -874,6 +874,8 @@ struct DumpData {
   std::vector<Col> filter_cols;
   std::vector<uint8_t> pk_bytes;  // the documents' primary keys by slot (a slot without a document: no bytes)
   std::vector<uint64_t> pk_off;
+  std::vector<uint8_t> orig_bytes;  // the documents' original texts by slot (MGDS v3; no bytes: the store holds none)
+  std::vector<uint64_t> orig_off;
   bool has_scores = false;  // the texts were stored: tf / doc_len columns exist
   ~DumpData() { DestroyColumns(cols); }
 };
@@ -980,6 +982,7 @@ int DumpOpen(const uint8_t* data, uint64_t len, const char* table, DumpData** ou
   struct Doc {
     uint32_t id;
     uint64_t text_at, text_len;
+    uint64_t orig_at, orig_len;
     std::string pk;
     std::vector<std::pair<uint32_t, std::pair<uint8_t, std::pair<uint64_t, uint64_t>>>> filters;  // column -> (type, (value | str at, str len))
   };
@@ -1031,6 +1034,8 @@ int DumpOpen(const uint8_t* data, uint64_t len, const char* table, DumpData** ou
     if (dsv >= 3) {
       const uint32_t ol = dr.U32();
       if (!dr.Need(ol)) return fail(MGX_ERR_INVALID_ARGUMENT, "truncated original text");
+      doc.orig_at = dr.at;
+      doc.orig_len = ol;
       dr.at += ol;
     }
     if (!dr.ok) return fail(MGX_ERR_INVALID_ARGUMENT, "truncated document");
@@ -1074,6 +1079,13 @@ int DumpOpen(const uint8_t* data, uint64_t len, const char* table, DumpData** ou
     dump->pk_off[sl + 1] = dump->pk_bytes.size();
   }
   dump->pk_bytes.push_back(0);  // (an address even when every key is empty)
+  dump->orig_off.assign(dump->n_docs + 1, 0);
+  for (uint64_t sl = 0; sl < dump->n_docs; ++sl) {
+    if (by_slot[sl] && by_slot[sl]->orig_len)
+      dump->orig_bytes.insert(dump->orig_bytes.end(), dr.p + by_slot[sl]->orig_at, dr.p + by_slot[sl]->orig_at + by_slot[sl]->orig_len);
+    dump->orig_off[sl + 1] = dump->orig_bytes.size();
+  }
+  dump->orig_bytes.push_back(0);
   // filter columns by slot
   dump->filter_cols.resize(col_names.size());
   for (size_t c = 0; c < col_names.size(); ++c) {
@@ -1163,6 +1175,10 @@ bool DumpFilterColumn(const DumpData* d, uint32_t i, mgx_dump_filter_column* o) 
 void DumpPrimaryKeys(const DumpData* d, const uint8_t** bytes, const uint64_t** off) {
   *bytes = d->pk_bytes.data();
   *off = d->pk_off.data();
+}
+void DumpOriginalTexts(const DumpData* d, const uint8_t** bytes, const uint64_t** off) {
+  *bytes = d->orig_bytes.data();
+  *off = d->orig_off.data();
 }
 Columns* DumpTakeColumns(DumpData* d) {
   Columns* c = d->cols;

@@ -13,6 +13,14 @@
 //   4. copies the windows' bytes into the entry's record, lanes side by side, and writes the record's header and windows.
 // Every store is a vector store of one lane. Reads of the text stay inside [0, n) of the document, writes inside the
 // record's capacities (Header::flags says when a capacity cut the record short: never on valid UTF-8).
+//
+// highlight_original_kernel is the same wave program for a batch whose indexes carry original texts
+// (mgx_index_attach_original_text; Highlighter::GenerateOriginal, highlighter.cpp:311-356). For an entry whose document
+// has an original, step 2 still scans the NORMALIZED text, but every kept match is translated to code points of the
+// original (TranslateMatch) and passes the pending-range filter (PendingRange) before Builder sees it, so the spans are
+// code points too; step 3 walks the ORIGINAL and turns windows and spans into byte offsets in one pass; step 4 copies the
+// original's bytes and sets kFlagOriginal. A document without an original takes the steps above unchanged. Reads of the
+// original, its kind and its map stay inside what mgx_index_attach_original_text checked and uploaded.
 #include <hip/hip_runtime.h>
 
 #include "mgx_highlight.hpp"
@@ -36,7 +44,27 @@ __device__ __forceinline__ unsigned long long hl_below(uint32_t p) {  // bits [0
   return p >= 64 ? ~0ull : ((1ull << p) - 1ull);
 }
 
-__global__ __launch_bounds__(kHlWaves * 64) void highlight_kernel(const DevHlBatch hb) {
+// The originals of the batch's two text sources (highlight_original_kernel only).
+struct DevHlOriginals {
+  hl::DevOriginals mapped, plain;
+};
+
+// Code points of text[0, n), counted by the wave; the walk stops once the count exceeds `stop_above`.
+__device__ __forceinline__ uint32_t hl_count_cps(const uint8_t* text, uint32_t n, uint32_t stop_above, uint32_t lane) {
+  uint32_t c = 0;
+  for (uint32_t base = 0; base < n && c <= stop_above; base += 64) {
+    const uint32_t pos = base + lane;
+    c += static_cast<uint32_t>(__popcll(__ballot(pos < n && hl::IsLead(text[pos]))));
+  }
+  return c;
+}
+
+// One page entry, by one wave. kOrig = false is highlight_kernel as it always was; kOrig = true (an index of the batch
+// carries originals) adds, for an entry whose document has one: the matches found in the normalized text are translated
+// to code points of the original and pass the pending-range filter before Builder sees them, the windows AND the spans
+// are turned into byte offsets by a walk over the ORIGINAL, and the record's bytes are the original's.
+template <bool kOrig>
+__device__ __forceinline__ void hl_entry(const DevHlBatch& hb, const DevHlOriginals* ho) {
   __shared__ hl::Window s_win[kHlWaves][hl::kMaxFragments];
   __shared__ uint32_t s_next[kHlWaves][kHlMaxTerms];
   const uint32_t lane = threadIdx.x & 63u;
@@ -72,6 +100,9 @@ __global__ __launch_bounds__(kHlWaves * 64) void highlight_kernel(const DevHlBat
   // ---- 1. the text ----
   const uint8_t* text = nullptr;
   uint32_t n = 0;
+  const uint8_t* otext = nullptr;  // (kOrig) the original, its kind and its map
+  uint32_t on = 0, kind = hl::kOrigNone, n_pairs = 0;
+  const hl::MapPair* map = nullptr;
   {
     const uint8_t* src_text = nullptr;
     const uint64_t* src_off = nullptr;
@@ -99,10 +130,28 @@ __global__ __launch_bounds__(kHlWaves * 64) void highlight_kernel(const DevHlBat
       const uint64_t len = t1 > t0 ? t1 - t0 : 0;
       n = len > 0x7FFFFF00ull ? 0x7FFFFF00u : static_cast<uint32_t>(len);
       text = src_text + t0;
+      if constexpr (kOrig) {  // the document's original, in the index its text came from
+        const hl::DevOriginals& o = src_text == hb.mapped.text ? ho->mapped : ho->plain;
+        if (o.kind) kind = o.kind[slot];
+        if (kind > hl::kOrigUnmappable) kind = hl::kOrigNone;
+        if (kind != hl::kOrigNone) {
+          const uint64_t o0 = o.off[slot], o1 = o.off[slot + 1];
+          const uint64_t olen = o1 > o0 ? o1 - o0 : 0;
+          on = olen > 0x7FFFFF00ull ? 0x7FFFFF00u : static_cast<uint32_t>(olen);
+          otext = o.bytes + o0;
+        }
+        if (kind == hl::kOrigMapped) {
+          const uint64_t m0 = o.map_off[slot], m1 = o.map_off[slot + 1];
+          const uint64_t pairs = m1 > m0 ? m1 - m0 : 0;
+          n_pairs = pairs > 0x7FFFFF00ull ? 0x7FFFFF00u : static_cast<uint32_t>(pairs);
+          map = o.map + m0;
+        }
+      }
     }
   }
-  if (n == 0) {  // an empty text gives an empty snippet (highlighter.cpp:301-305)
-    if (lane == 0) *g_head = hl::Header{0, 0, 0, 0};
+  const bool om = kOrig && kind != hl::kOrigNone;  // this entry is built from an original
+  if (om ? on == 0 : n == 0) {  // an empty text gives an empty snippet (highlighter.cpp:301-305, :315-319)
+    if (lane == 0) *g_head = hl::Header{0, om ? hl::kFlagOriginal : 0u, 0, 0};
     return;
   }
 
@@ -118,7 +167,13 @@ __global__ __launch_bounds__(kHlWaves * 64) void highlight_kernel(const DevHlBat
   bd.Init(q.snippet_length, q.max_fragments, win, g_spans, q.span_cap);
   const unsigned long long lt_mask = hl_below(lane);
   uint32_t cp_base = 0, last_end = 0;
-  for (uint32_t base = 0; base < n && !bd.done; base += 64) {
+  uint32_t n_scan = n;
+  hl::PendingRange pr;
+  pr.Init();
+  if constexpr (kOrig) {  // an unmappable original, or no usable term: the no-match window (:323-325, :342-344)
+    if (om && (kind == hl::kOrigUnmappable || n_terms == 0)) n_scan = 0;
+  }
+  for (uint32_t base = 0; base < n_scan && !bd.done; base += 64) {
     const uint32_t pos = base + lane;
     const bool inb = pos < n;
     const uint8_t c = inb ? text[pos] : static_cast<uint8_t>(0x80);
@@ -162,13 +217,33 @@ __global__ __launch_bounds__(kHlWaves * 64) void highlight_kernel(const DevHlBat
       const uint32_t b_len = static_cast<uint32_t>(__shfl(static_cast<int>(best_len), static_cast<int>(p)));
       if (ms < last_end) continue;
       last_end = ms + b_cps;
+      if constexpr (kOrig) {
+        if (om) {  // (the spans are code points of the original until step 3 walks it)
+          uint32_t xs, xe, os, oe;
+          if (hl::TranslateMatch(kind, map, n_pairs, ms, ms + b_cps, &xs, &xe) && pr.Push(xs, xe, &os, &oe))
+            bd.Feed(os, oe, os, oe, writer);
+          if (bd.done) break;
+          continue;
+        }
+      }
       bd.Feed(ms, ms + b_cps, base + p, base + p + b_len, writer);
       if (bd.done) break;
     }
     cp_base += static_cast<uint32_t>(__popcll(lead));
     hl_wave_sync();  // (the writer's next_ok words, read by every lane in the next chunk)
   }
-  const uint32_t total = bd.done ? hl::kNoTotal : cp_base;
+  uint32_t total = bd.done ? hl::kNoTotal : cp_base;
+  if constexpr (kOrig) {
+    if (om && !bd.done) {
+      uint32_t os, oe;
+      if (pr.Flush(&os, &oe)) bd.Feed(os, oe, os, oe, writer);
+      // the clamp and the trailing "..." need the ORIGINAL's code points: an identity document's are the normalized
+      // text's; the no-match window only asks whether there are more than snippet_length
+      if (bd.done) total = hl::kNoTotal;
+      else if (n_scan == 0) total = hl_count_cps(otext, on, q.snippet_length, lane);
+      else if (kind != hl::kOrigIdentity) total = hl_count_cps(otext, on, hl::kNoTotal, lane);
+    }
+  }
   bd.Finish(total, writer);
   uint32_t flags = bd.flags;
   const uint32_t n_win = bd.n_win;
@@ -177,7 +252,64 @@ __global__ __launch_bounds__(kHlWaves * 64) void highlight_kernel(const DevHlBat
   hl_wave_sync();  // (the windows, written by the writer)
 
   // ---- 3. window bounds: code points -> bytes (targets ascend: start0 <= end0 <= start1 ...) ----
-  {
+  if (om) {
+    if constexpr (kOrig) {
+      // over the ORIGINAL, and the spans with them: both ascend, so the next target is the smaller of the two heads. A
+      // span bound behind the last window's end stops there (the renderer clips a span to its window). The spans are
+      // in the record, written and read back by the writer lane alone.
+      const uint32_t n_wt = 2 * n_win, n_st = 2 * bd.n_spans;
+      const uint32_t last = n_win ? win[n_win - 1].end : 0;
+      uint32_t wi = 0, si = 0, cps = 0;
+      uint32_t sp_at = 0xFFFFFFFFu, sp_s = 0, sp_e = 0;  // the span whose bounds are in sp_s / sp_e
+      for (uint32_t base = 0; wi < n_wt || si < n_st; base += 64) {
+        if (base >= on) {  // at or past the end of the text
+          for (; wi < n_wt; ++wi)
+            if (writer) (wi & 1u ? win[wi >> 1].end : win[wi >> 1].start) = on;
+          for (; si < n_st; ++si)
+            if (writer) (si & 1u ? g_spans[si >> 1].end : g_spans[si >> 1].start) = on;
+          break;
+        }
+        const uint32_t pos = base + lane;
+        const bool is_lead = pos < on && hl::IsLead(otext[pos]);
+        const unsigned long long lead = __ballot(is_lead);
+        const uint32_t rank = static_cast<uint32_t>(__popcll(lead & lt_mask));
+        const uint32_t cnt = static_cast<uint32_t>(__popcll(lead));
+        while (wi < n_wt || si < n_st) {
+          const bool hw = wi < n_wt, hs = si < n_st;
+          const uint32_t tw = hw ? (wi & 1u ? win[wi >> 1].end : win[wi >> 1].start) : 0u;
+          uint32_t ts = 0;
+          if (hs) {
+            if (sp_at != (si >> 1)) {
+              sp_at = si >> 1;
+              uint32_t a = 0, b = 0;
+              if (writer) {
+                a = g_spans[sp_at].start;
+                b = g_spans[sp_at].end;
+              }
+              sp_s = static_cast<uint32_t>(__shfl(static_cast<int>(a), 0));
+              sp_e = static_cast<uint32_t>(__shfl(static_cast<int>(b), 0));
+            }
+            ts = si & 1u ? sp_e : sp_s;
+            if (ts > last) ts = last;
+          }
+          const bool take_span = hs && (!hw || ts <= tw);
+          const uint32_t tc = take_span ? ts : tw;
+          if (tc - cps >= cnt) break;  // (tc >= cps: targets ascend)
+          const unsigned long long sel = __ballot(is_lead && rank == tc - cps);
+          const uint32_t byte = base + static_cast<uint32_t>(__builtin_ctzll(sel));
+          if (take_span) {
+            if (writer) (si & 1u ? g_spans[si >> 1].end : g_spans[si >> 1].start) = byte;
+            ++si;
+          } else {
+            if (writer) (wi & 1u ? win[wi >> 1].end : win[wi >> 1].start) = byte;
+            ++wi;
+            hl_wave_sync();
+          }
+        }
+        cps += cnt;
+      }
+    }
+  } else {
     uint32_t ti = 0;
     const uint32_t n_tgt = 2 * n_win;
     uint32_t cps = 0;
@@ -207,27 +339,44 @@ __global__ __launch_bounds__(kHlWaves * 64) void highlight_kernel(const DevHlBat
 
   // ---- 4. the record ----
   hl_wave_sync();
+  const uint8_t* src = om ? otext : text;  // the windows' bytes: the original's where there is one
+  const uint32_t sn = om ? on : n;
+  if (om) flags |= hl::kFlagOriginal;
   uint32_t out = 0;
   for (uint32_t i = 0; i < n_win; ++i) {
-    const uint32_t bs = win[i].start < n ? win[i].start : n;
-    uint32_t be = win[i].end < n ? win[i].end : n;
+    const uint32_t bs = win[i].start < sn ? win[i].start : sn;
+    uint32_t be = win[i].end < sn ? win[i].end : sn;
     if (be < bs) be = bs;
     uint32_t len = be - bs;
     if (len > q.byte_cap - out) {
       len = q.byte_cap - out;
       flags |= hl::kFlagOverflow;
     }
-    for (uint32_t o = lane; o < len; o += 64) g_bytes[out + o] = text[bs + o];
+    for (uint32_t o = lane; o < len; o += 64) g_bytes[out + o] = src[bs + o];
     if (writer) g_win[i] = hl::Window{bs, bs + len, win[i].span_end, out};
     out += len;
   }
   if (writer) *g_head = hl::Header{n_win, flags, bd.n_spans, out};
 }
 
+__global__ __launch_bounds__(kHlWaves * 64) void highlight_kernel(const DevHlBatch hb) { hl_entry<false>(hb, nullptr); }
+
+__global__ __launch_bounds__(kHlWaves * 64) void highlight_original_kernel(const DevHlBatch hb, const DevHlOriginals ho) {
+  hl_entry<true>(hb, &ho);
+}
+
 int LaunchHighlight(const DevHlBatch& hb, hipStream_t s) {
   if (hb.n_entries == 0) return 0;
   const uint32_t grid = (hb.n_entries + kHlWaves - 1) / kHlWaves;
   hipLaunchKernelGGL(highlight_kernel, dim3(grid), dim3(kHlWaves * 64), 0, s, hb);
+  return static_cast<int>(hipGetLastError());
+}
+
+int LaunchHighlightOriginal(const DevHlBatch& hb, const hl::DevOriginals& mapped, const hl::DevOriginals& plain,
+                            hipStream_t s) {
+  if (hb.n_entries == 0) return 0;
+  const uint32_t grid = (hb.n_entries + kHlWaves - 1) / kHlWaves;
+  hipLaunchKernelGGL(highlight_original_kernel, dim3(grid), dim3(kHlWaves * 64), 0, s, hb, DevHlOriginals{mapped, plain});
   return static_cast<int>(hipGetLastError());
 }
 

@@ -186,6 +186,90 @@ MGX_HL_HD uint32_t CpToByteFrom(const uint8_t* t, uint32_t n, uint32_t cp, uint3
   return i;
 }
 
+// ---- original texts: Highlighter::GenerateOriginal (:311-356) --------------------------------------------------------
+// A document may carry the text the user wrote next to its normalized text. Matches are still found in the normalized
+// text; each kept match [s, e) of normalized code points is translated to code points of the ORIGINAL through the map
+// the host built per document (one (cp_start, cp_end) pair per normalized code point: the original segment the code
+// point came from, :328-336), the translated ranges pass RemoveOverlappingMatchPositions once more (:355), and the
+// windows, the clamp, the "..." and the bytes are all the original's.
+//
+// Contract (checked by mgx_index_attach_original_text): the original is valid UTF-8; an identity document has as many
+// code points as its normalized text; a mapped document has one pair per normalized code point, start < end <= the
+// original's code points, starts and ends non-decreasing. On other input every routine stays inside what it is given.
+constexpr uint32_t kOrigNone = 0;        // no original: Generate over the normalized text
+constexpr uint32_t kOrigIdentity = 1;    // normalized code point i <-> original code points [i, i + 1): no map stored
+constexpr uint32_t kOrigMapped = 2;      // an explicit pair per normalized code point
+constexpr uint32_t kOrigUnmappable = 3;  // :342-344: the no-match window over the original, whatever the terms
+constexpr uint32_t kFlagOriginal = 8u;   // the record's windows, spans and bytes are the ORIGINAL text's
+
+struct MapPair {
+  uint32_t first, second;  // code points [first, second) of the original
+};
+
+// Where a device index keeps its originals (by doc slot; all null on an index without them).
+struct DevOriginals {
+  const uint8_t* bytes;
+  const uint64_t* off;      // [n_docs + 1]
+  const uint8_t* kind;      // [n_docs] kOrig*
+  const MapPair* map;       // the kOrigMapped documents' pairs
+  const uint64_t* map_off;  // [n_docs + 1], in pairs
+};
+
+// One kept match [s, e) of normalized code points -> code points of the original (:349-354). False: the match is
+// dropped as the reference drops it (outside the map).
+MGX_HL_HD bool TranslateMatch(uint32_t kind, const MapPair* map, uint32_t n_pairs, uint32_t s, uint32_t e, uint32_t* xs,
+                              uint32_t* xe) {
+  if (kind == kOrigIdentity) {
+    *xs = s;
+    *xe = e;
+    return true;
+  }
+  if (s >= n_pairs || e == 0 || e > n_pairs) return false;
+  *xs = map[s].first;
+  *xe = map[e - 1].second;
+  return true;
+}
+
+// RemoveOverlappingMatchPositions (:227-248) as a stream with one range of look-ahead. The translated ranges arrive with
+// non-decreasing starts and non-decreasing ends (the segments are in text order), so the sort is the arrival order except
+// inside a run of equal starts, where the longest is the last: a range that shares the held one's start replaces it, one
+// that starts inside the held one is dropped, any other one releases it. Every member is wave-uniform on the device.
+struct PendingRange {
+  uint32_t s, e;
+  bool held;
+
+  MGX_HL_HD void Init() {
+    s = e = 0;
+    held = false;
+  }
+  // True: a range leaves the filter in (*os, *oe).
+  MGX_HL_HD bool Push(uint32_t xs, uint32_t xe, uint32_t* os, uint32_t* oe) {
+    if (!held) {
+      held = true;
+      s = xs;
+      e = xe;
+      return false;
+    }
+    if (xs == s) {  // the longest for a shared start (:232-237)
+      if (xe > e) e = xe;
+      return false;
+    }
+    if (xs < e) return false;  // starts inside the kept range (:242-244)
+    *os = s;
+    *oe = e;
+    s = xs;
+    e = xe;
+    return true;
+  }
+  MGX_HL_HD bool Flush(uint32_t* os, uint32_t* oe) {
+    if (!held) return false;
+    held = false;
+    *os = s;
+    *oe = e;
+    return true;
+  }
+};
+
 // ---- host scanner + whole Generate (scalar) -------------------------------------------------------------------------
 
 struct Term {
@@ -275,6 +359,76 @@ MGX_HL_HD uint32_t WindowsToBytes(const uint8_t* text, uint32_t n, Window* win, 
     out += b1 - b0;
   }
   return out;
+}
+
+// The same for a record built from an original text, whose spans are code points too (the matches were translated, so
+// their bytes are not known while they are found): windows and spans both ascend, one walk serves both. A span bound
+// behind the last window's end stops there — the renderer clips a span to its window. Scalar form of the kernel's step.
+MGX_HL_HD uint32_t OriginalToBytes(const uint8_t* text, uint32_t n, Window* win, uint32_t n_win, Span* spans,
+                                   uint32_t n_spans) {
+  const uint32_t last = n_win ? win[n_win - 1].end : 0;
+  uint32_t byte = 0, seen = 0, wi = 0, si = 0;
+  while (wi < 2 * n_win || si < 2 * n_spans) {
+    uint32_t tw = 0, ts = 0;
+    if (wi < 2 * n_win) tw = wi & 1u ? win[wi >> 1].end : win[wi >> 1].start;
+    if (si < 2 * n_spans) {
+      ts = si & 1u ? spans[si >> 1].end : spans[si >> 1].start;
+      if (ts > last) ts = last;
+    }
+    if (si < 2 * n_spans && (wi >= 2 * n_win || ts <= tw)) {
+      const uint32_t b = CpToByteFrom(text, n, ts, &byte, &seen);
+      (si & 1u ? spans[si >> 1].end : spans[si >> 1].start) = b;
+      ++si;
+    } else {
+      const uint32_t b = CpToByteFrom(text, n, tw, &byte, &seen);
+      (wi & 1u ? win[wi >> 1].end : win[wi >> 1].start) = b;
+      ++wi;
+    }
+  }
+  uint32_t out = 0;
+  for (uint32_t i = 0; i < n_win; ++i) {
+    win[i].aux = out;
+    out += win[i].end - win[i].start;
+  }
+  return out;
+}
+
+// PendingRange over a whole list (the test hook's form): writes the ranges that leave the filter, returns their number.
+MGX_HL_HD size_t FilterRanges(const MapPair* in, size_t n, MapPair* out) {
+  PendingRange pr;
+  pr.Init();
+  size_t m = 0;
+  uint32_t os, oe;
+  for (size_t i = 0; i < n; ++i)
+    if (pr.Push(in[i].first, in[i].second, &os, &oe)) out[m++] = MapPair{os, oe};
+  if (pr.Flush(&os, &oe)) out[m++] = MapPair{os, oe};
+  return m;
+}
+
+// GenerateOriginal (:311-356) over one document, scalar: the record of a non-empty original of kind 1..3, windows and
+// spans as byte offsets of the ORIGINAL. win[max_fragments], spans[span_cap], scratch[n_terms + 1] are the caller's.
+MGX_HL_HD Header GenerateOriginalRecord(const uint8_t* original, uint32_t on, const uint8_t* normalized, uint32_t n,
+                                        uint32_t kind, const MapPair* map, uint32_t n_pairs, const Term* terms,
+                                        uint32_t n_terms, uint32_t snippet_length, uint32_t max_fragments, Window* win,
+                                        Span* spans, uint32_t span_cap, uint32_t* scratch) {
+  Builder bd;
+  bd.Init(snippet_length, max_fragments, win, spans, span_cap);
+  if (kind != kOrigUnmappable && n_terms != 0) {  // (:323-325, :342-344: else the no-match window)
+    Scanner sc;
+    sc.Init(normalized, n, terms, n_terms, scratch);
+    PendingRange pr;
+    pr.Init();
+    uint32_t ms, me, bs, be, xs, xe, os, oe;
+    while (!bd.done && sc.Next(&ms, &me, &bs, &be))
+      if (TranslateMatch(kind, map, n_pairs, ms, me, &xs, &xe) && pr.Push(xs, xe, &os, &oe)) bd.Feed(os, oe, os, oe, true);
+    if (!bd.done && pr.Flush(&os, &oe)) bd.Feed(os, oe, os, oe, true);
+  }
+  const uint32_t total = bd.done ? kNoTotal : CountCps(original, on);
+  bd.Finish(total, true);
+  FinalizeWindows(win, bd.n_win, bd.matched, snippet_length, total, &bd.flags);
+  Header h{bd.n_win, bd.flags | kFlagOriginal, bd.n_spans, 0};
+  h.n_bytes = OriginalToBytes(original, on, win, bd.n_win, spans, bd.n_spans);
+  return h;
 }
 
 // GenerateWithPositions' rendering loop (:188-222) over a finished record. `bytes`: the windows' text; window i's

@@ -22,6 +22,7 @@ void DumpDestroy(DumpData* d);
 void DumpView(const DumpData* d, mgx_dump_view* v);
 bool DumpFilterColumn(const DumpData* d, uint32_t i, mgx_dump_filter_column* o);
 void DumpPrimaryKeys(const DumpData* d, const uint8_t** bytes, const uint64_t** off);
+void DumpOriginalTexts(const DumpData* d, const uint8_t** bytes, const uint64_t** off);
 Columns* DumpTakeColumns(DumpData* d);
 
 // thread-local last-error message

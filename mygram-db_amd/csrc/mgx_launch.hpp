@@ -93,5 +93,12 @@ int LaunchSortByScore(const uint32_t* docs, const double* scores, uint64_t n, in
                       uint32_t hi, uint64_t* keys_tmp, uint32_t* dprime_tmp, uint32_t* out, hipStream_t s);
 // HIGHLIGHT: one wave per (highlighted query, page entry), after the kernel that finalises the page (mgx_highlight.hip)
 int LaunchHighlight(const DevHlBatch& hb, hipStream_t s);
+// The same where an index of the batch carries original texts (mgx_index_attach_original_text): the originals of
+// hb.mapped and of hb.plain (mgx_highlight.hpp; all null for an index without them)
+namespace highlight {
+struct DevOriginals;
+}
+int LaunchHighlightOriginal(const DevHlBatch& hb, const highlight::DevOriginals& mapped,
+                            const highlight::DevOriginals& plain, hipStream_t s);
 
 }  // namespace mgx

@@ -242,3 +242,49 @@ extern "C" int mgxt_highlight_generate(const uint8_t* text, size_t text_len, con
   *out_len = hl::Render(h, win.data(), spans.data(), text, true, open_tag, open_len, close_tag, close_len, out, cap);
   return 0;
 }
+
+// Highlighter::GenerateOriginal (:311-356) with the map given instead of a normalizer: the scalar path of the source
+// highlight_original_kernel runs (translation, the pending-range filter, Builder, the code point -> byte walk).
+extern "C" int mgxt_highlight_generate_original(const uint8_t* original, size_t original_len, const uint8_t* normalized,
+                                                size_t normalized_len, uint32_t kind, const uint32_t* map_pairs,
+                                                size_t n_pairs, const uint8_t* const* terms, const size_t* term_lens,
+                                                uint32_t n_terms, uint32_t snippet_length, uint32_t max_fragments,
+                                                const uint8_t* open_tag, size_t open_len, const uint8_t* close_tag,
+                                                size_t close_len, uint8_t* out, size_t cap, size_t* out_len) {
+  if (kind == hl::kOrigNone)
+    return mgxt_highlight_generate(normalized, normalized_len, terms, term_lens, n_terms, snippet_length, max_fragments,
+                                   open_tag, open_len, close_tag, close_len, out, cap, out_len);
+  if (out_len) *out_len = 0;
+  std::vector<hl::Term> tv;
+  if (!out_len || (cap != 0 && !out) || (open_len != 0 && !open_tag) || (close_len != 0 && !close_tag) ||
+      (original == nullptr && original_len != 0) || original_len > 0x7FFFFFFFu || kind > hl::kOrigUnmappable ||
+      (n_pairs != 0 && !map_pairs) || n_pairs > 0x7FFFFFFFu ||
+      !HighlightTerms(normalized, normalized_len, terms, term_lens, n_terms, &tv))
+    return 2;
+  if (snippet_length < 1 || snippet_length > hl::kMaxSnippetLength || max_fragments < 1 ||
+      max_fragments > hl::kMaxFragments || open_len > hl::kMaxTagBytes || close_len > hl::kMaxTagBytes)
+    return 3;
+  if (original_len == 0) return 0;  // an empty original gives an empty snippet (:315-319)
+  const uint32_t on = static_cast<uint32_t>(original_len);
+  const uint32_t n = static_cast<uint32_t>(normalized_len);
+  const hl::MapPair* map = reinterpret_cast<const hl::MapPair*>(map_pairs);
+  std::vector<uint32_t> scratch(tv.size() + 1);
+  std::vector<hl::Window> win(max_fragments);
+  // (a window of L code points holds at most L matches, and every match is one of the normalized text's)
+  const size_t span_cap = std::min<size_t>(static_cast<size_t>(max_fragments) * snippet_length, normalized_len);
+  std::vector<hl::Span> spans(span_cap + 1);
+  const hl::Header h = hl::GenerateOriginalRecord(original, on, normalized, n, kind, map, static_cast<uint32_t>(n_pairs),
+                                                  tv.data(), static_cast<uint32_t>(tv.size()), snippet_length,
+                                                  max_fragments, win.data(), spans.data(),
+                                                  static_cast<uint32_t>(span_cap), scratch.data());
+  *out_len = hl::Render(h, win.data(), spans.data(), original, true, open_tag, open_len, close_tag, close_len, out, cap);
+  return 0;
+}
+
+// The pending-range filter of the same source over a list of (start, end) pairs with non-decreasing starts and ends.
+extern "C" int mgxt_highlight_filter_ranges(const uint32_t* pairs, size_t n_pairs, uint32_t* out_pairs, size_t* n_out) {
+  if (n_out) *n_out = 0;
+  if (!n_out || (n_pairs != 0 && (!pairs || !out_pairs))) return 2;
+  *n_out = hl::FilterRanges(reinterpret_cast<const hl::MapPair*>(pairs), n_pairs, reinterpret_cast<hl::MapPair*>(out_pairs));
+  return 0;
+}

@@ -20,6 +20,7 @@
 #include <iterator>
 #include <map>
 #include <mutex>
+#include <set>
 #include <thread>
 #include <unordered_map>
 
@@ -208,6 +209,10 @@ struct Index::Impl {
   // index built from the table's documents (main, delta, a compacted main) takes its slots' keys from it. Under mu.
   mutable std::map<DocId, std::string> primary_keys;
   std::string primary_key_column;  // SetPrimaryKeyColumn
+  // The original text of every document of the table that has one (AddDocument(..., original_text)), kept like the keys
+  // and for the same span; `invalid_originals`: those that are not valid UTF-8, which the host renders. Under mu.
+  mutable std::map<DocId, std::string> originals;
+  mutable std::set<DocId> invalid_originals;
   mutable mgx_columns* cols = nullptr;
   mutable mgx_index* dev = nullptr;
   mutable mgx_columns_view view{};
@@ -527,7 +532,44 @@ struct GenerationSpec {
   const std::vector<DocId>* existing = nullptr;  // the ids that exist, when some of [first, first + n) do not
   const NamedValues* columns = nullptr;          // filter values by doc slot
   const std::map<DocId, std::string>* primary_keys = nullptr;  // the table's (those of [first, first + n) are taken)
+  const std::map<DocId, std::string>* originals = nullptr;     // likewise; needs text_bytes and `normalizer`
+  std::function<std::string(std::string_view)> normalizer = nullptr;  // the index's NormalizeText
 };
+
+// The original texts of an index's doc slots to the device (mgx_index_attach_original_text), with the map of each
+// (query::BuildOriginalMap). doc_of(slot): the slot's table id, ascending; text_bytes / text_off: the normalized texts by
+// slot. An original that is not valid UTF-8 is left out (kind "none": the host renders that document's entries). An
+// index none of whose documents has an original gets none and keeps launching the kernel it always launched.
+template <class DocOf>
+std::string UploadOriginals(mgx_index* dev, const std::map<DocId, std::string>& originals, uint64_t n, DocOf doc_of,
+                            const uint8_t* text_bytes, const uint64_t* text_off,
+                            const std::function<std::string(std::string_view)>& normalizer) {
+  if (originals.empty() || !text_bytes || !normalizer) return "";
+  std::vector<uint8_t> bytes, kind(n + 1, MGX_ORIG_NONE);
+  std::vector<uint32_t> pairs;
+  std::vector<uint64_t> off(n + 1, 0), map_off(n + 1, 0);
+  bool any = false;
+  auto it = n ? originals.lower_bound(doc_of(0)) : originals.end();
+  for (uint64_t slot = 0; slot < n; ++slot) {
+    const DocId doc = doc_of(slot);
+    while (it != originals.end() && it->first < doc) ++it;
+    if (it != originals.end() && it->first == doc && mygram::utils::IsValidUtf8(it->second)) {
+      const std::string_view normalized(reinterpret_cast<const char*>(text_bytes) + text_off[slot], text_off[slot + 1] - text_off[slot]);
+      query::OriginalMap m = query::BuildOriginalMap(it->second, normalized, normalizer);
+      kind[slot] = static_cast<uint8_t>(m.kind);
+      bytes.insert(bytes.end(), it->second.begin(), it->second.end());
+      pairs.insert(pairs.end(), m.pairs.begin(), m.pairs.end());
+      any = true;
+    }
+    off[slot + 1] = bytes.size();
+    map_off[slot + 1] = pairs.size() / 2;
+  }
+  if (!any) return "";
+  bytes.push_back(0);  // (an address even when every original is empty)
+  pairs.push_back(0);
+  return mgx_index_attach_original_text(dev, bytes.data(), off.data(), kind.data(), pairs.data(), map_off.data()) == MGX_OK
+             ? "" : mgx_last_error();
+}
 
 // The primary keys of an index's doc slots to the device (mgx_index_set_primary_keys). doc_of(slot): the slot's table id,
 // ascending with the slot (one walk over the table's keys).
@@ -607,6 +649,11 @@ std::string BuildGeneration(const GenerationSpec& in, Index::Impl::Generation* o
   }
   if (in.primary_keys) {
     const std::string err = UploadPrimaryKeys(dev, *in.primary_keys, v.n_docs, [&](uint64_t slot) { return v.first_doc_id + static_cast<DocId>(slot); });
+    if (!err.empty()) return err;
+  }
+  if (in.originals) {
+    const std::string err = UploadOriginals(dev, *in.originals, v.n_docs, [&](uint64_t slot) { return v.first_doc_id + static_cast<DocId>(slot); },
+                                            in.text_bytes, in.text_off, in.normalizer);
     if (!err.empty()) return err;
   }
   if (in.columns)
@@ -712,6 +759,23 @@ std::unique_ptr<Index> Index::FromDump(const void* data, size_t len, const std::
                           std::string(reinterpret_cast<const char*>(pk_bytes + pk_off[i]), static_cast<size_t>(pk_off[i + 1] - pk_off[i])));
   }
   spec.primary_keys = &keys;
+  // ... and every document's original text where the store holds one (MGDS v3)
+  std::map<DocId, std::string> originals;
+  {
+    const uint8_t* o_bytes = nullptr;
+    const uint64_t* o_off = nullptr;
+    if (mgx_dump_original_texts_get(dump, &o_bytes, &o_off) != MGX_OK) {
+      mgx_columns_destroy(spec.cols);
+      return fail(mgx_last_error());
+    }
+    for (uint64_t i = 0; i < v.n_docs; ++i)
+      if (v.exists[i] && o_off[i + 1] > o_off[i])
+        originals.emplace_hint(originals.end(), v.first_doc_id + static_cast<DocId>(i),
+                               std::string(reinterpret_cast<const char*>(o_bytes + o_off[i]), static_cast<size_t>(o_off[i + 1] - o_off[i])));
+  }
+  spec.originals = &originals;
+  const Index* self = idx.get();
+  spec.normalizer = [self](std::string_view t) { return self->NormalizeText(t); };
   Impl::Generation gen;
   const std::string err = BuildGeneration(spec, &gen);
   if (!err.empty()) return fail(err);
@@ -719,6 +783,9 @@ std::unique_ptr<Index> Index::FromDump(const void* data, size_t len, const std::
     std::lock_guard<std::mutex> lock(im->mu);
     im->Install(std::move(gen));
     im->primary_keys = std::move(keys);
+    for (const auto& kv : originals)
+      if (!mygram::utils::IsValidUtf8(kv.second)) im->invalid_originals.insert(kv.first);
+    im->originals = std::move(originals);
   }
   g_last_finalized.store(idx.get());
   return idx;
@@ -757,8 +824,17 @@ std::string EnsureMutable(Index::Impl* im) {
 
 namespace {
 // Both forms of AddDocument, in one critical section: the text and its filter values are recorded together or not at all.
+// im->mu held: the document's original becomes `original` (nullptr: it has none).
+void SetOriginalLocked(Index::Impl* im, DocId doc_id, const std::string_view* original) {
+  im->originals.erase(doc_id);
+  im->invalid_originals.erase(doc_id);
+  if (!original) return;
+  im->originals[doc_id] = std::string(*original);
+  if (!mygram::utils::IsValidUtf8(*original)) im->invalid_originals.insert(doc_id);
+}
+
 bool AddDocumentLocked(const Index& index, DocId doc_id, std::string_view text, const storage::FilterMap* filters,
-                       const std::string_view* primary_key = nullptr) {
+                       const std::string_view* primary_key = nullptr, const std::string_view* original = nullptr) {
   Index::Impl* im = index.impl();
   std::lock_guard<std::mutex> lock(im->mu);
   if (im->finalized) {  // index.cpp:39-74 on a built index: the document joins the delta
@@ -780,6 +856,7 @@ bool AddDocumentLocked(const Index& index, DocId doc_id, std::string_view text, 
   }
   if (primary_key) im->primary_keys[doc_id] = std::string(*primary_key);
   else im->primary_keys.erase(doc_id);  // (an id added again without a key has none)
+  SetOriginalLocked(im, doc_id, original);
   return !GenerateHybridNgrams(text, index.GetNgramSize(), index.GetKanjiNgramSize(), index.GetCrossBoundaryNgrams()).empty();
 }
 }  // namespace
@@ -790,6 +867,10 @@ bool Index::AddDocument(DocId doc_id, std::string_view text, const storage::Filt
 }
 bool Index::AddDocument(DocId doc_id, std::string_view text, const storage::FilterMap& filters, std::string_view primary_key) {
   return AddDocumentLocked(*this, doc_id, text, &filters, &primary_key);
+}
+bool Index::AddDocument(DocId doc_id, std::string_view text, const storage::FilterMap& filters,
+                        std::optional<std::string_view> primary_key, std::string_view original_text) {
+  return AddDocumentLocked(*this, doc_id, text, &filters, primary_key ? &*primary_key : nullptr, &original_text);
 }
 void Index::SetPrimaryKeyColumn(const std::string& name) {
   std::lock_guard<std::mutex> lock(impl_->mu);
@@ -840,6 +921,7 @@ void Index::RemoveDocument(DocId doc_id, std::string_view text) {
   }
   RemoveLocked(*this, impl_.get(), doc_id, text);
   impl_->primary_keys.erase(doc_id);  // (UpdateDocument and UpdateFilters go through RemoveLocked and keep the key)
+  SetOriginalLocked(impl_.get(), doc_id, nullptr);
 }
 
 void Index::UpdateDocument(DocId doc_id, std::string_view old_text, std::string_view new_text) {
@@ -873,23 +955,36 @@ void Index::UpdateDocument(DocId doc_id, std::string_view old_text, std::string_
   RemoveLocked(*this, im, doc_id, old_text);
   im->mut.delta_docs[doc_id] = std::string(new_text);
   if (!keep.empty()) im->mut.delta_filters[doc_id] = std::move(keep);
+  SetOriginalLocked(im, doc_id, nullptr);  // (the old original no longer belongs to the new text)
   im->mut.Record(/*delta=*/true);
 }
 
-void Index::UpdateDocument(DocId doc_id, std::string_view old_text, std::string_view new_text,
-                           const storage::FilterMap& filters) {
-  Finalize();
-  std::lock_guard<std::mutex> lock(impl_->mu);
-  Impl* im = impl_.get();
+namespace {
+void UpdateDocumentWithFilters(const Index& index, DocId doc_id, std::string_view old_text, std::string_view new_text,
+                               const storage::FilterMap& filters, const std::string_view* original) {
+  index.Finalize();
+  Index::Impl* im = index.impl();
+  std::lock_guard<std::mutex> lock(im->mu);
   const std::string err = EnsureMutable(im);
   if (!err.empty()) {
     im->last_error = "UpdateDocument: " + err;
     return;
   }
-  RemoveLocked(*this, im, doc_id, old_text);
+  RemoveLocked(index, im, doc_id, old_text);
   im->mut.delta_docs[doc_id] = std::string(new_text);
   im->mut.delta_filters[doc_id] = filters;
+  SetOriginalLocked(im, doc_id, original);  // (none given: the old one no longer belongs to the new text)
   im->mut.Record(/*delta=*/true);
+}
+}  // namespace
+
+void Index::UpdateDocument(DocId doc_id, std::string_view old_text, std::string_view new_text,
+                           const storage::FilterMap& filters) {
+  UpdateDocumentWithFilters(*this, doc_id, old_text, new_text, filters, nullptr);
+}
+void Index::UpdateDocument(DocId doc_id, std::string_view old_text, std::string_view new_text,
+                           const storage::FilterMap& filters, std::string_view original_text) {
+  UpdateDocumentWithFilters(*this, doc_id, old_text, new_text, filters, &original_text);
 }
 
 bool Index::UpdateFilters(DocId doc_id, const storage::FilterMap& filters) {
@@ -975,9 +1070,20 @@ std::map<DocId, std::string> DeltaKeys(const Index::Impl* im) {
   return keys;
 }
 
+// Likewise the originals of the delta's documents. im->mu held.
+std::map<DocId, std::string> DeltaOriginals(const Index::Impl* im) {
+  std::map<DocId, std::string> out;
+  if (im->originals.empty()) return out;
+  for (const auto& kv : im->mut.delta_docs) {
+    const auto it = im->originals.find(kv.first);
+    if (it != im->originals.end()) out.emplace_hint(out.end(), *it);
+  }
+  return out;
+}
+
 BuiltDelta BuildDelta(const Index& self, const std::map<DocId, std::string>& docs,
                       const std::map<DocId, storage::FilterMap>& filters, std::vector<std::string> column_names,
-                      const std::map<DocId, std::string>& primary_keys) {
+                      const std::map<DocId, std::string>& primary_keys, const std::map<DocId, std::string>& originals) {
   BuiltDelta out;
   out.rebuilt = true;
   if (docs.empty()) return out;
@@ -989,7 +1095,10 @@ BuiltDelta BuildDelta(const Index& self, const std::map<DocId, std::string>& doc
   ids.reserve(docs.size());
   DocId local = 1;
   for (const auto& kv : docs) {  // (ascending table id -> ascending local id: rank order and ties are kept)
-    nd->AddDocument(local++, kv.second);
+    nd->AddDocument(local, kv.second);
+    const auto orig = originals.find(kv.first);  // (by local id: the delta's own generation uploads them)
+    if (orig != originals.end()) nd->impl()->originals.emplace(local, orig->second);
+    ++local;
     ids.push_back(kv.first);
   }
   const std::string err = nd->Finalize();
@@ -1165,9 +1274,10 @@ std::string ApplyLocked(const Index& self, bool force) {
         m.build = std::async(std::launch::async, [&self, changed, docs = changed ? m.delta_docs : decltype(m.delta_docs)(),
                                                   filters = changed ? m.delta_filters : decltype(m.delta_filters)(),
                                                   names = ColumnNames(im),
-                                                  keys = changed ? DeltaKeys(im) : std::map<DocId, std::string>()] {
+                                                  keys = changed ? DeltaKeys(im) : std::map<DocId, std::string>(),
+                                                  originals = changed ? DeltaOriginals(im) : std::map<DocId, std::string>()] {
           pthread_setname_np(pthread_self(), "mgx-delta");
-          return changed ? BuildDelta(self, docs, filters, names, keys) : BuiltDelta{};
+          return changed ? BuildDelta(self, docs, filters, names, keys, originals) : BuiltDelta{};
         });
         return "";
       }
@@ -1179,7 +1289,7 @@ std::string ApplyLocked(const Index& self, bool force) {
           built = m.build.get();
         } else {
           snap = TakeSnapshot(m);
-          if (snap.delta_changed) built = BuildDelta(self, m.delta_docs, m.delta_filters, ColumnNames(im), DeltaKeys(im));
+          if (snap.delta_changed) built = BuildDelta(self, m.delta_docs, m.delta_filters, ColumnNames(im), DeltaKeys(im), DeltaOriginals(im));
         }
         Laps lap;
         const std::string err = InstallMutations(im, snap, built, lap);
@@ -1289,6 +1399,8 @@ std::string Index::Compact() const {
   if (existing.size() != n2) spec.existing = &existing;
   spec.columns = &columns;
   spec.primary_keys = &im->primary_keys;  // (removed documents' keys are gone from it: a gap of the new range has none)
+  spec.originals = &im->originals;        // (likewise)
+  spec.normalizer = [this](std::string_view t) { return NormalizeText(t); };
   Impl::Generation gen;
   const std::string err = BuildGeneration(spec, &gen);
   if (!err.empty()) return fail(err);
@@ -1334,7 +1446,9 @@ std::string Index::AddFilterColumn(const std::string& name, const std::vector<st
 
 void Index::AddDocumentBatch(const std::vector<DocumentItem>& documents) {
   for (const auto& d : documents) {
-    if (d.primary_key) AddDocument(d.doc_id, d.text, {}, *d.primary_key);
+    if (d.original_text)
+      AddDocument(d.doc_id, d.text, {}, d.primary_key ? std::optional<std::string_view>(*d.primary_key) : std::nullopt, *d.original_text);
+    else if (d.primary_key) AddDocument(d.doc_id, d.text, {}, *d.primary_key);
     else AddDocument(d.doc_id, d.text);
   }
 }
@@ -1369,6 +1483,8 @@ std::string Index::Finalize() const {
                       bytes.data(),  off.data(),             first,       n};
   if (existing.size() != n && !existing.empty()) spec.existing = &existing;
   spec.primary_keys = &impl_->primary_keys;
+  spec.originals = &impl_->originals;
+  spec.normalizer = [this](std::string_view t) { return NormalizeText(t); };
   Impl::Generation gen;
   impl_->last_error = BuildGeneration(spec, &gen);
   if (!impl_->last_error.empty()) return impl_->last_error;
@@ -1881,6 +1997,74 @@ HighlightResult Highlighter::Generate(std::string_view normalized_text, const st
                                 options.close_tag.size(), nullptr, 0);
   result.snippet.resize(len);
   hl::Render(h, win.data(), spans.data(), text, true, ot, options.open_tag.size(), ct, options.close_tag.size(),
+             reinterpret_cast<uint8_t*>(result.snippet.data()), len);
+  return result;
+}
+
+OriginalMap BuildOriginalMap(std::string_view original_text, std::string_view normalized_text,
+                             const std::function<std::string(std::string_view)>& normalizer) {
+  OriginalMap m;
+  bool identity = true;
+  uint32_t total = 0;
+  for (const auto& seg : mygram::utils::SegmentOriginalText(original_text)) {  // (:329-336)
+    const std::string piece = normalizer(original_text.substr(seg.byte_begin, seg.byte_end - seg.byte_begin));
+    const uint32_t n = hl::CountCps(reinterpret_cast<const uint8_t*>(piece.data()), piece.size());
+    for (uint32_t i = 0; i < n; ++i) {
+      identity = identity && seg.cp_begin == m.pairs.size() / 2 && seg.cp_end == seg.cp_begin + 1;
+      m.pairs.push_back(seg.cp_begin);
+      m.pairs.push_back(seg.cp_end);
+    }
+    total = seg.cp_end;
+  }
+  const size_t normalized_cps = hl::CountCps(reinterpret_cast<const uint8_t*>(normalized_text.data()), normalized_text.size());
+  if (m.pairs.size() / 2 != normalized_cps) {  // (:342-344)
+    m.kind = MGX_ORIG_UNMAPPABLE;
+    m.pairs.clear();
+  } else if (identity && total == normalized_cps) {
+    m.kind = MGX_ORIG_IDENTITY;
+    m.pairs.clear();
+  } else {
+    m.kind = MGX_ORIG_MAPPED;
+  }
+  return m;
+}
+
+HighlightResult Highlighter::GenerateOriginal(std::string_view original_text,
+                                              const std::vector<std::string>& normalized_search_terms,
+                                              const std::function<std::string(std::string_view)>& normalizer,
+                                              const HighlightOptions& options) {
+  HighlightResult result;
+  if (original_text.empty() || original_text.size() > 0x7FFFFFFFu) return result;  // (:315-319)
+  if (options.snippet_length < 1 || options.snippet_length > hl::kMaxSnippetLength || options.max_fragments < 1 ||
+      options.max_fragments > hl::kMaxFragments || options.open_tag.size() > hl::kMaxTagBytes ||
+      options.close_tag.size() > hl::kMaxTagBytes)
+    return result;
+  std::string normalized;
+  OriginalMap m;
+  m.kind = MGX_ORIG_UNMAPPABLE;  // (no terms, :323-325: the no-match window; nothing is normalized)
+  if (!normalized_search_terms.empty()) {
+    normalized = normalizer(original_text);  // (:327)
+    if (normalized.size() > 0x7FFFFFFFu) return result;
+    m = BuildOriginalMap(original_text, normalized, normalizer);
+  }
+  const auto* original = reinterpret_cast<const uint8_t*>(original_text.data());
+  const auto* text = reinterpret_cast<const uint8_t*>(normalized.data());
+  const uint32_t on = static_cast<uint32_t>(original_text.size()), n = static_cast<uint32_t>(normalized.size());
+  const std::vector<hl::Term> tv = HighlightScanTerms(normalized, normalized_search_terms);
+  std::vector<uint32_t> scratch(tv.size() + 1);
+  std::vector<hl::Window> win(options.max_fragments);
+  const size_t span_cap = std::min<size_t>(static_cast<size_t>(options.max_fragments) * options.snippet_length, n);
+  std::vector<hl::Span> spans(span_cap + 1);
+  const hl::Header h = hl::GenerateOriginalRecord(
+      original, on, text, n, m.kind, reinterpret_cast<const hl::MapPair*>(m.pairs.data()),
+      static_cast<uint32_t>(m.pairs.size() / 2), tv.data(), static_cast<uint32_t>(tv.size()), options.snippet_length,
+      options.max_fragments, win.data(), spans.data(), static_cast<uint32_t>(span_cap), scratch.data());
+  const auto* ot = reinterpret_cast<const uint8_t*>(options.open_tag.data());
+  const auto* ct = reinterpret_cast<const uint8_t*>(options.close_tag.data());
+  const size_t len = hl::Render(h, win.data(), spans.data(), original, true, ot, options.open_tag.size(), ct,
+                                options.close_tag.size(), nullptr, 0);
+  result.snippet.resize(len);
+  hl::Render(h, win.data(), spans.data(), original, true, ot, options.open_tag.size(), ct, options.close_tag.size(),
              reinterpret_cast<uint8_t*>(result.snippet.data()), len);
   return result;
 }
@@ -2752,6 +2936,14 @@ void CollectScoringLeaves(const query::QueryNode& node, bool under_not, std::vec
     if (c) CollectScoringLeaves(*c, under_not || node.type == query::NodeType::NOT, out);
 }
 
+// The reference's all_search_terms of a query through BuildHighlightTerms.
+std::vector<std::string> HighlightTermsOf(const BatchQuery& q, const index::Index& index) {
+  std::vector<std::string> all;
+  if (q.ast) CollectScoringLeaves(*q.ast, false, &all);
+  all.insert(all.end(), q.terms.begin(), q.terms.end());
+  return BuildHighlightTerms(all, &index);
+}
+
 // After prepare / reset and before the execute. `delta`: the table's delta index (its texts can be the longest).
 Error AttachHighlight(const index::Index& index, const index::Index* delta, const std::vector<BatchQuery>& queries,
                     const std::vector<PlannedQuery>& plans, mgx_batch* batch, HighlightRequests* h) {
@@ -2769,10 +2961,7 @@ Error AttachHighlight(const index::Index& index, const index::Index* delta, cons
     const BatchQuery& q = queries[qi];
     const size_t at = k++;
     if (!q.highlight) continue;
-    std::vector<std::string> all;
-    if (q.ast) CollectScoringLeaves(*q.ast, false, &all);
-    all.insert(all.end(), q.terms.begin(), q.terms.end());
-    h->terms[at] = BuildHighlightTerms(all, &index);
+    h->terms[at] = HighlightTermsOf(q, index);
     h->ptrs[at].clear();
     h->lens[at].clear();
     for (const std::string& t : h->terms[at]) {
@@ -2789,10 +2978,14 @@ Error AttachHighlight(const index::Index& index, const index::Index* delta, cons
     if (q.highlight->open_tag.size() > 256 || q.highlight->close_tag.size() > 256)  // query_parser.h:276
       return MakeError(ErrorCode::kOutOfRange, "highlight: a tag is at most 256 bytes");
   }
-  uint32_t longest = 0, dl = 0;
+  uint32_t longest = 0, dl = 0;  // over both texts of both indexes
   (void)mgx_index_max_text_bytes(index.impl()->dev, &longest);
+  (void)mgx_index_max_original_text_bytes(index.impl()->dev, &dl);
+  longest = std::max(longest, dl);
   if (delta != nullptr && delta->impl()->dev != nullptr) {
     (void)mgx_index_max_text_bytes(delta->impl()->dev, &dl);
+    longest = std::max(longest, dl);
+    (void)mgx_index_max_original_text_bytes(delta->impl()->dev, &dl);
     longest = std::max(longest, dl);
   }
   int rc = mgx_batch_set_highlight(batch, h->reqs.data(), static_cast<uint32_t>(h->reqs.size()), longest);
@@ -2802,9 +2995,18 @@ Error AttachHighlight(const index::Index& index, const index::Index* delta, cons
 }
 
 // After mgx_batch_fetch: the snippets of the highlighted queries' pages (the host adds tags and "...").
-int CollectSnippets(const std::vector<BatchQuery>& queries, const std::vector<PlannedQuery>& plans, mgx_batch* batch,
-                    const mgx_result_view& v, std::vector<BatchResult>* out) {
+// A document whose original is not valid UTF-8 is on the device without it: its entries are rendered here, from the
+// table's own copy, as the reference renders them (Highlighter::GenerateOriginal).
+int CollectSnippets(const index::Index& index, const std::vector<BatchQuery>& queries, const std::vector<PlannedQuery>& plans,
+                    mgx_batch* batch, const mgx_result_view& v, std::vector<BatchResult>* out) {
   if (!AnyHighlight(queries) || batch == nullptr || v.queries == nullptr) return MGX_OK;
+  std::map<DocId, std::string> on_host;
+  {
+    index::Index::Impl* im = index.impl();
+    std::lock_guard<std::mutex> lock(im->mu);
+    if (!im->invalid_originals.empty())  // (the common case: nothing is copied)
+      for (DocId d : im->invalid_originals) on_host.emplace(d, im->originals[d]);
+  }
   mgx_highlight_view hv{};
   int rc = mgx_batch_fetch_highlight(batch, &hv);
   if (rc != MGX_OK) return rc;
@@ -2827,6 +3029,12 @@ int CollectSnippets(const std::vector<BatchQuery>& queries, const std::vector<Pl
                                 reinterpret_cast<uint8_t*>(sn[j].data()), cap, &len);
       if (rc != MGX_OK) return rc;
       sn[j].resize(std::min(len, cap));
+      if (!on_host.empty()) {
+        const auto it = on_host.find(v.docs[r.docs_begin + j]);
+        if (it != on_host.end())
+          sn[j] = query::Highlighter::GenerateOriginal(it->second, HighlightTermsOf(queries[qi], index),
+                                                       [&](std::string_view t) { return index.NormalizeText(t); }, o).snippet;
+      }
     }
   }
   return MGX_OK;
@@ -3116,7 +3324,7 @@ Expected<std::vector<BatchResult>, Error> ExecuteBatch(const index::Index& index
     if (rc == MGX_OK) rc = mgx_batch_fetch(dbatch, &dv);
     if (rc != MGX_OK) return MakeUnexpected(MakeError(static_cast<ErrorCode>(rc), mgx_last_error()));
     Collect(plans, v, &out, &dv);
-    rc = CollectSnippets(queries, plans, batch, v, &out);
+    rc = CollectSnippets(index, queries, plans, batch, v, &out);
     if (rc != MGX_OK) return MakeUnexpected(MakeError(static_cast<ErrorCode>(rc), mgx_last_error()));
     const Error fe = CollectFacets(queries, plans, &dplans, batch, dbatch, &out);
     if (fe.code() != ErrorCode::kSuccess) return MakeUnexpected(fe);
@@ -3127,7 +3335,7 @@ Expected<std::vector<BatchResult>, Error> ExecuteBatch(const index::Index& index
   rc = mgx_batch_fetch(batch, &v);
   if (rc != MGX_OK) return MakeUnexpected(MakeError(static_cast<ErrorCode>(rc), mgx_last_error()));
   Collect(plans, v, &out);
-  rc = CollectSnippets(queries, plans, batch, v, &out);
+  rc = CollectSnippets(index, queries, plans, batch, v, &out);
   if (rc != MGX_OK) return MakeUnexpected(MakeError(static_cast<ErrorCode>(rc), mgx_last_error()));
   const Error fe = CollectFacets(queries, plans, nullptr, batch, nullptr, &out);
   if (fe.code() != ErrorCode::kSuccess) return MakeUnexpected(fe);
@@ -3636,7 +3844,7 @@ Error BatchExecutor::WaitInto(uint64_t ticket, std::vector<BatchResult>* results
   }
   Collect(s->plans, v, &out, s->delta ? &dv : nullptr);
   if (!s->mq.empty()) {
-    const int rc = CollectSnippets(s->queries, s->plans, s->batch, v, &out);
+    const int rc = CollectSnippets(impl_->index, s->queries, s->plans, s->batch, v, &out);
     if (rc != MGX_OK) {
       const Error e = MakeError(static_cast<ErrorCode>(rc), mgx_last_error());
       lock.lock();

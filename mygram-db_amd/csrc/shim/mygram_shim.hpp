@@ -25,6 +25,7 @@
 
 #include <chrono>
 #include <cstdint>
+#include <functional>
 #include <memory>
 #include <optional>
 #include <string>
@@ -98,6 +99,16 @@ class Expected {
 // Unicode lower-casing; without ICU: ASCII lower-casing only (the reference's own non-ICU branch, :371-377).
 [[nodiscard]] std::string NormalizeText(std::string_view text, bool nfkc, std::string_view width, bool lower);
 [[nodiscard]] bool NormalizeTextUsesIcu();  // which of the two branches this build runs
+[[nodiscard]] bool IsValidUtf8(std::string_view text);  // string_utils.cpp:543-555
+// The cut of an original text that GenerateOriginal maps through, equal in behaviour to the reference's
+// SegmentOriginalText (src/query/highlighter.cpp:31-75): grapheme clusters (ICU character breaks, root locale) when the
+// build has ICU and the text is well-formed, else one segment per character. Each segment is a byte range and a
+// code-point range of the text; the segments are in text order and cover it.
+struct OriginalSegment {
+  size_t byte_begin = 0, byte_end = 0;
+  uint32_t cp_begin = 0, cp_end = 0;
+};
+[[nodiscard]] std::vector<OriginalSegment> SegmentOriginalText(std::string_view text);
 [[nodiscard]] uint64_t GetTextNormalizationFailureCount();
 void ResetTextNormalizationFailureCountForTesting();
 
@@ -149,6 +160,7 @@ class Index {
     DocId doc_id;
     std::string text;  // normalized
     std::optional<std::string> primary_key = std::nullopt;  // DocumentStore's primary key of the document, if it has one
+    std::optional<std::string> original_text = std::nullopt;  // the text as the user wrote it, if the store holds it
   };
 
   // Recorded on the host until the first search. Returns whether the text yields any n-gram.
@@ -258,6 +270,18 @@ class Index {
   // documents: the main index, a delta, a compacted main index. A document keeps its key through UpdateDocument and
   // UpdateFilters (it moves to the delta with it); RemoveDocument drops it; FromDump takes the dump's keys.
   bool AddDocument(DocId doc_id, std::string_view text, const storage::FilterMap& filters, std::string_view primary_key);
+  // Original texts (the reference's DocumentStore keeps them beside the normalized ones; HIGHLIGHT then answers with what
+  // the user wrote: SearchHandler::GenerateHighlightSnippets, search_handler.cpp:289-301). They stay on the host for the
+  // table's lifetime, like primary keys, and go to the device, with the normalized-to-original map of every document
+  // (BuildOriginalMap with this index's NormalizeText), with each index built from the table's documents: the main index,
+  // the delta, a compacted main index. UpdateDocument without an original drops the document's (the old one no longer
+  // belongs to the new text), UpdateFilters keeps it, RemoveDocument drops it, Compact() keeps it. An original that is not
+  // valid UTF-8 goes to the device as "none"; its page entries are rendered on the host (Highlighter::GenerateOriginal)
+  // after the fetch. `primary_key`: nullopt = the document has none.
+  bool AddDocument(DocId doc_id, std::string_view text, const storage::FilterMap& filters,
+                   std::optional<std::string_view> primary_key, std::string_view original_text);
+  void UpdateDocument(DocId doc_id, std::string_view old_text, std::string_view new_text,
+                      const storage::FilterMap& filters, std::string_view original_text);
   // The name of the table's primary-key column (TableConfig::primary_key): BatchQuery::sort_column equal to it, ASCII
   // case-insensitively, sorts by the primary key, before any filter column of that name (result_sorter.cpp:239, :516).
   // Table configuration: set it before the first query (the planner reads it without the index lock).
@@ -389,10 +413,24 @@ struct HighlightResult {  // src/query/highlighter.h:30-32
   std::string snippet;
 };
 // query::Highlighter (src/query/highlighter.h; impl highlighter.cpp:252-309) over a NORMALIZED text, on the host: the
-// host build of the source the device's highlight_kernel compiles (csrc/mgx_highlight.hpp). GenerateOriginal is not
-// provided: the project holds normalized texts only. Options outside the parser's ranges give an empty snippet.
+// host build of the source the device's highlight kernels compile (csrc/mgx_highlight.hpp). Options outside the parser's
+// ranges give an empty snippet. GenerateOriginal (:311-356) highlights the text the user wrote: the matches are found in
+// normalizer(original) and mapped back through the segments of SegmentOriginalText, each normalized on its own.
+// BuildOriginalMap is that map as mgx_index_attach_original_text takes it for one document: the MGX_ORIG_* kind
+// (IDENTITY when pair i is (i, i + 1) throughout and the original has as many code points; UNMAPPABLE when the pieces'
+// code points differ in number from the normalized text's, :342-344) and, for MAPPED, the flat (start, end) pairs.
+struct OriginalMap {
+  uint32_t kind = 0;
+  std::vector<uint32_t> pairs;
+};
+OriginalMap BuildOriginalMap(std::string_view original_text, std::string_view normalized_text,
+                             const std::function<std::string(std::string_view)>& normalizer);
 class Highlighter {
  public:
+  static HighlightResult GenerateOriginal(std::string_view original_text,
+                                          const std::vector<std::string>& normalized_search_terms,
+                                          const std::function<std::string(std::string_view)>& normalizer,
+                                          const HighlightOptions& options);
   static HighlightResult Generate(std::string_view normalized_text, const std::vector<std::string>& search_terms,
                                   const HighlightOptions& options);
   static std::vector<std::pair<uint32_t, uint32_t>> FindMatchPositions(std::string_view normalized_text,

@@ -10,9 +10,11 @@
 
 #include <atomic>
 #include <cstring>
+#include <memory>
 #include <vector>
 
 #ifdef MGX_USE_ICU
+#include <unicode/ubrk.h>
 #include <unicode/uloc.h>
 #include <unicode/unorm2.h>
 #include <unicode/ustring.h>
@@ -20,6 +22,73 @@
 #endif
 
 namespace mygram::utils {
+
+// The cut of an original text GenerateOriginal maps through (behaviour of src/query/highlighter.cpp:31-75): grapheme
+// clusters — ICU's character breaks in the root locale — when the build has ICU and the text is well-formed UTF-8, else
+// one segment per character with an ill-formed byte as a character of its own. The text is decoded once with ParseUtf8
+// into UTF-16 units for the break iterator (ICU's C API, as the rest of this file); the break offsets are then walked
+// over the UTF-8 itself, counting bytes and code points, so no cluster is ever converted back.
+std::vector<OriginalSegment> SegmentOriginalText(std::string_view text) {
+  const auto* bytes = reinterpret_cast<const uint8_t*>(text.data());
+  const size_t n = text.size();
+  std::vector<OriginalSegment> cut;
+#ifdef MGX_USE_ICU
+  std::vector<UChar> units;
+  units.reserve(n);
+  bool well_formed = n <= 0x3FFFFFFFu;
+  for (size_t at = 0; at < n && well_formed;) {
+    uint32_t c = 0;
+    const int k = mgx::text::ParseUtf8(bytes + at, n - at, &c);
+    if (k <= 0) {
+      well_formed = false;
+      break;
+    }
+    if (c < 0x10000u) {
+      units.push_back(static_cast<UChar>(c));
+    } else {
+      units.push_back(static_cast<UChar>(0xD7C0u + (c >> 10)));
+      units.push_back(static_cast<UChar>(0xDC00u + (c & 0x3FFu)));
+    }
+    at += static_cast<size_t>(k);
+  }
+  if (well_formed && !units.empty()) {
+    UErrorCode st = U_ZERO_ERROR;
+    UBreakIterator* bi = ubrk_open(UBRK_CHARACTER, "", units.data(), static_cast<int32_t>(units.size()), &st);
+    if (U_SUCCESS(st) && bi != nullptr) {
+      size_t byte_at = 0;
+      uint32_t cp_at = 0;
+      int32_t unit_at = ubrk_first(bi);
+      for (int32_t stop = ubrk_next(bi); stop != UBRK_DONE; stop = ubrk_next(bi)) {
+        OriginalSegment seg{byte_at, byte_at, cp_at, cp_at};
+        while (unit_at < stop && seg.byte_end < n) {  // the code points of this cluster
+          uint32_t c = 0;
+          const int k = mgx::text::ParseUtf8(bytes + seg.byte_end, n - seg.byte_end, &c);
+          seg.byte_end += static_cast<size_t>(k);
+          seg.cp_end += 1;
+          unit_at += c < 0x10000u ? 1 : 2;
+        }
+        cut.push_back(seg);
+        byte_at = seg.byte_end;
+        cp_at = seg.cp_end;
+      }
+      ubrk_close(bi);
+      if (byte_at == n) return cut;  // (the clusters cover the text)
+      cut.clear();
+    } else if (bi != nullptr) {
+      ubrk_close(bi);
+    }
+  }
+#endif
+  uint32_t index = 0;
+  for (size_t at = 0; at < n; ++index) {
+    uint32_t c = 0;
+    const int k = mgx::text::ParseUtf8(bytes + at, n - at, &c);
+    const size_t len = k > 0 ? static_cast<size_t>(k) : 1;
+    cut.push_back(OriginalSegment{at, at + len, index, index + 1});
+    at += len;
+  }
+  return cut;
+}
 
 namespace {
 
@@ -114,6 +183,8 @@ bool IcuNormalize(std::string_view text, bool nfkc, std::string_view width, bool
 #endif
 
 }  // namespace
+
+bool IsValidUtf8(std::string_view text) { return ValidUtf8(text); }
 
 bool NormalizeTextUsesIcu() {
 #ifdef MGX_USE_ICU

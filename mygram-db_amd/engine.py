@@ -275,6 +275,31 @@ class DeviceIndex:
         """Normalized doc text into HBM (text-level BM25 terms: tf/df by text scan)."""
         check(load().mgx_index_attach_text(self._h, corpus.text_bytes.ctypes.data, corpus.text_off.ctypes.data))
 
+    def attach_original_text(self, originals, kinds, maps=None):
+        """mgx_index_attach_original_text, after attach_text: the documents' texts as the user wrote them, by doc slot.
+        originals[i]: bytes / str (ignored for kind 0); kinds[i]: _capi.ORIG_*; maps[i]: the (cp_start, cp_end) pairs of
+        an ORIG_MAPPED document, one per code point of its normalized text (None otherwise). HIGHLIGHT then builds a
+        page entry's snippet from the original of a document that has one."""
+        enc = [b"" if o is None else (o.encode("utf-8") if isinstance(o, str) else bytes(o)) for o in originals]
+        blob = np.frombuffer(b"".join(enc) + b"\0", dtype=np.uint8)
+        off = np.zeros(len(enc) + 1, dtype=np.uint64)
+        np.cumsum([len(o) for o in enc], out=off[1:])
+        kind = np.ascontiguousarray(kinds, dtype=np.uint8)
+        maps = list(maps) if maps is not None else [None] * len(enc)
+        if not len(kind) == len(enc) == len(maps):
+            raise ValueError("originals, kinds and maps are by doc slot: one entry per document each")
+        pairs = [np.asarray(m if m is not None else [], dtype=np.uint32).reshape(-1, 2) for m in maps]
+        map_off = np.zeros(len(enc) + 1, dtype=np.uint64)
+        np.cumsum([len(m) for m in pairs], out=map_off[1:])
+        flat = np.ascontiguousarray(np.concatenate(pairs + [np.zeros((1, 2), np.uint32)]))
+        check(load().mgx_index_attach_original_text(self._h, blob.ctypes.data, off.ctypes.data, kind.ctypes.data,
+                                                    flat.ctypes.data, map_off.ctypes.data))
+
+    def max_original_text_bytes(self):
+        n = C.c_uint32()
+        check(load().mgx_index_max_original_text_bytes(self._h, C.byref(n)))
+        return int(n.value)
+
     def add_filter_bitmap(self, docids):
         a = np.ascontiguousarray(docids, dtype=np.uint32)
         out = C.c_uint32()
@@ -770,6 +795,11 @@ class Index:
             po = np.ctypeslib.as_array(C.cast(pko, C.POINTER(C.c_uint64)), shape=(n + 1,)).copy()
             pb = np.ctypeslib.as_array(C.cast(pkb, C.POINTER(C.c_uint8)), shape=(int(po[-1]) + 1,)).tobytes()
             self.dump_primary_keys = [pb[int(po[k]): int(po[k + 1])] if self.exists[k] else None for k in range(n)]
+            check(L.mgx_dump_original_texts_get(h, C.byref(pkb), C.byref(pko)))
+            oo = np.ctypeslib.as_array(C.cast(pko, C.POINTER(C.c_uint64)), shape=(n + 1,)).copy()
+            ob = np.ctypeslib.as_array(C.cast(pkb, C.POINTER(C.c_uint8)), shape=(int(oo[-1]) + 1,)).tobytes()
+            # the store's original texts (None: it holds none for the slot); attach_original_text takes them with their maps
+            self.dump_original_texts = [ob[int(oo[k]): int(oo[k + 1])] if oo[k + 1] > oo[k] else None for k in range(n)]
             ch = C.c_void_p()
             check(L.mgx_dump_take_columns(h, C.byref(ch)))
             cols = Columns.__new__(Columns)
@@ -808,6 +838,12 @@ class Index:
         if not self._text_attached:
             self.device_index.attach_text(self.corpus)
             self._text_attached = True
+
+    def attach_original_text(self, originals, kinds, maps=None):
+        """The documents' original texts (DeviceIndex.attach_original_text): SearchResult.snippets then come from the
+        original of every page entry whose document has one, as Highlighter::GenerateOriginal builds them."""
+        self.ensure_text()
+        self.device_index.attach_original_text(originals, kinds, maps)
 
     def _ids(self, terms):
         """gram strings -> (ids of known grams, saw_unknown)."""
