@@ -604,6 +604,89 @@ typedef struct mgx_facet_view {
  * next execute, reset or destroy. */
 int mgx_batch_fetch_facets(mgx_batch* batch, mgx_facet_view* out);
 
+/* ---- Page documents (what turns a page into a response: DocumentStore::GetPrimaryKeysBatch behind the TCP handler's
+ * "OK RESULTS <total> <pk> ...", response_formatter.cpp:280-332, and DocumentStore::GetDocumentsBatch behind the HTTP
+ * handler's {primary_key, filters} objects, http_server.cpp:1396-1424) ----
+ * mgx_index_attach_primary_key_bytes keeps the raw key bytes resident by local doc slot: key i is
+ * bytes[off[i] .. off[i + 1]), off has n_docs + 1 ascending entries, has_key (n_docs bytes, may be NULL: every document
+ * has a key) marks the documents that have one. The host copies are not kept. It is independent of
+ * mgx_index_set_primary_keys (which keeps the keys' SORT form only: "007" and "7" are one value there); an index that
+ * never calls it uses no more memory. Calling it again replaces the bytes. mgx_index_max_primary_key_bytes: the longest
+ * attached key (0 without keys).
+ * mgx_batch_set_documents attaches the requests to a prepared or reset batch, BEFORE its first execute and once;
+ * requests[i] belongs to query i (n_queries = the batch's); mgx_batch_reset drops them. A requesting query (enabled != 0)
+ * may have any sort, forward or reverse, and any offset, with 0 < limit <= 1024. column_ids are ids of
+ * mgx_index_add_filter_column, repeats allowed, or MGX_DOC_NO_COLUMN: a column this index does not hold, NULL for every
+ * document; n_columns 0: keys only. max_key_bytes sizes the records' key room: 0 = the longest key of the batch's own
+ * index; a table with a delta passes the larger of the two indexes'. One more kernel (document_gather_kernel) runs behind
+ * the kernel that finalises each page — in the execute for the score and doc-page groups, in mgx_batch_merge_local for
+ * those groups of a table with a delta, and where mgx_batch_fetch cuts the pages of the bitmap group (deep SORT _score,
+ * column and key sorts) — and adds no host synchronisation. A batch without a request allocates, launches and copies
+ * nothing. The records' device memory and pinned block are kept across mgx_batch_reset and only grow.
+ * mgx_batch_defer_documents(batch, 1): the execute skips the kernel and mgx_batch_merge_local runs it over the merged
+ * page (the primary batch of a table with a delta; the delta's batch carries a request of the same shape, whose column
+ * ids are the delta index's: same n_columns, same order).
+ * Refused, each message naming the query: null arguments, a wrong n_queries, a second call, a call after the first
+ * execute, a request on a faceted query, an index without attached key bytes, mgx_batch_fetch_documents before
+ * mgx_batch_fetch: MGX_ERR_INVALID_ARGUMENT; limit 0 or above 1024, an unknown column id, more than MGX_DOC_MAX_COLUMNS
+ * columns, a batch whose records could exceed MGX_DOC_ARENA_CAP bytes (the message names what to lower):
+ * MGX_ERR_OUT_OF_RANGE. With MGX_ERR_NOT_IMPLEMENTED, before anything is touched: every sharded entry point
+ * (mgx_batch_export_topk / _export_buffer, mgx_batch_merge_shards, mgx_batch_exchange, mgx_batch_execute_gather /
+ * _sharded), because the rows live on other ranks; mgx_batch_merge_local over anything but one main index and one
+ * delta. */
+#define MGX_DOC_MAX_COLUMNS 32u
+#define MGX_DOC_MAX_LIMIT 1024u
+#define MGX_DOC_ARENA_CAP (256ull << 20)
+#define MGX_DOC_NO_COLUMN 0xFFFFFFFFu
+#define MGX_DOC_FOUND 1u   /* the doc id resolved to a slot of one of the batch's indexes */
+#define MGX_DOC_HAS_KEY 2u
+#define MGX_DOC_MAPPED 4u  /* the row came from the index that names documents through a doc map (the delta): a string
+                            * rank in `values` belongs to that index's dictionary */
+int mgx_index_attach_primary_key_bytes(mgx_index* idx, const uint8_t* bytes, const uint64_t* off, const uint8_t* has_key);
+int mgx_index_max_primary_key_bytes(mgx_index* idx, uint32_t* out);
+typedef struct mgx_document_request {
+  uint32_t enabled;
+  uint32_t n_columns;          /* <= MGX_DOC_MAX_COLUMNS; 0: keys only */
+  const uint32_t* column_ids;  /* n_columns */
+} mgx_document_request;
+int mgx_batch_set_documents(mgx_batch* batch, const mgx_document_request* requests, uint32_t n_queries,
+                            uint32_t max_key_bytes);
+int mgx_batch_defer_documents(mgx_batch* batch, int defer);
+typedef struct mgx_document_entry {
+  uint32_t flags;      /* MGX_DOC_* */
+  uint32_t key_len;
+  uint32_t null_mask;  /* bit c: values[c] is NULL */
+  uint32_t n_columns;
+  const uint8_t* key;      /* key_len bytes */
+  const uint64_t* values;  /* n_columns: the column's stored 8 bytes (int64, uint64, rank or double bits) */
+} mgx_document_entry;
+typedef struct mgx_document_view {
+  uint32_t n_entries;  /* = the docs of the fetched view: entry i belongs to mgx_result_view.docs[i]; all zero for the
+                        * queries without a request and for a doc id that no index of the batch holds */
+  const mgx_document_entry* entries;
+} mgx_document_view;
+/* After mgx_batch_fetch of the same execute: no further wait, no further copy. The view stays valid until the batch's
+ * next execute, reset or destroy. */
+int mgx_batch_fetch_documents(mgx_batch* batch, mgx_document_view* out);
+/* The same rows without a batch (DocumentStore::GetPrimaryKeysBatch / GetDocumentsBatch over a caller's id list,
+ * document_store_retrieval.cpp:37-103): one pass of document_gather_kernel over doc_ids on a leased stand-alone call, like
+ * the single operators; safe from many threads at once. `mapped`: NULL, or the table's delta index (mgx_index_set_doc_map)
+ * on the same device, searched first; mapped_column_ids are its ids for the same n_columns columns (MGX_DOC_NO_COLUMN
+ * on either side: NULL). *records_out (malloc: mgx_free) holds n_docs records of *stride_out bytes, record i for
+ * doc_ids[i]: [mgx_document_record_header | n_columns x uint64_t values | key bytes], all zero for an id neither index
+ * holds. max_key_bytes 0: the longest key of the indexes given. Refused: null arguments, an index without attached key
+ * bytes, a `mapped` that is no delta: MGX_ERR_INVALID_ARGUMENT; an unknown column id, more than MGX_DOC_MAX_COLUMNS
+ * columns, records above MGX_DOC_ARENA_CAP bytes, a key longer than max_key_bytes: MGX_ERR_OUT_OF_RANGE. */
+typedef struct mgx_document_record_header {
+  uint32_t flags;      /* MGX_DOC_* */
+  uint32_t key_len;
+  uint32_t null_mask;
+  uint32_t n_columns;
+} mgx_document_record_header;
+int mgx_documents_gather(mgx_index* idx, mgx_index* mapped, const uint32_t* doc_ids, uint64_t n_docs, uint32_t n_columns,
+                         const uint32_t* column_ids, const uint32_t* mapped_column_ids, uint32_t max_key_bytes,
+                         uint8_t** records_out, uint64_t* stride_out);
+
 /* Multi-GPU exchange (one rank per doc-range shard). The batch must be all MGX_SORT_SCORE, or all docid-ordered
  * pages (MGX_SORT_DOCID with 0 < limit <= 16384): a page is a best-first list under the key "doc id" (or its
  * complement for ascending order), so the same two calls serve both.

@@ -126,6 +126,23 @@ int mgxs_search_by_primary_key(mgxs_table* table, uint32_t n_terms, const char* 
                                const char* const* not_terms, uint32_t n_cond, const char* const* cond_columns,
                                const uint32_t* cond_ops, const char* const* cond_values, int descending, uint32_t limit,
                                uint32_t offset, uint64_t* total, uint32_t* n_docs, uint32_t* docs);
+/* mgxs_search with the page's documents (BatchQuery::return_documents: what ResponseFormatter's GetPrimaryKeysBatch and the
+ * HTTP handler's GetDocumentsBatch read per request, response_formatter.cpp:294, http_server.cpp:1396), gathered on the
+ * device behind the page. 0 < limit <= 1024. sort_column: NULL or a filter column's name (mgxs_search_sorted);
+ * sort_primary_key: mgxs_search_by_primary_key's order. `columns`: n_columns names of filter columns, at most 32 (0: keys
+ * only). Per page entry k: found[k] (0: the table does not hold the id), has_key[k] (a non-empty key), the key's bytes
+ * keys[key_off[k] .. key_off[k + 1]), values[k * n_columns + c] = column c's stored 8 bytes (integers widened, bool 0 / 1,
+ * time as seconds, double bits; a string column: the value's rank among the column's distinct strings in the index the
+ * row came from) and bit c of null_masks[k] set where the value is NULL. docs, found, has_key, null_masks have room for
+ * `limit` entries, key_off for limit + 1, values for limit * n_columns; MGX_ERR_OUT_OF_RANGE when the keys exceed
+ * keys_cap. An unknown column fails the call with the host layer's kIndexNotFound (4000). */
+int mgxs_search_documents(mgxs_table* table, uint32_t n_terms, const char* const* terms, uint32_t n_not,
+                          const char* const* not_terms, uint32_t n_cond, const char* const* cond_columns, const uint32_t* cond_ops,
+                          const char* const* cond_values, int sort_by_score, int descending, uint32_t limit, uint32_t offset,
+                          const char* sort_column /* may be NULL */, int sort_primary_key, uint32_t n_columns,
+                          const char* const* columns, uint64_t* total, uint32_t* n_docs, uint32_t* docs,
+                          double* scores /* may be NULL */, uint8_t* found, uint8_t* has_key, char* keys, size_t keys_cap,
+                          uint32_t* key_off, uint64_t* values, uint32_t* null_masks);
 /* mgxs_search with HIGHLIGHT (BatchQuery::highlight: GenerateHighlightSnippets on the page, search_handler.cpp:473-482, on the
  * device): the page's snippets, packed into `snippets`; doc k's snippet is snippets[snippet_off[k] .. snippet_off[k+1]).
  * snippet_off has room for limit + 1 entries. Tags NUL-terminated, at most 256 bytes; snippet_length 1..10000,

@@ -39,6 +39,8 @@ EXPORTS = [
     "mgxt_highlight_filter_ranges",
     "mgx_batch_set_facets", "mgx_batch_fetch_facets",
     "mgx_index_set_primary_keys", "mgx_index_set_primary_key_shortcut", "mgx_dump_primary_keys_get", "mgx_dump_original_texts_get",
+    "mgx_index_attach_primary_key_bytes", "mgx_index_max_primary_key_bytes", "mgx_batch_set_documents",
+    "mgx_batch_defer_documents", "mgx_batch_fetch_documents", "mgx_documents_gather",
 ]
 
 
@@ -157,6 +159,28 @@ class FacetView(C.Structure):
     _fields_ = [("n_entries", C.c_uint32), ("entries", C.POINTER(FacetEntry))]
 
 
+class DocumentRequest(C.Structure):
+    _fields_ = [("enabled", C.c_uint32), ("n_columns", C.c_uint32), ("column_ids", C.POINTER(C.c_uint32))]
+
+
+class DocumentEntry(C.Structure):
+    _fields_ = [("flags", C.c_uint32), ("key_len", C.c_uint32), ("null_mask", C.c_uint32), ("n_columns", C.c_uint32),
+                ("key", C.POINTER(C.c_uint8)), ("values", C.POINTER(C.c_uint64))]
+
+
+class DocumentRecordHeader(C.Structure):
+    _fields_ = [("flags", C.c_uint32), ("key_len", C.c_uint32), ("null_mask", C.c_uint32), ("n_columns", C.c_uint32)]
+
+
+class DocumentView(C.Structure):
+    _fields_ = [("n_entries", C.c_uint32), ("entries", C.POINTER(DocumentEntry))]
+
+
+DOC_MAX_COLUMNS = 32
+DOC_MAX_LIMIT = 1024
+DOC_ARENA_CAP = 256 << 20
+DOC_NO_COLUMN = 0xFFFFFFFF
+DOC_FOUND, DOC_HAS_KEY, DOC_MAPPED = 1, 2, 4
 FACET_MAX_COLUMNS = 8
 FACET_ARENA_CAP = 256 << 20
 FACET_LDS_BINS = 8192
@@ -272,6 +296,12 @@ def load():
     L.mgx_dump_primary_keys_get.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
     L.mgx_dump_original_texts_get.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
     L.mgx_index_set_doc_map.argtypes = [vp, vp, u64]
+    L.mgx_index_attach_primary_key_bytes.argtypes = [vp, vp, vp, vp]
+    L.mgx_index_max_primary_key_bytes.argtypes = [vp, C.POINTER(u32)]
+    L.mgx_batch_set_documents.argtypes = [vp, C.POINTER(DocumentRequest), u32, u32]
+    L.mgx_batch_defer_documents.argtypes = [vp, i32]
+    L.mgx_batch_fetch_documents.argtypes = [vp, C.POINTER(DocumentView)]
+    L.mgx_documents_gather.argtypes = [vp, vp, vp, u64, u32, vp, vp, u32, C.POINTER(vp), C.POINTER(u64)]
     L.mgx_batch_merge_local.argtypes = [vp, C.POINTER(vp), u32, vp]
     _lib = L
     return L

@@ -11,7 +11,7 @@ LIB_PATH = os.path.join(_HERE, "libmygram_shim.so")
 EXPORTS = ["mgxs_last_error", "mgxs_table_adopt", "mgxs_table_set_global_stats", "mgxs_table_destroy",
            "mgxs_table_set_normalization", "mgxs_table_set_absent_grams", "mgxs_normalize_uses_icu", "mgxs_normalize_text",
            "mgxs_executor_create", "mgxs_executor_create_sharded", "mgxs_executor_destroy", "mgxs_executor_warm",
-           "mgxs_submit", "mgxs_wait", "mgxs_table_from_dump", "mgxs_table_add_filter_column", "mgxs_search", "mgxs_search_sorted", "mgxs_search_by_primary_key", "mgxs_facet", "mgxs_facet_columns", "mgxs_search_highlight", "mgxs_highlight_generate",
+           "mgxs_submit", "mgxs_wait", "mgxs_table_from_dump", "mgxs_table_add_filter_column", "mgxs_search", "mgxs_search_sorted", "mgxs_search_by_primary_key", "mgxs_facet", "mgxs_facet_columns", "mgxs_search_highlight", "mgxs_highlight_generate", "mgxs_search_documents",
            "mgxs_table_add_document", "mgxs_table_update_document", "mgxs_table_remove_document", "mgxs_table_mutation_stats", "mgxs_table_compact", "mgxs_table_set_mutation_staleness", "mgxs_table_update_filters",
            "mgxs_batcher_create", "mgxs_batcher_destroy", "mgxs_batcher_search", "mgxs_batcher_stats"]
 _lib = None
@@ -52,6 +52,8 @@ def load():
     L.mgxs_search.argtypes = [vp, u32, vp, u32, vp, u32, vp, vp, vp, i32, i32, u32, u32, C.POINTER(u64), C.POINTER(u32), vp, vp]
     L.mgxs_search_sorted.argtypes = [vp, u32, vp, u32, vp, u32, vp, vp, vp, i32, i32, u32, u32, C.c_char_p, C.POINTER(u64),
                                      C.POINTER(u32), vp, vp]
+    L.mgxs_search_documents.argtypes = [vp, u32, vp, u32, vp, u32, vp, vp, vp, i32, i32, u32, u32, C.c_char_p, i32, u32, vp,
+                                        C.POINTER(u64), C.POINTER(u32), vp, vp, vp, vp, vp, C.c_size_t, vp, vp, vp]
     L.mgxs_search_by_primary_key.argtypes = [vp, u32, vp, u32, vp, u32, vp, vp, vp, i32, u32, u32, C.POINTER(u64),
                                              C.POINTER(u32), vp]
     L.mgxs_search_highlight.argtypes = [vp, u32, vp, u32, vp, i32, i32, u32, u32, C.c_char_p, C.c_char_p, u32, u32,
@@ -284,6 +286,37 @@ class Table:
                                          int(descending), limit, offset, sort_column.encode("utf-8"), C.byref(total),
                                          C.byref(n), docs.ctypes.data, None))
         return int(total.value), docs[: n.value].copy()
+
+    def search_documents(self, terms, columns=(), not_terms=(), conditions=(), sort_by_score=False, descending=True, limit=100,
+                         offset=0, sort_column=None, sort_primary_key=False, keys_cap=1 << 20):
+        """mgxs_search_documents: one query with its page's rows -> (total, docs, [None | (key bytes or None, values as
+        np.uint64, null mask)] per doc)."""
+        t, nt = self._strs(terms)
+        x, nx = self._strs(not_terms)
+        cols, ops, vals, nc = self._conds(list(conditions))
+        names, n_names = self._strs(columns)
+        total, n = C.c_uint64(), C.c_uint32()
+        docs = np.zeros(max(limit, 1), np.uint32)
+        found, has_key = np.zeros(max(limit, 1), np.uint8), np.zeros(max(limit, 1), np.uint8)
+        keys = C.create_string_buffer(keys_cap)
+        key_off = np.zeros(limit + 1, np.uint32)
+        values = np.zeros(max(limit * n_names, 1), np.uint64)
+        masks = np.zeros(max(limit, 1), np.uint32)
+        _check(load().mgxs_search_documents(self._h, nt, C.cast(t, C.c_void_p), nx, C.cast(x, C.c_void_p), nc,
+                                            C.cast(cols, C.c_void_p), ops.ctypes.data, C.cast(vals, C.c_void_p),
+                                            int(sort_by_score), int(descending), limit, offset,
+                                            sort_column.encode("utf-8") if sort_column else None, int(sort_primary_key), n_names,
+                                            C.cast(names, C.c_void_p), C.byref(total), C.byref(n), docs.ctypes.data, None,
+                                            found.ctypes.data, has_key.ctypes.data, keys, keys_cap, key_off.ctypes.data,
+                                            values.ctypes.data, masks.ctypes.data))
+        rows = []
+        for k in range(n.value):
+            if not found[k]:
+                rows.append(None)
+                continue
+            key = keys.raw[key_off[k]:key_off[k + 1]] if has_key[k] else None
+            rows.append((key, values[k * n_names:(k + 1) * n_names].copy(), int(masks[k])))
+        return int(total.value), docs[: n.value].copy(), rows
 
     def search_by_primary_key(self, terms, not_terms=(), conditions=(), descending=True, limit=100, offset=0):
         """SORT by primary key ASC|DESC: one query -> (total, docs in rank order)."""

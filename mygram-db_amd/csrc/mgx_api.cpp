@@ -33,6 +33,7 @@
 #include "mgx_colsort.hpp"
 #include "mgx_pkey.hpp"
 #include "mgx_facet.hpp"
+#include "mgx_documents.hpp"
 #include "mgx_host.hpp"
 #include "mgx_internal.hpp"
 #include "mgx_launch.hpp"
@@ -143,8 +144,8 @@ struct Arena {
 struct BatchResources {
   Arena upload{true}, out{false};
   bool uploaded = false;
-  void* h_down[4] = {nullptr, nullptr, nullptr, nullptr};  // pinned result blocks (score group, docid-page group, highlight records, facet counts)
-  size_t h_down_cap[4] = {0, 0, 0, 0};
+  void* h_down[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // pinned result blocks (score group, docid-page group, highlight records, facet counts, document records)
+  size_t h_down_cap[5] = {0, 0, 0, 0, 0};
   hipEvent_t fork_ev = nullptr, join_ev = nullptr;  // fork/join of the side-stream launch
   // A batch object is one pipeline slot: with a NULL stream argument it runs on its own non-blocking stream, and the
   // copy of its (small) result block to pinned memory is part of the execute, fenced by done_ev — so fetching batch i
@@ -407,6 +408,10 @@ struct mgx_index {
   uint32_t pk_kind = mgx::pkey::kKeyNumeric;
   bool pk_any_missing = false;
   DevBuf d_pk_values, d_pk_off, d_pk_bytes;
+  // mgx_index_attach_primary_key_bytes (page documents, mgx_documents.hpp): the raw key bytes by doc slot. Guarded by mu.
+  DevBuf d_pkb_bytes, d_pkb_off, d_pkb_has;
+  bool has_pk_bytes = false;
+  uint32_t max_pk_bytes = 0;  // the longest attached key (sizes the document records)
   std::atomic<bool> pk_monotone{true};  // the keys never decrease with the slot (true without keys: doc ids ascend)
   std::atomic<bool> pk_shortcut{true};  // mgx_index_set_primary_key_shortcut
   std::atomic<bool> has_doc_map{false};  // d_doc_map is set (a delta index: its keys are never in doc-id order of a table)
@@ -1425,6 +1430,44 @@ int mgx_index_set_primary_key_shortcut(mgx_index* idx, int enable) {
   return MGX_OK;
 }
 
+int mgx_index_attach_primary_key_bytes(mgx_index* idx, const uint8_t* bytes, const uint64_t* off, const uint8_t* has_key) {
+  if (!idx || !off) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_index_attach_primary_key_bytes: null argument");
+  const uint64_t n = idx->dev.n_docs;
+  uint64_t longest = 0;
+  for (uint64_t i = 0; i < n; ++i) {
+    if (off[i + 1] < off[i]) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_index_attach_primary_key_bytes: offsets must ascend");
+    if (!has_key || has_key[i]) longest = std::max(longest, off[i + 1] - off[i]);
+  }
+  if (off[n] != off[0] && !bytes) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_index_attach_primary_key_bytes: null key bytes");
+  if (longest > 0x7FFFFF00ull) return mgx::Fail(MGX_ERR_OUT_OF_RANGE, "mgx_index_attach_primary_key_bytes: a key exceeds 2 GiB");
+  try {
+    std::lock_guard<std::mutex> lock(idx->mu);
+    MGX_HIP(hipSetDevice(idx->device));
+    if (idx->has_pk_bytes) MGX_HIP(hipDeviceSynchronize());  // (the replaced bytes may still be read by a batch's kernel)
+    // the offsets are kept relative to the first key's, the bytes from there (one byte of padding: an index whose keys
+    // are all empty still needs an address)
+    std::vector<uint64_t> rel(n + 1);
+    for (uint64_t i = 0; i <= n; ++i) rel[i] = off[i] - off[0];
+    const std::vector<uint8_t> pad(1, 0);
+    MGX_HIP(mgx::Upload(idx->d_pkb_off, rel.data(), rel.size()));
+    MGX_HIP(mgx::Upload(idx->d_pkb_bytes, rel[n] ? bytes + off[0] : pad.data(), std::max<size_t>(1, rel[n])));
+    idx->d_pkb_has.Free();
+    if (has_key) MGX_HIP(mgx::Upload(idx->d_pkb_has, has_key, n));
+    idx->max_pk_bytes = static_cast<uint32_t>(longest);
+    idx->has_pk_bytes = true;
+    return MGX_OK;
+  } catch (const std::exception& e) {
+    return mgx::Fail(MGX_ERR_INTERNAL, std::string("mgx_index_attach_primary_key_bytes: ") + e.what());
+  }
+}
+
+int mgx_index_max_primary_key_bytes(mgx_index* idx, uint32_t* out) {
+  if (!idx || !out) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_index_max_primary_key_bytes: null argument");
+  std::lock_guard<std::mutex> lock(idx->mu);
+  *out = idx->has_pk_bytes ? idx->max_pk_bytes : 0;
+  return MGX_OK;
+}
+
 int mgx_index_invalidate_statistics(mgx_index* idx) {
   if (!idx) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_index_invalidate_statistics: null index");
   MGX_HIP(hipSetDevice(idx->device));
@@ -1583,6 +1626,22 @@ struct mgx_batch {
     bool faceted(uint32_t qi) const { return on() && of_query[qi] >= 0; }
   };
   Facets fc;
+  // Page documents (mgx_batch_set_documents): the plan of mgx_documents.hpp, the requested columns of the batch's own
+  // index, and the records document_gather_kernel fills behind the kernel that finalises each page
+  struct Documents {
+    mgx::documents::Plan plan;
+    std::vector<int32_t> of_query;  // batch query -> index into plan.queries, or -1
+    std::vector<mgx::documents::DevQuery> early;  // the score / doc-page group's queries, in request order
+    std::vector<mgx::documents::DevQuery> late;   // the bitmap group's, built where its pages are cut
+    DevBuf d_early, d_columns, d_late, d_arena;
+    void* h_arena = nullptr;  // pinned (BatchResources)
+    std::vector<uint64_t> fetch_off;  // per plan query: where the last fetch's records begin in h_arena
+    bool defer = false;  // mgx_batch_defer_documents: mgx_batch_merge_local runs the kernel, execute does not
+    std::vector<mgx_document_entry> entries;  // of the last fetch
+    bool on() const { return !plan.queries.empty(); }
+    bool requested(uint32_t qi) const { return on() && of_query[qi] >= 0; }
+  };
+  Documents doc;
   bool fetched = false;  // mgx_batch_fetch assembled h_results for the last execute
   // host results
   std::vector<mgx_query_result> h_results;
@@ -2808,6 +2867,121 @@ static int RunFacets(mgx_batch* b, hipStream_t s) {
   return MGX_OK;
 }
 
+// Page documents: what document_gather_kernel reads of one index. `cols`: the requested columns of that index, resolved by
+// the batch that was prepared on it (device memory once that batch's inputs are uploaded).
+static documents::DevSource DocumentSource(const mgx_index* ix, const mgx_batch* cols, bool with_map) {
+  documents::DevSource src{};
+  if (!ix) return src;
+  src.key_bytes = ix->d_pkb_bytes.as<uint8_t>();
+  src.key_off = ix->d_pkb_off.as<uint64_t>();
+  src.has_key = ix->d_pkb_has.as<uint8_t>();
+  src.doc_map = with_map ? ix->d_doc_map.as<uint32_t>() : nullptr;
+  src.columns = cols->doc.d_columns.as<documents::DevColumn>();
+  src.first_doc_id = ix->dev.first_doc_id;
+  src.n_docs = ix->dev.n_docs;
+  return src;
+}
+
+// A table with a delta: the two batches carry requests of the same shape (each with its own index's column ids), and both
+// indexes hold key bytes.
+static int CheckDocumentSides(const mgx_batch* primary, const mgx_batch* other, const char* entry) {
+  const mgx_batch::Documents& a = primary->doc;
+  const mgx_batch::Documents& o = other->doc;
+  bool same = o.on() && o.plan.queries.size() == a.plan.queries.size() && o.of_query == a.of_query;
+  for (size_t i = 0; same && i < a.plan.queries.size(); ++i)
+    same = a.plan.queries[i].n_columns == o.plan.queries[i].n_columns;
+  if (!same)
+    return Fail(MGX_ERR_INVALID_ARGUMENT, std::string(entry) + ": page documents need a request of the same shape (the same queries, "
+                                          "the same number of columns) on every batch");
+  if (!primary->idx->has_pk_bytes || !other->idx->has_pk_bytes)
+    return Fail(MGX_ERR_INVALID_ARGUMENT, std::string(entry) + ": page documents need mgx_index_attach_primary_key_bytes on every index");
+  return MGX_OK;
+}
+
+// Page documents of the score and doc-page groups: the records of the requesting queries' page entries, behind the
+// kernel that finalised the page, and their copy to pinned memory (the caller records the batch's done event after it).
+// `mapped` / `plain`: as RunHighlight's, each with the batch prepared on it.
+static int RunDocuments(mgx_batch* b, hipStream_t s, bool merged, const mgx_batch* mapped, const mgx_batch* plain) {
+  mgx_batch::Documents& d = b->doc;
+  if (d.early.empty()) return MGX_OK;
+  documents::DevBatch db{};
+  db.queries = d.d_early.as<documents::DevQuery>();
+  db.n_queries = static_cast<uint32_t>(d.early.size());
+  db.n_entries = d.plan.early_entries;
+  db.arena = d.d_arena.as<uint8_t>();
+  db.mapped = DocumentSource(mapped ? mapped->idx : nullptr, mapped, true);
+  db.plain = DocumentSource(plain ? plain->idx : nullptr, plain, false);
+  db.key_cap = d.plan.key_cap;
+  db.merged = merged ? 1u : 0u;
+  MGX_LAUNCH(LaunchDocumentGather(db, s));
+  MGX_HIP(hipMemcpyAsync(d.h_arena, d.d_arena.p, d.plan.early_bytes, hipMemcpyDeviceToHost, s));
+  return MGX_OK;
+}
+
+// Page documents of the bitmap group, where its pages are cut (FetchBitmapPages): the page sizes are known on the host,
+// so the records are packed by them behind the early queries' and one copy brings exactly those. `pdocs`: the group's
+// pages on the device, query i's at page_off[i], page_n[i] entries. The caller's synchronisation covers kernel and copy.
+static int RunLateDocuments(mgx_batch* a, hipStream_t s, const std::vector<uint64_t>& page_off,
+                            const std::vector<uint64_t>& page_n, const uint32_t* pdocs) {
+  mgx_batch::Documents& d = a->doc;
+  mgx_batch* const other = a->merge_other;
+  const mgx_batch* mapped = nullptr;
+  const mgx_batch* plain = a;  // (one index: its own ids)
+  if (other) {
+    mapped = plain = nullptr;
+    for (const mgx_batch* x : {static_cast<const mgx_batch*>(a), static_cast<const mgx_batch*>(other)}) {
+      const mgx_batch*& slot = x->idx->d_doc_map.p ? mapped : plain;
+      if (slot) return Fail(MGX_ERR_NOT_IMPLEMENTED, "mgx_batch_fetch: page documents read one main index and one delta");
+      slot = x;
+    }
+  }
+  if (other) {
+    const int rc = CheckDocumentSides(a, other, "mgx_batch_fetch");
+    if (rc) return rc;
+  }
+  std::vector<documents::DevQuery>& late = d.late;  // (a member: the copy below may read it after this returns)
+  late.clear();
+  uint64_t at = d.plan.early_bytes;
+  uint32_t n_entries = 0;
+  const mgx_batch::Group& g = a->bitmap;
+  for (size_t i = 0; i < g.qids.size(); ++i) {
+    if (!d.requested(g.qids[i])) continue;
+    const size_t pi = static_cast<size_t>(d.of_query[g.qids[i]]);
+    const documents::QueryPlan& qp = d.plan.queries[pi];
+    d.fetch_off[pi] = at;
+    const uint32_t n = static_cast<uint32_t>(std::min<uint64_t>(page_n[i], qp.limit));
+    if (n == 0) continue;
+    documents::DevQuery q{};
+    q.page_docs = pdocs + page_off[i];
+    q.limit = n;
+    q.count = n;
+    q.entry_begin = n_entries;
+    q.n_columns = qp.n_columns;
+    q.col_begin = qp.col_begin;
+    q.rec_off = at;
+    q.rec_stride = qp.rec_stride;
+    at += qp.rec_stride * n;
+    n_entries += n;
+    late.push_back(q);
+  }
+  if (late.empty()) return MGX_OK;
+  if (at > d.plan.arena_bytes) return Fail(MGX_ERR_INTERNAL, "page documents: the records exceed their arena");
+  if (d.d_late.bytes < late.size() * sizeof(documents::DevQuery)) return Fail(MGX_ERR_INTERNAL, "page documents: descriptor room");
+  MGX_HIP(hipMemcpyAsync(d.d_late.p, late.data(), late.size() * sizeof(documents::DevQuery), hipMemcpyHostToDevice, s));
+  documents::DevBatch db{};
+  db.queries = d.d_late.as<documents::DevQuery>();
+  db.n_queries = static_cast<uint32_t>(late.size());
+  db.n_entries = n_entries;
+  db.arena = d.d_arena.as<uint8_t>();
+  db.mapped = DocumentSource(mapped ? mapped->idx : nullptr, mapped, true);
+  db.plain = DocumentSource(plain ? plain->idx : nullptr, plain, false);
+  db.key_cap = d.plan.key_cap;
+  MGX_LAUNCH(LaunchDocumentGather(db, s));
+  const uint64_t e0 = d.plan.early_bytes;
+  MGX_HIP(hipMemcpyAsync(static_cast<char*>(d.h_arena) + e0, d.d_arena.as<char>() + e0, at - e0, hipMemcpyDeviceToHost, s));
+  return MGX_OK;
+}
+
 static int ExecuteImpl(mgx_batch* b, hipStream_t s, const SeedGather* sg = nullptr) {
   mgx_index* idx = b->idx;
   MGX_HIP(hipSetDevice(idx->device));
@@ -2997,6 +3171,10 @@ static int ExecuteImpl(mgx_batch* b, hipStream_t s, const SeedGather* sg = nullp
   }
   if (b->fc.on()) {
     const int rc = RunFacets(b, s);
+    if (rc) return rc;
+  }
+  if (b->doc.on() && !b->doc.defer) {
+    const int rc = RunDocuments(b, s, /*merged=*/false, nullptr, b);  // (a page of one index holds that index's own ids)
     if (rc) return rc;
   }
   {
@@ -3386,6 +3564,10 @@ static int FetchBitmapPages(mgx_batch* a, BitmapPages* m) {
   MGX_LAUNCH(LaunchKeyMerge(reinterpret_cast<const pkey::KeyMergeRun*>(base + o_kruns),
                             reinterpret_cast<const uint64_t*>(base + o_kstart), static_cast<uint32_t>(kruns.size()), kelems,
                             pk[0].side, pk[1].side, keys, dprime, pdocs, pscores, s));
+  if (a->doc.on()) {  // page documents of this group's pages, behind the kernels that cut them
+    const int rc = RunLateDocuments(a, s, m->page_off, m->page_n, pdocs);
+    if (rc) return rc;
+  }
   m->docs.resize(pages);
   if (pages) MGX_HIP(hipMemcpyAsync(m->docs.data(), pdocs, pages * 4, hipMemcpyDeviceToHost, s));
   if (pages && n_keys) {  // (scores: a deep SORT _score page is in the batch)
@@ -3878,6 +4060,178 @@ int mgx_batch_fetch_facets(mgx_batch* batch, mgx_facet_view* out) {
   }
 }
 
+int mgx_batch_set_documents(mgx_batch* batch, const mgx_document_request* requests, uint32_t n_queries,
+                            uint32_t max_key_bytes) {
+  namespace dc = mgx::documents;
+  if (!batch || (n_queries && !requests)) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_batch_set_documents: null argument");
+  if (!batch->res_owned) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_batch_set_documents: not a prepared batch object");
+  if (n_queries != batch->n_queries)
+    return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_batch_set_documents: one request per query of the batch");
+  if (batch->res->uploaded || batch->executed || batch->doc.on())
+    return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_batch_set_documents: call it once, after prepare / reset and before the first execute");
+  try {
+    mgx_index* idx = batch->idx;
+    std::vector<dc::Request> reqs;
+    std::vector<int32_t> of_query(n_queries, -1);
+    std::vector<dc::DevColumn> columns;
+    uint32_t longest = max_key_bytes;
+    {
+      std::lock_guard<std::mutex> lock(idx->mu);  // (a column is immutable once added; the vector that holds them may grow)
+      for (uint32_t qi = 0; qi < n_queries; ++qi) {
+        const mgx_document_request& r = requests[qi];
+        if (!r.enabled) continue;
+        const std::string who = "mgx_batch_set_documents: query " + std::to_string(qi) + ": ";
+        if (!idx->has_pk_bytes)
+          return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, who + "page documents without mgx_index_attach_primary_key_bytes");
+        if (r.n_columns > MGX_DOC_MAX_COLUMNS)
+          return mgx::Fail(MGX_ERR_OUT_OF_RANGE, who + "more than MGX_DOC_MAX_COLUMNS (32) columns");
+        if (r.n_columns && !r.column_ids) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, who + "null column list");
+        if (batch->fc.faceted(qi))
+          return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, who + "a faceted query returns counts, not a page: no documents");
+        const mgx::QuerySpec& sp = batch->specs[qi];
+        if (sp.limit == 0 || sp.limit > MGX_DOC_MAX_LIMIT)
+          return mgx::Fail(MGX_ERR_OUT_OF_RANGE, who + "page documents need a page of 1..1024 entries (limit)");
+        for (uint32_t c = 0; c < r.n_columns; ++c) {
+          const uint32_t id = r.column_ids[c];
+          dc::DevColumn col{nullptr, nullptr};
+          if (id != MGX_DOC_NO_COLUMN) {
+            if (id >= idx->filter_columns.size()) return mgx::Fail(MGX_ERR_OUT_OF_RANGE, who + "unknown filter column");
+            const mgx_index::FilterColumn& fc = *idx->filter_columns[id];
+            col.values = fc.d_values.as<uint64_t>();
+            col.is_null = fc.d_null.as<uint8_t>();
+          }
+          columns.push_back(col);
+        }
+        dc::Request rq;
+        rq.query = qi;
+        rq.limit = sp.limit;
+        rq.n_columns = r.n_columns;
+        rq.late = (sp.mode == mgx::kModeScore || sp.mode == mgx::kModeDocPage) ? 0u : 1u;
+        of_query[qi] = static_cast<int32_t>(reqs.size());
+        reqs.push_back(rq);
+      }
+      if (longest == 0) longest = idx->max_pk_bytes;
+    }
+    if (reqs.empty()) return MGX_OK;  // nothing is requested: the batch allocates, launches and copies nothing new
+    dc::Plan plan;
+    size_t bad = 0;
+    switch (dc::Build(reqs, longest, &plan, &bad)) {
+      case dc::kOk:
+        break;
+      case dc::kTooManyColumns:
+        return mgx::Fail(MGX_ERR_OUT_OF_RANGE, "mgx_batch_set_documents: query " + std::to_string(reqs[bad].query) +
+                                                   ": more than MGX_DOC_MAX_COLUMNS (32) columns");
+      case dc::kBadLimit:
+        return mgx::Fail(MGX_ERR_OUT_OF_RANGE, "mgx_batch_set_documents: query " + std::to_string(reqs[bad].query) +
+                                                   ": page documents need a page of 1..1024 entries (limit)");
+      case dc::kArenaTooLarge:
+        return mgx::Fail(MGX_ERR_OUT_OF_RANGE,
+                         "mgx_batch_set_documents: the batch's records can exceed MGX_DOC_ARENA_CAP (256 MiB) at query " +
+                             std::to_string(reqs[bad].query) + " (" +
+                             std::to_string(dc::RecordStride(reqs[bad].n_columns, longest)) +
+                             " bytes per page entry); lower limit (or max_key_bytes, or the columns), or request the "
+                             "documents of fewer queries per batch");
+    }
+    std::vector<uint32_t> pos_in_group(n_queries, 0);
+    for (size_t i = 0; i < batch->score.qids.size(); ++i) pos_in_group[batch->score.qids[i]] = static_cast<uint32_t>(i);
+    for (size_t i = 0; i < batch->page.qids.size(); ++i) pos_in_group[batch->page.qids[i]] = static_cast<uint32_t>(i);
+    std::vector<dc::DevQuery> early;
+    size_t n_late = 0;
+    for (const dc::QueryPlan& qp : plan.queries) {
+      if (qp.late) {
+        ++n_late;
+        continue;
+      }
+      const mgx::QuerySpec& sp = batch->specs[qp.query];
+      const uint32_t gi = pos_in_group[qp.query];
+      dc::DevQuery q{};
+      if (sp.mode == mgx::kModeScore) {
+        q.page_docs = batch->sc_docs() + static_cast<size_t>(gi) * batch->page_stride;
+        q.page_n = batch->sc_n() + gi;
+      } else {
+        q.page_docs = batch->page.dev.page_docs + static_cast<size_t>(gi) * batch->doc_page_stride;
+        q.total_exec = static_cast<const unsigned long long*>(batch->d_page_out.p) + static_cast<size_t>(gi) * 8 + 4;
+        q.total_merged = reinterpret_cast<const unsigned long long*>(batch->page.dev.totals) + gi;
+      }
+      q.limit = qp.limit;
+      q.entry_begin = qp.entry_begin;
+      q.n_columns = qp.n_columns;
+      q.col_begin = qp.col_begin;
+      q.rec_off = qp.rec_off;
+      q.rec_stride = qp.rec_stride;
+      early.push_back(q);
+    }
+    mgx::ResourceScope scope(batch->res);
+    MGX_HIP(hipSetDevice(idx->device));
+    mgx_batch::Documents& d = batch->doc;
+    if (!early.empty()) MGX_HIP(mgx::Upload(d.d_early, early.data(), early.size()));
+    MGX_HIP(mgx::Upload(d.d_columns, columns.data(), columns.size(), 1));
+    if (n_late) MGX_HIP(d.d_late.Alloc(n_late * sizeof(dc::DevQuery)));
+    MGX_HIP(d.d_arena.Alloc(plan.arena_bytes));
+    MGX_HIP(batch->res->Pinned(4, plan.arena_bytes, &d.h_arena));
+    d.fetch_off.resize(plan.queries.size());
+    for (size_t i = 0; i < plan.queries.size(); ++i) d.fetch_off[i] = plan.queries[i].rec_off;
+    d.of_query = std::move(of_query);
+    d.early = std::move(early);
+    d.plan = std::move(plan);
+    return MGX_OK;
+  } catch (const std::exception& e) {
+    return mgx::Fail(MGX_ERR_INTERNAL, std::string("mgx_batch_set_documents: ") + e.what());
+  }
+}
+
+int mgx_batch_defer_documents(mgx_batch* batch, int defer) {
+  if (!batch) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_batch_defer_documents: null batch");
+  batch->doc.defer = defer != 0;
+  return MGX_OK;
+}
+
+int mgx_batch_fetch_documents(mgx_batch* batch, mgx_document_view* out) {
+  namespace dc = mgx::documents;
+  if (out) std::memset(out, 0, sizeof(*out));
+  if (!batch || !out) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_batch_fetch_documents: null argument");
+  if (!batch->executed || !batch->fetched)
+    return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_batch_fetch_documents: call mgx_batch_fetch for this execute first");
+  try {
+    mgx_batch::Documents& d = batch->doc;
+    d.entries.assign(batch->h_docs.size(), mgx_document_entry{});
+    for (uint32_t qi = 0; qi < batch->n_queries && d.on(); ++qi) {
+      if (d.of_query[qi] < 0) continue;
+      const size_t pi = static_cast<size_t>(d.of_query[qi]);
+      const dc::QueryPlan& q = d.plan.queries[pi];
+      const mgx_query_result& r = batch->h_results[qi];
+      for (uint32_t j = 0; j < r.n_docs && j < q.limit; ++j) {
+        const uint8_t* rec = static_cast<const uint8_t*>(d.h_arena) + d.fetch_off[pi] + static_cast<uint64_t>(j) * q.rec_stride;
+        dc::Header head;
+        std::memcpy(&head, rec, sizeof(head));
+        if ((head.flags & dc::kTruncated) || head.key_len > d.plan.key_cap || head.n_columns > q.n_columns)
+          return mgx::Fail(MGX_ERR_OUT_OF_RANGE,
+                           "mgx_batch_fetch_documents: query " + std::to_string(qi) + ": a page entry's key is longer than "
+                           "the max_key_bytes the records were sized for");
+        if (!(head.flags & dc::kFound)) continue;  // (a doc id no index of the batch holds: a zero entry)
+        mgx_document_entry& e = d.entries[r.docs_begin + j];
+        e.flags = head.flags;
+        e.key_len = head.key_len;
+        e.null_mask = head.null_mask;
+        e.n_columns = head.n_columns;
+        e.values = reinterpret_cast<const uint64_t*>(rec + sizeof(dc::Header));
+        e.key = rec + sizeof(dc::Header) + 8ull * q.n_columns;
+      }
+    }
+    out->n_entries = static_cast<uint32_t>(d.entries.size());
+    out->entries = d.entries.data();
+    return MGX_OK;
+  } catch (const std::exception& e) {
+    return mgx::Fail(MGX_ERR_INTERNAL, std::string("mgx_batch_fetch_documents: ") + e.what());
+  }
+}
+
+static_assert(MGX_DOC_MAX_COLUMNS == mgx::documents::kMaxColumns && MGX_DOC_MAX_LIMIT == mgx::documents::kMaxLimit &&
+                  MGX_DOC_ARENA_CAP == mgx::documents::kArenaCap && MGX_DOC_NO_COLUMN == mgx::documents::kNoColumn &&
+                  MGX_DOC_FOUND == mgx::documents::kFound && MGX_DOC_HAS_KEY == mgx::documents::kHasKey &&
+                  MGX_DOC_MAPPED == mgx::documents::kMapped,
+              "the header's constants are the planner's");
+
 int mgx_highlight_render(const mgx_highlight_entry* entry, const uint8_t* open_tag, size_t open_len,
                          const uint8_t* close_tag, size_t close_len, uint8_t* out, size_t cap, size_t* out_len) {
   namespace hl = mgx::highlight;
@@ -3939,6 +4293,10 @@ static int RefuseColumnSort(const mgx_batch* batch, const char* entry) {
 }
 
 // (the counts of a sharded table's facets would need an all-reduce across the ranks: out of scope)
+// (the rows of a sharded table's page live on other ranks: out of scope)
+static int RefuseDocuments(const char* entry) {
+  return mgx::Fail(MGX_ERR_NOT_IMPLEMENTED, std::string(entry) + ": page documents (mgx_batch_set_documents) on a sharded table are not implemented: the page's rows live on other ranks");
+}
 static int RefuseFacets(const char* entry) {
   return mgx::Fail(MGX_ERR_NOT_IMPLEMENTED, std::string(entry) + ": facets (mgx_batch_set_facets) on a sharded table are not implemented: the counts of the shards are not reduced");
 }
@@ -3951,6 +4309,7 @@ int mgx_batch_export_topk(mgx_batch* batch, uint64_t* blob64, uint32_t* blob32, 
                           void* hip_stream) {
   if (!batch || !stride) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_batch_export_topk: null argument");
   if (batch->fc.on()) return RefuseFacets("mgx_batch_export_topk");
+  if (batch->doc.on()) return RefuseDocuments("mgx_batch_export_topk");
   if (batch->hl.on()) return mgx::Fail(MGX_ERR_NOT_IMPLEMENTED, "mgx_batch_export_topk: highlight on a sharded table is not implemented: the page's texts live on other ranks");
   if (const int rc_cs = RefuseColumnSort(batch, "mgx_batch_export_topk")) return rc_cs;
   const bool pages = batch->score.qids.empty() && batch->bitmap.qids.empty() && !batch->page.qids.empty();
@@ -3993,6 +4352,7 @@ int mgx_batch_export_buffer(mgx_batch* batch, void** device_blob, uint64_t* byte
   if (!batch || !device_blob || !bytes || !offset32)
     return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_batch_export_buffer: null argument");
   if (batch->fc.on()) return RefuseFacets("mgx_batch_export_buffer");
+  if (batch->doc.on()) return RefuseDocuments("mgx_batch_export_buffer");
   if (batch->hl.on())
     return mgx::Fail(MGX_ERR_NOT_IMPLEMENTED, "mgx_batch_export_buffer: highlight on a sharded table is not implemented: the page's texts live on other ranks");
   if (const int rc_cs = RefuseColumnSort(batch, "mgx_batch_export_buffer")) return rc_cs;
@@ -4008,6 +4368,7 @@ int mgx_batch_merge_shards(mgx_batch* batch, uint32_t n_shards, const uint64_t* 
   if (!batch || !blob64 || !blob32 || n_shards == 0)
     return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_batch_merge_shards: null argument");
   if (batch->fc.on()) return RefuseFacets("mgx_batch_merge_shards");
+  if (batch->doc.on()) return RefuseDocuments("mgx_batch_merge_shards");
   if (batch->hl.on()) return mgx::Fail(MGX_ERR_NOT_IMPLEMENTED, "mgx_batch_merge_shards: highlight on a sharded table is not implemented: the page's texts live on other ranks");
   if (const int rc_cs = RefuseColumnSort(batch, "mgx_batch_merge_shards")) return rc_cs;
   const bool pages = batch->score.qids.empty() && batch->bitmap.qids.empty() && !batch->page.qids.empty();
@@ -4133,6 +4494,22 @@ int mgx_batch_merge_local(mgx_batch* primary, mgx_batch* const* others, uint32_t
                            "64-bit sort key is NULL's (INT64_MIN, or the double whose bits are all ones)");
       }
     }
+    // page documents: one main index (its own ids) and one delta (table ids through its doc map), before anything is touched
+    const mgx_batch* doc_mapped = nullptr;
+    const mgx_batch* doc_plain = nullptr;
+    if (primary->doc.on()) {
+      for (uint32_t j = 0; j <= n_others; ++j) {
+        const mgx_batch* x = j == 0 ? primary : others[j - 1];
+        const mgx_batch*& slot = x->idx->d_doc_map.p ? doc_mapped : doc_plain;
+        if (slot || n_others > 1)
+          return mgx::Fail(MGX_ERR_NOT_IMPLEMENTED, "mgx_batch_merge_local: page documents read one main index and one delta");
+        slot = x;
+      }
+      if (n_others == 1) {
+        const int rc = mgx::CheckDocumentSides(primary, others[0], "mgx_batch_merge_local");
+        if (rc) return rc;
+      }
+    }
     MGX_HIP(hipSetDevice(primary->idx->device));
     if (!primary->bitmap.qids.empty() && n_others == 1) {
       // the bitmap group's page sizes need the totals on the host: its merge runs inside mgx_batch_fetch(primary)
@@ -4203,6 +4580,12 @@ int mgx_batch_merge_local(mgx_batch* primary, mgx_batch* const* others, uint32_t
       rc = mgx::RunHighlight(primary, s, /*merged=*/true, mapped, plain);
       if (rc) return rc;
       MGX_HIP(hipEventRecord(primary->res->done_ev, s));  // (the records replace those of the primary's own page)
+    }
+    if (primary->doc.on()) {
+      // the same for page documents: the delta's rows through its doc map and its own batch's column ids
+      rc = mgx::RunDocuments(primary, s, /*merged=*/true, doc_mapped, doc_plain);
+      if (rc) return rc;
+      MGX_HIP(hipEventRecord(primary->res->done_ev, s));
     }
     return MGX_OK;
   } catch (const std::exception& e) {
@@ -4332,6 +4715,7 @@ int mgx_batch_exchange_df(mgx_batch* batch, mgx_comm* comm, void* hip_stream) {
 
 int mgx_batch_exchange(mgx_batch* batch, mgx_comm* comm, void* hip_stream) {
   if (batch && batch->fc.on()) return RefuseFacets("mgx_batch_exchange");  // (before anything else is looked at)
+  if (batch && batch->doc.on()) return RefuseDocuments("mgx_batch_exchange");
   if (!batch || !comm) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_batch_exchange: null argument");
   if (batch->hl.on()) return mgx::Fail(MGX_ERR_NOT_IMPLEMENTED, "mgx_batch_exchange: highlight on a sharded table is not implemented: the page's texts live on other ranks");
   if (const int rc_cs = RefuseColumnSort(batch, "mgx_batch_exchange")) return rc_cs;
@@ -4397,6 +4781,7 @@ static int RcclGather(void* user, const void* mine, void* all, uint64_t bytes, v
 int mgx_batch_execute_gather(mgx_batch* batch, int world, mgx_gather_fn gather, void* user, void* hip_stream) {
   if (!batch || !gather || world < 1) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_batch_execute_gather: bad argument");
   if (batch->fc.on()) return RefuseFacets("mgx_batch_execute_gather");
+  if (batch->doc.on()) return RefuseDocuments("mgx_batch_execute_gather");
   if (batch->hl.on()) return mgx::Fail(MGX_ERR_NOT_IMPLEMENTED, "mgx_batch_execute_gather: highlight on a sharded table is not implemented: the page's texts live on other ranks");
   if (const int rc_cs = RefuseColumnSort(batch, "mgx_batch_execute_gather")) return rc_cs;
   try {
@@ -4425,6 +4810,7 @@ int mgx_batch_execute_gather(mgx_batch* batch, int world, mgx_gather_fn gather, 
 
 int mgx_batch_execute_sharded(mgx_batch* batch, mgx_comm* comm, void* hip_stream) {
   if (batch && batch->fc.on()) return RefuseFacets("mgx_batch_execute_sharded");
+  if (batch && batch->doc.on()) return RefuseDocuments("mgx_batch_execute_sharded");
   if (!batch || !comm) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_batch_execute_sharded: null argument");
   if (!comm->comm) return mgx::Fail(MGX_ERR_INTERNAL, "mgx_batch_execute_sharded: the communicator was aborted");
   return mgx_batch_execute_gather(batch, comm->world, &mgx::RcclGather, comm->comm, hip_stream);
@@ -4797,6 +5183,104 @@ int mgx_score_documents(mgx_index* idx, const uint32_t* candidates, uint64_t n_c
     MGX_HIP(lease.CopyBack(scores_out, d_s.p, n_cand * 8));
     return MGX_OK;
   });
+}
+
+// Page documents without a batch: one pass of document_gather_kernel over the caller's id list, on a lease.
+int mgx_documents_gather(mgx_index* idx, mgx_index* mapped, const uint32_t* doc_ids, uint64_t n_docs, uint32_t n_columns,
+                         const uint32_t* column_ids, const uint32_t* mapped_column_ids, uint32_t max_key_bytes,
+                         uint8_t** records_out, uint64_t* stride_out) {
+  namespace dc = mgx::documents;
+  if (records_out) *records_out = nullptr;
+  if (stride_out) *stride_out = 0;
+  if (!idx || !records_out || !stride_out || (n_docs && !doc_ids) || (n_columns && (!column_ids || (mapped && !mapped_column_ids))))
+    return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_documents_gather: null argument");
+  if (n_columns > MGX_DOC_MAX_COLUMNS)
+    return mgx::Fail(MGX_ERR_OUT_OF_RANGE, "mgx_documents_gather: more than MGX_DOC_MAX_COLUMNS (32) columns");
+  if (mapped && (mapped == idx || mapped->device != idx->device || !mapped->d_doc_map.p || idx->d_doc_map.p))
+    return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_documents_gather: `mapped` is a delta index (mgx_index_set_doc_map) on the device of `idx`, which is none");
+  // each index's requested columns and longest key, read under that index's lock
+  std::vector<dc::DevColumn> cols[2];
+  uint32_t longest = 0;
+  mgx_index* const side[2] = {idx, mapped};
+  const uint32_t* const ids[2] = {column_ids, mapped_column_ids};
+  for (int k = 0; k < 2; ++k) {
+    mgx_index* ix = side[k];
+    if (!ix) continue;
+    std::lock_guard<std::mutex> lock(ix->mu);
+    if (!ix->has_pk_bytes)
+      return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_documents_gather: page documents without mgx_index_attach_primary_key_bytes");
+    longest = std::max(longest, ix->max_pk_bytes);
+    for (uint32_t c = 0; c < n_columns; ++c) {
+      dc::DevColumn col{nullptr, nullptr};
+      if (ids[k][c] != MGX_DOC_NO_COLUMN) {
+        if (ids[k][c] >= ix->filter_columns.size()) return mgx::Fail(MGX_ERR_OUT_OF_RANGE, "mgx_documents_gather: unknown filter column");
+        const mgx_index::FilterColumn& fc = *ix->filter_columns[ids[k][c]];
+        col.values = fc.d_values.as<uint64_t>();
+        col.is_null = fc.d_null.as<uint8_t>();
+      }
+      cols[k].push_back(col);
+    }
+  }
+  const uint32_t key_cap = max_key_bytes ? max_key_bytes : longest;
+  const uint64_t stride = dc::RecordStride(n_columns, key_cap);
+  *stride_out = stride;
+  if (n_docs == 0) return MGX_OK;
+  if (n_docs > 0xFFFFFFFFull || n_docs * stride > MGX_DOC_ARENA_CAP)
+    return mgx::Fail(MGX_ERR_OUT_OF_RANGE, "mgx_documents_gather: the records exceed MGX_DOC_ARENA_CAP (256 MiB): pass fewer ids per call "
+                                           "(or lower max_key_bytes, or the columns)");
+  uint8_t* host = static_cast<uint8_t*>(std::malloc(n_docs * stride));
+  if (!host) return mgx::Fail(MGX_ERR_INTERNAL, "mgx_documents_gather: out of memory");
+  const int rc = WithLease(idx, "mgx_documents_gather", true, [&](SingleLease& lease) {
+    DevBuf d_ids, d_query, d_cols[2], d_arena;
+    MGX_HIP(mgx::Upload(d_ids, doc_ids, n_docs));
+    for (int k = 0; k < 2; ++k) MGX_HIP(mgx::Upload(d_cols[k], cols[k].data(), cols[k].size(), 1));
+    MGX_HIP(d_arena.Alloc(n_docs * stride));
+    dc::DevQuery q{};
+    q.page_docs = d_ids.as<uint32_t>();
+    q.limit = q.count = static_cast<uint32_t>(n_docs);
+    q.n_columns = n_columns;
+    q.rec_stride = stride;
+    MGX_HIP(mgx::Upload(d_query, &q, 1));
+    MGX_HIP(lease.Ship());
+    auto source = [&](const mgx_index* ix, int k) {
+      dc::DevSource src{};
+      if (!ix) return src;
+      src.key_bytes = ix->d_pkb_bytes.as<uint8_t>();
+      src.key_off = ix->d_pkb_off.as<uint64_t>();
+      src.has_key = ix->d_pkb_has.as<uint8_t>();
+      src.doc_map = k == 1 ? ix->d_doc_map.as<uint32_t>() : nullptr;
+      src.columns = d_cols[k].as<dc::DevColumn>();
+      src.first_doc_id = ix->dev.first_doc_id;
+      src.n_docs = ix->dev.n_docs;
+      return src;
+    };
+    dc::DevBatch db{};
+    db.queries = d_query.as<dc::DevQuery>();
+    db.n_queries = 1;
+    db.n_entries = static_cast<uint32_t>(n_docs);
+    db.arena = d_arena.as<uint8_t>();
+    db.plain = source(idx, 0);
+    db.mapped = source(mapped, 1);
+    db.key_cap = key_cap;
+    MGX_LAUNCH(mgx::LaunchDocumentGather(db, lease.stream));
+    MGX_HIP(lease.CopyBack(host, d_arena.p, n_docs * stride));
+    return MGX_OK;
+  });
+  if (rc == MGX_OK)
+    for (uint64_t i = 0; i < n_docs; ++i) {
+      dc::Header h;
+      std::memcpy(&h, host + i * stride, sizeof(h));
+      if (h.flags & dc::kTruncated) {
+        std::free(host);
+        return mgx::Fail(MGX_ERR_OUT_OF_RANGE, "mgx_documents_gather: a key is longer than max_key_bytes");
+      }
+    }
+  if (rc != MGX_OK) {
+    std::free(host);
+    return rc;
+  }
+  *records_out = host;
+  return MGX_OK;
 }
 
 int mgx_score_documents_text(mgx_index* idx, const uint32_t* candidates, uint64_t n_cand, const uint8_t* term_bytes,

@@ -208,6 +208,12 @@ struct Index::Impl {
   // SORT by primary key orders by. Kept here for the table's lifetime, as the reference's DocumentStore keeps them: every
   // index built from the table's documents (main, delta, a compacted main) takes its slots' keys from it. Under mu.
   mutable std::map<DocId, std::string> primary_keys;
+  // the device index that holds the table's raw key bytes (mgx_index_attach_primary_key_bytes; page documents): not `dev`
+  // until the first batch that asks for documents, and again after Compact() installed a new one. Under mu.
+  mutable mgx_index* pk_bytes_dev = nullptr;
+  // a delta index: the table id of each of its slots (its doc map), kept with the index itself so that a batch that still
+  // runs on this delta after the table built a newer one can attach its key bytes. Written once, before the delta is shared.
+  std::vector<DocId> doc_map_ids;
   std::string primary_key_column;  // SetPrimaryKeyColumn
   // The original text of every document of the table that has one (AddDocument(..., original_text)), kept like the keys
   // and for the same span; `invalid_originals`: those that are not valid UTF-8, which the host renders. Under mu.
@@ -377,6 +383,7 @@ struct Index::Impl {
     filter_columns = std::move(g.filter_columns);
     condition_cache.clear();
     have_empty_bitmap = false;
+    pk_bytes_dev = nullptr;
   }
 
   // FilterIndex::ResolveColumnName (filter_index.cpp:122-147): exact name first, else the one unambiguous ASCII
@@ -1110,6 +1117,7 @@ BuiltDelta BuildDelta(const Index& self, const std::map<DocId, std::string>& doc
     out.error = mgx_last_error();
     return out;
   }
+  nd->impl()->doc_map_ids = ids;
   out.error = UploadPrimaryKeys(nd->impl()->dev, primary_keys, ids.size(), [&](uint64_t slot) { return ids[slot]; });  // (after the doc map)
   if (!out.error.empty()) return out;
   const NamedValues columns = ValuesByName(filters, std::move(column_names), ids.size(), [&](DocId doc) {
@@ -2498,6 +2506,7 @@ BatchQuery FacetSearchPart(const BatchQuery& query) {
 // table with a delta the other index may hold it), and the search part planned as a limit-0 doc-id query.
 void PlanFacetQuery(const index::Index& index, const BatchQuery& q, uint64_t total_docs, double avgdl, PlannedQuery* p) {
   if (q.highlight) return Fail(p, ErrorCode::kInvalidArgument, "facet_columns and highlight: a faceted query returns counts, not a page");
+  if (q.return_documents) return Fail(p, ErrorCode::kInvalidArgument, "facet_columns and return_documents: a faceted query returns counts, not a page");
   if (q.facet_columns.size() > MGX_FACET_MAX_COLUMNS)
     return Fail(p, ErrorCode::kOutOfRange, "more than MGX_FACET_MAX_COLUMNS (8) facet columns in one query");
   index.FlushPendingFilterColumns();
@@ -2887,6 +2896,9 @@ void Collect(const std::vector<PlannedQuery>& plans, const mgx_result_view& v, s
     o.empty_term_detected = false;
     o.snippets.clear();
     o.facets.clear();
+    o.documents.clear();
+    o.document_words.clear();
+    o.document_null_masks.clear();
     if (!plans[qi].on_device) {
       o.empty_term_detected = plans[qi].empty_term_detected;
       continue;
@@ -3087,6 +3099,207 @@ void PageFacetValues(const std::vector<storage::FilterValue>& dict, const std::v
     out->value_counts.emplace_back(storage::SerializeFilterValue(dict[order[k]]), counts[order[k]]);
     out->display.push_back(storage::FilterValueToDisplayString(dict[order[k]]));
   }
+}
+
+// ---- page documents ---------------------------------------------------------------------------------------------------
+// The requests of one batch's device queries (mgx_batch_set_documents), the ids they point at and the column names the
+// ids stand for (the same list for the main index's batch and the delta's).
+struct DocumentRequests {
+  std::vector<mgx_document_request> reqs;
+  std::vector<std::vector<uint32_t>> ids;
+  std::vector<std::vector<std::string>> names;
+};
+
+bool AnyDocuments(const std::vector<BatchQuery>& queries) {
+  for (const auto& q : queries)
+    if (q.return_documents) return true;
+  return false;
+}
+
+// BatchQuery::document_columns, or every filter column of the table: the main index's, then those only the delta holds.
+std::vector<std::string> DocumentColumnsOf(const index::Index& index, const index::Index* delta, const BatchQuery& q) {
+  if (!q.document_columns.empty()) return q.document_columns;
+  std::vector<std::string> names;
+  for (const index::Index* ix : {&index, delta}) {
+    if (ix == nullptr) continue;
+    const index::Index::Impl* im = ix->impl();
+    std::lock_guard<std::mutex> lock(im->filter_mu);
+    for (const auto& c : im->filter_columns)
+      if (std::find(names.begin(), names.end(), c.name) == names.end()) names.push_back(c.name);
+  }
+  return names;
+}
+
+// The table's raw key bytes on the device, by doc slot, for every index of the table that does not hold them yet: the
+// first batch that asks for documents, and again after a delta rebuild or Compact() made a new device index.
+Error EnsureKeyBytes(const index::Index& index, const index::Index* delta) {
+  index::Index::Impl* im = index.impl();
+  std::lock_guard<std::mutex> lock(im->mu);
+  auto attach = [&](index::Index::Impl* target, uint64_t n, auto doc_of) -> std::string {
+    const std::map<DocId, std::string>& keys = im->primary_keys;  // (the table's: a delta's documents are in it too)
+    if (keys.empty()) {
+      // a table that was given no keys here (an adopted device index): what its owner attached through the C ABI stays
+      // (the gather of no ids succeeds exactly when the index holds key bytes)
+      uint8_t* none = nullptr;
+      uint64_t stride = 0;
+      if (mgx_documents_gather(target->dev, nullptr, nullptr, 0, 0, nullptr, nullptr, 0, &none, &stride) == MGX_OK) {
+        target->pk_bytes_dev = target->dev;
+        return "";
+      }
+    }
+    std::vector<uint8_t> bytes, has(n, 0);
+    std::vector<uint64_t> off(n + 1, 0);
+    auto it = n ? keys.lower_bound(doc_of(0)) : keys.end();
+    for (uint64_t slot = 0; slot < n; ++slot) {
+      const DocId doc = doc_of(slot);
+      while (it != keys.end() && it->first < doc) ++it;
+      if (it != keys.end() && it->first == doc) {
+        bytes.insert(bytes.end(), it->second.begin(), it->second.end());
+        has[slot] = 1;
+      }
+      off[slot + 1] = bytes.size();
+    }
+    bytes.push_back(0);  // (an address even when every key is empty)
+    if (mgx_index_attach_primary_key_bytes(target->dev, bytes.data(), off.data(), has.data()) != MGX_OK) return mgx_last_error();
+    target->pk_bytes_dev = target->dev;
+    return "";
+  };
+  std::string err;
+  if (im->pk_bytes_dev != im->dev) {
+    const DocId first = im->view.first_doc_id;
+    err = attach(im, im->view.n_docs, [first](uint64_t slot) { return first + static_cast<DocId>(slot); });
+  }
+  if (err.empty() && delta != nullptr) {
+    index::Index::Impl* dim = delta->impl();
+    if (dim->pk_bytes_dev != dim->dev) {
+      // (the delta's own doc map: the table may have built a newer delta since the batch took this one; the keys are the
+      // table's current ones, so a document removed in between has none)
+      const std::vector<DocId>& ids = dim->doc_map_ids;
+      if (ids.size() != dim->view.n_docs)
+        return MakeError(ErrorCode::kInternalError, "page documents: the delta index holds no doc map");
+      err = attach(dim, ids.size(), [&ids](uint64_t slot) { return ids[slot]; });
+    }
+  }
+  return err.empty() ? Error{ErrorCode::kSuccess, ""} : MakeError(ErrorCode::kInternalError, err);
+}
+
+Error DocumentColumnNotFound(const std::string& column) {
+  return MakeError(ErrorCode::kIndexNotFound, "Document column \"" + column + "\" not found");
+}
+
+// After prepare / reset and before the execute, once for the main index's batch (`own` = the main index) and once for
+// the delta's (`own` = the delta): the same names, each batch with its own index's column ids; a column the own index
+// does not hold is MGX_DOC_NO_COLUMN. `plans`: those of `batch`.
+Error AttachDocuments(const index::Index& index, const index::Index* delta, const index::Index& own,
+                      const std::vector<BatchQuery>& queries, const std::vector<PlannedQuery>& plans, mgx_batch* batch,
+                      DocumentRequests* d) {
+  d->reqs.clear();
+  if (!AnyDocuments(queries)) return Error{ErrorCode::kSuccess, ""};
+  index.FlushPendingFilterColumns();
+  {
+    const Error e = EnsureKeyBytes(index, delta);
+    if (e.code() != ErrorCode::kSuccess) return e;
+  }
+  size_t n_dev = 0;
+  for (const auto& p : plans) n_dev += p.on_device ? 1 : 0;
+  d->reqs.assign(n_dev, mgx_document_request{});
+  d->ids.resize(n_dev);
+  d->names.resize(n_dev);
+  size_t k = 0;
+  for (size_t qi = 0; qi < queries.size(); ++qi) {
+    if (!plans[qi].on_device) continue;
+    const BatchQuery& q = queries[qi];
+    const size_t at = k++;
+    if (!q.return_documents) continue;
+    d->names[at] = DocumentColumnsOf(index, delta, q);
+    d->ids[at].clear();
+    for (const std::string& name : d->names[at]) {
+      bool known = false;
+      uint32_t id = MGX_DOC_NO_COLUMN;
+      for (const index::Index* ix : {&index, delta}) {
+        if (ix == nullptr) continue;
+        const index::Index::Impl* im = ix->impl();
+        std::lock_guard<std::mutex> lock(im->filter_mu);
+        const index::Index::Impl::FilterColumn* col = im->ResolveColumn(name);
+        if (col == nullptr) continue;
+        known = true;
+        if (ix == &own) id = col->device_id;
+      }
+      if (!known) return DocumentColumnNotFound(name);
+      d->ids[at].push_back(id);
+    }
+    mgx_document_request& r = d->reqs[at];
+    r.enabled = 1;
+    r.n_columns = static_cast<uint32_t>(d->ids[at].size());
+    r.column_ids = d->ids[at].data();
+  }
+  uint32_t longest = 0, dl = 0;  // over both indexes: the merged page's records hold either's keys
+  (void)mgx_index_max_primary_key_bytes(index.impl()->dev, &longest);
+  if (delta != nullptr && delta->impl()->dev != nullptr) {
+    (void)mgx_index_max_primary_key_bytes(delta->impl()->dev, &dl);
+    longest = std::max(longest, dl);
+  }
+  int rc = mgx_batch_set_documents(batch, d->reqs.data(), static_cast<uint32_t>(d->reqs.size()), longest);
+  // (with a delta the page is final only after mgx_batch_merge_local: the kernel runs once, there or in the fetch)
+  if (rc == MGX_OK && delta != nullptr) rc = mgx_batch_defer_documents(batch, 1);
+  return rc == MGX_OK ? Error{ErrorCode::kSuccess, ""} : MakeError(static_cast<ErrorCode>(rc), mgx_last_error());
+}
+
+// After mgx_batch_fetch: BatchResult::documents of the requesting queries' pages. A value comes back in its column's own
+// type, a string through the dictionary of the index the row came from (MGX_DOC_MAPPED: the delta).
+int CollectDocuments(const index::Index& index, const index::Index* delta, const std::vector<BatchQuery>& queries,
+                     const std::vector<PlannedQuery>& plans, mgx_batch* batch, const mgx_result_view& v,
+                     const DocumentRequests& d, std::vector<BatchResult>* out) {
+  if (!AnyDocuments(queries) || batch == nullptr || v.queries == nullptr) return MGX_OK;
+  mgx_document_view dv{};
+  const int rc = mgx_batch_fetch_documents(batch, &dv);
+  if (rc != MGX_OK) return rc;
+  const index::Index::Impl* im = index.impl();
+  const index::Index::Impl* dim = delta != nullptr ? delta->impl() : nullptr;
+  std::unique_lock<std::mutex> ml(im->filter_mu), dl;
+  if (dim != nullptr) dl = std::unique_lock<std::mutex>(dim->filter_mu);
+  std::vector<const index::Index::Impl::FilterColumn*> mcols, dcols;
+  size_t k = 0;
+  for (size_t qi = 0; qi < plans.size(); ++qi) {
+    if (!plans[qi].on_device) continue;
+    const size_t at = k;
+    const mgx_query_result& r = v.queries[k++];
+    if (!queries[qi].return_documents) continue;
+    const std::vector<std::string>& names = d.names[at];
+    mcols.assign(names.size(), nullptr);
+    dcols.assign(names.size(), nullptr);
+    for (size_t c = 0; c < names.size(); ++c) {
+      mcols[c] = im->ResolveColumn(names[c]);
+      if (dim != nullptr) dcols[c] = dim->ResolveColumn(names[c]);
+    }
+    std::vector<std::optional<storage::Document>>& docs = (*out)[qi].documents;
+    docs.assign(r.n_docs, std::nullopt);
+    const bool raw = !queries[qi].document_columns.empty();  // (the caller named the columns: their words by position)
+    std::vector<uint64_t>& words = (*out)[qi].document_words;
+    std::vector<uint32_t>& masks = (*out)[qi].document_null_masks;
+    if (raw) {
+      words.assign(static_cast<size_t>(r.n_docs) * names.size(), 0);
+      masks.assign(r.n_docs, names.size() >= 32 ? 0xFFFFFFFFu : (1u << names.size()) - 1u);
+    }
+    for (uint32_t j = 0; j < r.n_docs; ++j) {
+      const mgx_document_entry& e = dv.entries[r.docs_begin + j];
+      if ((e.flags & MGX_DOC_FOUND) == 0) continue;
+      if (raw) {
+        masks[j] = e.null_mask;
+        for (uint32_t c = 0; c < e.n_columns && c < names.size(); ++c) words[j * names.size() + c] = e.values[c];
+      }
+      storage::Document doc;
+      doc.doc_id = v.docs[r.docs_begin + j];
+      if (e.flags & MGX_DOC_HAS_KEY) doc.primary_key.assign(reinterpret_cast<const char*>(e.key), e.key_len);
+      const auto& cols = (e.flags & MGX_DOC_MAPPED) ? dcols : mcols;
+      for (uint32_t c = 0; c < e.n_columns && c < cols.size(); ++c) {
+        if (((e.null_mask >> c) & 1u) != 0 || cols[c] == nullptr || cols[c]->type == 0) continue;
+        doc.filters[cols[c]->name] = index::FilterValueFromBits(cols[c]->type, e.values[c], cols[c]->dict);
+      }
+      docs[j] = std::move(doc);
+    }
+  }
+  return MGX_OK;
 }
 
 // ---- FACET in a batch -------------------------------------------------------------------------------------------------
@@ -3300,11 +3513,14 @@ Expected<std::vector<BatchResult>, Error> ExecuteBatch(const index::Index& index
   std::unique_ptr<mgx_batch, void (*)(mgx_batch*)> guard(batch, mgx_batch_destroy);
   HighlightRequests hreq;
   FacetRequests freq, dfreq;
+  DocumentRequests docreq, ddocreq;
   {
     const Error he = AttachHighlight(index, delta.get(), queries, plans, batch, &hreq);
     if (he.code() != ErrorCode::kSuccess) return MakeUnexpected(he);
     const Error fe = AttachFacets(plans, batch, &freq);
     if (fe.code() != ErrorCode::kSuccess) return MakeUnexpected(fe);
+    const Error de = AttachDocuments(index, delta.get(), index, queries, plans, batch, &docreq);
+    if (de.code() != ErrorCode::kSuccess) return MakeUnexpected(de);
   }
   if (delta) {
     mgx_batch* dbatch = nullptr;
@@ -3314,6 +3530,8 @@ Expected<std::vector<BatchResult>, Error> ExecuteBatch(const index::Index& index
     {
       const Error fe = AttachFacets(dplans, dbatch, &dfreq);  // both batches carry the requests
       if (fe.code() != ErrorCode::kSuccess) return MakeUnexpected(fe);
+      const Error de = AttachDocuments(index, delta.get(), *delta, queries, dplans, dbatch, &ddocreq);
+      if (de.code() != ErrorCode::kSuccess) return MakeUnexpected(de);
     }
     void* stream = nullptr;
     rc = mgx_batch_stream(batch, &stream);
@@ -3325,6 +3543,7 @@ Expected<std::vector<BatchResult>, Error> ExecuteBatch(const index::Index& index
     if (rc != MGX_OK) return MakeUnexpected(MakeError(static_cast<ErrorCode>(rc), mgx_last_error()));
     Collect(plans, v, &out, &dv);
     rc = CollectSnippets(index, queries, plans, batch, v, &out);
+    if (rc == MGX_OK) rc = CollectDocuments(index, delta.get(), queries, plans, batch, v, docreq, &out);
     if (rc != MGX_OK) return MakeUnexpected(MakeError(static_cast<ErrorCode>(rc), mgx_last_error()));
     const Error fe = CollectFacets(queries, plans, &dplans, batch, dbatch, &out);
     if (fe.code() != ErrorCode::kSuccess) return MakeUnexpected(fe);
@@ -3336,6 +3555,7 @@ Expected<std::vector<BatchResult>, Error> ExecuteBatch(const index::Index& index
   if (rc != MGX_OK) return MakeUnexpected(MakeError(static_cast<ErrorCode>(rc), mgx_last_error()));
   Collect(plans, v, &out);
   rc = CollectSnippets(index, queries, plans, batch, v, &out);
+  if (rc == MGX_OK) rc = CollectDocuments(index, nullptr, queries, plans, batch, v, docreq, &out);
   if (rc != MGX_OK) return MakeUnexpected(MakeError(static_cast<ErrorCode>(rc), mgx_last_error()));
   const Error fe = CollectFacets(queries, plans, nullptr, batch, nullptr, &out);
   if (fe.code() != ErrorCode::kSuccess) return MakeUnexpected(fe);
@@ -3433,6 +3653,7 @@ struct BatchExecutor::Impl {
     std::vector<mgx_query> dq;
     HighlightRequests hreq;  // mgx_batch_set_highlight of this batch (storage re-used from batch to batch)
     FacetRequests freq, dfreq;  // mgx_batch_set_facets of the batch and of the delta's batch
+    DocumentRequests docreq, ddocreq;  // mgx_batch_set_documents likewise
     mgx_batch* dbatch = nullptr;
     uint64_t total_docs = 0;  // BM25Stats the batch is planned with (a mutable table's change between batches)
     double avgdl = 0.0;
@@ -3530,6 +3751,8 @@ struct BatchExecutor::Impl {
     if (slot->error.code() != ErrorCode::kSuccess) return;
     slot->error = AttachFacets(slot->plans, slot->batch, &slot->freq);
     if (slot->error.code() != ErrorCode::kSuccess) return;
+    slot->error = AttachDocuments(index, slot->delta.get(), index, slot->queries, slot->plans, slot->batch, &slot->docreq);
+    if (slot->error.code() != ErrorCode::kSuccess) return;
     if (slot->dbatch && slot->dbatch_index != slot->delta) {  // the delta index was rebuilt (or went away)
       mgx_batch_destroy(slot->dbatch);
       slot->dbatch = nullptr;
@@ -3547,6 +3770,8 @@ struct BatchExecutor::Impl {
       return;
     }
     slot->error = AttachFacets(slot->dplans, slot->dbatch, &slot->dfreq);
+    if (slot->error.code() != ErrorCode::kSuccess) return;
+    slot->error = AttachDocuments(index, slot->delta.get(), *slot->delta, slot->queries, slot->dplans, slot->dbatch, &slot->ddocreq);
   }
 
   // device side, in ticket order. Called with mu held; the HIP calls themselves (they only enqueue, but a batch is a
@@ -3749,6 +3974,10 @@ Expected<uint64_t, Error> BatchExecutor::Submit(std::vector<BatchQuery>&& querie
     return MakeUnexpected(MakeError(ErrorCode::kNotImplemented,
                                     "facet_columns on a sharded table (Options::comm) is not implemented: the counts of "
                                     "the shards are not reduced"));
+  if (impl_->opt.comm && AnyDocuments(queries))
+    return MakeUnexpected(MakeError(ErrorCode::kNotImplemented,
+                                    "return_documents on a sharded table (Options::comm) is not implemented: the page's "
+                                    "rows live on other ranks"));
   if (impl_->opt.comm && AnyHighlight(queries))
     return MakeUnexpected(MakeError(ErrorCode::kNotImplemented,
                                     "highlight on a sharded table (Options::comm) is not implemented: the page's texts "
@@ -3844,7 +4073,8 @@ Error BatchExecutor::WaitInto(uint64_t ticket, std::vector<BatchResult>* results
   }
   Collect(s->plans, v, &out, s->delta ? &dv : nullptr);
   if (!s->mq.empty()) {
-    const int rc = CollectSnippets(impl_->index, s->queries, s->plans, s->batch, v, &out);
+    int rc = CollectSnippets(impl_->index, s->queries, s->plans, s->batch, v, &out);
+    if (rc == MGX_OK) rc = CollectDocuments(impl_->index, s->delta.get(), s->queries, s->plans, s->batch, v, s->docreq, &out);
     if (rc != MGX_OK) {
       const Error e = MakeError(static_cast<ErrorCode>(rc), mgx_last_error());
       lock.lock();
@@ -4002,4 +4232,111 @@ MicroBatcher::Stats MicroBatcher::GetStats() const {
 }
 
 }  // namespace search_pipeline
+
+// ---- storage::DocumentStore::GetDocumentsBatch / GetPrimaryKeysBatch ------------------------------------------------------
+namespace {
+using storage::DocId;
+// The rows of an id list from the device: one mgx_documents_gather over the main index and the table's delta. `with_filters`:
+// every filter column of the table. nullopt for an id the table does not hold: no slot in either index, a gap of the main
+// index's range, or a main document removed or superseded (the device's live row, as the single operators read it).
+std::vector<std::optional<storage::Document>> GatherDocuments(const index::Index& index, const std::vector<DocId>& doc_ids,
+                                                              bool with_filters) {
+  using search_pipeline::DeltaOf;
+  index::ClearDeviceError();
+  std::vector<std::optional<storage::Document>> out(doc_ids.size());
+  auto fail = [&](const std::string& msg) {
+    index::SetDeviceError(msg);
+    out.assign(doc_ids.size(), std::nullopt);
+    return out;
+  };
+  index.Finalize();
+  index::Index::Impl* im = index.impl();
+  if (!im->dev) return fail(im->last_error);
+  {
+    const std::string merr = index.ApplyMutations();
+    if (!merr.empty()) return fail(merr);
+  }
+  if (doc_ids.empty()) return out;
+  const std::shared_ptr<index::Index> delta = DeltaOf(index);
+  index.FlushPendingFilterColumns();
+  {
+    const mygram::utils::Error e = search_pipeline::EnsureKeyBytes(index, delta.get());
+    if (e.code() != mygram::utils::ErrorCode::kSuccess) return fail(e.message());
+  }
+  const index::Index::Impl* dim = delta ? delta->impl() : nullptr;
+  search_pipeline::BatchQuery all;  // (no names: every column of the table)
+  const std::vector<std::string> names =
+      with_filters ? search_pipeline::DocumentColumnsOf(index, delta.get(), all) : std::vector<std::string>();
+  if (names.size() > MGX_DOC_MAX_COLUMNS) return fail("GetDocumentsBatch: the table holds more than 32 filter columns");
+  std::vector<uint32_t> mids(names.size(), MGX_DOC_NO_COLUMN), dids(names.size(), MGX_DOC_NO_COLUMN);
+  {
+    std::lock_guard<std::mutex> lock(im->filter_mu);
+    for (size_t c = 0; c < names.size(); ++c)
+      if (const auto* col = im->ResolveColumn(names[c])) mids[c] = col->device_id;
+  }
+  if (dim != nullptr) {
+    std::lock_guard<std::mutex> lock(dim->filter_mu);
+    for (size_t c = 0; c < names.size(); ++c)
+      if (const auto* col = dim->ResolveColumn(names[c])) dids[c] = col->device_id;
+  }
+  uint8_t* records = nullptr;
+  uint64_t stride = 0;
+  if (mgx_documents_gather(im->dev, dim ? dim->dev : nullptr, doc_ids.data(), doc_ids.size(), static_cast<uint32_t>(names.size()),
+                           mids.data(), dids.data(), 0, &records, &stride) != MGX_OK)
+    return fail(mgx_last_error());
+  std::unique_ptr<uint8_t, void (*)(void*)> guard(records, mgx_free);
+  std::vector<uint8_t> live(doc_ids.size(), 1);
+  {
+    std::lock_guard<std::mutex> lock(im->mu);
+    const DocId first = im->view.first_doc_id;
+    for (size_t i = 0; i < doc_ids.size(); ++i) {
+      const DocId d = doc_ids[i];
+      if (d < first || d - first >= im->view.n_docs) continue;  // (not a slot of the main index)
+      const uint64_t slot = d - first;
+      if (im->has_gaps && slot / 64 < im->exists_bits.size() && ((im->exists_bits[slot >> 6] >> (slot & 63)) & 1) == 0) live[i] = 0;
+      if (im->mut.active && !im->LiveApplied(d)) live[i] = 0;
+    }
+  }
+  std::unique_lock<std::mutex> ml(im->filter_mu), dl;
+  if (dim != nullptr) dl = std::unique_lock<std::mutex>(dim->filter_mu);
+  std::vector<const index::Index::Impl::FilterColumn*> mcols(names.size(), nullptr), dcols(names.size(), nullptr);
+  for (size_t c = 0; c < names.size(); ++c) {
+    mcols[c] = im->ResolveColumn(names[c]);
+    if (dim != nullptr) dcols[c] = dim->ResolveColumn(names[c]);
+  }
+  for (size_t i = 0; i < doc_ids.size(); ++i) {
+    const uint8_t* rec = records + i * stride;
+    mgx_document_record_header h;
+    std::memcpy(&h, rec, sizeof(h));
+    if ((h.flags & MGX_DOC_FOUND) == 0) continue;
+    const bool mapped = (h.flags & MGX_DOC_MAPPED) != 0;
+    if (!mapped && !live[i]) continue;
+    storage::Document doc;
+    doc.doc_id = doc_ids[i];
+    const uint8_t* key = rec + sizeof(h) + 8ull * names.size();
+    if (h.flags & MGX_DOC_HAS_KEY) doc.primary_key.assign(reinterpret_cast<const char*>(key), h.key_len);
+    const auto& cols = mapped ? dcols : mcols;
+    for (uint32_t c = 0; c < h.n_columns && c < cols.size(); ++c) {
+      if (((h.null_mask >> c) & 1u) != 0 || cols[c] == nullptr || cols[c]->type == 0) continue;
+      uint64_t w;
+      std::memcpy(&w, rec + sizeof(h) + 8ull * c, 8);
+      doc.filters[cols[c]->name] = index::FilterValueFromBits(cols[c]->type, w, cols[c]->dict);
+    }
+    out[i] = std::move(doc);
+  }
+  return out;
+}
+}  // namespace
+
+std::vector<std::optional<storage::Document>> storage::DocumentStore::GetDocumentsBatch(const std::vector<DocId>& doc_ids) const {
+  return GatherDocuments(*index_, doc_ids, true);
+}
+
+std::vector<std::optional<std::string>> storage::DocumentStore::GetPrimaryKeysBatch(const std::vector<DocId>& doc_ids) const {
+  const std::vector<std::optional<storage::Document>> docs = GatherDocuments(*index_, doc_ids, false);
+  std::vector<std::optional<std::string>> out(docs.size());
+  for (size_t i = 0; i < docs.size(); ++i)
+    if (docs[i]) out[i] = docs[i]->primary_key;
+  return out;
+}
 }  // namespace mygramdb

@@ -126,6 +126,12 @@ struct TimeValue {
 using FilterValue = std::variant<std::monostate, bool, int8_t, uint8_t, int16_t, uint16_t, int32_t, uint32_t, int64_t,
                                  uint64_t, TimeValue, std::string, double>;
 using FilterMap = std::unordered_map<std::string, FilterValue>;
+// src/storage/document_store.h:98-102: one row of a response (GetDocumentsBatch, http_server.cpp:1396-1424).
+struct Document {
+  DocId doc_id = 0;
+  std::string primary_key;  // "" for a document without one
+  FilterMap filters;        // the non-NULL values only
+};
 // FilterIndex::SerializeFilterValue (src/storage/filter_index.cpp:177-258): type tag + little-endian value bytes — the key
 // FACET reports a value under; DeserializeToDisplayString (:314-372) is its printable form.
 std::string SerializeFilterValue(const FilterValue& value);
@@ -342,6 +348,14 @@ class DocumentStore {
   [[nodiscard]] const index::Index& index() const { return *index_; }
   [[nodiscard]] bool IsStoreTextsEnabled() const { return true; }  // document_store.h: SORT _score / HIGHLIGHT need texts
   [[nodiscard]] size_t Size() const;                                 // documents with a text
+  // src/storage/document_store.h:255-268 (document_store_retrieval.cpp:37-103), the reference's signatures: the rows of a
+  // caller's id list, element i for doc_ids[i], nullopt for an id the table does not hold (never added, or removed). One
+  // pass of the device's gather kernel over the list on a leased stand-alone call (mgx_documents_gather), like the
+  // single operators: the keys and filter values are resident in HBM. A document without a primary key has "".
+  // GetDocumentsBatch materialises every filter column of the table. A device failure gives nullopt throughout and sets
+  // index::LastDeviceError().
+  [[nodiscard]] std::vector<std::optional<Document>> GetDocumentsBatch(const std::vector<DocId>& doc_ids) const;
+  [[nodiscard]] std::vector<std::optional<std::string>> GetPrimaryKeysBatch(const std::vector<DocId>& doc_ids) const;
 
  private:
   const index::Index* index_;
@@ -524,6 +538,17 @@ struct BatchQuery {
   // runs by key string (key_merge_kernel) and is served like any other. Together with sort_by_score: kInvalidArgument.
   // Refused (kNotImplemented) on a sharded executor and beside `highlight`.
   bool sort_primary_key = false;
+  // Page documents: what turns the page into a response (ResponseFormatter::FormatSearchResponse's GetPrimaryKeysBatch,
+  // response_formatter.cpp:280-332; the HTTP handler's GetDocumentsBatch, http_server.cpp:1396-1424), gathered on the
+  // device behind the kernel that finalises the page (mgx_batch_set_documents): BatchResult::documents then holds each
+  // page entry's primary key and the values of `document_columns`, names of Index::AddFilterColumn resolved as
+  // filter_conditions resolve them; an empty list means every filter column of the table, which is what
+  // GetDocumentsBatch materialises. Any sort order and offset, 0 < limit <= 1024 (kOutOfRange otherwise); at most 32
+  // columns; a name no index of the table knows: kIndexNotFound; beside facet_columns: kInvalidArgument; refused
+  // (kNotImplemented) on a sharded executor (Options::comm): the page's rows live on other ranks. The table's raw key
+  // bytes go to the device with the first batch that asks, and again for an index a delta rebuild or Compact() made.
+  bool return_documents = false;
+  std::vector<std::string> document_columns;
 };
 
 // search_pipeline::BuildHighlightTerms (src/server/search_pipeline.cpp:712-745) without the synonym branch: normalize
@@ -552,6 +577,16 @@ struct BatchResult {
   bool empty_term_detected = false;
   std::vector<std::string> snippets;   // parallel to results when the query asked for highlight, else empty
   std::vector<FacetOutput> facets;     // one per BatchQuery::facet_columns name, else empty
+  // parallel to results when the query asked for documents, else empty: {doc_id, primary_key, filters} as the
+  // reference's storage::Document; `filters` holds exactly the non-NULL values the document was last given (AddDocument /
+  // UpdateDocument / UpdateFilters / a dump), each in its column's own type, strings through the dictionary of the index
+  // the row came from; nullopt when the entry was not found
+  std::vector<std::optional<storage::Document>> documents;
+  // the same rows as the device returned them, for a caller that formats them itself (the C face): per entry
+  // `document_columns.size()` words (a requested column's stored 8 bytes: integers widened, double bits, a string's rank
+  // in the dictionary of the index the row came from) and one null mask; empty when document_columns is
+  std::vector<uint64_t> document_words;
+  std::vector<uint32_t> document_null_masks;
 };
 
 // N queries planned like ExecuteFullPipeline's regular branch (GenerateTermInfos with df, sort by estimated size,

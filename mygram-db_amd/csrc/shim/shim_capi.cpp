@@ -491,6 +491,58 @@ int mgxs_search_by_primary_key(mgxs_table* table, uint32_t n_terms, const char* 
   }
 }
 
+int mgxs_search_documents(mgxs_table* table, uint32_t n_terms, const char* const* terms, uint32_t n_not,
+                          const char* const* not_terms, uint32_t n_cond, const char* const* cond_columns, const uint32_t* cond_ops,
+                          const char* const* cond_values, int sort_by_score, int descending, uint32_t limit, uint32_t offset,
+                          const char* sort_column, int sort_primary_key, uint32_t n_columns, const char* const* columns,
+                          uint64_t* total, uint32_t* n_docs, uint32_t* docs, double* scores, uint8_t* found, uint8_t* has_key,
+                          char* keys, size_t keys_cap, uint32_t* key_off, uint64_t* values, uint32_t* null_masks) {
+  if (!table || !total || !n_docs || !docs || !found || !has_key || !key_off || (keys_cap && !keys) ||
+      (n_columns && (!columns || !values || !null_masks)))
+    return Fail(MGX_ERR_INVALID_ARGUMENT, "mgxs_search_documents: null argument");
+  try {
+    BatchQuery q = MakeQuery(n_terms, terms, n_not, not_terms, n_cond, cond_columns, cond_ops, cond_values, sort_by_score,
+                             descending, limit, offset);
+    if (sort_column) q.sort_column = sort_column;
+    q.sort_primary_key = sort_primary_key != 0;
+    q.return_documents = true;
+    for (uint32_t c = 0; c < n_columns; ++c) {
+      if (!columns[c]) return Fail(MGX_ERR_INVALID_ARGUMENT, "mgxs_search_documents: null column name");
+      q.document_columns.emplace_back(columns[c]);
+    }
+    auto r = mygramdb::search_pipeline::ExecuteBatch(*table->index, {q});
+    if (!r) return Fail(static_cast<int>(r.error().code()), r.error().message());
+    const auto& res = (*r)[0];
+    *total = res.total;
+    const size_t n = std::min<size_t>(res.results.size(), limit);
+    *n_docs = static_cast<uint32_t>(n);
+    size_t at = 0;
+    key_off[0] = 0;
+    for (size_t k = 0; k < n; ++k) {
+      docs[k] = res.results[k];
+      if (scores) scores[k] = k < res.scores.size() ? res.scores[k] : 0.0;
+      const auto& d = res.documents[k];
+      found[k] = d ? 1 : 0;
+      // (a document without a key and one whose key is "" both have "" here: the reference's Document cannot tell them
+      // apart either)
+      has_key[k] = d && !d->primary_key.empty() ? 1 : 0;
+      if (d) {
+        if (at + d->primary_key.size() > keys_cap) return Fail(MGX_ERR_OUT_OF_RANGE, "mgxs_search_documents: key buffer too small");
+        std::memcpy(keys + at, d->primary_key.data(), d->primary_key.size());
+        at += d->primary_key.size();
+      }
+      key_off[k + 1] = static_cast<uint32_t>(at);
+      if (n_columns) {
+        null_masks[k] = res.document_null_masks[k];
+        for (uint32_t c = 0; c < n_columns; ++c) values[k * n_columns + c] = res.document_words[k * n_columns + c];
+      }
+    }
+    return MGX_OK;
+  } catch (const std::exception& e) {
+    return Fail(MGX_ERR_INTERNAL, e.what());
+  }
+}
+
 int mgxs_search_highlight(mgxs_table* table, uint32_t n_terms, const char* const* terms, uint32_t n_not,
                           const char* const* not_terms, int sort_by_score, int descending, uint32_t limit, uint32_t offset,
                           const char* open_tag, const char* close_tag, uint32_t snippet_length, uint32_t max_fragments,

@@ -340,6 +340,22 @@ class DeviceIndex:
         check(load().mgx_index_set_primary_keys(self._h, blob.ctypes.data, off.ctypes.data,
                                                 None if has.all() else has.ctypes.data))
 
+    def attach_primary_key_bytes(self, keys):
+        """mgx_index_attach_primary_key_bytes: the documents' raw primary keys by doc slot (bytes or str; None: the
+        document has no key), kept resident for Query(documents=...). Calling it again replaces them."""
+        enc = [None if k is None else (k if isinstance(k, bytes) else str(k).encode("utf-8")) for k in keys]
+        blob = np.frombuffer(b"".join(k or b"" for k in enc) or b"\0", dtype=np.uint8)
+        off = np.zeros(len(enc) + 1, dtype=np.uint64)
+        np.cumsum([len(k or b"") for k in enc], out=off[1:])
+        has = np.asarray([k is not None for k in enc], dtype=np.uint8)
+        check(load().mgx_index_attach_primary_key_bytes(self._h, blob.ctypes.data, off.ctypes.data,
+                                                        None if has.all() else has.ctypes.data))
+
+    def max_primary_key_bytes(self):
+        n = C.c_uint32()
+        check(load().mgx_index_max_primary_key_bytes(self._h, C.byref(n)))
+        return int(n.value)
+
     def set_primary_key_shortcut(self, enable=True):
         """mgx_index_set_primary_key_shortcut: off on a main index while a delta index merges with it."""
         check(load().mgx_index_set_primary_key_shortcut(self._h, int(bool(enable))))
@@ -393,7 +409,7 @@ class Query:
 
     def __init__(self, terms=(), not_terms=(), filters=(), sort_score=False, limit=100, offset=0, descending=True,
                  k1=1.2, b=0.75, fuzzy=0, expr=None, universe=None, verify_text=False, highlight=None, conditions=(),
-                 sort_column=None, sort_key_bias=0, sort_ranks=False, facet_columns=None, sort_primary_key=False):
+                 sort_column=None, sort_key_bias=0, sort_ranks=False, facet_columns=None, sort_primary_key=False, documents=None):
         """`expr`: boolean tree over term strings instead of the plain AND of `terms` (query::QueryNode):
         "term" | ("and", e, ...) | ("or", e, ...) | ("not", e). `universe` = (first_doc_id, count) of the NOT universe
         (DocumentStore::GetAllDocIds); None = every slot of the index."""
@@ -430,6 +446,12 @@ class Query:
             if sort_score or sort_column is not None or sort_primary_key or self.highlight is not None:
                 raise ValueError("a faceted query returns counts, not a page: no sort order and no highlight")
             self.limit, self.offset = 0, 0
+        # documents: page documents (mgx_batch_set_documents): None = off; a list of ids DeviceIndex.add_filter_column
+        # returned (or _capi.DOC_NO_COLUMN), at most 32, repeats allowed, [] = keys only. SearchResult.documents then holds
+        # one PageDocument (or None: not found) per returned doc, gathered on the device behind the page
+        self.documents = [int(c) for c in documents] if documents is not None else None
+        if self.documents is not None and self.facet_columns:
+            raise ValueError("a faceted query returns counts, not a page: no documents")
         if expr is not None and not self.terms:
             seen = []
 
@@ -479,9 +501,19 @@ class TermInfo:
                  "fuzzy_empty")
 
 
+class PageDocument:
+    """One page entry's row (mgx_document_entry): `key` = the primary key's bytes or None, `values` = the requested
+    columns' stored 8 bytes as np.uint64, bit c of `null_mask` = values[c] is NULL, `mapped` = the row came from the
+    index that names its documents through a doc map (a delta)."""
+    __slots__ = ("key", "values", "null_mask", "mapped")
+
+    def __init__(self, key, values, null_mask, mapped):
+        self.key, self.values, self.null_mask, self.mapped = key, values, null_mask, mapped
+
+
 class SearchResult:
     __slots__ = ("total", "docs", "scores", "total_candidates", "after_intersection", "after_not", "after_filters",
-                 "empty_term_detected", "term_order", "snippets", "facets")
+                 "empty_term_detected", "term_order", "snippets", "facets", "documents")
 
     def __init__(self):
         self.total = 0
@@ -492,6 +524,7 @@ class SearchResult:
         self.term_order = []
         self.snippets = []  # bytes per returned doc, when the query asked for highlight
         self.facets = []  # np.uint64 counts per value id, one array per requested facet column
+        self.documents = []  # PageDocument (or None) per returned doc, when the query asked for documents
 
 
 def _take_u32(ptr, n):
@@ -513,10 +546,19 @@ def _render_snippet(entry, opts):
     return buf.raw[:n.value]
 
 
+def _page_document(e):
+    """mgx_document_entry -> PageDocument, or None for a doc id no index of the batch holds."""
+    if not e.flags & _capi.DOC_FOUND:
+        return None
+    key = C.string_at(e.key, e.key_len) if e.flags & _capi.DOC_HAS_KEY else None
+    values = (np.ctypeslib.as_array(e.values, shape=(e.n_columns,)).copy() if e.n_columns else np.zeros(0, np.uint64))
+    return PageDocument(key, values, int(e.null_mask), bool(e.flags & _capi.DOC_MAPPED))
+
+
 class PreparedBatch:
     """mgx_batch: a compiled, device-resident batch of queries that can be executed repeatedly."""
 
-    def __init__(self, index, cqueries, keep, shells, orders, highlights=None, facets=None):
+    def __init__(self, index, cqueries, keep, shells, orders, highlights=None, facets=None, documents=None):
         self.index, self._keep, self._shells, self._orders = index, keep, shells, orders
         self.n = len(cqueries)
         self._h = None
@@ -527,6 +569,21 @@ class PreparedBatch:
             self._adopt(h)
         self._set_highlight(highlights)
         self._set_facets(facets)
+        self._set_documents(documents)
+
+    def _set_documents(self, documents, max_key_bytes=0):
+        """mgx_batch_set_documents: documents[i] = None or the column ids of device query i."""
+        self._documents = documents if documents and any(d is not None for d in documents) else None
+        if not self._documents or not self._h:
+            return
+        reqs = (_capi.DocumentRequest * self.n)()
+        for i, d in enumerate(self._documents):
+            if d is None:
+                continue
+            ids = (C.c_uint32 * max(len(d), 1))(*d)
+            self._keep.append(ids)
+            reqs[i] = _capi.DocumentRequest(1, len(d), ids)
+        check(load().mgx_batch_set_documents(self._h, reqs, self.n, max_key_bytes))
 
     def _set_facets(self, facets):
         """mgx_batch_set_facets: facets[i] = None or the column ids of device query i."""
@@ -570,7 +627,7 @@ class PreparedBatch:
                 load().mgx_batch_destroy(self._h)
             self._h = None
 
-    def reset(self, cqueries, keep, shells, orders, highlights=None, facets=None):
+    def reset(self, cqueries, keep, shells, orders, highlights=None, facets=None, documents=None):
         """mgx_batch_reset: the same batch object (device arenas, pinned result block) for a new set of queries."""
         self._keep, self._shells, self._orders = keep, shells, orders
         self.n = len(cqueries)
@@ -584,6 +641,7 @@ class PreparedBatch:
             check(load().mgx_batch_reset(self._h, arr, self.n))
         self._set_highlight(highlights)
         self._set_facets(facets)
+        self._set_documents(documents)
 
     def execute(self, stream=None):
         if self._h:
@@ -631,6 +689,9 @@ class PreparedBatch:
                 e = fv.entries[j]
                 counts_of.setdefault(e.query, []).append(
                     np.ctypeslib.as_array(e.counts, shape=(e.n_values,)).copy() if e.n_values else np.zeros(0, np.uint64))
+        dv = _capi.DocumentView()
+        if self._h and self._documents:
+            check(load().mgx_batch_fetch_documents(self._h, C.byref(dv)))
         out = []
         k = 0
         for qi, shell in enumerate(self._shells):
@@ -651,6 +712,8 @@ class PreparedBatch:
                 opts = self._highlights[k - 1][0]
                 s.snippets = [_render_snippet(hv.entries[r.docs_begin + j], opts) for j in range(r.n_docs)]
             s.facets = counts_of.get(k - 1, [])
+            if self._documents and self._documents[k - 1] is not None:
+                s.documents = [_page_document(dv.entries[r.docs_begin + j]) for j in range(r.n_docs)]
             out.append(s)
         return out
 
@@ -1261,10 +1324,12 @@ class Index:
             if shell is not None and w:
                 known = self.device_index.facet_values
                 shell.facets = [np.zeros(known.get(c, 0), np.uint64) for c in w]
+        # page documents: the requests of the device queries; a query resolved on the host has no page
+        documents = [getattr(q, "documents", None) for q, shell in zip(queries, shells) if shell is None]
         if into is not None:
-            into.reset(cqueries, keep, shells, orders, highlights, facets)
+            into.reset(cqueries, keep, shells, orders, highlights, facets, documents)
             return into
-        return PreparedBatch(self, cqueries, keep, shells, orders, highlights, facets)
+        return PreparedBatch(self, cqueries, keep, shells, orders, highlights, facets, documents)
 
     def facet_counts(self, query, column_id, n_values):
         """mgx_facet_counts: (matched documents, counts per value id) of the query's whole result set."""
