@@ -7,7 +7,7 @@ LIB := mygram-db_amd/libmygram_gpu.so
 CXXFLAGS := -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wextra -Wno-unused-parameter -Iinclude
 HIPFLAGS := --offload-arch=$(ARCH) $(CXXFLAGS)
 
-OBJS := $(CSRC)/mgx_kernels.o $(CSRC)/mgx_highlight.o $(CSRC)/mgx_colsort.o $(CSRC)/mgx_facet.o $(CSRC)/mgx_documents.o $(CSRC)/mgx_api.o $(CSRC)/mgx_compile.o $(CSRC)/mgx_columns.o $(CSRC)/mgx_tools.o
+OBJS := $(CSRC)/mgx_kernels.o $(CSRC)/mgx_highlight.o $(CSRC)/mgx_colsort.o $(CSRC)/mgx_facet.o $(CSRC)/mgx_documents.o $(CSRC)/mgx_build.o $(CSRC)/mgx_api.o $(CSRC)/mgx_compile.o $(CSRC)/mgx_columns.o $(CSRC)/mgx_tools.o
 
 SHIM := mygram-db_amd/libmygram_shim.so
 
@@ -28,11 +28,15 @@ $(CSRC)/mgx_facet.o: $(CSRC)/mgx_facet.hip $(CSRC)/mgx_facet.hpp
 # plan, which compiles without HIP)
 $(CSRC)/mgx_documents.o: $(CSRC)/mgx_documents.hip $(CSRC)/mgx_documents.hpp
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(CSRC)/mgx_api.o: $(CSRC)/mgx_api.cpp $(CSRC)/mgx_colsort.hpp $(CSRC)/mgx_pkey.hpp $(CSRC)/mgx_facet.hpp $(CSRC)/mgx_documents.hpp $(CSRC)/mgx_compile.hpp $(CSRC)/mgx_internal.hpp $(CSRC)/mgx_launch.hpp $(CSRC)/mgx_host.hpp $(CSRC)/mgx_highlight.hpp $(CSRC)/mgx_text.hpp include/mygram_gpu.h
+# the device column builder: a unit of its own as well (mgx_build.hpp also holds the key packing and the storage plan,
+# which compile without HIP)
+$(CSRC)/mgx_build.o: $(CSRC)/mgx_build.hip $(CSRC)/mgx_build.hpp $(CSRC)/mgx_text.hpp include/mygram_gpu.h
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+$(CSRC)/mgx_api.o: $(CSRC)/mgx_api.cpp $(CSRC)/mgx_build.hpp $(CSRC)/mgx_colsort.hpp $(CSRC)/mgx_pkey.hpp $(CSRC)/mgx_facet.hpp $(CSRC)/mgx_documents.hpp $(CSRC)/mgx_compile.hpp $(CSRC)/mgx_internal.hpp $(CSRC)/mgx_launch.hpp $(CSRC)/mgx_host.hpp $(CSRC)/mgx_highlight.hpp $(CSRC)/mgx_text.hpp include/mygram_gpu.h
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
 $(CSRC)/mgx_compile.o: $(CSRC)/mgx_compile.cpp $(CSRC)/mgx_compile.hpp $(CSRC)/mgx_internal.hpp $(CSRC)/mgx_host.hpp include/mygram_gpu.h
 	g++ $(CXXFLAGS) -c $< -o $@
-$(CSRC)/mgx_columns.o: $(CSRC)/mgx_columns.cpp $(CSRC)/mgx_host.hpp $(CSRC)/mgx_text.hpp include/mygram_gpu.h
+$(CSRC)/mgx_columns.o: $(CSRC)/mgx_columns.cpp $(CSRC)/mgx_build.hpp $(CSRC)/mgx_host.hpp $(CSRC)/mgx_text.hpp include/mygram_gpu.h
 	g++ $(CXXFLAGS) -pthread -c $< -o $@
 $(CSRC)/mgx_tools.o: $(CSRC)/mgx_tools.cpp include/mygram_tools.h $(CSRC)/mgx_fuzzy.hpp $(CSRC)/mgx_highlight.hpp $(CSRC)/mgx_text.hpp
 	g++ $(CXXFLAGS) -pthread -c $< -o $@
@@ -57,7 +61,7 @@ oracle:
 ablation:
 	$(HIPCC) $(HIPFLAGS) -DMGX_ABLATION -c $(CSRC)/mgx_kernels.hip -o /tmp/mgx_kernels_abl.o
 	$(HIPCC) $(HIPFLAGS) -DMGX_ABLATION -x hip -c $(CSRC)/mgx_api.cpp -o /tmp/mgx_api_abl.o
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o mygram-db_amd/libmygram_gpu_ablation.so /tmp/mgx_kernels_abl.o $(CSRC)/mgx_highlight.o $(CSRC)/mgx_colsort.o $(CSRC)/mgx_facet.o $(CSRC)/mgx_documents.o /tmp/mgx_api_abl.o $(CSRC)/mgx_compile.o $(CSRC)/mgx_columns.o $(CSRC)/mgx_tools.o -pthread
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o mygram-db_amd/libmygram_gpu_ablation.so /tmp/mgx_kernels_abl.o $(CSRC)/mgx_highlight.o $(CSRC)/mgx_colsort.o $(CSRC)/mgx_facet.o $(CSRC)/mgx_documents.o $(CSRC)/mgx_build.o /tmp/mgx_api_abl.o $(CSRC)/mgx_compile.o $(CSRC)/mgx_columns.o $(CSRC)/mgx_tools.o -pthread
 
 # the host pieces of mgx_colsort.hpp (key transform, collision scan) under the sanitizers: a stand-alone program, no GPU
 colsort-host-asan:
@@ -82,7 +86,12 @@ documents-host-asan:
 	g++ -O1 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -o documents_plan_check_asan tests/cpp/documents_plan_check.cpp
 	./documents_plan_check_asan
 
+# the host side of mgx_build.hpp (key packing, storage plan) and the decode rule of mgx_build.hip likewise
+build-host-asan:
+	g++ -O1 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -o build_host_check_asan tests/cpp/build_host_check.cpp
+	./build_host_check_asan
+
 clean:
-	rm -f $(OBJS) $(LIB) $(SHIM) colsort_host_check_asan colsort_host_check_lines.txt pksort_host_check_asan pksort_host_check_lines.txt highlight_original_host_check_asan highlight_original_host_check_lines.txt documents_plan_check_asan
+	rm -f $(OBJS) $(LIB) $(SHIM) build_host_check_asan colsort_host_check_asan colsort_host_check_lines.txt pksort_host_check_asan pksort_host_check_lines.txt highlight_original_host_check_asan highlight_original_host_check_lines.txt documents_plan_check_asan
 	$(MAKE) -C oracle clean
-.PHONY: all oracle clean ablation colsort-host-asan pksort-host-asan highlight-original-host-asan documents-host-asan
+.PHONY: all oracle clean ablation colsort-host-asan pksort-host-asan highlight-original-host-asan documents-host-asan build-host-asan

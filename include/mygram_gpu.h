@@ -97,6 +97,17 @@ typedef struct mgx_columns_view {
 /* Docs are first_doc_id, first_doc_id+1, ...; doc i's normalized text is text_bytes[text_off[i] .. text_off[i+1]). */
 int mgx_columns_build(const mgx_build_params* params, const uint8_t* text_bytes, const uint64_t* text_off,
                       uint32_t first_doc_id, uint64_t n_docs, mgx_columns** out);
+/* The same columns, built on HIP device `device`: every array and scalar of the result's view equals what
+ * mgx_columns_build returns for the same inputs, padding included, and every call that takes an mgx_columns takes it.
+ * params->n_threads is ignored. Nothing is read past text_bytes[text_off[n_docs]]. Safe to call from many threads.
+ * Refusals, in this order: NULL arguments, bad struct_size / version: MGX_ERR_INVALID_ARGUMENT; doc ids past uint32:
+ * MGX_ERR_OUT_OF_RANGE; ngram_size > 3 or an effective kanji_ngram_size > 3 (a gram is packed into 64 bits on the
+ * device): MGX_ERR_NOT_IMPLEMENTED; text_off that descends: MGX_ERR_INVALID_ARGUMENT; no HIP device: MGX_ERR_INTERNAL
+ * (there is no CPU fallback behind this call); 4 GiB of text or more, or temporary storage beyond the device's free
+ * memory (the message states both numbers; nothing stays allocated): MGX_ERR_OUT_OF_RANGE. After NOT_IMPLEMENTED or
+ * OUT_OF_RANGE, mgx_columns_build builds the same columns on the host. */
+int mgx_columns_build_device(const mgx_build_params* params, const uint8_t* text_bytes, const uint64_t* text_off,
+                             uint32_t first_doc_id, uint64_t n_docs, int device, mgx_columns** out);
 /* The reference's index dump ("MGIX" v1..v4: Index::SaveToStream / LoadFromData, src/index/index_serialization.cpp:113-194,
  * :260-420; posting lists as fixed-width deltas or Roaring portable bytes, src/index/posting_list.cpp:973-1073) ->
  * columns. The CRC32 trailer (v2+) is verified. A dump holds doc ids only: the view's tf / doc_len are NULL (an index

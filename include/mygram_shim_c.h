@@ -98,6 +98,9 @@ int mgxs_table_update_filters(mgxs_table* table, uint32_t doc_id, uint32_t n_fil
                               const int* types, const void* values, const char* const* strings);
 /* Index::SetMutationStaleness: recorded changes become visible at most this long after they were made (0: at once). */
 int mgxs_table_set_mutation_staleness(mgxs_table* table, uint64_t microseconds);
+/* Index::SetDeviceBuild: the column arrays of every later build of this table (the first, the delta rebuilds, compact) are
+ * built on its device (mgx_columns_build_device); what that builder declines is built on the host. 0 (default): the host. */
+int mgxs_table_set_device_build(mgxs_table* table, int on);
 /* Index::Compact: the main index rebuilt from the table's current documents; the delta goes. */
 int mgxs_table_compact(mgxs_table* table);
 int mgxs_table_mutation_stats(mgxs_table* table, uint64_t* main_documents, uint64_t* delta_documents,

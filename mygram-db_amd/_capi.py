@@ -20,7 +20,7 @@ GATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
 
 EXPORTS = [
     "mgx_abi_version", "mgx_last_error", "mgx_free", "mgx_device_count",
-    "mgx_columns_build", "mgx_columns_from_mgix", "mgx_dump_open", "mgx_dump_view_get", "mgx_dump_filter_column_get",
+    "mgx_columns_build", "mgx_columns_build_device", "mgx_columns_from_mgix", "mgx_dump_open", "mgx_dump_view_get", "mgx_dump_filter_column_get",
     "mgx_dump_take_columns", "mgx_dump_destroy", "mgx_columns_view_get", "mgx_columns_lookup", "mgx_columns_destroy",
     "mgx_index_create", "mgx_index_destroy", "mgx_posting_size", "mgx_index_memory_bytes",
     "mgx_index_add_filter_bitmap", "mgx_index_add_filter_column", "mgx_index_filter_compare", "mgx_facet_counts",
@@ -213,6 +213,7 @@ def load():
     L.mgx_free.restype = None
     L.mgx_device_count.restype = i32
     L.mgx_columns_build.argtypes = [C.POINTER(BuildParams), vp, vp, u32, u64, C.POINTER(vp)]
+    L.mgx_columns_build_device.argtypes = [C.POINTER(BuildParams), vp, vp, u32, u64, C.c_int, C.POINTER(vp)]
     L.mgx_columns_view_get.argtypes = [vp, C.POINTER(ColumnsView)]
     L.mgx_columns_lookup.argtypes = [vp, C.c_char_p, sz, C.POINTER(u32), C.POINTER(i32)]
     L.mgx_columns_destroy.argtypes = [vp]

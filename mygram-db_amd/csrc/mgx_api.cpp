@@ -34,6 +34,7 @@
 #include "mgx_pkey.hpp"
 #include "mgx_facet.hpp"
 #include "mgx_documents.hpp"
+#include "mgx_build.hpp"
 #include "mgx_host.hpp"
 #include "mgx_internal.hpp"
 #include "mgx_launch.hpp"
@@ -620,6 +621,46 @@ int mgx_columns_build(const mgx_build_params* params, const uint8_t* text_bytes,
     return MGX_OK;
   } catch (const std::exception& e) {
     return mgx::Fail(MGX_ERR_INTERNAL, std::string("mgx_columns_build: ") + e.what());
+  }
+}
+
+int mgx_columns_build_device(const mgx_build_params* params, const uint8_t* text_bytes, const uint64_t* text_off,
+                             uint32_t first_doc_id, uint64_t n_docs, int device, mgx_columns** out) {
+  if (out) *out = nullptr;
+  // ---- host-only checks first: they answer without a device ---------------------------------------------------------------
+  if (!params || !out || !text_off || (n_docs && !text_bytes && text_off[n_docs] != text_off[0]))
+    return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_columns_build_device: null argument");
+  if (params->struct_size < sizeof(mgx_build_params) || params->version != MGX_ABI_VERSION)
+    return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_columns_build_device: bad struct_size/version");
+  if (static_cast<uint64_t>(first_doc_id) + n_docs > 0xFFFFFFFFull)
+    return mgx::Fail(MGX_ERR_OUT_OF_RANGE, "mgx_columns_build_device: doc ids exceed uint32");
+  const int kanji_n = params->kanji_ngram_size > 0 ? params->kanji_ngram_size : params->ngram_size;
+  if (params->ngram_size > mgx::build::kMaxGram || kanji_n > mgx::build::kMaxGram)
+    return mgx::Fail(MGX_ERR_NOT_IMPLEMENTED,
+                     "mgx_columns_build_device: n-grams of more than 3 code points are not built on the device (a gram is "
+                     "packed into 64 bits); use mgx_columns_build");
+  for (uint64_t d = 0; d < n_docs; ++d)
+    if (text_off[d + 1] < text_off[d])
+      return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_columns_build_device: text_off descends");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+    (void)hipGetLastError();
+    return mgx::Fail(MGX_ERR_INTERNAL, "no HIP device available: libmygram_gpu has no CPU fallback");
+  }
+  if (device < 0 || device >= ndev) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_columns_build_device: bad device");
+  if (text_off[n_docs] - text_off[0] > mgx::build::kMaxTextBytes)
+    return mgx::Fail(MGX_ERR_OUT_OF_RANGE, "mgx_columns_build_device: " + std::to_string(text_off[n_docs] - text_off[0]) +
+                                               " bytes of text, the device builder takes " +
+                                               std::to_string(mgx::build::kMaxTextBytes) + "; use mgx_columns_build");
+  try {
+    mgx::build::PackedColumns packed;
+    std::string err;
+    const int rc = mgx::build::BuildOnDevice(*params, text_bytes, text_off, first_doc_id, n_docs, device, &packed, &err);
+    if (rc != MGX_OK) return mgx::Fail(rc, err);
+    *out = reinterpret_cast<mgx_columns*>(mgx::ColumnsFromPacked(*params, text_off, first_doc_id, n_docs, std::move(packed)));
+    return MGX_OK;
+  } catch (const std::exception& e) {
+    return mgx::Fail(MGX_ERR_INTERNAL, std::string("mgx_columns_build_device: ") + e.what());
   }
 }
 

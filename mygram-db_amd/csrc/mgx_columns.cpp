@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/mygram_gpu.h"
+#include "mgx_build.hpp"
 #include "mgx_host.hpp"
 #include "mgx_text.hpp"
 
@@ -531,6 +532,49 @@ int BuildColumns(const mgx_build_params& bp, const uint8_t* text_bytes, const ui
   }
   *out = cols.release();
   return MGX_OK;
+}
+
+// The device builder's result (mgx_build.hip) as Columns: the packed keys become the 128-bit keys and the key bytes (G is
+// small beside the postings); every other array is taken as it came.
+Columns* ColumnsFromPacked(const mgx_build_params& bp, const uint64_t* text_off, uint32_t first_doc_id, uint64_t n_docs,
+                           build::PackedColumns&& p) {
+  auto cols = std::make_unique<Columns>();
+  cols->params = bp;
+  cols->first_doc_id = first_doc_id;
+  cols->n_docs = n_docs;
+  cols->doc_len = std::move(p.doc_len);
+  for (uint64_t d = 0; d < n_docs; ++d)
+    if (text_off[d + 1] > text_off[d]) {  // counted when the text has BYTES (binlog_event_processor.cpp:98-99)
+      cols->bm25_doc_count++;
+      cols->bm25_total_len += cols->doc_len[d];
+    }
+  const uint64_t G = p.keys.size();
+  cols->sorted_keys.resize(G);
+  cols->key_off.resize(G + 1);
+  cols->key_off[0] = 0;
+  cols->key_bytes.reserve(G * 4);
+  for (uint64_t g = 0; g < G; ++g) {
+    uint8_t buf[4 * build::kMaxGram];
+    size_t nb = 0;
+    for (int j = 0; j < build::kMaxGram; ++j) {
+      const uint32_t f = build::KeyField(p.keys[g], j);
+      if (f) nb += EncodeUtf8(f - 1, buf + nb);
+    }
+    cols->sorted_keys[g] = MakeKey(buf, nb);
+    cols->key_bytes.insert(cols->key_bytes.end(), buf, buf + nb);
+    cols->key_off[g + 1] = static_cast<uint32_t>(cols->key_bytes.size());
+  }
+  cols->key_bytes.shrink_to_fit();
+  cols->offsets = std::move(p.offsets);
+  cols->docids = std::move(p.docids);
+  cols->tf = std::move(p.tf);
+  cols->tf_ovf_pos.reserve(p.overflow.size());
+  cols->tf_ovf_val.reserve(p.overflow.size());
+  for (uint64_t e : p.overflow) {
+    cols->tf_ovf_pos.push_back(e >> 32);
+    cols->tf_ovf_val.push_back(static_cast<uint32_t>(e));
+  }
+  return cols.release();
 }
 
 void ColumnsView(const Columns* c, mgx_columns_view* v) {

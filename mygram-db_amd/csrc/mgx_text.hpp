@@ -11,7 +11,8 @@
 #include <utility>
 #include <vector>
 
-// ParseUtf8 is also compiled for the device (the fuzzy matcher of the tile kernel, mgx_fuzzy.hpp)
+// ParseUtf8 is also compiled for the device (the fuzzy matcher of the tile kernel, mgx_fuzzy.hpp), and so are EncodeUtf8,
+// IsCjkIdeograph and the pointer form of WindowAt (the device column builder, mgx_build.hip)
 #if defined(__HIPCC__)
 #define MGX_TEXT_HD __host__ __device__ inline
 #else
@@ -50,7 +51,7 @@ MGX_TEXT_HD int ParseUtf8(const uint8_t* d, size_t avail, uint32_t* cp) {
 }
 
 // src/utils/string_utils.cpp:241-272 (CodepointsToUtf8, one code point)
-inline size_t EncodeUtf8(uint32_t c, uint8_t* o) {
+MGX_TEXT_HD size_t EncodeUtf8(uint32_t c, uint8_t* o) {
   if (c <= 0x7F) {
     o[0] = static_cast<uint8_t>(c);
     return 1;
@@ -74,7 +75,7 @@ inline size_t EncodeUtf8(uint32_t c, uint8_t* o) {
 }
 
 // src/utils/string_utils.cpp:441-448 — kana is NOT an ideograph here
-inline bool IsCjkIdeograph(uint32_t c) {
+MGX_TEXT_HD bool IsCjkIdeograph(uint32_t c) {
   return (c >= 0x4E00 && c <= 0x9FFF) || (c >= 0x3400 && c <= 0x4DBF) || (c >= 0x20000 && c <= 0x2A6DF) ||
          (c >= 0x2A700 && c <= 0x2B73F) || (c >= 0x2B740 && c <= 0x2B81F) || (c >= 0xF900 && c <= 0xFAFF);
 }
@@ -107,6 +108,16 @@ inline int WindowAt(const std::vector<uint32_t>& cps, size_t p, int ascii_n, int
   const bool cjk = IsCjkIdeograph(cps[p]);
   const int w = cjk ? kanji_n : ascii_n;
   if (w <= 0 || p + static_cast<size_t>(w) > cps.size()) return 0;
+  if (!cross)
+    for (int j = 1; j < w; ++j)
+      if (IsCjkIdeograph(cps[p + j]) != cjk) return 0;
+  return w;
+}
+// The same over a plain array of n code points (host and device)
+MGX_TEXT_HD int WindowAt(const uint32_t* cps, size_t n, size_t p, int ascii_n, int kanji_n, bool cross) {
+  const bool cjk = IsCjkIdeograph(cps[p]);
+  const int w = cjk ? kanji_n : ascii_n;
+  if (w <= 0 || p + static_cast<size_t>(w) > n) return 0;
   if (!cross)
     for (int j = 1; j < w; ++j)
       if (IsCjkIdeograph(cps[p + j]) != cjk) return 0;

@@ -201,6 +201,7 @@ void ClearDeviceErrorForSorter() { ClearDeviceError(); }
 struct Index::Impl {
   int device = 0;
   double dense_threshold = 0.0;
+  std::atomic<bool> device_build{false};  // SetDeviceBuild: column arrays are built by mgx_columns_build_device
   int query_kanji = 0;  // table-config kanji size used for QUERY n-grams (the Index itself keeps kanji = ngram if 0)
   mutable std::mutex mu;
   mutable std::map<DocId, std::string> pending;  // documents recorded before the first search
@@ -536,6 +537,7 @@ struct GenerationSpec {
   const uint64_t* text_off = nullptr;
   DocId first = 1;
   uint64_t n = 0;
+  bool device_build = false;  // build the column arrays on `device` (the host builds what the device builder declines)
   const std::vector<DocId>* existing = nullptr;  // the ids that exist, when some of [first, first + n) do not
   const NamedValues* columns = nullptr;          // filter values by doc slot
   const std::map<DocId, std::string>* primary_keys = nullptr;  // the table's (those of [first, first + n) are taken)
@@ -611,9 +613,21 @@ std::string BuildGeneration(const GenerationSpec& in, Index::Impl::Generation* o
   g.handles = std::make_shared<Index::Impl::Handles>();  // (owns what follows: gone with `g` on every early return)
   g.handles->cols = in.cols;
   const auto t0 = std::chrono::steady_clock::now();
+  bool on_device = false;
   if (!g.handles->cols) {
     mgx_build_params bp{sizeof(mgx_build_params), MGX_ABI_VERSION, in.ngram, in.kanji, in.cross ? 1 : 0, 0};
-    if (mgx_columns_build(&bp, in.text_bytes, in.text_off, in.first, in.n, &g.handles->cols) != MGX_OK) {
+    int rc = MGX_ERR_NOT_IMPLEMENTED;
+    if (in.device_build) {
+      // what the device builder declines (grams of more than 3 code points, no room on the device) the host builds: the
+      // result is the same by contract. Every other error is the caller's.
+      rc = mgx_columns_build_device(&bp, in.text_bytes, in.text_off, in.first, in.n, in.device, &g.handles->cols);
+      on_device = rc == MGX_OK;
+      if (rc != MGX_OK && rc != MGX_ERR_NOT_IMPLEMENTED && rc != MGX_ERR_OUT_OF_RANGE) {
+        g.handles->cols = nullptr;
+        return mgx_last_error();
+      }
+    }
+    if (rc != MGX_OK && mgx_columns_build(&bp, in.text_bytes, in.text_off, in.first, in.n, &g.handles->cols) != MGX_OK) {
       g.handles->cols = nullptr;
       return mgx_last_error();
     }
@@ -634,8 +648,9 @@ std::string BuildGeneration(const GenerationSpec& in, Index::Impl::Generation* o
   // counted in the text on the device
   if (in.text_bytes && mgx_index_attach_text(dev, in.text_bytes, in.text_off) != MGX_OK) return mgx_last_error();
   if (kTrace)
-    fprintf(stderr, "[shim] generation of %llu docs: columns %.2f ms, device index %.2f ms, texts %.2f ms\n",
-            static_cast<unsigned long long>(v.n_docs), std::chrono::duration<double, std::milli>(t1 - t0).count(),
+    fprintf(stderr, "[shim] generation of %llu docs: columns (%s) %.2f ms, device index %.2f ms, texts %.2f ms\n",
+            static_cast<unsigned long long>(v.n_docs), in.cols ? "given" : on_device ? "device builder" : "host builder",
+            std::chrono::duration<double, std::milli>(t1 - t0).count(),
             std::chrono::duration<double, std::milli>(t2 - t1).count(),
             std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t2).count());
   // DocumentStore::GetAllDocIds (the NOT universe of boolean expressions) is the set of ids that were added (deleted ids
@@ -1098,6 +1113,7 @@ BuiltDelta BuildDelta(const Index& self, const std::map<DocId, std::string>& doc
   auto nd = std::make_shared<Index>(self.GetNgramSize(), im->query_kanji, im->dense_threshold, self.GetCrossBoundaryNgrams(),
                                     self.GetNormalizeNfkc(), self.GetNormalizeWidth(), self.GetNormalizeLower(), im->device);
   nd->impl()->internal = true;
+  nd->impl()->device_build = im->device_build.load();
   std::vector<DocId> ids;
   ids.reserve(docs.size());
   DocId local = 1;
@@ -1312,6 +1328,8 @@ std::string ApplyLocked(const Index& self, bool force) {
 }
 }  // namespace
 
+void Index::SetDeviceBuild(bool on) { impl_->device_build = on; }
+
 void Index::SetMutationStaleness(std::chrono::microseconds max_staleness) {
   std::lock_guard<std::mutex> lock(impl_->mu);
   impl_->mut.staleness = max_staleness;
@@ -1404,6 +1422,7 @@ std::string Index::Compact() const {
   // ---- the new generation ----------------------------------------------------------------------------------------------
   GenerationSpec spec{im->device, im->dense_threshold, ngram_size_, kanji_ngram_size_, cross_boundary_, nullptr,
                       bytes.data(), off.data(),    first,       n2};
+  spec.device_build = im->device_build.load();
   if (existing.size() != n2) spec.existing = &existing;
   spec.columns = &columns;
   spec.primary_keys = &im->primary_keys;  // (removed documents' keys are gone from it: a gap of the new range has none)
@@ -1489,6 +1508,7 @@ std::string Index::Finalize() const {
   impl_->pending.clear();
   GenerationSpec spec{impl_->device, impl_->dense_threshold, ngram_size_, kanji_ngram_size_, cross_boundary_, nullptr,
                       bytes.data(),  off.data(),             first,       n};
+  spec.device_build = impl_->device_build.load();
   if (existing.size() != n && !existing.empty()) spec.existing = &existing;
   spec.primary_keys = &impl_->primary_keys;
   spec.originals = &impl_->originals;

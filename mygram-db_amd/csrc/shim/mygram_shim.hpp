@@ -227,6 +227,11 @@ class Index {
   // queries run on the old state, and installed (a few milliseconds) by the next entry point that finds it ready.
   // 0 (default): every query sees every change recorded before it.
   void SetMutationStaleness(std::chrono::microseconds max_staleness);
+  // Column arrays (the initial build, the delta rebuild of ApplyMutations, Compact) are built on the index's device by
+  // mgx_columns_build_device instead of on the host. The arrays are the same either way; what the device builder declines
+  // (grams of more than 3 code points, no room on the device) is built on the host. Off by default. Takes effect with the
+  // next build.
+  void SetDeviceBuild(bool on);
   // Folds the delta back: the main index is rebuilt from the table's current documents (the texts of its live documents come
   // back from the device, where BM25 keeps them; filter values likewise) and the delta and the live row go. What the
   // reference's Optimize / a dump-and-reload do for a grown index. Same exclusion rule as the mutation-applying entry

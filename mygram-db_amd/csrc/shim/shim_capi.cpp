@@ -393,6 +393,12 @@ int mgxs_table_update_filters(mgxs_table* table, uint32_t doc_id, uint32_t n_fil
   }
 }
 
+int mgxs_table_set_device_build(mgxs_table* table, int on) {
+  if (!table) return Fail(MGX_ERR_INVALID_ARGUMENT, "mgxs_table_set_device_build: null argument");
+  table->index->SetDeviceBuild(on != 0);
+  return MGX_OK;
+}
+
 int mgxs_table_set_mutation_staleness(mgxs_table* table, uint64_t microseconds) {
   if (!table) return Fail(MGX_ERR_INVALID_ARGUMENT, "mgxs_table_set_mutation_staleness: null argument");
   table->index->SetMutationStaleness(std::chrono::microseconds(microseconds));

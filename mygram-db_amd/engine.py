@@ -161,16 +161,22 @@ class Corpus:
 
 
 class Columns:
-    """mgx_columns: gram dictionary + CSR postings + tf + doc_len, built on the host by libmygram_gpu."""
+    """mgx_columns: gram dictionary + CSR postings + tf + doc_len, built by libmygram_gpu: on the host, or with
+    `device=k` on HIP device k (mgx_columns_build_device: the same arrays)."""
 
-    def __init__(self, corpus, first_doc_id=1, ngram_size=2, kanji_ngram_size=0, cross_boundary=True, n_threads=0):
+    def __init__(self, corpus, first_doc_id=1, ngram_size=2, kanji_ngram_size=0, cross_boundary=True, n_threads=0,
+                 device=None):
         L = load()
         self.ngram_size, self.kanji_ngram_size, self.cross_boundary = ngram_size, kanji_ngram_size, cross_boundary
         bp = _capi.BuildParams(C.sizeof(_capi.BuildParams), _capi.ABI_VERSION, ngram_size, kanji_ngram_size,
                                int(cross_boundary), n_threads)
         h = C.c_void_p()
-        check(L.mgx_columns_build(C.byref(bp), corpus.text_bytes.ctypes.data, corpus.text_off.ctypes.data,
-                                  first_doc_id, corpus.n_docs, C.byref(h)))
+        if device is None:
+            check(L.mgx_columns_build(C.byref(bp), corpus.text_bytes.ctypes.data, corpus.text_off.ctypes.data,
+                                      first_doc_id, corpus.n_docs, C.byref(h)))
+        else:
+            check(L.mgx_columns_build_device(C.byref(bp), corpus.text_bytes.ctypes.data, corpus.text_off.ctypes.data,
+                                             first_doc_id, corpus.n_docs, int(device), C.byref(h)))
         self._adopt(h)
 
     @classmethod
@@ -779,7 +785,7 @@ class Index:
 
     def __init__(self, corpus=None, texts=None, first_doc_id=1, ngram_size=2, kanji_ngram_size=0, cross_boundary=True,
                  device=0, dense_threshold=0.0, total_docs=None, avg_doc_length=None, global_posting_sizes=None,
-                 n_threads=0, normalize_nfkc=True, normalize_width="keep", normalize_lower=True):
+                 n_threads=0, normalize_nfkc=True, normalize_width="keep", normalize_lower=True, build_device=None):
         if corpus is None:
             corpus = Corpus.from_texts(texts if texts is not None else [])
         self.ngram_size = ngram_size
@@ -788,7 +794,8 @@ class Index:
         self.cross_boundary = cross_boundary
         # index.h:58-60: how QUERY terms are normalised; document texts arrive normalised (as Index::AddDocument's do)
         self.normalize_nfkc, self.normalize_width, self.normalize_lower = normalize_nfkc, normalize_width, normalize_lower
-        self.columns = Columns(corpus, first_doc_id, ngram_size, kanji_ngram_size, cross_boundary, n_threads)
+        self.columns = Columns(corpus, first_doc_id, ngram_size, kanji_ngram_size, cross_boundary, n_threads,
+                               device=build_device)
         self.device_index = DeviceIndex(self.columns, device, dense_threshold)
         self.corpus = corpus        # the DocumentStore's normalized texts
         self._text_attached = False
