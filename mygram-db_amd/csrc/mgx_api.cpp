@@ -32,6 +32,7 @@
 #include "mgx_highlight.hpp"
 #include "mgx_colsort.hpp"
 #include "mgx_pkey.hpp"
+#include "mgx_pages.hpp"
 #include "mgx_facet.hpp"
 #include "mgx_documents.hpp"
 #include "mgx_build.hpp"
@@ -2923,6 +2924,20 @@ static documents::DevSource DocumentSource(const mgx_index* ix, const mgx_batch*
   return src;
 }
 
+// The batches of a merged page by how their index names its documents: `mapped` by table id through its doc map (the
+// delta of a mutable table), `plain` by its own ids (the main index). False: a second batch of either kind.
+static bool MainAndDelta(const mgx_batch* primary, mgx_batch* const* others, uint32_t n_others, const mgx_batch** mapped,
+                         const mgx_batch** plain) {
+  *mapped = *plain = nullptr;
+  for (uint32_t j = 0; j <= n_others; ++j) {
+    const mgx_batch* x = j == 0 ? primary : others[j - 1];
+    const mgx_batch*& slot = x->idx->d_doc_map.p ? *mapped : *plain;
+    if (slot) return false;
+    slot = x;
+  }
+  return true;
+}
+
 // A table with a delta: the two batches carry requests of the same shape (each with its own index's column ids), and both
 // indexes hold key bytes.
 static int CheckDocumentSides(const mgx_batch* primary, const mgx_batch* other, const char* entry) {
@@ -2961,22 +2976,15 @@ static int RunDocuments(mgx_batch* b, hipStream_t s, bool merged, const mgx_batc
 
 // Page documents of the bitmap group, where its pages are cut (FetchBitmapPages): the page sizes are known on the host,
 // so the records are packed by them behind the early queries' and one copy brings exactly those. `pdocs`: the group's
-// pages on the device, query i's at page_off[i], page_n[i] entries. The caller's synchronisation covers kernel and copy.
-static int RunLateDocuments(mgx_batch* a, hipStream_t s, const std::vector<uint64_t>& page_off,
-                            const std::vector<uint64_t>& page_n, const uint32_t* pdocs) {
+// pages on the device, query i's as the plan places it. The caller's synchronisation covers kernel and copy.
+static int RunLateDocuments(mgx_batch* a, hipStream_t s, const pages::Plan& plan, const uint32_t* pdocs) {
   mgx_batch::Documents& d = a->doc;
   mgx_batch* const other = a->merge_other;
   const mgx_batch* mapped = nullptr;
   const mgx_batch* plain = a;  // (one index: its own ids)
   if (other) {
-    mapped = plain = nullptr;
-    for (const mgx_batch* x : {static_cast<const mgx_batch*>(a), static_cast<const mgx_batch*>(other)}) {
-      const mgx_batch*& slot = x->idx->d_doc_map.p ? mapped : plain;
-      if (slot) return Fail(MGX_ERR_NOT_IMPLEMENTED, "mgx_batch_fetch: page documents read one main index and one delta");
-      slot = x;
-    }
-  }
-  if (other) {
+    if (!MainAndDelta(a, &other, 1, &mapped, &plain))
+      return Fail(MGX_ERR_NOT_IMPLEMENTED, "mgx_batch_fetch: page documents read one main index and one delta");
     const int rc = CheckDocumentSides(a, other, "mgx_batch_fetch");
     if (rc) return rc;
   }
@@ -2990,10 +2998,10 @@ static int RunLateDocuments(mgx_batch* a, hipStream_t s, const std::vector<uint6
     const size_t pi = static_cast<size_t>(d.of_query[g.qids[i]]);
     const documents::QueryPlan& qp = d.plan.queries[pi];
     d.fetch_off[pi] = at;
-    const uint32_t n = static_cast<uint32_t>(std::min<uint64_t>(page_n[i], qp.limit));
+    const uint32_t n = static_cast<uint32_t>(std::min<uint64_t>(plan.queries[i].page_n, qp.limit));
     if (n == 0) continue;
     documents::DevQuery q{};
-    q.page_docs = pdocs + page_off[i];
+    q.page_docs = pdocs + plan.queries[i].page_off;
     q.limit = n;
     q.count = n;
     q.entry_begin = n_entries;
@@ -3254,368 +3262,326 @@ static std::vector<double> DeepIdfs(const mgx_batch* b, const QuerySpec& sp) {
 //     sorted by primary key come from key_merge_kernel instead when two sides merge and not both hold numeric keys
 //     only: their values are ranks in two dictionaries, or a rank and a number, and compare as key strings.
 // Everything lives in the batch's d_merge scratch. On the delta's batch of a merge (merged_away) every page is empty:
-// the primary's fetch returned them.
+// the primary's fetch returned them. All sizes, offsets and run descriptors come from pages::Build (mgx_pages.hpp, host
+// only); FetchBitmapPages reads the totals, fills the plan's inputs and runs the steps below in the order of this list.
 struct BitmapPages {
   std::vector<uint64_t> total, page_off, page_n;
   std::vector<uint32_t> docs;
   std::vector<double> scores;  // (deep SORT _score pages only)
 };
 
-static uint64_t Align8(uint64_t x) { return (x + 7) & ~7ull; }
+// What the steps of one fetch share: its sides, its stream and, once the plan is uploaded, the typed arrays of d_merge.
+struct SortCol {
+  const uint64_t* values;
+  const uint8_t* is_null;
+  uint32_t value_class;
+};
+struct PageSide {
+  mgx_batch* batch = nullptr;
+  const uint32_t* doc_map = nullptr;  // a merge: local slot -> table id; one index returns its own ids
+  // SORT by primary key: the index's key column (no keys set: no values, the value is the table doc id)
+  pkey::KeySide keys{pkey::kKeyNumeric, nullptr, nullptr};
+  const uint64_t* key_values = nullptr;
+  std::map<uint32_t, SortCol> columns;  // every sort column its queries name (pages::kKeyColumn: the key column), looked up once
+  std::vector<uint64_t> take, out_off;  // (sources of ExpandSides' copies: they live until the fetch has synchronised)
+  const QuerySpec& spec(size_t i) const { return batch->specs[batch->bitmap.qids[i]]; }
+};
+struct PageFetch {
+  mgx_batch* a = nullptr;
+  int n_side = 1;
+  size_t n = 0;  // queries of the group
+  hipStream_t s = nullptr;
+  PageSide side[2];
+  std::vector<char> up;  // (source of UploadPlan's copy, likewise)
+  char* base = nullptr;
+  uint32_t *docs = nullptr, *dprime = nullptr, *pdocs = nullptr;
+  uint64_t* keys = nullptr;
+  double *scores = nullptr, *pscores = nullptr;
+  template <typename T>
+  T* at(uint64_t off) const { return reinterpret_cast<T*>(base + off); }
+};
+
+// [n, cap) of a run of (key, docid') pairs: padding (0, 0) that sorts to the tail.
+static int PadPairs(uint64_t* keys, uint32_t* dprime, uint64_t n, uint64_t cap, hipStream_t s) {
+  if (cap > n) {
+    MGX_HIP(hipMemsetAsync(keys + n, 0, (cap - n) * 8, s));
+    MGX_HIP(hipMemsetAsync(dprime + n, 0, (cap - n) * 4, s));
+  }
+  return MGX_OK;
+}
 
 // One scored run as (key, docid') pairs sorted best first by the bitonic network: keys/dprime[0, n) from docs and
-// scores, [n, n2) padding (0, 0) that sorts to the tail (n2: a power of two, at least one LDS run).
+// scores, [n, n2) padding (n2: pages::SortCapacity(n)).
 static int SortRun(const uint32_t* docs, const double* scores, uint64_t n, uint64_t n2, int descending, uint64_t* keys,
                    uint32_t* dprime, hipStream_t s) {
-  if (n2 > n) {
-    MGX_HIP(hipMemsetAsync(keys + n, 0, (n2 - n) * 8, s));
-    MGX_HIP(hipMemsetAsync(dprime + n, 0, (n2 - n) * 4, s));
-  }
+  if (const int rc = PadPairs(keys, dprime, n, n2, s)) return rc;
   MGX_LAUNCH(LaunchMakeSortKeys(docs, scores, n, descending, keys, dprime, s));
   MGX_LAUNCH(LaunchSortPairs(keys, dprime, n2, s));
   return MGX_OK;
 }
 
-static int FetchBitmapPages(mgx_batch* a, BitmapPages* m) {
-  mgx_batch* const side[2] = {a, a->merge_other};
-  const int n_side = a->merge_other ? 2 : 1;
-  hipStream_t s = n_side == 2 ? a->merge_stream : a->last_stream;
-  mgx_batch::Group& g = a->bitmap;
-  const size_t n = g.qids.size();
-  for (int k = 0; k < n_side; ++k)
-    if (side[k]->last_stream != s) MGX_HIP(hipStreamSynchronize(side[k]->last_stream));
-  // ---- the one synchronisation of the group: counters of the primary, totals of every side ----
-  std::vector<uint64_t> tot[2] = {std::vector<uint64_t>(n), std::vector<uint64_t>(n)};
-  MGX_HIP(hipMemcpyAsync(g.h_counters.data(), g.d_counters.p, n * 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-  for (int k = 0; k < n_side; ++k)
-    MGX_HIP(hipMemcpyAsync(tot[k].data(), side[k]->d_totals.p, n * 8, hipMemcpyDeviceToHost, s));
-  MGX_HIP(hipStreamSynchronize(s));
-  // ---- sizes and the scratch layout ----
-  m->total.resize(n);
-  m->page_off.resize(n);
-  m->page_n.resize(n);
-  std::vector<uint64_t> take[2], off[2], soff[2], koff[2], n2[2], toff[2], run_n[2];
-  std::vector<int> job_side;
-  std::vector<uint32_t> job_column;
-  std::vector<colsort::TopkJob> jobs;  // SORT <filter column> pages the fused selection serves, one per (query, side)
+// The one synchronisation of the group: counters of the primary, totals of every side (side k's at totals[k * n]).
+static int ReadTotals(const PageFetch& f, std::vector<uint64_t>* totals) {
+  mgx_batch::Group& g = f.a->bitmap;
+  totals->assign(f.n_side * f.n, 0);
+  MGX_HIP(hipMemcpyAsync(g.h_counters.data(), g.d_counters.p, f.n * 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, f.s));
+  for (int k = 0; k < f.n_side; ++k)
+    MGX_HIP(hipMemcpyAsync(totals->data() + k * f.n, f.side[k].batch->d_totals.p, f.n * 8, hipMemcpyDeviceToHost, f.s));
+  MGX_HIP(hipStreamSynchronize(f.s));
+  return MGX_OK;
+}
+
+// What pages::Build reads of the two batches. Each side's key column and sort columns are read under that index's lock
+// (a column is immutable once added; the vector that holds them may grow).
+static pages::Input PlanInput(PageFetch& f, const std::vector<uint64_t>& totals) {
+  const mgx_batch* a = f.a;
+  const mgx_batch::Group& g = a->bitmap;
+  pages::Input in;
+  in.n_side = f.n_side;
+  in.merged_away = a->merged_away;
   const char* const full_env = std::getenv("MGX_COLSORT_FULL");
-  const bool colsort_full = full_env != nullptr && full_env[0] != '\0' && full_env[0] != '0';
-  uint64_t n_lists = 0;
-  uint32_t n_groups_total = 0, max_cap = 0, max_job_elems = 0;
-  // SORT by primary key: each side's key column, read under that index's lock
-  constexpr uint32_t kKeyColumn = 0xFFFFFFFFu;  // its place among a side's resolved sort columns
-  struct SideKeys {
-    pkey::KeySide side{pkey::kKeyNumeric, nullptr, nullptr};
-    const uint64_t* values = nullptr;  // nullptr: no keys set, the value is the table doc id
-  };
-  SideKeys pk[2];
+  in.colsort_full = full_env != nullptr && full_env[0] != '\0' && full_env[0] != '0';
+  in.queries.resize(f.n);
   bool any_pk = false;
-  for (size_t i = 0; i < n && !any_pk; ++i) any_pk = a->specs[g.qids[i]].pk_sort && a->specs[g.qids[i]].col_sort;
-  if (any_pk)
-    for (int k = 0; k < n_side; ++k) {
-      const mgx_index* ix = side[k]->idx;
-      std::lock_guard<std::mutex> lock(const_cast<mgx_index*>(ix)->mu);
-      if (!ix->has_pkeys) continue;
-      pk[k].side = pkey::KeySide{ix->pk_kind, ix->d_pk_off.as<uint64_t>(), ix->d_pk_bytes.as<uint8_t>()};
-      pk[k].values = ix->d_pk_values.as<uint64_t>();
-    }
-  // two sides whose values do not compare as numbers: those pages are merged by key string
-  const bool merge_by_string = n_side == 2 && !(pk[0].side.kind == pkey::kKeyNumeric && pk[1].side.kind == pkey::kKeyNumeric);
-  std::vector<pkey::KeyMergeRun> kruns;
-  std::vector<uint64_t> krun_start;
-  std::vector<size_t> krun_query;
-  uint64_t kelems = 0;
-  for (int k = 0; k < 2; ++k) {
-    run_n[k].assign(n, 0);
-    take[k].assign(n, 0);
-    off[k].assign(n, 0);
-    soff[k].assign(n, 0);
-    koff[k].assign(n, 0);
-    n2[k].assign(n, 0);
-    toff[k].assign(n, 0);
-  }
-  std::vector<DevMergeRun> runs(n);
-  std::vector<uint64_t> run_start(n + 1);
-  std::vector<uint32_t> terms;
-  std::vector<double> idfs;
-  uint64_t at[2] = {0, 0}, n_scores = 0, n_keys = 0, pages = 0, elems = 0;
-  for (size_t i = 0; i < n; ++i) {
+  for (size_t i = 0; i < f.n; ++i) {
     const QuerySpec& sp = a->specs[g.qids[i]];
-    const uint64_t t = a->merged_away ? 0 : tot[0][i] + tot[1][i];  // (merged_away: sizes the empty page only)
-    uint64_t lo = 0, hi = 0;
-    if (a->fc.faceted(g.qids[i])) {
-      // a faceted query returns its counts, no page: nothing is expanded for it
-    } else if (sp.deep_score || sp.col_sort) {
-      lo = std::min<uint64_t>(sp.offset, t);
-      hi = sp.limit == 0 ? t : std::min<uint64_t>(lo + sp.limit, t);
-    } else {
-      hi = sp.limit == 0 ? t : std::min<uint64_t>(t, sp.limit);  // (docid order: no offset, see Compile)
-    }
-    // one index reports the funnel's count (slot 4) like the other groups; a merge, the table-wide sum
-    m->total[i] = n_side == 2 ? t : g.h_counters[i * 8 + 4];
-    m->page_off[i] = pages;
-    m->page_n[i] = hi - lo;
-    pages += hi - lo;
-    DevMergeRun& r = runs[i];
-    r.kind = (sp.deep_score || sp.col_sort) ? kMergeScore : sp.reverse ? kMergeDocDesc : kMergeDocAsc;
-    // the fused selection holds offset + limit <= 1024 pairs per side; past that every match is sorted
-    const bool col_topk = sp.col_sort && !colsort_full && hi <= colsort::kMaxNeeded;
-    r.descending = sp.reverse ? 1u : 0u;
-    r.lo = static_cast<uint32_t>(lo);
-    r.hi = static_cast<uint32_t>(hi);
-    r.out_off = m->page_off[i];
-    for (int k = 0; k < n_side; ++k) {
-      // a docid page needs each side's first hi ids in page order; a score page needs every match
-      take[k][i] = hi == lo ? 0 : (sp.deep_score || sp.col_sort) ? tot[k][i] : std::min<uint64_t>(tot[k][i], hi);
-      run_n[k][i] = take[k][i];
-      if (col_topk && take[k][i] != 0) {  // nothing is expanded: the run comes from the side's result bitmap
-        const QuerySpec& ks = side[k]->specs[g.qids[i]];
-        const mgx_index* ix = side[k]->idx;
-        run_n[k][i] = std::min<uint64_t>(tot[k][i], hi);
-        take[k][i] = 0;
-        koff[k][i] = n_keys;
-        n_keys += run_n[k][i];
-        colsort::TopkJob j{};
-        j.rbits = side[k]->bitmap.dev.rbits;
-        j.doc_map = n_side == 2 ? ix->d_doc_map.as<uint32_t>() : nullptr;
-        j.n_words = ix->dev.n_tiles * kWordsPerTile;
-        j.word_begin = static_cast<uint64_t>(i) * j.n_words;
-        j.out_off = koff[k][i];
-        j.list_off = n_lists;
-        j.n_docs = ix->dev.n_docs;
-        j.first_doc_id = ix->dev.first_doc_id;
-        j.needed = static_cast<uint32_t>(run_n[k][i]);
-        j.cap = 64;
-        while (j.cap < j.needed) j.cap <<= 1;
-        // workgroups per job: about 8192 in the launch (32 per CU), so that a query with ten times the matches of the
-        // others is spread over several and the launch has no long tail; a workgroup covers at least two tiles
-        const uint32_t want = static_cast<uint32_t>((8192 + n - 1) / n);
-        j.n_groups = std::max<uint32_t>(1, std::min<uint32_t>({want, colsort::kTopkMaxGroups, (ix->dev.n_tiles + 1) / 2}));
-        j.group_begin = n_groups_total;
-        j.ranks = ks.sort_ranks;
-        j.bias = ks.sort_bias;
-        j.descending = sp.reverse ? 1u : 0u;
-        n_groups_total += j.n_groups;
-        n_lists += static_cast<uint64_t>(j.n_groups) * j.needed;
-        max_cap = std::max(max_cap, j.cap);
-        max_job_elems = std::max(max_job_elems, j.n_groups * j.needed);
-        jobs.push_back(j);
-        job_side.push_back(k);
-        job_column.push_back(ks.pk_sort ? kKeyColumn : ks.sort_column);  // (resolved to its class and arrays below, under the index's lock)
-      }
-      off[k][i] = at[k];
-      at[k] += take[k][i];
-      if (sp.col_sort && take[k][i] != 0) {  // every match, keyed and sorted whole
-        n2[k][i] = 2048;  // (LaunchSortPairs: a power of two, at least one LDS run)
-        while (n2[k][i] < take[k][i]) n2[k][i] <<= 1;
-        koff[k][i] = n_keys;
-        n_keys += n2[k][i];
-      }
-      if (sp.deep_score && take[k][i] != 0) {
-        const QuerySpec& ks = side[k]->specs[g.qids[i]];
-        soff[k][i] = n_scores;
-        n_scores += take[k][i];
-        n2[k][i] = 2048;  // (SortRun: a power of two, at least one LDS run)
-        while (n2[k][i] < take[k][i]) n2[k][i] <<= 1;
-        koff[k][i] = n_keys;
-        n_keys += n2[k][i];
-        toff[k][i] = terms.size();
-        const std::vector<double> ki = DeepIdfs(side[k], ks);
-        terms.insert(terms.end(), ks.deep_grams.begin(), ks.deep_grams.end());
-        idfs.insert(idfs.end(), ki.begin(), ki.end());
-      }
-    }
-    r.a_n = static_cast<uint32_t>(run_n[0][i]);
-    r.b_n = static_cast<uint32_t>(run_n[1][i]);  // (one index: 0, so an element's rank is its index in its own run)
-    if (sp.pk_sort && sp.col_sort && merge_by_string) {  // key_merge_kernel's query: the rank merge sees two empty runs
-      krun_start.push_back(kelems);
-      kelems += run_n[0][i] + run_n[1][i];
-      kruns.push_back(pkey::KeyMergeRun{0, 0, r.out_off, r.a_n, r.b_n, r.lo, r.hi, r.descending, 0});
-      krun_query.push_back(i);
-      r.a_n = r.b_n = 0;
-    }
-    run_start[i] = elems;
-    elems += r.a_n + r.b_n;
+    pages::Query& q = in.queries[i];
+    q.deep_score = sp.deep_score;
+    q.col_sort = sp.col_sort;
+    q.pk_sort = sp.pk_sort;
+    q.faceted = a->fc.faceted(g.qids[i]);
+    q.reverse = sp.reverse;
+    q.offset = sp.offset;
+    q.limit = sp.limit;
+    q.funnel_total = g.h_counters[i * 8 + 4];
+    any_pk = any_pk || (sp.pk_sort && sp.col_sort);
   }
-  run_start[n] = elems;
-  krun_start.push_back(kelems);
-  if (elems + kelems == 0) return MGX_OK;  // every page is empty
-  if (elems > 0xFFFFFFFFull || kelems > 0xFFFFFFFFull || pages > 0xFFFFFFFFull || n_keys > 0xFFFFFFFFull || n_lists > 0xFFFFFFFFull)
-    return Fail(MGX_ERR_OUT_OF_RANGE, "batch result exceeds 2^32 doc ids");
-  // SORT <filter column>: every column a side's queries name, read under that index's lock (a column is immutable once
-  // added; the vector that holds them may grow)
-  struct SortCol {
-    const uint64_t* values;
-    const uint8_t* is_null;
-    uint32_t value_class;
-  };
-  std::map<uint32_t, SortCol> resolved[2];  // per side: each column is looked up once, whatever the number of queries
-  for (int k = 0; k < n_side; ++k) {
-    const mgx_index* ix = side[k]->idx;
+  for (int k = 0; k < f.n_side; ++k) {
+    PageSide& x = f.side[k];
+    const mgx_index* ix = x.batch->idx;
     std::lock_guard<std::mutex> lock(const_cast<mgx_index*>(ix)->mu);
-    for (size_t i = 0; i < n; ++i) {
-      const QuerySpec& ks = side[k]->specs[g.qids[i]];
-      if (ks.col_sort && ks.pk_sort) {
-        resolved[k][kKeyColumn] = SortCol{pk[k].values, nullptr, colsort::kUnsigned};
-        continue;
+    in.side[k] = pages::Side{ix->dev.n_tiles, ix->dev.n_docs, ix->dev.first_doc_id};
+    if (any_pk && ix->has_pkeys) {
+      x.keys = pkey::KeySide{ix->pk_kind, ix->d_pk_off.as<uint64_t>(), ix->d_pk_bytes.as<uint8_t>()};
+      x.key_values = ix->d_pk_values.as<uint64_t>();
+    }
+    for (size_t i = 0; i < f.n; ++i) {
+      const QuerySpec& ks = x.spec(i);
+      pages::SideQuery& sq = in.queries[i].side[k];
+      sq.total = totals[k * f.n + i];
+      sq.n_terms = static_cast<uint32_t>(ks.deep_grams.size());
+      sq.sort_column = ks.pk_sort ? pages::kKeyColumn : ks.sort_column;
+      sq.sort_ranks = ks.sort_ranks;
+      sq.sort_bias = ks.sort_bias;
+      if (!ks.col_sort) continue;
+      if (ks.pk_sort) {
+        x.columns[pages::kKeyColumn] = SortCol{x.key_values, nullptr, colsort::kUnsigned};
+      } else if (!x.columns.count(ks.sort_column) && ks.sort_column < ix->filter_columns.size()) {
+        const mgx_index::FilterColumn& c = *ix->filter_columns[ks.sort_column];
+        x.columns[ks.sort_column] = SortCol{c.d_values.as<uint64_t>(), c.d_null.as<uint8_t>(), c.value_class};
       }
-      if (!ks.col_sort || resolved[k].count(ks.sort_column) || ks.sort_column >= ix->filter_columns.size()) continue;
-      const mgx_index::FilterColumn& c = *ix->filter_columns[ks.sort_column];
-      resolved[k][ks.sort_column] = SortCol{c.d_values.as<uint64_t>(), c.d_null.as<uint8_t>(), c.value_class};
     }
   }
-  auto sort_col = [&](int k, uint32_t id, SortCol* out) {
-    const auto it = resolved[k].find(id);
-    if (it == resolved[k].end()) return false;
-    *out = it->second;
-    return true;
-  };
-  for (size_t j = 0; j < jobs.size(); ++j) {
-    SortCol c{};
-    if (!sort_col(job_side[j], job_column[j], &c)) return Fail(MGX_ERR_INTERNAL, "sort column vanished");
-    jobs[j].values = c.values;
-    jobs[j].is_null = c.is_null;
-    jobs[j].value_class = c.value_class;
-  }
-  for (size_t i = 0; i < n; ++i) {
-    DevMergeRun& r = runs[i];
-    r.a_off = r.kind == kMergeScore ? koff[0][i] : off[0][i];
-    r.b_off = r.kind == kMergeScore ? koff[1][i] : at[0] + off[1][i];
-  }
-  for (size_t j = 0; j < kruns.size(); ++j) {
-    kruns[j].a_off = koff[0][krun_query[j]];
-    kruns[j].b_off = koff[1][krun_query[j]];
-  }
-  // [runs | run_start | terms | idfs] uploaded as one block, then device-only arrays
-  const uint64_t o_start = Align8(n * sizeof(DevMergeRun));
-  const uint64_t o_terms = o_start + (n + 1) * 8;
-  const uint64_t o_idfs = Align8(o_terms + terms.size() * 4);
-  const uint64_t o_jobs = o_idfs + idfs.size() * 8;
-  const uint64_t o_kruns = Align8(o_jobs + jobs.size() * sizeof(colsort::TopkJob));
-  const uint64_t o_kstart = o_kruns + kruns.size() * sizeof(pkey::KeyMergeRun);
-  const uint64_t up_bytes = o_kstart + krun_start.size() * 8;
-  const uint64_t o_docs = Align8(up_bytes);
-  const uint64_t o_scores = Align8(o_docs + (at[0] + at[1]) * 4);
-  const uint64_t o_keys = o_scores + n_scores * 8;
-  const uint64_t o_dprime = o_keys + n_keys * 8;
-  const uint64_t o_pdocs = Align8(o_dprime + n_keys * 4);
-  const uint64_t o_pscores = Align8(o_pdocs + pages * 4);
-  const uint64_t o_lkeys = o_pscores + pages * 8;
-  const uint64_t o_ldocs = o_lkeys + n_lists * 8;
-  const uint64_t o_ln = Align8(o_ldocs + n_lists * 4);
-  const uint64_t bytes = o_ln + static_cast<uint64_t>(n_groups_total) * 4;
-  if (a->d_merge.bytes < bytes) MGX_HIP(a->d_merge.Alloc(bytes));
-  char* base = static_cast<char*>(a->d_merge.p);
-  std::vector<char> up(up_bytes);
-  std::memcpy(up.data(), runs.data(), n * sizeof(DevMergeRun));
-  std::memcpy(up.data() + o_start, run_start.data(), (n + 1) * 8);
-  if (!terms.empty()) std::memcpy(up.data() + o_terms, terms.data(), terms.size() * 4);
-  if (!idfs.empty()) std::memcpy(up.data() + o_idfs, idfs.data(), idfs.size() * 8);
-  if (!jobs.empty()) std::memcpy(up.data() + o_jobs, jobs.data(), jobs.size() * sizeof(colsort::TopkJob));
-  if (!kruns.empty()) std::memcpy(up.data() + o_kruns, kruns.data(), kruns.size() * sizeof(pkey::KeyMergeRun));
-  std::memcpy(up.data() + o_kstart, krun_start.data(), krun_start.size() * 8);
-  MGX_HIP(hipMemcpyAsync(base, up.data(), up_bytes, hipMemcpyHostToDevice, s));
-  uint32_t* docs = reinterpret_cast<uint32_t*>(base + o_docs);
-  double* scores = reinterpret_cast<double*>(base + o_scores);
-  uint64_t* keys = reinterpret_cast<uint64_t*>(base + o_keys);
-  uint32_t* dprime = reinterpret_cast<uint32_t*>(base + o_dprime);
-  uint32_t* pdocs = reinterpret_cast<uint32_t*>(base + o_pdocs);
-  double* pscores = reinterpret_cast<double*>(base + o_pscores);
-  // ---- each side materialises its part (expand_kernel, page order: ascending, or descending for reverse docid pages)
-  std::vector<uint64_t> out_off[2];
-  for (int k = 0; k < n_side; ++k) {
-    mgx_batch* x = side[k];
-    out_off[k] = off[k];
-    if (k == 1)
-      for (uint64_t& o : out_off[k]) o += at[0];
-    MGX_HIP(hipMemcpyAsync(x->d_take.p, take[k].data(), n * 8, hipMemcpyHostToDevice, s));
-    MGX_HIP(hipMemcpyAsync(x->d_out_off.p, out_off[k].data(), n * 8, hipMemcpyHostToDevice, s));
-    if (at[k])
-      MGX_LAUNCH(LaunchExpand(x->bitmap.dev.rbits, x->d_tile_start.as<uint64_t>(), x->d_totals.as<uint64_t>(),
-                              x->d_take.as<uint64_t>(), x->d_out_off.as<uint64_t>(), x->d_reverse.as<uint32_t>(),
-                              static_cast<uint32_t>(n), x->idx->dev.n_tiles, x->idx->dev.first_doc_id, docs, s));
-  }
-  // ---- deep SORT _score: scores on each side's own columns, by local slot ----
-  const uint32_t* d_terms = reinterpret_cast<const uint32_t*>(base + o_terms);
-  const double* d_idfs = reinterpret_cast<const double*>(base + o_idfs);
-  for (size_t i = 0; i < n; ++i)
-    for (int k = 0; k < n_side; ++k) {
-      if (n2[k][i] == 0 || !a->specs[g.qids[i]].deep_score) continue;
-      mgx_batch* x = side[k];
-      const QuerySpec& ks = x->specs[g.qids[i]];
-      MGX_LAUNCH(LaunchScoreCandidatesMixed(x->idx->dev, docs + out_off[k][i], take[k][i], d_terms + toff[k][i],
-                                            d_idfs + toff[k][i], static_cast<uint32_t>(ks.deep_grams.size()),
-                                            x->d_patterns.as<uint8_t>(), x->d_text_terms.as<DevTextTerm>(), ks.k1,
-                                            ks.b, ks.avgdl, scores + soff[k][i], s));
+  // two sides whose values do not compare as numbers: those pages are merged by key string
+  in.merge_by_string = f.n_side == 2 && !(f.side[0].keys.kind == pkey::kKeyNumeric && f.side[1].keys.kind == pkey::kKeyNumeric);
+  return in;
+}
+
+// Grows d_merge to the plan's layout and uploads its first part as one block: the plan's runs and jobs, with what only
+// the batches know filled in (each deep run's terms and idfs, each job's device arrays).
+static int UploadPlan(PageFetch& f, const pages::Plan& plan) {
+  const pages::Scratch& o = plan.at;
+  if (f.a->d_merge.bytes < o.bytes) MGX_HIP(f.a->d_merge.Alloc(o.bytes));
+  f.base = static_cast<char*>(f.a->d_merge.p);
+  f.docs = f.at<uint32_t>(o.docs);
+  f.scores = f.at<double>(o.scores);
+  f.keys = f.at<uint64_t>(o.keys);
+  f.dprime = f.at<uint32_t>(o.dprime);
+  f.pdocs = f.at<uint32_t>(o.pdocs);
+  f.pscores = f.at<double>(o.pscores);
+  f.up.assign(o.up_bytes, 0);
+  char* const up = f.up.data();
+  for (size_t i = 0; i < f.n; ++i) {
+    std::memcpy(up + i * sizeof(DevMergeRun), &plan.queries[i].run, sizeof(DevMergeRun));
+    for (int k = 0; k < f.n_side; ++k) {
+      const pages::SidePlan& sp = plan.queries[i].side[k];
+      const QuerySpec& ks = f.side[k].spec(i);
+      if (sp.key_cap == 0 || !f.side[0].spec(i).deep_score || ks.deep_grams.empty()) continue;
+      const std::vector<double> idfs = DeepIdfs(f.side[k].batch, ks);
+      std::memcpy(up + o.terms + sp.term_off * 4, ks.deep_grams.data(), ks.deep_grams.size() * 4);
+      std::memcpy(up + o.idfs + sp.term_off * 8, idfs.data(), idfs.size() * 8);
     }
-  if (std::getenv("MGX_VERBOSE")) {
-    size_t full_runs = 0;
-    for (size_t i = 0; i < n; ++i)
-      for (int k = 0; k < n_side; ++k) full_runs += (a->specs[g.qids[i]].col_sort && n2[k][i] != 0) ? 1 : 0;
-    if (!jobs.empty() || full_runs)
-      fprintf(stderr, "[mgx] column sort: %zu fused runs in %u workgroups, %zu full-sort runs\n", jobs.size(), n_groups_total, full_runs);
-    if (!kruns.empty())
-      fprintf(stderr, "[mgx] key merge: %zu queries, %llu elements\n", kruns.size(), static_cast<unsigned long long>(kelems));
   }
-  // ---- SORT <filter column>: the fused selection from the result bitmaps; the expanded runs' pairs from local slots,
-  // their docid' a table id already (the doc map is read here: the slots are gone once the docs below are remapped)
-  if (!jobs.empty())
-    MGX_LAUNCH(LaunchColumnTopk(reinterpret_cast<const colsort::TopkJob*>(base + o_jobs), static_cast<uint32_t>(jobs.size()),
-                                n_groups_total, max_cap, max_job_elems, reinterpret_cast<uint64_t*>(base + o_lkeys),
-                                reinterpret_cast<uint32_t*>(base + o_ldocs), reinterpret_cast<uint32_t*>(base + o_ln), keys,
-                                dprime, s));
-  for (size_t i = 0; i < n; ++i)
-    for (int k = 0; k < n_side; ++k) {
-      mgx_batch* x = side[k];
-      const QuerySpec& ks = x->specs[g.qids[i]];
-      if (!ks.col_sort || n2[k][i] == 0) continue;
-      SortCol c{};
-      if (!sort_col(k, ks.pk_sort ? kKeyColumn : ks.sort_column, &c)) return Fail(MGX_ERR_INTERNAL, "sort column vanished");
-      const uint64_t cnt = take[k][i];
-      if (n2[k][i] > cnt) {
-        MGX_HIP(hipMemsetAsync(keys + koff[k][i] + cnt, 0, (n2[k][i] - cnt) * 8, s));
-        MGX_HIP(hipMemsetAsync(dprime + koff[k][i] + cnt, 0, (n2[k][i] - cnt) * 4, s));
-      }
-      MGX_LAUNCH(LaunchColumnKeys(docs + out_off[k][i], cnt, c.values, c.is_null,
-                                  n_side == 2 ? x->idx->d_doc_map.as<uint32_t>() : nullptr, x->idx->dev.first_doc_id,
-                                  x->idx->dev.n_docs, c.value_class, ks.sort_ranks, ks.sort_bias, runs[i].descending,
-                                  keys + koff[k][i], dprime + koff[k][i], s));
-      MGX_LAUNCH(LaunchSortPairs(keys + koff[k][i], dprime + koff[k][i], n2[k][i], s));
+  std::memcpy(up + o.run_start, plan.run_start.data(), plan.run_start.size() * 8);
+  for (size_t j = 0; j < plan.jobs.size(); ++j) {
+    const PageSide& x = f.side[plan.jobs[j].side];
+    const auto col = x.columns.find(plan.jobs[j].column);
+    if (col == x.columns.end()) return Fail(MGX_ERR_INTERNAL, "sort column vanished");
+    colsort::TopkJob job = plan.jobs[j].job;
+    job.rbits = x.batch->bitmap.dev.rbits;
+    job.doc_map = x.doc_map;
+    job.values = col->second.values;
+    job.is_null = col->second.is_null;
+    job.value_class = col->second.value_class;
+    std::memcpy(up + o.jobs + j * sizeof(job), &job, sizeof(job));
+  }
+  if (!plan.kruns.empty()) std::memcpy(up + o.kruns, plan.kruns.data(), plan.kruns.size() * sizeof(pkey::KeyMergeRun));
+  std::memcpy(up + o.krun_start, plan.krun_start.data(), plan.krun_start.size() * 8);
+  MGX_HIP(hipMemcpyAsync(f.base, up, o.up_bytes, hipMemcpyHostToDevice, f.s));
+  return MGX_OK;
+}
+
+// Each side materialises its part (expand_kernel, page order: ascending, or descending for reverse docid pages).
+static int ExpandSides(PageFetch& f, const pages::Plan& plan) {
+  for (int k = 0; k < f.n_side; ++k) {
+    PageSide& x = f.side[k];
+    mgx_batch* b = x.batch;
+    for (const pages::QueryPlan& qp : plan.queries) {
+      x.take.push_back(qp.side[k].take);
+      x.out_off.push_back(qp.side[k].docs_off);
     }
-  // ---- a merge: local slots -> table ids (a delta index numbers its documents in ascending table-id order; one index's
-  // fetch returns its own ids) ----
-  if (n_side == 2)
-    for (int k = 0; k < 2; ++k) {
-      const mgx_index* ix = side[k]->idx;
-      if (ix->d_doc_map.p && at[k])
-        MGX_LAUNCH(LaunchRemapDocs(docs + (k == 0 ? 0 : at[0]), at[k], ix->d_doc_map.as<uint32_t>(), ix->dev.first_doc_id,
-                                   ix->dev.n_docs, s));
+    MGX_HIP(hipMemcpyAsync(b->d_take.p, x.take.data(), f.n * 8, hipMemcpyHostToDevice, f.s));
+    MGX_HIP(hipMemcpyAsync(b->d_out_off.p, x.out_off.data(), f.n * 8, hipMemcpyHostToDevice, f.s));
+    if (plan.expanded[k])
+      MGX_LAUNCH(LaunchExpand(b->bitmap.dev.rbits, b->d_tile_start.as<uint64_t>(), b->d_totals.as<uint64_t>(),
+                              b->d_take.as<uint64_t>(), b->d_out_off.as<uint64_t>(), b->d_reverse.as<uint32_t>(),
+                              static_cast<uint32_t>(f.n), b->idx->dev.n_tiles, b->idx->dev.first_doc_id, f.docs, f.s));
+  }
+  return MGX_OK;
+}
+
+// Deep SORT _score: scores on each side's own columns, by local slot.
+static int ScoreDeepRuns(const PageFetch& f, const pages::Plan& plan) {
+  const uint32_t* d_terms = f.at<const uint32_t>(plan.at.terms);
+  const double* d_idfs = f.at<const double>(plan.at.idfs);
+  for (size_t i = 0; i < f.n; ++i)
+    for (int k = 0; k < f.n_side; ++k) {
+      const pages::SidePlan& sp = plan.queries[i].side[k];
+      if (sp.key_cap == 0 || !f.side[0].spec(i).deep_score) continue;
+      const mgx_batch* x = f.side[k].batch;
+      const QuerySpec& ks = f.side[k].spec(i);
+      MGX_LAUNCH(LaunchScoreCandidatesMixed(x->idx->dev, f.docs + sp.docs_off, sp.take, d_terms + sp.term_off,
+                                            d_idfs + sp.term_off, static_cast<uint32_t>(ks.deep_grams.size()),
+                                            x->d_patterns.as<uint8_t>(), x->d_text_terms.as<DevTextTerm>(), ks.k1, ks.b,
+                                            ks.avgdl, f.scores + sp.score_off, f.s));
     }
-  // ---- deep SORT _score: (key, docid') runs, each sorted best first ----
-  for (size_t i = 0; i < n; ++i)
-    for (int k = 0; k < n_side; ++k) {
-      if (n2[k][i] == 0 || !a->specs[g.qids[i]].deep_score) continue;
-      const int rc = SortRun(docs + out_off[k][i], scores + soff[k][i], take[k][i], n2[k][i], runs[i].descending,
-                             keys + koff[k][i], dprime + koff[k][i], s);
+  return MGX_OK;
+}
+
+// SORT <filter column | primary key>, offset + limit <= 1024: the fused selection from the result bitmaps.
+static int SelectColumnTopk(const PageFetch& f, const pages::Plan& plan) {
+  if (plan.jobs.empty()) return MGX_OK;
+  MGX_LAUNCH(LaunchColumnTopk(f.at<const colsort::TopkJob>(plan.at.jobs), static_cast<uint32_t>(plan.jobs.size()),
+                              plan.n_groups_total, plan.max_cap, plan.max_job_elems, f.at<uint64_t>(plan.at.lkeys),
+                              f.at<uint32_t>(plan.at.ldocs), f.at<uint32_t>(plan.at.ln), f.keys, f.dprime, f.s));
+  return MGX_OK;
+}
+
+// ... past that: the expanded runs' pairs from local slots, their docid' a table id already (the doc map is read here:
+// the slots are gone once RemapToTableIds has run), each run sorted whole.
+static int KeyAndSortFullRuns(const PageFetch& f, const pages::Plan& plan) {
+  for (size_t i = 0; i < f.n; ++i)
+    for (int k = 0; k < f.n_side; ++k) {
+      const PageSide& x = f.side[k];
+      const pages::SidePlan& sp = plan.queries[i].side[k];
+      const QuerySpec& ks = x.spec(i);
+      if (!ks.col_sort || sp.key_cap == 0) continue;
+      const auto col = x.columns.find(ks.pk_sort ? pages::kKeyColumn : ks.sort_column);
+      if (col == x.columns.end()) return Fail(MGX_ERR_INTERNAL, "sort column vanished");
+      const SortCol& c = col->second;
+      const mgx_index* ix = x.batch->idx;
+      uint64_t* keys = f.keys + sp.key_off;
+      uint32_t* dprime = f.dprime + sp.key_off;
+      if (const int rc = PadPairs(keys, dprime, sp.take, sp.key_cap, f.s)) return rc;
+      MGX_LAUNCH(LaunchColumnKeys(f.docs + sp.docs_off, sp.take, c.values, c.is_null, x.doc_map, ix->dev.first_doc_id,
+                                  ix->dev.n_docs, c.value_class, ks.sort_ranks, ks.sort_bias,
+                                  plan.queries[i].run.descending, keys, dprime, f.s));
+      MGX_LAUNCH(LaunchSortPairs(keys, dprime, sp.key_cap, f.s));
+    }
+  return MGX_OK;
+}
+
+// A merge: local slots -> table ids (a delta index numbers its documents in ascending table-id order; one index's fetch
+// returns its own ids).
+static int RemapToTableIds(const PageFetch& f, const pages::Plan& plan) {
+  for (int k = 0; k < f.n_side && f.n_side == 2; ++k) {
+    const mgx_index* ix = f.side[k].batch->idx;
+    if (ix->d_doc_map.p && plan.expanded[k])
+      MGX_LAUNCH(LaunchRemapDocs(f.docs + (k == 0 ? 0 : plan.expanded[0]), plan.expanded[k], ix->d_doc_map.as<uint32_t>(),
+                                 ix->dev.first_doc_id, ix->dev.n_docs, f.s));
+  }
+  return MGX_OK;
+}
+
+// Deep SORT _score: (key, docid') runs, each sorted best first.
+static int SortDeepRuns(const PageFetch& f, const pages::Plan& plan) {
+  for (size_t i = 0; i < f.n; ++i)
+    for (int k = 0; k < f.n_side; ++k) {
+      const pages::SidePlan& sp = plan.queries[i].side[k];
+      if (sp.key_cap == 0 || !f.side[0].spec(i).deep_score) continue;
+      const int rc = SortRun(f.docs + sp.docs_off, f.scores + sp.score_off, sp.take, sp.key_cap,
+                             plan.queries[i].run.descending, f.keys + sp.key_off, f.dprime + sp.key_off, f.s);
       if (rc) return rc;
     }
-  // ---- every query's page from its runs ----
-  MGX_LAUNCH(LaunchRankMerge(reinterpret_cast<const DevMergeRun*>(base), reinterpret_cast<const uint64_t*>(base + o_start),
-                             static_cast<uint32_t>(n), elems, docs, keys, dprime, pdocs, pscores, s));
-  MGX_LAUNCH(LaunchKeyMerge(reinterpret_cast<const pkey::KeyMergeRun*>(base + o_kruns),
-                            reinterpret_cast<const uint64_t*>(base + o_kstart), static_cast<uint32_t>(kruns.size()), kelems,
-                            pk[0].side, pk[1].side, keys, dprime, pdocs, pscores, s));
-  if (a->doc.on()) {  // page documents of this group's pages, behind the kernels that cut them
-    const int rc = RunLateDocuments(a, s, m->page_off, m->page_n, pdocs);
-    if (rc) return rc;
+  return MGX_OK;
+}
+
+// Every query's page from its runs: by rank, or (SORT by primary key across two dictionaries) by key string.
+static int CutPages(const PageFetch& f, const pages::Plan& plan) {
+  MGX_LAUNCH(LaunchRankMerge(f.at<const DevMergeRun>(0), f.at<const uint64_t>(plan.at.run_start), static_cast<uint32_t>(f.n),
+                             plan.elems, f.docs, f.keys, f.dprime, f.pdocs, f.pscores, f.s));
+  MGX_LAUNCH(LaunchKeyMerge(f.at<const pkey::KeyMergeRun>(plan.at.kruns), f.at<const uint64_t>(plan.at.krun_start),
+                            static_cast<uint32_t>(plan.kruns.size()), plan.kelems, f.side[0].keys, f.side[1].keys, f.keys,
+                            f.dprime, f.pdocs, f.pscores, f.s));
+  return MGX_OK;
+}
+
+static int FetchBitmapPages(mgx_batch* a, BitmapPages* m) {
+  PageFetch f;
+  f.a = a;
+  f.n_side = a->merge_other ? 2 : 1;
+  f.n = a->bitmap.qids.size();
+  f.s = f.n_side == 2 ? a->merge_stream : a->last_stream;
+  f.side[0].batch = a;
+  f.side[1].batch = a->merge_other;
+  for (int k = 0; k < f.n_side; ++k) {
+    if (f.n_side == 2) f.side[k].doc_map = f.side[k].batch->idx->d_doc_map.as<uint32_t>();
+    if (f.side[k].batch->last_stream != f.s) MGX_HIP(hipStreamSynchronize(f.side[k].batch->last_stream));
   }
-  m->docs.resize(pages);
-  if (pages) MGX_HIP(hipMemcpyAsync(m->docs.data(), pdocs, pages * 4, hipMemcpyDeviceToHost, s));
-  if (pages && n_keys) {  // (scores: a deep SORT _score page is in the batch)
-    m->scores.resize(pages);
-    MGX_HIP(hipMemcpyAsync(m->scores.data(), pscores, pages * 8, hipMemcpyDeviceToHost, s));
+  std::vector<uint64_t> totals;
+  if (const int rc0 = ReadTotals(f, &totals)) return rc0;
+  const pages::Plan plan = pages::Build(PlanInput(f, totals));
+  for (const pages::QueryPlan& qp : plan.queries) {
+    m->total.push_back(qp.total);
+    m->page_off.push_back(qp.page_off);
+    m->page_n.push_back(qp.page_n);
   }
-  MGX_HIP(hipStreamSynchronize(s));
+  if (plan.status == pages::kEmpty) return MGX_OK;  // every page is empty
+  if (plan.status == pages::kTooLarge) return Fail(MGX_ERR_OUT_OF_RANGE, "batch result exceeds 2^32 doc ids");
+  if (std::getenv("MGX_VERBOSE")) {
+    if (!plan.jobs.empty() || plan.full_runs)
+      fprintf(stderr, "[mgx] column sort: %zu fused runs in %u workgroups, %zu full-sort runs\n", plan.jobs.size(),
+              plan.n_groups_total, plan.full_runs);
+    if (!plan.kruns.empty())
+      fprintf(stderr, "[mgx] key merge: %zu queries, %llu elements\n", plan.kruns.size(), static_cast<unsigned long long>(plan.kelems));
+  }
+  int rc = UploadPlan(f, plan);
+  if (!rc) rc = ExpandSides(f, plan);
+  if (!rc) rc = ScoreDeepRuns(f, plan);
+  if (!rc) rc = SelectColumnTopk(f, plan);
+  if (!rc) rc = KeyAndSortFullRuns(f, plan);
+  if (!rc) rc = RemapToTableIds(f, plan);
+  if (!rc) rc = SortDeepRuns(f, plan);
+  if (!rc) rc = CutPages(f, plan);
+  if (!rc && a->doc.on()) rc = RunLateDocuments(a, f.s, plan, f.pdocs);  // behind the kernels that cut the pages
+  if (rc) return rc;
+  m->docs.resize(plan.pages);
+  if (plan.pages) MGX_HIP(hipMemcpyAsync(m->docs.data(), f.pdocs, plan.pages * 4, hipMemcpyDeviceToHost, f.s));
+  if (plan.pages && plan.n_keys) {  // (scores: a deep SORT _score page is in the batch)
+    m->scores.resize(plan.pages);
+    MGX_HIP(hipMemcpyAsync(m->scores.data(), f.pscores, plan.pages * 8, hipMemcpyDeviceToHost, f.s));
+  }
+  MGX_HIP(hipStreamSynchronize(f.s));
   return MGX_OK;
 }
 
@@ -4539,13 +4505,8 @@ int mgx_batch_merge_local(mgx_batch* primary, mgx_batch* const* others, uint32_t
     const mgx_batch* doc_mapped = nullptr;
     const mgx_batch* doc_plain = nullptr;
     if (primary->doc.on()) {
-      for (uint32_t j = 0; j <= n_others; ++j) {
-        const mgx_batch* x = j == 0 ? primary : others[j - 1];
-        const mgx_batch*& slot = x->idx->d_doc_map.p ? doc_mapped : doc_plain;
-        if (slot || n_others > 1)
-          return mgx::Fail(MGX_ERR_NOT_IMPLEMENTED, "mgx_batch_merge_local: page documents read one main index and one delta");
-        slot = x;
-      }
+      if (n_others > 1 || !mgx::MainAndDelta(primary, others, n_others, &doc_mapped, &doc_plain))
+        return mgx::Fail(MGX_ERR_NOT_IMPLEMENTED, "mgx_batch_merge_local: page documents read one main index and one delta");
       if (n_others == 1) {
         const int rc = mgx::CheckDocumentSides(primary, others[0], "mgx_batch_merge_local");
         if (rc) return rc;
@@ -4608,14 +4569,11 @@ int mgx_batch_merge_local(mgx_batch* primary, mgx_batch* const* others, uint32_t
     }
     if (primary->hl.on()) {
       // the merged page names every document by its table id: the delta's through its doc map, the main index's own
-      const mgx_index* mapped = nullptr;
-      const mgx_index* plain = nullptr;
-      for (uint32_t j = 0; j <= n_others; ++j) {
-        const mgx_index* ix = (j == 0 ? primary : others[j - 1])->idx;
-        const mgx_index*& slot = ix->d_doc_map.p ? mapped : plain;
-        if (slot) return mgx::Fail(MGX_ERR_NOT_IMPLEMENTED, "mgx_batch_merge_local: highlight reads one main index and one delta");
-        slot = ix;
-      }
+      const mgx_batch *hl_mapped = nullptr, *hl_plain = nullptr;
+      if (!mgx::MainAndDelta(primary, others, n_others, &hl_mapped, &hl_plain))
+        return mgx::Fail(MGX_ERR_NOT_IMPLEMENTED, "mgx_batch_merge_local: highlight reads one main index and one delta");
+      const mgx_index* mapped = hl_mapped ? hl_mapped->idx : nullptr;
+      const mgx_index* plain = hl_plain ? hl_plain->idx : nullptr;
       if ((mapped && !mapped->dev.text) || (plain && !plain->dev.text))
         return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_batch_merge_local: highlight needs mgx_index_attach_text on every index");
       rc = mgx::RunHighlight(primary, s, /*merged=*/true, mapped, plain);
@@ -5386,8 +5344,7 @@ int mgx_sort_by_score(mgx_index* idx, const uint32_t* results, const double* sco
         // the full-sort fallback (result_sorter.cpp:661-716 sorts whatever it is given; deep OFFSETs are benchmarked,
         // docs/releases/v1.3.5.md:238): every pair sorted best first by the bitonic network, then the page is cut out
         // of the one sorted run by rank_merge_kernel (an element's rank is its index in the run)
-        uint64_t n2 = 2048;
-        while (n2 < n) n2 <<= 1;
+        const uint64_t n2 = mgx::pages::SortCapacity(n);
         mgx::DevMergeRun run{};
         run.kind = mgx::kMergeScore;
         run.descending = descending ? 1u : 0u;
