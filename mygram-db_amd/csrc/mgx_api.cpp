@@ -936,6 +936,9 @@ static int IndexCreateImpl(const mgx_index_desc* d, mgx_index** out) {
     idx->h_fine_map = fine_map;
     MGX_HIP(mgx::Upload(idx->d_fine_rows, fine_rows.data(), fine_rows.size(), 1));
   }
+  if (std::getenv("MGX_VERBOSE"))
+    fprintf(stderr, "[mgx] index: %u tiles, block-max bounds per quarter for %u of %u bitmap rows\n", n_tiles, idx->n_fine_rows,
+            idx->n_bitmap_rows);
   v.gb_row_stride = mgx::kWordsPerTile;
   idx->filter_row_stride = idx->words_per_row + 32 * ((n_tiles % 2) ? 1 : 3);  // 256 B / 768 B of padding
   v.fb_tile_stride = mgx::kWordsPerTile;
@@ -1760,6 +1763,7 @@ struct GroupPlan {
   std::vector<DevItem> items;  // (d) grouped by query, (e) in launch order; query i's lists [list_begin[i], list_begin[i + 1])
   std::vector<uint32_t> list_begin, item_begin;
   std::vector<DevItem> block, wave, wave_lists, fast[kFastMaxScore], cand, merge;  // (e) each route's, in launch order
+  std::vector<uint8_t> seed_cut;  // (d) [n] the query's first item is a seed item
   std::vector<uint8_t> has_seed;
 };
 
@@ -2142,6 +2146,7 @@ static void CutItems(const mgx_batch* b, const Group& g, const std::vector<Query
   const uint32_t n = p.n, n_tiles = b->idx->dev.n_tiles;
   p.list_begin.assign(n + 1, 0);
   p.item_begin.assign(n + 1, 0);  // a query's own items (none for the members of a group)
+  p.seed_cut.assign(n, 0);
   uint32_t n_lists = 0;
   for (uint32_t i = 0; i < n; ++i) {
     const QuerySpec& s = specs[g.qids[i]];
@@ -2176,6 +2181,7 @@ static void CutItems(const mgx_batch* b, const Group& g, const std::vector<Query
     const uint32_t seed_tiles = std::min<uint32_t>(kSeedTiles, (n_tiles / 8) & ~7u);  // (8 on a 77-tile shard)
     if (fast && seed_tiles && n_tiles > 4 * seed_tiles) {
       p.items.push_back(DevItem{i, 0, seed_tiles, n_lists++});
+      p.seed_cut[i] = 1;
       t0 = seed_tiles;
     }
     for (uint32_t t = t0; t < n_tiles; t += tiles) {
@@ -2258,8 +2264,9 @@ static int ScheduleItems(const mgx_batch* b, Group& g, const std::vector<QuerySp
   for (int pass = 0; pass < 2; ++pass) {  // pass 0: the fast path's seed items (a query's first list), then the rest
     for (const DevItem& it : p.items) {
       const Route route = p.route[it.query];
-      const bool seed = route == Route::kFast && it.list == p.list_begin[it.query] && it.tile_begin == 0 &&
-                        p.list_begin[it.query + 1] - p.list_begin[it.query] > 1 && it.n_tiles <= 16;
+      // (what CutItems cut as one: a first item that merely is short — a table too small for seeds, MGX_SEED_TILES=0 —
+      // is an ordinary item and stays in band order)
+      const bool seed = route == Route::kFast && p.seed_cut[it.query] != 0 && it.list == p.list_begin[it.query];
       if (seed != (pass == 0)) continue;
       switch (route) {
         case Route::kBlock: p.block.push_back(it); break;
@@ -2437,14 +2444,24 @@ static int UploadGroup(mgx_batch* b, Group& g, uint32_t mode, const std::vector<
   if (std::getenv("MGX_VERBOSE")) {
     size_t fast_queries = 0;
     for (Route r : p.route) fast_queries += r == Route::kFast ? 1 : 0;
+    // the fast path's schedule: its seed items, the most items one query was cut into, the longest item in tiles
+    uint32_t fast_seeds = 0, fast_most = 0, fast_longest = 0;
+    std::vector<uint32_t> per_query(p.n, 0);
+    for (int t = 0; t < kFastMaxScore; ++t) {
+      fast_seeds += g.n_seed_fast[t];
+      for (const DevItem& it : p.fast[t]) {
+        fast_most = std::max(fast_most, ++per_query[it.query]);
+        fast_longest = std::max(fast_longest, it.n_tiles);
+      }
+    }
     fprintf(stderr,
             "[mgx] %s group: %u queries; fast path %zu items (%zu queries, lds %u B, ring %u), wave kernel %zu items "
             "(lds %u B, lists %zu), block kernel %zu items (lds %u B), candidate-driven %zu queries, list merge %zu "
-            "items\n",
+            "items; fast schedule: %u seed items, at most %u items per query, longest item %u tiles\n",
             p.score_mode ? "score" : p.page_mode ? "docid-page" : p.df_mode ? "df" : "bitmap", p.n,
             p.fast[0].size() + p.fast[1].size() + p.fast[2].size() + p.fast[3].size() + p.fast[4].size(), fast_queries,
             g.fplan.bytes, g.fplan.ring, p.wave.size() + p.wave_lists.size(), g.wplan.bytes, p.wave_lists.size(),
-            p.block.size(), g.plan.bytes, p.cand.size(), p.merge.size());
+            p.block.size(), g.plan.bytes, p.cand.size(), p.merge.size(), fast_seeds, fast_most, fast_longest);
   }
   return MGX_OK;
 }
