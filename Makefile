@@ -30,7 +30,7 @@ $(CSRC)/mgx_documents.o: $(CSRC)/mgx_documents.hip $(CSRC)/mgx_documents.hpp
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 # the device column builder: a unit of its own as well (mgx_build.hpp also holds the key packing and the storage plan,
 # which compile without HIP)
-$(CSRC)/mgx_build.o: $(CSRC)/mgx_build.hip $(CSRC)/mgx_build.hpp $(CSRC)/mgx_text.hpp include/mygram_gpu.h
+$(CSRC)/mgx_build.o: $(CSRC)/mgx_build.hip $(CSRC)/mgx_build.hpp $(CSRC)/mgx_internal.hpp $(CSRC)/mgx_text.hpp include/mygram_gpu.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 $(CSRC)/mgx_api.o: $(CSRC)/mgx_api.cpp $(CSRC)/mgx_build.hpp $(CSRC)/mgx_colsort.hpp $(CSRC)/mgx_pkey.hpp $(CSRC)/mgx_pages.hpp $(CSRC)/mgx_facet.hpp $(CSRC)/mgx_documents.hpp $(CSRC)/mgx_compile.hpp $(CSRC)/mgx_internal.hpp $(CSRC)/mgx_launch.hpp $(CSRC)/mgx_host.hpp $(CSRC)/mgx_highlight.hpp $(CSRC)/mgx_text.hpp include/mygram_gpu.h
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
@@ -96,7 +96,12 @@ build-host-asan:
 	g++ -O1 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -o build_host_check_asan tests/cpp/build_host_check.cpp
 	./build_host_check_asan
 
+# the resident ending of mgx_build.hpp (mgx_index_build_device: allocation sizes, the lanes of resident_rows_kernel) likewise
+resident-host-asan:
+	g++ -O1 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -o resident_plan_check_asan tests/cpp/resident_plan_check.cpp
+	./resident_plan_check_asan
+
 clean:
-	rm -f $(OBJS) $(LIB) $(SHIM) build_host_check_asan colsort_host_check_asan colsort_host_check_lines.txt pksort_host_check_asan pksort_host_check_lines.txt highlight_original_host_check_asan highlight_original_host_check_lines.txt documents_plan_check_asan pages_plan_check_asan
+	rm -f $(OBJS) $(LIB) $(SHIM) build_host_check_asan resident_plan_check_asan colsort_host_check_asan colsort_host_check_lines.txt pksort_host_check_asan pksort_host_check_lines.txt highlight_original_host_check_asan highlight_original_host_check_lines.txt documents_plan_check_asan pages_plan_check_asan
 	$(MAKE) -C oracle clean
-.PHONY: all oracle clean ablation colsort-host-asan pksort-host-asan highlight-original-host-asan documents-host-asan pages-host-asan build-host-asan
+.PHONY: all oracle clean ablation colsort-host-asan pksort-host-asan highlight-original-host-asan documents-host-asan pages-host-asan build-host-asan resident-host-asan

@@ -202,6 +202,37 @@ typedef struct mgx_index_desc {
 
 /* Host arrays are copied; the caller keeps ownership. */
 int mgx_index_create(const mgx_index_desc* desc, mgx_index** out);
+/* A serving index from normalized texts in one call, the postings never on the host: the device builder's docids / tf
+ * columns, doc lengths and (attach_text) the texts stay in device memory after the texts' single upload and become the
+ * index's own arrays. *index_out is indistinguishable from what mgx_index_create makes of mgx_columns_build's columns of
+ * the same texts (with mgx_index_attach_text(the same buffers) applied when attach_text is set): every device array holds
+ * the same bytes, mgx_index_memory_bytes is equal. *dictionary_out holds what a host caller reads: the keys
+ * (mgx_columns_lookup works), offsets, n_postings, first_doc_id, n_docs, doc_len, the BM25 statistics and the tf overflow
+ * lists, each equal to the host builder's; its view has docids == NULL and tf == NULL, so mgx_index_create over it answers
+ * MGX_ERR_INVALID_ARGUMENT. Release both as usual (mgx_columns_destroy, mgx_index_destroy).
+ * Refusals, answered on the host before any device work, in this order: those of mgx_columns_build_device up to the
+ * descending text_off (a bad struct_size / version of either struct: MGX_ERR_INVALID_ARGUMENT); a tile_shift
+ * mgx_index_create refuses: MGX_ERR_NOT_IMPLEMENTED; n_docs == 0: MGX_ERR_OUT_OF_RANGE; no HIP device: MGX_ERR_INTERNAL;
+ * a bad device: MGX_ERR_INVALID_ARGUMENT; 4 GiB of text or more, or no room on the device for the temporary storage and
+ * the index's arrays: MGX_ERR_OUT_OF_RANGE. On any failure both outputs are NULL and nothing stays allocated. After
+ * NOT_IMPLEMENTED for the gram size or OUT_OF_RANGE for the text or the memory, mgx_columns_build + mgx_index_create build
+ * the same index through the host. Safe to call from many threads. */
+typedef struct mgx_index_build_desc {
+  uint32_t struct_size; /* sizeof(mgx_index_build_desc) */
+  uint32_t version;     /* MGX_ABI_VERSION */
+  int32_t device;       /* as mgx_index_desc */
+  uint32_t tile_shift;  /* as mgx_index_desc */
+  double dense_threshold; /* as mgx_index_desc */
+  uint32_t attach_text; /* 1: the index keeps the normalized texts, exactly as after mgx_index_attach_text(same buffers) */
+  uint32_t reserved;    /* 0 */
+} mgx_index_build_desc;
+int mgx_index_build_device(const mgx_build_params* params, const mgx_index_build_desc* desc, const uint8_t* text_bytes,
+                           const uint64_t* text_off, uint32_t first_doc_id, uint64_t n_docs, mgx_columns** dictionary_out,
+                           mgx_index** index_out);
+/* One gram's posting list as the index holds it in device memory: its doc ids and tf bytes (either buffer may be NULL;
+ * both NULL: only *n). An index made without tf fills doc ids only. An unknown gram: MGX_ERR_OUT_OF_RANGE; capacity (in
+ * postings) below the list's length: MGX_ERR_OUT_OF_RANGE with *n set to the length. */
+int mgx_index_read_postings(mgx_index* idx, uint32_t gram_id, uint32_t* docids, uint8_t* tf, uint64_t capacity, uint64_t* n);
 void mgx_index_destroy(mgx_index* idx);
 int mgx_posting_size(const mgx_index* idx, uint32_t gram_id, uint64_t* out);
 /* Device bytes held by the index (postings, tf, doc_len, skip tables, dense bitmaps). */

@@ -101,6 +101,13 @@ int mgxs_table_set_mutation_staleness(mgxs_table* table, uint64_t microseconds);
 /* Index::SetDeviceBuild: the column arrays of every later build of this table (the first, the delta rebuilds, compact) are
  * built on its device (mgx_columns_build_device); what that builder declines is built on the host. 0 (default): the host. */
 int mgxs_table_set_device_build(mgxs_table* table, int on);
+/* Index::SetBuildMode: 0 the host, 1 the device builds the column arrays (what mgxs_table_set_device_build(1) selects),
+ * 2 the device builds columns, device index and attached texts in one call (mgx_index_build_device) and the postings never
+ * come to the host. What the device declines the host builds. */
+int mgxs_table_set_build_mode(mgxs_table* table, int mode);
+/* Index::BuildCounters: generations this table built since creation (first build, delta rebuilds, compactions), by the
+ * mode that did build each. */
+int mgxs_table_build_counters(mgxs_table* table, uint64_t* host, uint64_t* device_columns, uint64_t* device_resident);
 /* Index::Compact: the main index rebuilt from the table's current documents; the delta goes. */
 int mgxs_table_compact(mgxs_table* table);
 int mgxs_table_mutation_stats(mgxs_table* table, uint64_t* main_documents, uint64_t* delta_documents,

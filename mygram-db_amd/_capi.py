@@ -22,7 +22,7 @@ EXPORTS = [
     "mgx_abi_version", "mgx_last_error", "mgx_free", "mgx_device_count",
     "mgx_columns_build", "mgx_columns_build_device", "mgx_columns_from_mgix", "mgx_dump_open", "mgx_dump_view_get", "mgx_dump_filter_column_get",
     "mgx_dump_take_columns", "mgx_dump_destroy", "mgx_columns_view_get", "mgx_columns_lookup", "mgx_columns_destroy",
-    "mgx_index_create", "mgx_index_destroy", "mgx_posting_size", "mgx_index_memory_bytes",
+    "mgx_index_create", "mgx_index_build_device", "mgx_index_read_postings", "mgx_index_destroy", "mgx_posting_size", "mgx_index_memory_bytes",
     "mgx_index_add_filter_bitmap", "mgx_index_add_filter_column", "mgx_index_filter_compare", "mgx_facet_counts",
     "mgx_index_filter_column_read", "mgx_index_copy_text", "mgx_index_read_text", "mgx_index_filter_column_export", "mgx_index_set_live_bitmap", "mgx_index_clear_postings", "mgx_index_update_filter_bitmap", "mgx_index_set_doc_map",
     "mgx_index_invalidate_statistics", "mgx_index_synchronize", "mgx_batch_df_merge_local", "mgx_batch_merge_local",
@@ -69,6 +69,11 @@ class IndexDesc(C.Structure):
                 ("n_grams", C.c_uint64), ("offsets", C.c_void_p), ("docids", C.c_void_p), ("tf", C.c_void_p),
                 ("doc_len", C.c_void_p), ("dense_threshold", C.c_double),
                 ("tf_overflow_pos", C.c_void_p), ("tf_overflow_val", C.c_void_p), ("n_tf_overflow", C.c_uint64)]
+
+
+class IndexBuildDesc(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("version", C.c_uint32), ("device", C.c_int32), ("tile_shift", C.c_uint32),
+                ("dense_threshold", C.c_double), ("attach_text", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class Term(C.Structure):
@@ -219,6 +224,9 @@ def load():
     L.mgx_columns_destroy.argtypes = [vp]
     L.mgx_columns_destroy.restype = None
     L.mgx_index_create.argtypes = [C.POINTER(IndexDesc), C.POINTER(vp)]
+    L.mgx_index_build_device.argtypes = [C.POINTER(BuildParams), C.POINTER(IndexBuildDesc), vp, vp, u32, u64, C.POINTER(vp),
+                                         C.POINTER(vp)]
+    L.mgx_index_read_postings.argtypes = [vp, u32, vp, vp, u64, C.POINTER(u64)]
     L.mgx_index_destroy.argtypes = [vp]
     L.mgx_index_destroy.restype = None
     L.mgx_posting_size.argtypes = [vp, u32, C.POINTER(u64)]

@@ -12,7 +12,7 @@ EXPORTS = ["mgxs_last_error", "mgxs_table_adopt", "mgxs_table_set_global_stats",
            "mgxs_table_set_normalization", "mgxs_table_set_absent_grams", "mgxs_normalize_uses_icu", "mgxs_normalize_text",
            "mgxs_executor_create", "mgxs_executor_create_sharded", "mgxs_executor_destroy", "mgxs_executor_warm",
            "mgxs_submit", "mgxs_wait", "mgxs_table_from_dump", "mgxs_table_add_filter_column", "mgxs_search", "mgxs_search_sorted", "mgxs_search_by_primary_key", "mgxs_facet", "mgxs_facet_columns", "mgxs_search_highlight", "mgxs_highlight_generate", "mgxs_search_documents",
-           "mgxs_table_add_document", "mgxs_table_update_document", "mgxs_table_remove_document", "mgxs_table_mutation_stats", "mgxs_table_compact", "mgxs_table_set_mutation_staleness", "mgxs_table_set_device_build", "mgxs_table_update_filters",
+           "mgxs_table_add_document", "mgxs_table_update_document", "mgxs_table_remove_document", "mgxs_table_mutation_stats", "mgxs_table_compact", "mgxs_table_set_mutation_staleness", "mgxs_table_set_device_build", "mgxs_table_set_build_mode", "mgxs_table_build_counters", "mgxs_table_update_filters",
            "mgxs_batcher_create", "mgxs_batcher_destroy", "mgxs_batcher_search", "mgxs_batcher_stats"]
 _lib = None
 
@@ -70,6 +70,8 @@ def load():
     L.mgxs_table_compact.argtypes = [vp]
     L.mgxs_table_set_mutation_staleness.argtypes = [vp, u64]
     L.mgxs_table_set_device_build.argtypes = [vp, i32]
+    L.mgxs_table_set_build_mode.argtypes = [vp, i32]
+    L.mgxs_table_build_counters.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
     L.mgxs_table_update_filters.argtypes = [vp, u32, u32, vp, vp, vp, vp]
     L.mgxs_table_mutation_stats.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
     L.mgxs_batcher_create.argtypes = [vp, u32, u32, i32, i32, C.POINTER(vp)]
@@ -244,6 +246,19 @@ class Table:
     def set_device_build(self, on):
         """Index::SetDeviceBuild: later builds of this table's column arrays run on its device (same arrays either way)."""
         _check(load().mgxs_table_set_device_build(self._h, int(bool(on))))
+
+    BUILD_HOST, BUILD_DEVICE_COLUMNS, BUILD_DEVICE_RESIDENT = 0, 1, 2
+
+    def set_build_mode(self, mode):
+        """Index::SetBuildMode: BUILD_HOST, BUILD_DEVICE_COLUMNS (= set_device_build(1)) or BUILD_DEVICE_RESIDENT (columns,
+        device index and texts by mgx_index_build_device: the postings never come to the host)."""
+        _check(load().mgxs_table_set_build_mode(self._h, int(mode)))
+
+    def build_counters(self):
+        """Index::BuildCounters: generations built since creation by the mode that built each."""
+        a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _check(load().mgxs_table_build_counters(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return {"host": a.value, "device_columns": b.value, "device_resident": c.value}
 
     def compact(self):
         """Index::Compact: the main index rebuilt from the current documents (delta and live row go)."""

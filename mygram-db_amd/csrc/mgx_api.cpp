@@ -749,6 +749,13 @@ void mgx_columns_destroy(mgx_columns* cols) { mgx::DestroyColumns(reinterpret_ca
 
 // ---- index ------------------------------------------------------------------------------------------------------
 
+// An index is made in two parts. The first brings the postings to the device: IndexCreateImpl takes them from the caller
+// (validate, then upload), mgx_index_build_device adopts the arrays the device builder left there. The second,
+// IndexDeriveRest, is shared: everything else comes from the resident columns and the host's copy of `offsets`.
+static int IndexOpenStreams(mgx_index* idx);
+static int IndexDeriveRest(mgx_index* idx, uint32_t first_doc_id, uint64_t n_docs, double dense_threshold,
+                           uint64_t n_tf_overflow, uint32_t max_doc_len);
+
 static int IndexCreateImpl(const mgx_index_desc* d, mgx_index** out) {
   auto idx = std::make_unique<mgx_index>();
   idx->device = d->device;
@@ -802,15 +809,7 @@ static int IndexCreateImpl(const mgx_index_desc* d, mgx_index** out) {
     return mgx::Fail(MGX_ERR_INTERNAL, "no HIP device available: libmygram_gpu has no CPU fallback");
   }
   if (d->device < 0 || d->device >= ndev) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_index_create: bad device");
-  MGX_HIP(hipSetDevice(d->device));
-  MGX_HIP(hipStreamCreateWithFlags(&idx->stream, hipStreamNonBlocking));
-  // The side stream (the few queries the main launch does not take: cand_kernel, the list-operand and general kernels)
-  // is created at the device's highest priority. At the default priority it shared a hardware queue with the batch
-  // streams, so its launch — a few dozen workgroups for ~0.27 ms on the benchmark batch — ran BEFORE the main launch
-  // instead of beside it; a high-priority stream gets a queue of its own.
-  int prio_least = 0, prio_greatest = 0;
-  MGX_HIP(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
-  MGX_HIP(hipStreamCreateWithPriority(&idx->side_stream, hipStreamNonBlocking, prio_greatest));
+  if (const int rc = IndexOpenStreams(idx.get())) return rc;
   const uint32_t n_tiles = static_cast<uint32_t>((n_docs + mgx::kTileDocs - 1) >> mgx::kTileShift);
   idx->n_grams = G;
   idx->h_offsets.assign(d->offsets, d->offsets + G + 1);
@@ -835,24 +834,54 @@ static int IndexCreateImpl(const mgx_index_desc* d, mgx_index** out) {
     MGX_HIP(mgx::Upload(idx->d_tf, d->tf, P, 4));
     MGX_HIP(mgx::Upload(idx->d_doc_len, d->doc_len, n_docs));
     for (uint64_t i = 0; i < n_docs; ++i) max_doc_len = std::max(max_doc_len, d->doc_len[i]);
+    // padded to whole tiles (zeros): group_score_kernel copies a tile's 16 KiB into LDS whole
+    std::vector<uint8_t> dl8((n_docs + mgx::kTileDocs - 1) / mgx::kTileDocs * mgx::kTileDocs, 0);
+    for (uint64_t i = 0; i < n_docs; ++i) dl8[i] = static_cast<uint8_t>(std::min<uint32_t>(d->doc_len[i], 255u));
+    MGX_HIP(mgx::Upload(idx->d_dl8, dl8.data(), dl8.size(), 16));
   }
+  if (const int rc = IndexDeriveRest(idx.get(), d->first_doc_id, n_docs, d->dense_threshold,
+                                     idx->can_score ? d->n_tf_overflow : 0, max_doc_len))
+    return rc;
+  *out = idx.release();
+  return MGX_OK;
+}
 
+static int IndexOpenStreams(mgx_index* idx) {
+  MGX_HIP(hipSetDevice(idx->device));
+  MGX_HIP(hipStreamCreateWithFlags(&idx->stream, hipStreamNonBlocking));
+  // The side stream (the few queries the main launch does not take: cand_kernel, the list-operand and general kernels)
+  // is created at the device's highest priority. At the default priority it shared a hardware queue with the batch
+  // streams, so its launch — a few dozen workgroups for ~0.27 ms on the benchmark batch — ran BEFORE the main launch
+  // instead of beside it; a high-priority stream gets a queue of its own.
+  int prio_least = 0, prio_greatest = 0;
+  MGX_HIP(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
+  MGX_HIP(hipStreamCreateWithPriority(&idx->side_stream, hipStreamNonBlocking, prio_greatest));
+  return MGX_OK;
+}
+
+// idx holds: device, streams, n_grams, h_offsets, words_per_row, can_score, and on the device offsets, docids and, when
+// it scores, tf, doc_len, dl8 and the tf overflow table.
+static int IndexDeriveRest(mgx_index* idx, uint32_t first_doc_id, uint64_t n_docs, double dense_threshold,
+                           uint64_t n_tf_overflow, uint32_t max_doc_len) {
+  const uint64_t G = idx->n_grams;
+  const uint64_t* offsets = idx->h_offsets.data();
+  const uint32_t n_tiles = static_cast<uint32_t>((n_docs + mgx::kTileDocs - 1) >> mgx::kTileShift);
   // which grams get a skip row / a dense bitmap
-  double dense_thr = d->dense_threshold == 0.0 ? 1.0 / 256.0 : d->dense_threshold;
+  double dense_thr = dense_threshold == 0.0 ? 1.0 / 256.0 : dense_threshold;
   const uint64_t skip_min = std::max<uint64_t>(64, static_cast<uint64_t>(n_tiles) + 1);
   idx->h_skip_row.assign(G, mgx::kNoRow);
   idx->h_bm_row.assign(G, mgx::kNoRow);
   std::vector<uint32_t> skip_grams, bm_grams;
   std::vector<uint64_t> bm_lo, bm_hi;
   for (uint64_t g = 0; g < G; ++g) {
-    const uint64_t len = d->offsets[g + 1] - d->offsets[g];
+    const uint64_t len = offsets[g + 1] - offsets[g];
     if (len > 0xFFFFFFFFull) return mgx::Fail(MGX_ERR_OUT_OF_RANGE, "a posting list exceeds 2^32 entries");
     const bool dense = len > 0 && static_cast<double>(len) >= dense_thr * static_cast<double>(n_docs);
     if (dense) {
       idx->h_bm_row[g] = static_cast<uint32_t>(bm_grams.size());
       bm_grams.push_back(static_cast<uint32_t>(g));
-      bm_lo.push_back(d->offsets[g]);
-      bm_hi.push_back(d->offsets[g + 1]);
+      bm_lo.push_back(offsets[g]);
+      bm_hi.push_back(offsets[g + 1]);
     }
     if (dense || len >= skip_min) {
       idx->h_skip_row[g] = static_cast<uint32_t>(skip_grams.size());
@@ -866,7 +895,7 @@ static int IndexCreateImpl(const mgx_index_desc* d, mgx_index** out) {
     MGX_HIP(idx->d_tile_off.Alloc(skip_grams.size() * (static_cast<size_t>(n_tiles) + 1) * sizeof(uint32_t)));
     MGX_LAUNCH(mgx::LaunchBuildTileOff(idx->d_offsets.as<uint64_t>(), idx->d_docids.as<uint32_t>(),
                                        d_rows.as<uint32_t>(), static_cast<uint32_t>(skip_grams.size()), n_tiles,
-                                       d->first_doc_id, idx->d_tile_off.as<uint32_t>(), idx->stream));
+                                       first_doc_id, idx->d_tile_off.as<uint32_t>(), idx->stream));
     MGX_HIP(hipStreamSynchronize(idx->stream));
   }
   if (!bm_grams.empty()) {
@@ -876,7 +905,7 @@ static int IndexCreateImpl(const mgx_index_desc* d, mgx_index** out) {
     MGX_HIP(idx->d_gram_bitmaps.Alloc(bm_grams.size() * idx->words_per_row * sizeof(uint64_t)));
     MGX_HIP(hipMemsetAsync(idx->d_gram_bitmaps.p, 0, idx->d_gram_bitmaps.bytes, idx->stream));
     MGX_LAUNCH(mgx::LaunchBuildBitmaps(idx->d_docids.as<uint32_t>(), d_lo.as<uint64_t>(), d_hi.as<uint64_t>(),
-                                       static_cast<uint32_t>(bm_grams.size()), d->first_doc_id, 0,
+                                       static_cast<uint32_t>(bm_grams.size()), first_doc_id, 0,
                                        /*tile_stride=*/bm_grams.size() * mgx::kWordsPerTile,
                                        /*row_stride=*/mgx::kWordsPerTile, idx->d_gram_bitmaps.as<uint64_t>(),
                                        idx->stream));
@@ -887,7 +916,7 @@ static int IndexCreateImpl(const mgx_index_desc* d, mgx_index** out) {
       MGX_HIP(idx->d_tfnib.Alloc(bm_grams.size() * stride + 256));
       MGX_HIP(hipMemsetAsync(idx->d_tfnib.p, 0, idx->d_tfnib.bytes, idx->stream));
       MGX_LAUNCH(mgx::LaunchBuildTfNib(idx->d_docids.as<uint32_t>(), idx->d_tf.as<uint8_t>(), d_lo.as<uint64_t>(),
-                                       d_hi.as<uint64_t>(), static_cast<uint32_t>(bm_grams.size()), d->first_doc_id,
+                                       d_hi.as<uint64_t>(), static_cast<uint32_t>(bm_grams.size()), first_doc_id,
                                        stride, idx->d_tfnib.as<uint8_t>(), idx->stream));
       MGX_HIP(hipStreamSynchronize(idx->stream));
       idx->dev.nib_row_stride = stride;
@@ -898,12 +927,6 @@ static int IndexCreateImpl(const mgx_index_desc* d, mgx_index** out) {
     idx->table_cap = static_cast<uint32_t>(std::min<uint64_t>(2 * bm_grams.size() + 4096, 1u << 20));
     MGX_HIP(idx->d_table_pool.Alloc(static_cast<size_t>(idx->table_cap) * idx->table_doubles() * sizeof(double)));
   }
-  if (idx->can_score) {
-    // padded to whole tiles (zeros): group_score_kernel copies a tile's 16 KiB into LDS whole
-    std::vector<uint8_t> dl8((n_docs + mgx::kTileDocs - 1) / mgx::kTileDocs * mgx::kTileDocs, 0);
-    for (uint64_t i = 0; i < n_docs; ++i) dl8[i] = static_cast<uint8_t>(std::min<uint32_t>(d->doc_len[i], 255u));
-    MGX_HIP(mgx::Upload(idx->d_dl8, dl8.data(), dl8.size(), 16));
-  }
 
   mgx::DevIndex& v = idx->dev;
   v.offsets = idx->d_offsets.as<uint64_t>();
@@ -911,7 +934,7 @@ static int IndexCreateImpl(const mgx_index_desc* d, mgx_index** out) {
   v.tf = idx->d_tf.as<uint8_t>();
   v.tf_ovf_pos = idx->d_tf_ovf_pos.as<uint64_t>();
   v.tf_ovf_val = idx->d_tf_ovf_val.as<uint32_t>();
-  v.n_tf_ovf = idx->can_score ? static_cast<uint32_t>(d->n_tf_overflow) : 0u;
+  v.n_tf_ovf = idx->can_score ? static_cast<uint32_t>(n_tf_overflow) : 0u;
   v.doc_len = idx->d_doc_len.as<uint32_t>();
   v.dl8 = idx->d_dl8.as<uint8_t>();
   v.tfnib = idx->d_tfnib.as<uint8_t>();
@@ -926,7 +949,7 @@ static int IndexCreateImpl(const mgx_index_desc* d, mgx_index** out) {
     static const double kFineDensity = std::getenv("MGX_FINE_DENSITY") ? atof(std::getenv("MGX_FINE_DENSITY")) : 0.05;
     std::vector<uint32_t> fine_map(bm_grams.size(), mgx::kNoRow), fine_rows;
     for (size_t r = 0; r < bm_grams.size(); ++r) {
-      const uint64_t sz = d->offsets[bm_grams[r] + 1] - d->offsets[bm_grams[r]];
+      const uint64_t sz = offsets[bm_grams[r] + 1] - offsets[bm_grams[r]];
       if (static_cast<double>(sz) > kFineDensity * static_cast<double>(n_docs)) {
         fine_map[r] = static_cast<uint32_t>(fine_rows.size());
         fine_rows.push_back(static_cast<uint32_t>(r));
@@ -944,12 +967,11 @@ static int IndexCreateImpl(const mgx_index_desc* d, mgx_index** out) {
   v.fb_tile_stride = mgx::kWordsPerTile;
   v.fb_row_stride = idx->filter_row_stride;
   v.filter_bitmaps = nullptr;
-  v.first_doc_id = d->first_doc_id;
+  v.first_doc_id = first_doc_id;
   v.n_docs = static_cast<uint32_t>(n_docs);
   v.n_tiles = n_tiles;
   v.max_doc_len = max_doc_len;
-  MGX_HIP(mgx::SyncDevIndex(idx.get()));
-  *out = idx.release();
+  MGX_HIP(mgx::SyncDevIndex(idx));
   return MGX_OK;
 }
 
@@ -967,6 +989,139 @@ int mgx_index_create(const mgx_index_desc* desc, mgx_index** out) {
   } catch (const std::exception& e) {
     return mgx::Fail(MGX_ERR_INTERNAL, std::string("mgx_index_create: ") + e.what());
   }
+}
+
+int mgx_index_build_device(const mgx_build_params* params, const mgx_index_build_desc* desc, const uint8_t* text_bytes,
+                           const uint64_t* text_off, uint32_t first_doc_id, uint64_t n_docs, mgx_columns** dictionary_out,
+                           mgx_index** index_out) {
+  if (dictionary_out) *dictionary_out = nullptr;
+  if (index_out) *index_out = nullptr;
+  // ---- host-only checks first: mgx_columns_build_device's, then mgx_index_create's; they answer without a device ---------
+  if (!params || !desc || !dictionary_out || !index_out || !text_off ||
+      (n_docs && !text_bytes && text_off[n_docs] != text_off[0]))
+    return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_index_build_device: null argument");
+  if (params->struct_size < sizeof(mgx_build_params) || params->version != MGX_ABI_VERSION ||
+      desc->struct_size < sizeof(mgx_index_build_desc) || desc->version != MGX_ABI_VERSION)
+    return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_index_build_device: bad struct_size/version");
+  if (static_cast<uint64_t>(first_doc_id) + n_docs > 0xFFFFFFFFull)
+    return mgx::Fail(MGX_ERR_OUT_OF_RANGE, "mgx_index_build_device: doc ids exceed uint32");
+  const int kanji_n = params->kanji_ngram_size > 0 ? params->kanji_ngram_size : params->ngram_size;
+  if (params->ngram_size > mgx::build::kMaxGram || kanji_n > mgx::build::kMaxGram)
+    return mgx::Fail(MGX_ERR_NOT_IMPLEMENTED,
+                     "mgx_index_build_device: n-grams of more than 3 code points are not built on the device (a gram is "
+                     "packed into 64 bits); use mgx_columns_build and mgx_index_create");
+  for (uint64_t d = 0; d < n_docs; ++d)
+    if (text_off[d + 1] < text_off[d])
+      return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_index_build_device: text_off descends");
+  if (desc->tile_shift != 0 && desc->tile_shift != static_cast<uint32_t>(mgx::kTileShift))
+    return mgx::Fail(MGX_ERR_NOT_IMPLEMENTED, "mgx_index_build_device: only tile_shift 14 is built");
+  if (n_docs == 0) return mgx::Fail(MGX_ERR_OUT_OF_RANGE, "mgx_index_build_device: n_docs must be in [1, 2^32) and ids fit uint32");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+    (void)hipGetLastError();
+    return mgx::Fail(MGX_ERR_INTERNAL, "no HIP device available: libmygram_gpu has no CPU fallback");
+  }
+  if (desc->device < 0 || desc->device >= ndev) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_index_build_device: bad device");
+  if (text_off[n_docs] - text_off[0] > mgx::build::kMaxTextBytes)
+    return mgx::Fail(MGX_ERR_OUT_OF_RANGE, "mgx_index_build_device: " + std::to_string(text_off[n_docs] - text_off[0]) +
+                                               " bytes of text, the device builder takes " +
+                                               std::to_string(mgx::build::kMaxTextBytes) + "; use mgx_columns_build");
+  mgx_index* made = nullptr;
+  mgx::Columns* cols = nullptr;
+  auto undo = [&](int rc) {
+    if (made) mgx_index_destroy(made);
+    if (cols) mgx::DestroyColumns(cols);
+    return rc;
+  };
+  static const bool kTrace = std::getenv("MGX_TRACE_HOST") != nullptr;
+  const auto t0 = std::chrono::steady_clock::now();
+  try {
+    const bool attach = desc->attach_text != 0;
+    mgx::build::PackedColumns packed;
+    mgx::build::ResidentArrays res;
+    std::string err;
+    const int rc = mgx::build::BuildOnDevice(*params, text_bytes, text_off, first_doc_id, n_docs, desc->device, &packed, &err,
+                                             &res, attach);
+    if (rc != MGX_OK) return mgx::Fail(rc, err);
+    const auto t1 = std::chrono::steady_clock::now();
+    cols = mgx::ColumnsFromPacked(*params, text_off, first_doc_id, n_docs, std::move(packed));
+    mgx_columns_view cv;
+    mgx::ColumnsView(cols, &cv);
+    const auto t2 = std::chrono::steady_clock::now();
+
+    // ---- the index adopts the builder's arrays: what IndexCreateImpl uploads is there already -----------------------------
+    auto idx = std::make_unique<mgx_index>();
+    idx->device = desc->device;
+    auto adopt = [](DevBuf& b, void*& p, uint64_t bytes) {
+      b.Free();
+      b.p = p;
+      b.bytes = static_cast<size_t>(bytes);
+      b.owned = true;
+      p = nullptr;
+    };
+    adopt(idx->d_docids, res.docids, res.plan.docids);
+    adopt(idx->d_tf, res.tf, res.plan.tf);
+    adopt(idx->d_doc_len, res.doc_len, res.plan.doc_len);
+    adopt(idx->d_dl8, res.dl8, res.plan.dl8);
+    if (attach) {
+      adopt(idx->d_text, res.text, res.plan.text);
+      adopt(idx->d_text_off, res.text_off, res.plan.text_off);
+    }
+    made = idx.release();
+    if (const int e = IndexOpenStreams(made)) return undo(e);
+    const uint64_t G = cv.n_grams;
+    const uint32_t n_tiles = static_cast<uint32_t>((n_docs + mgx::kTileDocs - 1) >> mgx::kTileShift);
+    made->n_grams = G;
+    made->h_offsets.assign(cv.offsets, cv.offsets + G + 1);
+    made->words_per_row = static_cast<uint64_t>(n_tiles) * mgx::kWordsPerTile;
+    made->can_score = true;
+    auto up = [&](hipError_t e, const char* what) {
+      if (e == hipSuccess) return 0;
+      (void)hipGetLastError();
+      return mgx::Fail(MGX_ERR_INTERNAL, std::string("mgx_index_build_device: ") + what + ": " + hipGetErrorString(e));
+    };
+    if (const int e = up(mgx::Upload(made->d_offsets, cv.offsets, G + 1), "offsets")) return undo(e);
+    if (cv.n_tf_overflow) {
+      if (const int e = up(mgx::Upload(made->d_tf_ovf_pos, cv.tf_overflow_pos, cv.n_tf_overflow), "tf overflow")) return undo(e);
+      if (const int e = up(mgx::Upload(made->d_tf_ovf_val, cv.tf_overflow_val, cv.n_tf_overflow), "tf overflow")) return undo(e);
+    }
+    uint32_t max_doc_len = 0;
+    for (uint64_t i = 0; i < n_docs; ++i) max_doc_len = std::max(max_doc_len, cv.doc_len[i]);
+    if (attach) {  // what mgx_index_attach_text leaves behind
+      uint64_t longest = 0;
+      for (uint64_t i = 0; i < n_docs; ++i) longest = std::max<uint64_t>(longest, text_off[i + 1] - text_off[i]);
+      made->max_text_bytes = static_cast<uint32_t>(longest);
+      made->dev.text = made->d_text.as<uint8_t>();
+      made->dev.text_off = made->d_text_off.as<uint64_t>();
+    }
+    if (const int e = IndexDeriveRest(made, first_doc_id, n_docs, desc->dense_threshold, cv.n_tf_overflow, max_doc_len))
+      return undo(e);
+    if (kTrace) {
+      const auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+      fprintf(stderr, "[mgx] resident build of %llu docs: device build and copies %.2f ms, dictionary %.2f ms, rest of the index %.2f ms\n",
+              static_cast<unsigned long long>(n_docs), ms(t0, t1), ms(t1, t2), ms(t2, std::chrono::steady_clock::now()));
+    }
+    *dictionary_out = reinterpret_cast<mgx_columns*>(cols);
+    *index_out = made;
+    return MGX_OK;
+  } catch (const std::exception& e) {
+    return undo(mgx::Fail(MGX_ERR_INTERNAL, std::string("mgx_index_build_device: ") + e.what()));
+  }
+}
+
+int mgx_index_read_postings(mgx_index* idx, uint32_t gram_id, uint32_t* docids, uint8_t* tf, uint64_t capacity, uint64_t* n) {
+  if (!idx || !n) return mgx::Fail(MGX_ERR_INVALID_ARGUMENT, "mgx_index_read_postings: null argument");
+  *n = 0;
+  std::lock_guard<std::mutex> lock(idx->mu);
+  if (gram_id >= idx->n_grams) return mgx::Fail(MGX_ERR_OUT_OF_RANGE, "mgx_index_read_postings: unknown gram id");
+  const uint64_t lo = idx->h_offsets[gram_id], len = idx->h_offsets[gram_id + 1] - lo;
+  *n = len;
+  if (len == 0 || (!docids && !tf)) return MGX_OK;  // size query
+  if (capacity < len) return mgx::Fail(MGX_ERR_OUT_OF_RANGE, "mgx_index_read_postings: buffer too small (*n holds the count)");
+  MGX_HIP(hipSetDevice(idx->device));
+  if (docids) MGX_HIP(hipMemcpy(docids, idx->d_docids.as<uint32_t>() + lo, len * 4, hipMemcpyDeviceToHost));
+  if (tf && idx->can_score) MGX_HIP(hipMemcpy(tf, idx->d_tf.as<uint8_t>() + lo, len, hipMemcpyDeviceToHost));
+  return MGX_OK;
 }
 
 void mgx_index_destroy(mgx_index* idx) {

@@ -16,6 +16,11 @@
 //   7  gram_heads_kernel          heads of (key, doc) runs and of keys, as two counters in one u64; exclusive scan
 //   8  gram_tf_kernel             one lane per run: left-greedy tf, docids / tf / overflow; one lane per key: offsets, keys
 // The texts are read twice (1 and 3, 16-byte loads); the second read of a delta-sized text comes from the L2.
+//
+// Two endings. mgx_columns_build_device copies every column down into host arrays. mgx_index_build_device (the resident
+// ending) copies down what a host caller reads (keys, offsets, doc_len, overflow entries, counters) and leaves docids, tf,
+// doc_len and the texts on the device, copied device to device into exactly sized allocations the index adopts:
+//   9  resident_rows_kernel       four doc slots per lane: the tile-padded dl8 row, the text offsets rebased to 0
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -24,6 +29,7 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include "mgx_build.hpp"
+#include "mgx_internal.hpp"
 #include "mgx_text.hpp"
 
 namespace mgx {
@@ -209,6 +215,38 @@ __global__ __launch_bounds__(kBlockThreads) void gram_tf_kernel(
   }
 }
 
+// The two rows an index derives from the build's doc_len and text offsets (the resident ending): dl8[slot] =
+// min(doc_len[slot], 255) with zeros from n_docs up to the tile boundary, and text_off[d] = off[d] - base. A lane takes
+// kResidentSlotsPerLane consecutive slots: one 16-byte load of doc_len, one 4-byte store of the packed bytes; a wave
+// reads 1 KiB and writes 256 bytes in a row. dl8_slots is a multiple of the slots per lane, doc_len is 16-byte aligned
+// and its allocation is rounded up to 256 bytes, so the full-width load of a lane below n_docs lies inside it.
+static_assert(kResidentSlotsPerLane == 4 && kResidentTileDocs % kResidentSlotsPerLane == 0, "one u32 store per lane");
+__global__ __launch_bounds__(kBlockThreads) void resident_rows_kernel(
+    const uint32_t* __restrict__ doc_len, const uint64_t* __restrict__ off, uint64_t base, uint64_t n_docs, uint64_t dl8_slots,
+    uint8_t* __restrict__ dl8, uint64_t* __restrict__ text_off) {
+  const uint64_t s0 = (static_cast<uint64_t>(blockIdx.x) * kBlockThreads + threadIdx.x) * kResidentSlotsPerLane;
+  if (s0 < dl8_slots) {
+    uint32_t len[kResidentSlotsPerLane] = {0, 0, 0, 0};
+    if (s0 + kResidentSlotsPerLane <= n_docs) {
+      const uint4 v = *reinterpret_cast<const uint4*>(doc_len + s0);
+      len[0] = v.x, len[1] = v.y, len[2] = v.z, len[3] = v.w;
+    } else {
+#pragma unroll
+      for (uint32_t j = 0; j < kResidentSlotsPerLane; ++j)
+        if (s0 + j < n_docs) len[j] = doc_len[s0 + j];
+    }
+    uint32_t packed = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < kResidentSlotsPerLane; ++j) packed |= (len[j] < 255u ? len[j] : 255u) << (8 * j);
+    *reinterpret_cast<uint32_t*>(dl8 + s0) = packed;
+  }
+  if (text_off) {
+#pragma unroll
+    for (uint32_t j = 0; j < kResidentSlotsPerLane; ++j)
+      if (s0 + j <= n_docs) text_off[s0 + j] = off[s0 + j] - base;
+  }
+}
+
 // The device allocation of a finished build is kept for the next one when it is small, so that the delta rebuilds of a
 // writer do not pay an allocation each; kept allocations are leased, concurrent callers get their own. The STREAM is made
 // for the call and destroyed with it: a stream that stays alive holds a hardware queue, and the streams of every device
@@ -267,16 +305,101 @@ struct Lease {
 
 inline unsigned Blocks(uint64_t n) { return static_cast<unsigned>((n + kBlockThreads - 1) / kBlockThreads); }
 
+// The resident ending: exactly sized allocations of the index's own, filled device to device on the build's stream, which
+// is synchronised before this returns (the arena may go to another thread right after). Null sources stand for a build
+// without text bytes: no postings, every length and offset 0. *no_room: an allocation failed for lack of memory.
+hipError_t FillResident(hipStream_t st, uint64_t n_postings, uint64_t n_docs, uint64_t n_bytes, uint64_t base,
+                        const uint32_t* s_docids, const uint8_t* s_tf, const uint32_t* s_doc_len, const uint8_t* s_text,
+                        const uint64_t* s_off, bool attach_text, ResidentArrays* r, bool* no_room) {
+  const ResidentPlan pl = PlanResident(n_docs, n_postings, n_bytes, attach_text);
+  r->plan = pl;
+  *no_room = false;
+#define MGX_RES_TRY(expr)                  \
+  do {                                     \
+    const hipError_t e__ = (expr);         \
+    if (e__ != hipSuccess) return e__;     \
+  } while (0)
+  auto alloc = [&](void** p, uint64_t bytes) {
+    const hipError_t e = hipMalloc(p, bytes ? bytes : 16);
+    if (e != hipSuccess) {
+      *p = nullptr;
+      *no_room = e == hipErrorOutOfMemory;
+    }
+    return e;
+  };
+  MGX_RES_TRY(alloc(&r->docids, pl.docids));
+  MGX_RES_TRY(alloc(&r->tf, pl.tf));
+  MGX_RES_TRY(alloc(&r->doc_len, pl.doc_len));
+  MGX_RES_TRY(alloc(&r->dl8, pl.dl8));
+  if (attach_text) {
+    MGX_RES_TRY(alloc(&r->text, pl.text));
+    MGX_RES_TRY(alloc(&r->text_off, pl.text_off));
+  }
+  uint8_t* docids = static_cast<uint8_t*>(r->docids);
+  uint8_t* tf = static_cast<uint8_t*>(r->tf);
+  uint8_t* dl8 = static_cast<uint8_t*>(r->dl8);
+  if (n_postings) MGX_RES_TRY(hipMemcpyAsync(docids, s_docids, n_postings * 4, hipMemcpyDeviceToDevice, st));
+  MGX_RES_TRY(hipMemsetAsync(docids + n_postings * 4, 0xFF, kResidentIdPad * 4, st));
+  if (n_postings) MGX_RES_TRY(hipMemcpyAsync(tf, s_tf, n_postings, hipMemcpyDeviceToDevice, st));
+  MGX_RES_TRY(hipMemsetAsync(tf + n_postings, 0xFF, kResidentIdPad, st));
+  MGX_RES_TRY(hipMemsetAsync(dl8 + pl.dl8_slots, 0xFF, kResidentDl8Pad, st));
+  if (attach_text) {
+    uint8_t* text = static_cast<uint8_t*>(r->text);
+    if (n_bytes) MGX_RES_TRY(hipMemcpyAsync(text, s_text, n_bytes, hipMemcpyDeviceToDevice, st));
+    MGX_RES_TRY(hipMemsetAsync(text + n_bytes, 0xFF, kResidentTextPad, st));
+  }
+  if (s_doc_len) {
+    MGX_RES_TRY(hipMemcpyAsync(r->doc_len, s_doc_len, n_docs * 4, hipMemcpyDeviceToDevice, st));
+    resident_rows_kernel<<<Blocks(pl.lanes), kBlockThreads, 0, st>>>(s_doc_len, s_off, base, n_docs, pl.dl8_slots, dl8,
+                                                                     static_cast<uint64_t*>(r->text_off));
+    MGX_RES_TRY(hipGetLastError());
+  } else {
+    MGX_RES_TRY(hipMemsetAsync(r->doc_len, 0, n_docs * 4, st));
+    MGX_RES_TRY(hipMemsetAsync(dl8, 0, pl.dl8_slots, st));
+    if (attach_text) MGX_RES_TRY(hipMemsetAsync(r->text_off, 0, pl.text_off, st));
+  }
+  return hipStreamSynchronize(st);
+#undef MGX_RES_TRY
+}
+
 }  // namespace
 
+static_assert(kResidentTileDocs == mgx::kTileDocs, "dl8 is padded to the index's tiles");
+
+void ResidentArrays::Free() {
+  for (void** p : {&docids, &tf, &doc_len, &dl8, &text, &text_off}) {
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+  }
+}
+
 int BuildOnDevice(const mgx_build_params& bp, const uint8_t* text_bytes, const uint64_t* text_off, uint32_t first_doc_id,
-                  uint64_t n_docs, int device, PackedColumns* out, std::string* err) {
+                  uint64_t n_docs, int device, PackedColumns* out, std::string* err, ResidentArrays* resident,
+                  bool attach_text) {
   hipStream_t st = nullptr;
+  const std::string who = resident ? "mgx_index_build_device: " : "mgx_columns_build_device: ";
   auto hip_fail = [&](const char* what, hipError_t e) {
     (void)hipGetLastError();
     if (st) (void)hipStreamSynchronize(st);  // (no copy into *out is in flight when the caller gets it back)
-    *err = std::string("mgx_columns_build_device: ") + what + ": " + hipGetErrorString(e);
+    if (resident) resident->Free();
+    *err = who + what + ": " + hipGetErrorString(e);
     return MGX_ERR_INTERNAL;
+  };
+  // the resident ending over the build's arrays (all null: a build without text bytes)
+  auto fill_resident = [&](uint64_t n_postings, uint64_t n_bytes, uint64_t base, const uint32_t* s_docids, const uint8_t* s_tf,
+                           const uint32_t* s_doc_len, const uint8_t* s_text, const uint64_t* s_off) {
+    bool no_room = false;
+    const hipError_t e = FillResident(st, n_postings, n_docs, n_bytes, base, s_docids, s_tf, s_doc_len, s_text, s_off,
+                                      attach_text, resident, &no_room);
+    if (e == hipSuccess) return static_cast<int>(MGX_OK);
+    if (!no_room) return hip_fail("the index's arrays", e);
+    (void)hipGetLastError();
+    (void)hipStreamSynchronize(st);
+    const uint64_t needed = resident->plan.total();
+    resident->Free();
+    *err = who + "the index's arrays need " + std::to_string(needed) + " bytes of device memory and device " +
+           std::to_string(device) + " has no room for them; build with mgx_columns_build";
+    return static_cast<int>(MGX_ERR_OUT_OF_RANGE);
   };
 #define MGX_BUILD_TRY(expr)                                    \
   do {                                                         \
@@ -289,6 +412,16 @@ int BuildOnDevice(const mgx_build_params& bp, const uint8_t* text_bytes, const u
   out->doc_len.assign(n_docs, 0);
   out->offsets.assign(1, 0);
   if (n_docs == 0 || n_bytes == 0) {  // nothing to decode: the columns of an empty index
+    if (resident) {
+      MGX_BUILD_TRY(hipSetDevice(device));
+      Lease lease(device);
+      if (!lease.ok) {
+        *err = who + "no stream";
+        return MGX_ERR_INTERNAL;
+      }
+      st = lease.stream;
+      return fill_resident(0, 0, base, nullptr, nullptr, nullptr, nullptr, nullptr);
+    }
     out->docids.assign(4, 0xFFFFFFFFu);
     out->tf.assign(4, 0);
     return MGX_OK;
@@ -297,7 +430,7 @@ int BuildOnDevice(const mgx_build_params& bp, const uint8_t* text_bytes, const u
   const Layout lay = PlanLayout(n_docs, n_bytes);
   Lease lease(device);
   if (!lease.ok) {
-    *err = "mgx_columns_build_device: no stream";
+    *err = who + "no stream";
     return MGX_ERR_INTERNAL;
   }
   st = lease.stream;
@@ -315,7 +448,7 @@ int BuildOnDevice(const mgx_build_params& bp, const uint8_t* text_bytes, const u
   }
   const uint64_t lib_tmp = Align256(std::max<uint64_t>({sort_tmp, scan_tmp, block_tmp, 256}));
   if (lib_tmp > kLibrarySlack + n_bytes) {
-    *err = "mgx_columns_build_device: the sort asks for " + std::to_string(lib_tmp) + " bytes of temporary storage, more than the " +
+    *err = who + "the sort asks for " + std::to_string(lib_tmp) + " bytes of temporary storage, more than the " +
            std::to_string(kLibrarySlack + n_bytes) + " planned for it; build with mgx_columns_build";
     return MGX_ERR_OUT_OF_RANGE;
   }
@@ -324,9 +457,13 @@ int BuildOnDevice(const mgx_build_params& bp, const uint8_t* text_bytes, const u
     lease.DropArena();
     size_t free_b = 0, total_b = 0;
     MGX_BUILD_TRY(hipMemGetInfo(&free_b, &total_b));
-    const Budget budget = PlanBudget(n_docs, n_bytes, free_b);
+    Budget budget = PlanBudget(n_docs, n_bytes, free_b);
+    if (resident) {  // (at most one posting per text byte)
+      budget.needed += PlanResident(n_docs, n_bytes, n_bytes, attach_text).total();
+      budget.fits = budget.needed <= free_b;
+    }
     if (!budget.fits) {
-      *err = "mgx_columns_build_device: the build needs " + std::to_string(budget.needed) + " bytes of temporary device storage, device " +
+      *err = who + "the build needs " + std::to_string(budget.needed) + " bytes of temporary device storage, device " +
              std::to_string(device) + " has " + std::to_string(free_b) + " bytes free; build with mgx_columns_build";
       return MGX_ERR_OUT_OF_RANGE;
     }
@@ -372,7 +509,7 @@ int BuildOnDevice(const mgx_build_params& bp, const uint8_t* text_bytes, const u
   MGX_BUILD_TRY(hipMemcpyAsync(&n_cps, d_bbase + lay.n_blocks, 4, hipMemcpyDeviceToHost, st));
   MGX_BUILD_TRY(hipStreamSynchronize(st));
   if (n_cps > rec_cap) {
-    *err = "mgx_columns_build_device: more code points than bytes";
+    *err = who + "more code points than bytes";
     return MGX_ERR_INTERNAL;
   }
   gram_decode_emit_kernel<<<nb, kBlockThreads, 0, st>>>(d_text, d_off, base, n_docs, n_bytes, d_mask, d_bbase, d_prefix, d_cps,
@@ -384,6 +521,8 @@ int BuildOnDevice(const mgx_build_params& bp, const uint8_t* text_bytes, const u
   MGX_BUILD_TRY(hipMemcpyAsync(out->doc_len.data(), d_doc_len, n_docs * 4, hipMemcpyDeviceToHost, st));
   uint64_t G = 0, P = 0;
   uint32_t n_ovf = 0;
+  uint32_t* d_docids = d_cps;  // (the columns take the place of the code points once the records are sorted)
+  uint8_t* d_tf = reinterpret_cast<uint8_t*>(d_cp_doc);
   if (n_cps > 0) {
     // ---- 5-6: records, sorted --------------------------------------------------------------------------------------------
     rocprim::double_buffer<uint64_t> keys(reinterpret_cast<uint64_t*>(at(lay.key0)), reinterpret_cast<uint64_t*>(at(lay.key1)));
@@ -401,8 +540,6 @@ int BuildOnDevice(const mgx_build_params& bp, const uint8_t* text_bytes, const u
     tmp_bytes = lib_tmp;
     MGX_BUILD_TRY(rocprim::exclusive_scan(d_tmp, tmp_bytes, d_flags, d_scan, uint64_t{0}, static_cast<size_t>(n_cps) + 1,
                                           rocprim::plus<uint64_t>(), st));
-    uint32_t* d_docids = d_cps;
-    uint8_t* d_tf = reinterpret_cast<uint8_t*>(d_cp_doc);
     const uint32_t ovf_cap = static_cast<uint32_t>(n_bytes / 255 + 1);
     gram_tf_kernel<<<Blocks(n_cps), kBlockThreads, 0, st>>>(keys.current(), vals.current(), d_flags, d_scan, n_cps, first_doc_id,
                                                             d_docids, d_tf, d_gkeys, d_goff, d_ovf, ovf_cap, d_counters);
@@ -414,24 +551,31 @@ int BuildOnDevice(const mgx_build_params& bp, const uint8_t* text_bytes, const u
     P = totals & 0xFFFFFFFFull;
     G = totals >> 32;
     if (P > n_cps || G > P || n_ovf > ovf_cap) {
-      *err = "mgx_columns_build_device: inconsistent counts";
+      *err = who + "inconsistent counts";
       return MGX_ERR_INTERNAL;
     }
     out->keys.resize(G);
     out->offsets.resize(G + 1);
-    out->docids.assign(P + 4, 0xFFFFFFFFu);
-    out->tf.assign(P + 4, 0);
     out->overflow.resize(n_ovf);
     if (G) MGX_BUILD_TRY(hipMemcpyAsync(out->keys.data(), d_gkeys, G * 8, hipMemcpyDeviceToHost, st));
     if (G) MGX_BUILD_TRY(hipMemcpyAsync(out->offsets.data(), d_goff, G * 8, hipMemcpyDeviceToHost, st));
-    if (P) MGX_BUILD_TRY(hipMemcpyAsync(out->docids.data(), d_docids, P * 4, hipMemcpyDeviceToHost, st));
-    if (P) MGX_BUILD_TRY(hipMemcpyAsync(out->tf.data(), d_tf, P, hipMemcpyDeviceToHost, st));
+    if (!resident) {
+      out->docids.assign(P + 4, 0xFFFFFFFFu);
+      out->tf.assign(P + 4, 0);
+      if (P) MGX_BUILD_TRY(hipMemcpyAsync(out->docids.data(), d_docids, P * 4, hipMemcpyDeviceToHost, st));
+      if (P) MGX_BUILD_TRY(hipMemcpyAsync(out->tf.data(), d_tf, P, hipMemcpyDeviceToHost, st));
+    }
     if (n_ovf) MGX_BUILD_TRY(hipMemcpyAsync(out->overflow.data(), d_ovf, n_ovf * 8ull, hipMemcpyDeviceToHost, st));
-  } else {
+  } else if (!resident) {
     out->docids.assign(4, 0xFFFFFFFFu);
     out->tf.assign(4, 0);
   }
-  MGX_BUILD_TRY(hipStreamSynchronize(st));
+  if (resident) {  // (synchronises the stream: the copies above have landed too)
+    const int rc = fill_resident(P, n_bytes, base, d_docids, d_tf, d_doc_len, d_text, d_off);
+    if (rc != MGX_OK) return rc;
+  } else {
+    MGX_BUILD_TRY(hipStreamSynchronize(st));
+  }
   out->offsets[G] = P;
   std::sort(out->overflow.begin(), out->overflow.end());  // (appended in any order; the posting index is the high word)
   return MGX_OK;

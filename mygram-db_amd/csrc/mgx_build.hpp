@@ -1,4 +1,5 @@
-// mgx_build.hpp — the device column builder (mgx_columns_build_device): what mgx_build.hip and its callers share.
+// mgx_build.hpp — the device column builder (mgx_columns_build_device, mgx_index_build_device): what mgx_build.hip and its
+// callers share.
 //
 //   key      a gram of at most kMaxGram code points packed into a u64: code point j as `cp + 1` in the 21-bit field at
 //            bits [42 - 21 j, 63 - 21 j), absent positions 0. Integer order of the packed keys == bytewise order of the
@@ -114,9 +115,55 @@ struct PackedColumns {
   std::vector<uint64_t> overflow;  // (posting index << 32) | true tf, ascending
 };
 
+// ---- the resident ending (mgx_index_build_device) ---------------------------------------------------------------------
+// The arrays a device index owns after a build that never brings the postings to the host: exactly the allocations
+// mgx_index_create and mgx_index_attach_text make for the same columns, byte for byte, their padding included.
+constexpr uint64_t kResidentTileDocs = 16384;   // mgx::kTileDocs (mgx_build.hip asserts it): dl8 is padded to whole tiles
+constexpr uint64_t kResidentIdPad = 4;          // entries of 0xFF behind docids and tf
+constexpr uint64_t kResidentDl8Pad = 16;        // bytes of 0xFF behind dl8
+constexpr uint64_t kResidentTextPad = 128;      // bytes of 0xFF behind the texts
+constexpr uint32_t kResidentSlotsPerLane = 4;   // doc slots one lane of resident_rows_kernel packs into one store
+
+struct ResidentPlan {
+  uint64_t dl8_slots = 0;  // n_docs rounded up to whole tiles
+  uint64_t docids = 0, tf = 0, doc_len = 0, dl8 = 0, text = 0, text_off = 0;  // bytes of each allocation
+  uint64_t lanes = 0;      // of resident_rows_kernel: covers dl8_slots and, with texts, the n_docs + 1 offsets
+  uint64_t total() const { return docids + tf + doc_len + dl8 + text + text_off; }
+};
+
+inline ResidentPlan PlanResident(uint64_t n_docs, uint64_t n_postings, uint64_t text_bytes, bool attach_text) {
+  ResidentPlan r;
+  r.dl8_slots = (n_docs + kResidentTileDocs - 1) / kResidentTileDocs * kResidentTileDocs;
+  r.docids = (n_postings + kResidentIdPad) * 4;
+  r.tf = n_postings + kResidentIdPad;
+  r.doc_len = n_docs * 4;
+  r.dl8 = r.dl8_slots + kResidentDl8Pad;
+  r.text = attach_text ? text_bytes + kResidentTextPad : 0;
+  r.text_off = attach_text ? (n_docs + 1) * 8 : 0;
+  const uint64_t slots = attach_text && n_docs + 1 > r.dl8_slots ? n_docs + 1 : r.dl8_slots;
+  r.lanes = (slots + kResidentSlotsPerLane - 1) / kResidentSlotsPerLane;
+  return r;
+}
+
+// Device allocations handed from the build to the index that adopts them (mgx_api.cpp); what is still here when the
+// object goes is freed.
+struct ResidentArrays {
+  ResidentPlan plan;
+  void *docids = nullptr, *tf = nullptr, *doc_len = nullptr, *dl8 = nullptr, *text = nullptr, *text_off = nullptr;
+  ResidentArrays() = default;
+  ResidentArrays(const ResidentArrays&) = delete;
+  ResidentArrays& operator=(const ResidentArrays&) = delete;
+  ~ResidentArrays() { Free(); }
+  void Free();  // mgx_build.hip
+};
+
 // mgx_build.hip. text_off[0 .. n_docs] ascends (the caller checked). Returns an MGX_* code and fills *err.
+// `resident` null: every column comes back in *out. Otherwise (n_docs >= 1): out->docids and out->tf stay empty, and the
+// postings, tf, doc_len, the padded dl8 row and, with attach_text, the texts and their offsets from 0 are left in
+// *resident, copied device to device out of the build's temporary storage.
 int BuildOnDevice(const mgx_build_params& bp, const uint8_t* text_bytes, const uint64_t* text_off, uint32_t first_doc_id,
-                  uint64_t n_docs, int device, PackedColumns* out, std::string* err);
+                  uint64_t n_docs, int device, PackedColumns* out, std::string* err, ResidentArrays* resident = nullptr,
+                  bool attach_text = false);
 
 }  // namespace build
 

@@ -582,7 +582,7 @@ void ColumnsView(const Columns* c, mgx_columns_view* v) {
   v->key_bytes = c->key_bytes.data();
   v->key_off = c->key_off.data();
   v->offsets = c->offsets.data();
-  v->docids = c->docids.data();
+  v->docids = c->docids.empty() ? nullptr : c->docids.data();  // (empty: the dictionary of mgx_index_build_device)
   v->tf = c->tf.empty() ? nullptr : c->tf.data();
   v->n_postings = c->offsets.empty() ? 0 : c->offsets.back();
   v->first_doc_id = c->first_doc_id;

@@ -201,7 +201,11 @@ void ClearDeviceErrorForSorter() { ClearDeviceError(); }
 struct Index::Impl {
   int device = 0;
   double dense_threshold = 0.0;
-  std::atomic<bool> device_build{false};  // SetDeviceBuild: column arrays are built by mgx_columns_build_device
+  std::atomic<int> build_mode{Index::kHost};  // SetBuildMode / SetDeviceBuild: who builds a generation's column arrays
+  // BuildCounters: generations built per mode since creation. A delta index is an Index of its own: its generations are
+  // counted where `built_sink` points, the table's array.
+  std::atomic<uint64_t> built[3] = {{0}, {0}, {0}};
+  std::atomic<uint64_t>* built_sink = built;
   int query_kanji = 0;  // table-config kanji size used for QUERY n-grams (the Index itself keeps kanji = ngram if 0)
   mutable std::mutex mu;
   mutable std::map<DocId, std::string> pending;  // documents recorded before the first search
@@ -537,7 +541,9 @@ struct GenerationSpec {
   const uint64_t* text_off = nullptr;
   DocId first = 1;
   uint64_t n = 0;
-  bool device_build = false;  // build the column arrays on `device` (the host builds what the device builder declines)
+  int build_mode = Index::kHost;  // Index::BuildMode: kDeviceColumns builds the column arrays on `device`, kDeviceResident
+                                  // the device index with them (the host builds what the device builder declines)
+  std::atomic<uint64_t>* built = nullptr;  // [3], by the mode that did build the generation (BuildCounters)
   const std::vector<DocId>* existing = nullptr;  // the ids that exist, when some of [first, first + n) do not
   const NamedValues* columns = nullptr;          // filter values by doc slot
   const std::map<DocId, std::string>* primary_keys = nullptr;  // the table's (those of [first, first + n) are taken)
@@ -613,11 +619,23 @@ std::string BuildGeneration(const GenerationSpec& in, Index::Impl::Generation* o
   g.handles = std::make_shared<Index::Impl::Handles>();  // (owns what follows: gone with `g` on every early return)
   g.handles->cols = in.cols;
   const auto t0 = std::chrono::steady_clock::now();
-  bool on_device = false;
+  bool on_device = false, resident = false;
   if (!g.handles->cols) {
     mgx_build_params bp{sizeof(mgx_build_params), MGX_ABI_VERSION, in.ngram, in.kanji, in.cross ? 1 : 0, 0};
     int rc = MGX_ERR_NOT_IMPLEMENTED;
-    if (in.device_build) {
+    if (in.build_mode == Index::kDeviceResident && in.text_bytes) {
+      // columns, device index and attached texts with one call: the postings and the texts stay on the device. The
+      // generation's columns are the dictionary (view.docids / view.tf are null; nothing below reads them). Declined
+      // builds fall to the host like the device builder's.
+      mgx_index_build_desc bd{sizeof(mgx_index_build_desc), MGX_ABI_VERSION, in.device, 0, in.dense_threshold, 1, 0};
+      rc = mgx_index_build_device(&bp, &bd, in.text_bytes, in.text_off, in.first, in.n, &g.handles->cols, &g.handles->dev);
+      resident = rc == MGX_OK;
+      if (rc != MGX_OK) {
+        g.handles->cols = nullptr;
+        g.handles->dev = nullptr;
+        if (rc != MGX_ERR_NOT_IMPLEMENTED && rc != MGX_ERR_OUT_OF_RANGE) return mgx_last_error();
+      }
+    } else if (in.build_mode != Index::kHost) {
       // what the device builder declines (grams of more than 3 code points, no room on the device) the host builds: the
       // result is the same by contract. Every other error is the caller's.
       rc = mgx_columns_build_device(&bp, in.text_bytes, in.text_off, in.first, in.n, in.device, &g.handles->cols);
@@ -631,25 +649,29 @@ std::string BuildGeneration(const GenerationSpec& in, Index::Impl::Generation* o
       g.handles->cols = nullptr;
       return mgx_last_error();
     }
+    if (in.built) in.built[resident ? Index::kDeviceResident : on_device ? Index::kDeviceColumns : Index::kHost]++;
   }
   const auto t1 = std::chrono::steady_clock::now();
   mgx_columns_view_get(g.handles->cols, &g.view);
   const auto& v = g.view;
-  mgx_index_desc d{sizeof(mgx_index_desc), MGX_ABI_VERSION, in.device, 0, v.first_doc_id, v.n_docs, v.n_grams,
-                   v.offsets,               v.docids,        v.tf,      v.doc_len, in.dense_threshold,
-                   v.tf_overflow_pos,       v.tf_overflow_val, v.n_tf_overflow};
-  if (mgx_index_create(&d, &g.handles->dev) != MGX_OK) {
-    g.handles->dev = nullptr;
-    return mgx_last_error();
+  if (!resident) {
+    mgx_index_desc d{sizeof(mgx_index_desc), MGX_ABI_VERSION, in.device, 0, v.first_doc_id, v.n_docs, v.n_grams,
+                     v.offsets,               v.docids,        v.tf,      v.doc_len, in.dense_threshold,
+                     v.tf_overflow_pos,       v.tf_overflow_val, v.n_tf_overflow};
+    if (mgx_index_create(&d, &g.handles->dev) != MGX_OK) {
+      g.handles->dev = nullptr;
+      return mgx_last_error();
+    }
   }
   mgx_index* dev = g.handles->dev;
   const auto t2 = std::chrono::steady_clock::now();
   // the shim's Index is also the DocumentStore of the texts it was given: BM25 terms longer than one n-gram are
   // counted in the text on the device
-  if (in.text_bytes && mgx_index_attach_text(dev, in.text_bytes, in.text_off) != MGX_OK) return mgx_last_error();
+  if (!resident && in.text_bytes && mgx_index_attach_text(dev, in.text_bytes, in.text_off) != MGX_OK) return mgx_last_error();
   if (kTrace)
     fprintf(stderr, "[shim] generation of %llu docs: columns (%s) %.2f ms, device index %.2f ms, texts %.2f ms\n",
-            static_cast<unsigned long long>(v.n_docs), in.cols ? "given" : on_device ? "device builder" : "host builder",
+            static_cast<unsigned long long>(v.n_docs),
+            in.cols ? "given" : resident ? "resident" : on_device ? "device builder" : "host builder",
             std::chrono::duration<double, std::milli>(t1 - t0).count(),
             std::chrono::duration<double, std::milli>(t2 - t1).count(),
             std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t2).count());
@@ -1113,7 +1135,8 @@ BuiltDelta BuildDelta(const Index& self, const std::map<DocId, std::string>& doc
   auto nd = std::make_shared<Index>(self.GetNgramSize(), im->query_kanji, im->dense_threshold, self.GetCrossBoundaryNgrams(),
                                     self.GetNormalizeNfkc(), self.GetNormalizeWidth(), self.GetNormalizeLower(), im->device);
   nd->impl()->internal = true;
-  nd->impl()->device_build = im->device_build.load();
+  nd->impl()->build_mode = im->build_mode.load();
+  nd->impl()->built_sink = im->built_sink;
   std::vector<DocId> ids;
   ids.reserve(docs.size());
   DocId local = 1;
@@ -1328,7 +1351,11 @@ std::string ApplyLocked(const Index& self, bool force) {
 }
 }  // namespace
 
-void Index::SetDeviceBuild(bool on) { impl_->device_build = on; }
+void Index::SetDeviceBuild(bool on) { impl_->build_mode = on ? kDeviceColumns : kHost; }
+void Index::SetBuildMode(BuildMode mode) { impl_->build_mode = mode; }
+Index::BuildCounts Index::BuildCounters() const {
+  return {impl_->built[kHost].load(), impl_->built[kDeviceColumns].load(), impl_->built[kDeviceResident].load()};
+}
 
 void Index::SetMutationStaleness(std::chrono::microseconds max_staleness) {
   std::lock_guard<std::mutex> lock(impl_->mu);
@@ -1422,7 +1449,8 @@ std::string Index::Compact() const {
   // ---- the new generation ----------------------------------------------------------------------------------------------
   GenerationSpec spec{im->device, im->dense_threshold, ngram_size_, kanji_ngram_size_, cross_boundary_, nullptr,
                       bytes.data(), off.data(),    first,       n2};
-  spec.device_build = im->device_build.load();
+  spec.build_mode = im->build_mode.load();
+  spec.built = im->built_sink;
   if (existing.size() != n2) spec.existing = &existing;
   spec.columns = &columns;
   spec.primary_keys = &im->primary_keys;  // (removed documents' keys are gone from it: a gap of the new range has none)
@@ -1508,7 +1536,8 @@ std::string Index::Finalize() const {
   impl_->pending.clear();
   GenerationSpec spec{impl_->device, impl_->dense_threshold, ngram_size_, kanji_ngram_size_, cross_boundary_, nullptr,
                       bytes.data(),  off.data(),             first,       n};
-  spec.device_build = impl_->device_build.load();
+  spec.build_mode = impl_->build_mode.load();
+  spec.built = impl_->built_sink;
   if (existing.size() != n && !existing.empty()) spec.existing = &existing;
   spec.primary_keys = &impl_->primary_keys;
   spec.originals = &impl_->originals;

@@ -231,7 +231,20 @@ class Index {
   // mgx_columns_build_device instead of on the host. The arrays are the same either way; what the device builder declines
   // (grams of more than 3 code points, no room on the device) is built on the host. Off by default. Takes effect with the
   // next build.
-  void SetDeviceBuild(bool on);
+  void SetDeviceBuild(bool on);  // kDeviceColumns / kHost
+  // Who builds a generation (the initial build, a delta rebuild, Compact). kDeviceColumns is SetDeviceBuild(true).
+  // kDeviceResident: mgx_index_build_device makes the column arrays, the device index and its attached texts in one call;
+  // the postings and the texts are never copied back to the host, and the generation's columns are the dictionary alone
+  // (keys, offsets, doc lengths, statistics: all this class reads of them). What the device call declines the host
+  // builds, as in kDeviceColumns. Takes effect with the next build.
+  enum BuildMode : int { kHost = 0, kDeviceColumns = 1, kDeviceResident = 2 };
+  void SetBuildMode(BuildMode mode);
+  // Generations this table built since creation, by the mode that did build each (a declined device build counts as
+  // the host's), deltas and compactions included.
+  struct BuildCounts {
+    uint64_t host = 0, device_columns = 0, device_resident = 0;
+  };
+  [[nodiscard]] BuildCounts BuildCounters() const;
   // Folds the delta back: the main index is rebuilt from the table's current documents (the texts of its live documents come
   // back from the device, where BM25 keeps them; filter values likewise) and the delta and the live row go. What the
   // reference's Optimize / a dump-and-reload do for a grown index. Same exclusion rule as the mutation-applying entry

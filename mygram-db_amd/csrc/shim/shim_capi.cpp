@@ -399,6 +399,22 @@ int mgxs_table_set_device_build(mgxs_table* table, int on) {
   return MGX_OK;
 }
 
+int mgxs_table_set_build_mode(mgxs_table* table, int mode) {
+  if (!table || mode < 0 || mode > 2) return Fail(MGX_ERR_INVALID_ARGUMENT, "mgxs_table_set_build_mode: bad argument");
+  table->index->SetBuildMode(static_cast<mygramdb::index::Index::BuildMode>(mode));
+  return MGX_OK;
+}
+
+int mgxs_table_build_counters(mgxs_table* table, uint64_t* host, uint64_t* device_columns, uint64_t* device_resident) {
+  if (!table || !host || !device_columns || !device_resident)
+    return Fail(MGX_ERR_INVALID_ARGUMENT, "mgxs_table_build_counters: null argument");
+  const auto c = table->index->BuildCounters();
+  *host = c.host;
+  *device_columns = c.device_columns;
+  *device_resident = c.device_resident;
+  return MGX_OK;
+}
+
 int mgxs_table_set_mutation_staleness(mgxs_table* table, uint64_t microseconds) {
   if (!table) return Fail(MGX_ERR_INVALID_ARGUMENT, "mgxs_table_set_mutation_staleness: null argument");
   table->index->SetMutationStaleness(std::chrono::microseconds(microseconds));

@@ -211,8 +211,9 @@ class Columns:
         self.key_off = _np_view(v.key_off, self.n_grams + 1, np.uint32)
         self.key_bytes = _np_view(v.key_bytes, int(self.key_off[-1]) if self.n_grams else 0, np.uint8)
         self.offsets = _np_view(v.offsets, self.n_grams + 1, np.uint64)
-        self.docids = _np_view(v.docids, self.n_postings, np.uint32)
-        self.tf = _np_view(v.tf, self.n_postings, np.uint8)
+        # the dictionary of mgx_index_build_device holds no postings: its view's docids / tf are NULL
+        self.docids = _np_view(v.docids, self.n_postings, np.uint32) if v.docids or not self.n_postings else None
+        self.tf = _np_view(v.tf, self.n_postings, np.uint8) if v.docids or not self.n_postings else None
         self.doc_len = _np_view(v.doc_len, self.n_docs, np.uint32)
         self.tf_overflow_pos = _np_view(v.tf_overflow_pos, int(v.n_tf_overflow), np.uint64)
         self.tf_overflow_val = _np_view(v.tf_overflow_val, int(v.n_tf_overflow), np.uint32)
@@ -249,6 +250,29 @@ class DeviceIndex:
                             v.n_tf_overflow if with_scoring else 0)
         h = C.c_void_p()
         check(L.mgx_index_create(C.byref(d), C.byref(h)))
+        self._adopt(h, device)
+
+    @classmethod
+    def build_resident(cls, corpus, first_doc_id=1, ngram_size=2, kanji_ngram_size=0, cross_boundary=True, device=0,
+                       dense_threshold=0.0, attach_text=True, tile_shift=0):
+        """mgx_index_build_device: (dictionary-only Columns, DeviceIndex) from normalized texts in one call; the postings
+        never come to the host."""
+        L = load()
+        bp = _capi.BuildParams(C.sizeof(_capi.BuildParams), _capi.ABI_VERSION, ngram_size, kanji_ngram_size,
+                               int(cross_boundary), 0)
+        d = _capi.IndexBuildDesc(C.sizeof(_capi.IndexBuildDesc), _capi.ABI_VERSION, int(device), tile_shift,
+                                 dense_threshold, int(bool(attach_text)), 0)
+        ch, ih = C.c_void_p(), C.c_void_p()
+        check(L.mgx_index_build_device(C.byref(bp), C.byref(d), corpus.text_bytes.ctypes.data, corpus.text_off.ctypes.data,
+                                       first_doc_id, corpus.n_docs, C.byref(ch), C.byref(ih)))
+        cols = Columns.__new__(Columns)
+        cols.ngram_size, cols.kanji_ngram_size, cols.cross_boundary = ngram_size, kanji_ngram_size, cross_boundary
+        cols._adopt(ch)
+        self = cls.__new__(cls)
+        self._adopt(ih, device)
+        return cols, self
+
+    def _adopt(self, h, device):
         self._h = h
         self.device = device
         self.facet_values = {}  # column id -> n_values of the columns added with value ids (the lengths of their counts)
@@ -272,6 +296,16 @@ class DeviceIndex:
         n = C.c_uint64()
         check(load().mgx_index_memory_bytes(self._h, C.byref(n)))
         return int(n.value)
+
+    def read_postings(self, gram_id):
+        """mgx_index_read_postings: (docids u32, tf u8) of one gram as device memory holds them."""
+        L = load()
+        n = C.c_uint64()
+        check(L.mgx_index_read_postings(self._h, gram_id, None, None, 0, C.byref(n)))
+        docids, tf = np.zeros(int(n.value), dtype=np.uint32), np.zeros(int(n.value), dtype=np.uint8)
+        if n.value:
+            check(L.mgx_index_read_postings(self._h, gram_id, docids.ctypes.data, tf.ctypes.data, n.value, C.byref(n)))
+        return docids, tf
 
     def set_batch_order(self, fifo=True):
         """mgx_index_set_batch_order: batches in flight run first-in-first-out (default) or time-slice the device."""
@@ -785,7 +819,8 @@ class Index:
 
     def __init__(self, corpus=None, texts=None, first_doc_id=1, ngram_size=2, kanji_ngram_size=0, cross_boundary=True,
                  device=0, dense_threshold=0.0, total_docs=None, avg_doc_length=None, global_posting_sizes=None,
-                 n_threads=0, normalize_nfkc=True, normalize_width="keep", normalize_lower=True, build_device=None):
+                 n_threads=0, normalize_nfkc=True, normalize_width="keep", normalize_lower=True, build_device=None,
+                 resident=False):
         if corpus is None:
             corpus = Corpus.from_texts(texts if texts is not None else [])
         self.ngram_size = ngram_size
@@ -794,11 +829,18 @@ class Index:
         self.cross_boundary = cross_boundary
         # index.h:58-60: how QUERY terms are normalised; document texts arrive normalised (as Index::AddDocument's do)
         self.normalize_nfkc, self.normalize_width, self.normalize_lower = normalize_nfkc, normalize_width, normalize_lower
-        self.columns = Columns(corpus, first_doc_id, ngram_size, kanji_ngram_size, cross_boundary, n_threads,
-                               device=build_device)
-        self.device_index = DeviceIndex(self.columns, device, dense_threshold)
+        if resident:
+            # mgx_index_build_device on `build_device`: `columns` is the dictionary (docids / tf None), the texts are attached
+            if build_device is None or build_device != device:
+                raise ValueError("resident=True builds on the device that serves: build_device must equal device")
+            self.columns, self.device_index = DeviceIndex.build_resident(
+                corpus, first_doc_id, ngram_size, kanji_ngram_size, cross_boundary, device, dense_threshold, attach_text=True)
+        else:
+            self.columns = Columns(corpus, first_doc_id, ngram_size, kanji_ngram_size, cross_boundary, n_threads,
+                                   device=build_device)
+            self.device_index = DeviceIndex(self.columns, device, dense_threshold)
         self.corpus = corpus        # the DocumentStore's normalized texts
-        self._text_attached = False
+        self._text_attached = bool(resident)
         self.total_docs = self.columns.bm25_doc_count if total_docs is None else total_docs
         self.avg_doc_length = self.columns.avg_doc_length() if avg_doc_length is None else avg_doc_length
         # df source: posting sizes of the WHOLE table (a shard passes the global sizes so idf is identical everywhere)

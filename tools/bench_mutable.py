@@ -10,6 +10,7 @@ deep SORT _score pages (offset+limit > 1024) and docid pages past 16384 rows or 
     python tools/bench_mutable.py [--docs 10000000] [--steps 100] [--deltas 1000,10000,100000]
     python tools/bench_mutable.py --batch 64 --deltas 10000 --sort score --offset 10000 --limit 100
     python tools/bench_mutable.py --write-rate 2000 --device-build    (delta rebuilds and compaction build on the device)
+    python tools/bench_mutable.py --resident    (they build with mgx_index_build_device: postings and texts stay on the device)
 """
 import argparse
 import json
@@ -57,7 +58,11 @@ def main():
     ap.add_argument("--sort", choices=("score", "docid"), default="score")
     ap.add_argument("--device-build", action="store_true",
                     help="the table's delta rebuilds and its compaction build their column arrays on the device")
+    ap.add_argument("--resident", action="store_true",
+                    help="they build columns, device index and texts with mgx_index_build_device: the postings never come to the host")
     args = ap.parse_args()
+    if args.resident and args.device_build:
+        raise SystemExit("--device-build and --resident are two build modes: choose one")
     PAGE.update(limit=args.limit, offset=args.offset, sort_by_score=args.sort == "score")
     page = {"limit": args.limit, "offset": args.offset, "sort": args.sort}
     import torch
@@ -77,7 +82,8 @@ def main():
         world = 1
     term_batches = bench.make_queries(mg, _Whole, 16, args.batch)
     shim_table = S.Table(index)
-    shim_table.set_device_build(args.device_build)
+    shim_table.set_build_mode(S.Table.BUILD_DEVICE_RESIDENT if args.resident else
+                              S.Table.BUILD_DEVICE_COLUMNS if args.device_build else S.Table.BUILD_HOST)
     depth = args.depth
     ex = S.Executor(shim_table, depth=depth, planner_threads=6)
     qbs = [S.QueryBatch(tb) for tb in term_batches]
@@ -88,7 +94,7 @@ def main():
     run(ex, qbs, 20, depth, outs)
     dt = run(ex, qbs, args.steps, depth, outs)
     static_qps = args.batch * args.steps / dt
-    print(json.dumps({"table": "static", "docs": args.docs, "device_build": args.device_build, "page": page, "queries_per_s": static_qps, "ms_per_step": 1e3 * dt / args.steps,
+    print(json.dumps({"table": "static", "docs": args.docs, "device_build": args.device_build, "resident": args.resident, "page": page, "queries_per_s": static_qps, "ms_per_step": 1e3 * dt / args.steps,
                       "host_ms_plan_compile_enqueue_wait": HOST_MS.round(3).tolist()}), flush=True)
     rng = np.random.default_rng(7)
     texts = {}
@@ -123,7 +129,7 @@ def main():
         run(ex, qbs, 10, depth, outs)
         dt = run(ex, qbs, args.steps, depth, outs)
         st = shim_table.mutation_stats()
-        print(json.dumps({"table": "mutable", "device_build": args.device_build, "page": page, "changed_documents": target, "delta_documents": st["delta_documents"],
+        print(json.dumps({"table": "mutable", "device_build": args.device_build, "resident": args.resident, "page": page, "changed_documents": target, "delta_documents": st["delta_documents"],
                           "removed_from_main": st["removed_from_main"], "mutation_calls_s": calls_s,
                           "calls_per_s": n_new / calls_s, "first_batch_after_changes_s": apply_s,
                           "queries_per_s": args.batch * args.steps / dt, "ms_per_step": 1e3 * dt / args.steps,
@@ -162,7 +168,7 @@ def main():
             dt = time.perf_counter() - t0
             stop.set()
             th.join()
-            print(json.dumps({"table": "steady writer", "device_build": args.device_build, "staleness_s": bound, "changes_per_s": made[0] / dt,
+            print(json.dumps({"table": "steady writer", "device_build": args.device_build, "resident": args.resident, "staleness_s": bound, "changes_per_s": made[0] / dt,
                               "queries_per_s": args.batch * steps / dt, "ms_per_step": 1e3 * dt / steps,
                               "vs_static": args.batch * steps / dt / static_qps,
                               "delta_documents": shim_table.mutation_stats()["delta_documents"]}), flush=True)
@@ -173,7 +179,7 @@ def main():
     compact_s = time.perf_counter() - t0
     run(ex, qbs, 10, depth, outs)
     dt = run(ex, qbs, args.steps, depth, outs)
-    print(json.dumps({"table": "compacted", "device_build": args.device_build, "compact_s": compact_s, "queries_per_s": args.batch * args.steps / dt,
+    print(json.dumps({"table": "compacted", "device_build": args.device_build, "resident": args.resident, "compact_s": compact_s, "queries_per_s": args.batch * args.steps / dt,
                       "ms_per_step": 1e3 * dt / args.steps, "vs_static": args.batch * args.steps / dt / static_qps,
                       "stats": shim_table.mutation_stats()}), flush=True)
 
